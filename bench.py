@@ -21,7 +21,7 @@ Workloads (--workload):
       N top-5 bases, so it is not the headline (LOCO_BENCH_K_TOTAL forces it: smoke test).
   p2_k64 (BASELINE config 3): FFHQ-P2 architecture, 64 probes sharded over the N
       ranks (strong scaling, 64/N per rank), keep the leading 20 rows; value = 20 /
-      step time.  The default run also times one step of it and reports it under
+      step time.  A --full run also times one step of it and reports it under
       "extra_workloads" next to the headline line.
   tloco_sd   (BASELINE config 4): latent T-LOCO on the Stable-Diffusion-shaped stand-ins (4x64x64 latent denoiser +
              the SD autoencoder's decoder geometry, Jacobian of the decoded 3x512x512 image); explicit workload only
@@ -32,7 +32,14 @@ Workloads (--workload):
       step time.  tloco_if64: the same on the round-2 stand-in (guided-diffusion U-Net, text through the time embedding).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload W] [--precision P]
-                    [--no-cpu-baseline] [--no-e2e] [--no-extra]
+                    [--dump-outputs DIR] [--full [--no-profile] [--no-cpu-baseline] [--no-e2e] [--no-extra]]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs
+(--dump-outputs) and prints the headline line.  --full adds the legs that run
+work of their own after the timed steps: the per-kernel profile step behind
+`roofline`, the parity of vT against the reference fixture, the end-to-end
+phases, the other precisions / stream mode / workloads under "extra_workloads"
+and the CPU baseline (each can be left out with its --no-* option).
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks
 itself (python -m torch.distributed.run, one process per GPU) before anything
@@ -80,14 +87,22 @@ def parse():
                          "package since round 6: -3.5 ... -4.7 %% per headline solve, same results) or on 1.  The per-kernel profile "
                          "behind `roofline` is always taken on ONE stream (isolated kernel durations, the ones rocprofv3 reports for "
                          "a one-stream run); the one-stream step is the extra line celeba_top5_one_stream")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true", help="skip the per-kernel HIP-event profile step")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end phase timing (inversion ... decode)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra workload (p2_k64) and extra precision lines")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the profile step (roofline), the parity leg, the end-to-end phases, "
+                         "the extra precision / stream / workload lines and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="--full: skip the per-kernel HIP-event profile step")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the end-to-end phase timing (inversion ... decode)")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the extra workload (p2_k64) and extra precision lines")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned (u, s, vT, n_iter) as DIR/<name>.npy (rank 0)")
     ap.add_argument("--precision", choices=["f32", "bf16x3", "f16"], default=os.environ.get("LOCO_PRECISION", "bf16x3"),
                     help="conv arithmetic: exact fp32 MFMA, split-bf16 (3 bf16 MFMAs per product, fp32-faithful), or "
                          "one f16 MFMA per product")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def launch_ranks(n):
@@ -207,6 +222,31 @@ def parity_vs_fixture(s, vT, name):
             "n_iter": int(g["n_iter"]), "cos_min": round(float(cos.min()), 6), "cos": [round(float(c), 6) for c in cos],
             "span_cos_min": round(float(ov.min()), 6), "s_relerr": float(f"{float(srel):.3e}"),
             "bar": "|cos| >= 0.99 (north_star)"}
+
+
+DUMP_BUDGET_BYTES = 60 << 20        # --dump-outputs stays below 64 MB in all, .npy headers included
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy, float64 kept, any other dtype as float32.  Should the arrays
+    together exceed DUMP_BUDGET_BYTES, every one above 1 MiB is cut to a fixed sample of its flattened elements (seed 0,
+    indices ascending; the same sample for the same shape on every run), sized so that the whole dump fits the budget."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    out = {}
+    for name, v in arrays.items():
+        x = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
+        out[name] = x.astype(np.float64 if x.dtype == np.float64 else np.float32)
+    big = {n for n, x in out.items() if x.nbytes > (1 << 20)}
+    total = sum(x.nbytes for x in out.values())
+    if total > DUMP_BUDGET_BYTES:
+        ratio = (DUMP_BUDGET_BYTES - (total - sum(out[n].nbytes for n in big))) / sum(out[n].nbytes for n in big)
+        for n in big:
+            x = out[n].reshape(-1)
+            idx = np.sort(np.random.default_rng(0).choice(x.size, max(1, int(x.size * ratio)), replace=False))
+            out[n] = x[idx]
+    for name, x in out.items():
+        np.save(os.path.join(path, name + ".npy"), x)
 
 
 def e2e_phases(eng, cfg, sched_cls, solver, device):
@@ -544,11 +584,15 @@ def main():
     # replicas: every rank kept `keep` directions of its own image in that (max-over-ranks) time
     value = keep * (world if replicas else 1) / (elapsed / a.steps)
     k_local = k if replicas else sharder.rows(k)[1] - sharder.rows(k)[0]
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"u": u, "s": s, "vT": vT, "n_iter": float(n_iter)})
+        _mark("outputs dumped")
 
-    # ---- roofline leg: per-kernel HIP-event profile of one more identical step
+    # ---- roofline leg (--full): per-kernel HIP-event profile of one more identical step
     roofline = None
     F = eng.unet_flops()
-    if not a.no_profile:
+    profile = a.full and not a.no_profile
+    if profile:
         # every rank runs the extra step (it contains the all-gather); only rank 0 records the per-kernel events
         if rank == 0:
             eng.profile_enable(True)
@@ -557,7 +601,7 @@ def main():
         w["step"]()
         torch.cuda.synchronize()
         t_prof = time.perf_counter() - tp0
-    if rank == 0 and not a.no_profile:
+    if rank == 0 and profile:
         rep = eng.profile_report()
         eng.profile_enable(False)
         if os.environ.get("LOCO_BENCH_SHAPES"):      # diagnostics: one more step profiled per LAYER SHAPE, dumped for tests/diag/shape_excess.py
@@ -617,9 +661,9 @@ def main():
         }
 
     _mark("profile step done")
-    # ---- parity leg (outside the timed region): the metric's second half, vT cosine vs the reference
+    # ---- parity leg (--full, outside the timed region): the metric's second half, vT cosine vs the reference
     parity = None
-    if a.workload == "celeba_top5" and not SMOKE_ITERS and not K_TOTAL:
+    if a.full and a.workload == "celeba_top5" and not SMOKE_ITERS and not K_TOTAL:
         if world == 1 or replicas:      # (rank 0's replica runs the fixture's inputs)
             ps, pvT = s, vT
         else:   # the k = 5 solve of the fixture, replicated on every rank (no collective), reported by rank 0
@@ -632,12 +676,12 @@ def main():
     _mark("parity leg done")
     extra = {}
     e2e = None
-    if rank == 0 and world == 1 and a.workload == "celeba_top5" and not a.no_e2e:
+    if a.full and rank == 0 and world == 1 and a.workload == "celeba_top5" and not a.no_e2e:
         try:
             e2e = e2e_phases(eng, cfg, YHCustomScheduler, solver, device)
         except Exception as ex:            # never lose the headline line to an optional leg
             e2e = {"error": repr(ex)[:200]}
-    if a.workload == "celeba_top5" and not a.no_extra:
+    if a.full and a.workload == "celeba_top5" and not a.no_extra:
         # other conv arithmetic modes on the same workload, one timed step each, with their measured cosine
         if world == 1:
             for prec in ("f16", "f32"):
@@ -769,7 +813,7 @@ def main():
                 extra["p2_k64"]["predicted_strong_scaling"] = {"error": repr(ex)[:200]}
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and a.workload == "celeba_top5":
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and a.workload == "celeba_top5":
         cpu = cpu_baseline(cfg, w["params"], t)
 
     if rank == 0:

@@ -10,7 +10,7 @@ for wl in WL:
   for rep in range(2):
     for v in vals:
         env = dict(os.environ, **{name: v})
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
                             "--no-e2e", "--no-extra", "--workload", wl], env=env, capture_output=True, text=True)
         try:
             d = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][0])

@@ -1,7 +1,7 @@
 """Diagnostic (by hand): rank the layer shapes of a per-shape conv profile (bench.py with LOCO_BENCH_SHAPES=<file>, any workload; the
 profile is the first engine context's) by their time above max(flops at 350 TFLOP/s, input + output bytes at 4 TB/s).
-    LOCO_BENCH_SHAPES=gpurun_out/s.json python3 bench.py --workload tloco_sd15 --steps 1 --warmup 1 --no-extra --no-e2e --no-cpu-baseline
-    python3 tests/diag/shape_excess.py gpurun_out/s.json [rows]"""
+    LOCO_BENCH_SHAPES=/tmp/shapes.json python3 bench.py --workload tloco_sd15 --steps 1 --warmup 1 --full --no-extra --no-e2e --no-cpu-baseline
+    python3 tests/diag/shape_excess.py /tmp/shapes.json [rows]"""
 import json, re, sys
 rep = json.load(open(sys.argv[1]))
 N = int(sys.argv[2]) if len(sys.argv) > 2 else 40

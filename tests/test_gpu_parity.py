@@ -716,9 +716,9 @@ def test_bench_two_ranks_share_one_gpu():
     env = dict(os.environ, LOCO_BENCH_BACKEND="gloo", LOCO_BENCH_MAX_BATCH="8",     # two 8-sample arenas on the one GPU (not 2 x 32)
                LOCO_BENCH_SMOKE_ITERS="3", LOCO_BENCH_K_TOTAL="5")
     env.pop("WORLD_SIZE", None)
-    # the driver's own command form: no external launcher, bench.py starts its ranks itself
+    # the driver's own command form: no external launcher, bench.py starts its ranks itself (--full: the profiled step)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-           "--no-cpu-baseline", "--no-extra", "--no-e2e"]
+           "--full", "--no-cpu-baseline", "--no-extra", "--no-e2e"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
