@@ -277,6 +277,38 @@ int  loco_lincomb(loco_ctx* ctx, const float* const* src, const float* coef, int
 int  loco_profile_enable(loco_ctx* ctx, int32_t on);
 int  loco_profile_report(loco_ctx* ctx, char* buf, int64_t cap);
 
+/* --- CLIP text encoder (Stable Diffusion prompt embeddings) ---
+ * The CLIPTextModel of transformers as diffusers' StableDiffusionPipeline.encode_prompt runs it (reference
+ * src/modules/edit.py:1187-1194): token + position embedding, `layers` pre-LN blocks (LayerNorm -> causal multi-head
+ * self-attention, scale head_dim^-0.5 -> residual; LayerNorm -> fc1 -> act -> fc2 -> residual), final_layer_norm; output
+ * last_hidden_state.  Exact fp32 throughout (independent of loco_set_precision / LOCO_PRECISION).  Its own handle: it shares
+ * nothing with a loco_ctx. */
+typedef struct loco_text loco_text;
+typedef struct loco_text_cfg {
+    int32_t vocab;        /* rows of embeddings.token_embedding (49408 for the SD checkpoints) */
+    int32_t width;        /* hidden_size: 768 (SD 1.x), 1024 (SD 2.x) */
+    int32_t layers;       /* num_hidden_layers: 12 / 23 */
+    int32_t heads;        /* num_attention_heads: 12 / 16 */
+    int32_t ffn;          /* intermediate_size: 3072 / 4096 */
+    int32_t positions;    /* max_position_embeddings = the token count L of every prompt (77), <= 128 */
+    int32_t act;          /* hidden_act: 0 quick_gelu x sigmoid(1.702 x) (SD 1.x), 1 exact erf gelu (SD 2.x) */
+    float   ln_eps;       /* layer_norm_eps (1e-5) */
+} loco_text_cfg;
+/* max_prompts: the largest n one loco_text_encode call may carry (the device workspace is sized for it). */
+int  loco_text_create(const loco_text_cfg* cfg, int32_t device, int32_t max_prompts, loco_text** out);
+/* One call per state_dict entry in CLIPTextTransformer naming, without a `text_model.` prefix (embeddings.token_embedding.weight,
+ * encoder.layers.{i}.self_attn.q_proj.weight, ..., final_layer_norm.bias).  `host`: fp32 values, a host or a device pointer. */
+int  loco_text_load_param(loco_text* t, const char* name, const float* host, const int64_t* shape, int32_t ndim);
+/* 0 when every parameter has been loaded, else the count still missing (first missing name in loco_text_last_error). */
+int  loco_text_params_missing(loco_text* t);
+/* out_dev[n][positions][width] = last_hidden_state of the n prompts ids_dev[n][positions] (int32 token ids, device).  One batch:
+ * every layer's weights are read once per call.  The ids are range-checked on the host (one copy + stream synchronisation
+ * before the first kernel), nothing synchronises between layers.  Each row is bit-identical whatever n and its position. */
+int  loco_text_encode(loco_text* t, const int32_t* ids_dev, int32_t n, float* out_dev, void* stream);
+/* Message of the last failed call on t; t == NULL: of the last failed loco_text_create. */
+const char* loco_text_last_error(loco_text* t);
+void loco_text_destroy(loco_text* t);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int GBM = 64, GBN = 64, GBK = 64;
 
-template <int NSEG>
+// EPI: activation applied after bias / colbias / residual (GemmAct; only the text encoder's fc1 launches use one)
+template <int NSEG, int EPI = GEMM_ACT_NONE>
 __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs g) {
     __shared__ float As[GBK][GBM + 1];
     __shared__ float Bs[GBK][GBN + 1];
@@ -85,6 +86,8 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs g) {
             if (g.bias) v += g.bias[m];
                 if (g.colbias) v += g.colbias[n];
             if (g.R) v += g.R[(long)bz * g.srb + (long)hz * g.sch + off];
+            if (EPI == GEMM_ACT_QUICK_GELU) v = v * (1.0f / (1.0f + expf(-1.702f * v)));
+            else if (EPI == GEMM_ACT_GELU) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
             *c = v;
         }
     }
@@ -380,6 +383,14 @@ void launch_gemm(const GemmArgs& g, hipStream_t st) {
     }
     dim3 grid((g.N + GBN - 1) / GBN, (g.M + GBM - 1) / GBM, g.batch * (g.batch2 > 0 ? g.batch2 : 1));
     if (g.A2) hipLaunchKernelGGL(gemm_f32_kernel<2>, grid, dim3(256), 0, st, g);
+    else hipLaunchKernelGGL(gemm_f32_kernel<1>, grid, dim3(256), 0, st, g);
+}
+
+void launch_gemm_fixed(const GemmArgs& g, int act, hipStream_t st) {
+    dim3 grid((g.N + GBN - 1) / GBN, (g.M + GBM - 1) / GBM, g.batch * (g.batch2 > 0 ? g.batch2 : 1));
+    if (g.A2) hipLaunchKernelGGL(gemm_f32_kernel<2>, grid, dim3(256), 0, st, g);
+    else if (act == GEMM_ACT_QUICK_GELU) hipLaunchKernelGGL((gemm_f32_kernel<1, GEMM_ACT_QUICK_GELU>), grid, dim3(256), 0, st, g);
+    else if (act == GEMM_ACT_GELU) hipLaunchKernelGGL((gemm_f32_kernel<1, GEMM_ACT_GELU>), grid, dim3(256), 0, st, g);
     else hipLaunchKernelGGL(gemm_f32_kernel<1>, grid, dim3(256), 0, st, g);
 }
 

@@ -179,6 +179,11 @@ struct GemmArgs {
     const float* A2; long sab2; const float* Bm2; long sbb2;
 };
 void launch_gemm(const GemmArgs& g, hipStream_t st);              // exact fp32 (f32-input MFMA)
+// the same exact-fp32 product on the 64 x 64 tiling whatever the shape, so every output element is the same chain of MFMAs
+// whatever N and the batch are (launch_gemm picks its tiling by grid size), with an activation after the bias (GemmAct;
+// the fc1 of the CLIP text encoder, textenc.hip).  A2 / B2 take no activation.
+enum GemmAct : int { GEMM_ACT_NONE = 0, GEMM_ACT_QUICK_GELU = 1, GEMM_ACT_GELU = 2 };
+void launch_gemm_fixed(const GemmArgs& g, int act, hipStream_t st);
 void launch_gemm_bf16x3(const GemmArgs& g, hipStream_t st);       // split-bf16 operands on the bf16 matrix pipe
 bool gemm_prefers_bf16x3(const GemmArgs& g);                      // long contraction, matrix-rate bound on the f32 MFMA
 // round 5 (gemm_rec.hip): the same products with both operands pre-split into records and streamed by LDS-DMA; `ws` must hold

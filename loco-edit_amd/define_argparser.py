@@ -106,7 +106,13 @@ def build_parser():
                    help='latent T-LOCO: decoder architecture (default: the Stable Diffusion autoencoder decoder geometry)')
     p.add_argument('--vae_ckpt_path', type=str, default='', help='latent T-LOCO: decoder state_dict in latent-diffusion `Decoder` naming')
     p.add_argument('--prompt_emb_path', type=str, default='',
-                   help="T-LOCO: torch file {'for','edit','null': [1, tokens, D]} of prompt embeddings (the text encoder is out of scope)")
+                   help="T-LOCO: torch file {'for','edit','null': [1, tokens, D]} of prompt embeddings (Stable Diffusion: or --text_encoder_path)")
+    p.add_argument('--text_encoder_path', type=str, default='',
+                   help='Stable Diffusion: CLIP text encoder that turns --for_prompt / --edit_prompt / ... into prompt states on the '
+                        'GPU: a diffusers pipeline root (text_encoder/ + tokenizer/), a text_encoder/ folder or a single '
+                        'state_dict file (CompVis SD 1.x .ckpt); excludes --prompt_emb_path')
+    p.add_argument('--tokenizer_path', type=str, default='',
+                   help='CLIP tokenizer folder (vocab.json, merges.txt, configs) when --text_encoder_path is not a pipeline root')
     p.add_argument('--cond_dim', type=int, default=16, help='T-LOCO stand-in: width of seeded prompt embeddings when no file is given')
     p.add_argument('--precision', type=str, default=None, choices=['f32', 'bf16x3', 'f16'],
                    help="conv arithmetic of the HIP engine: 'f32' exact fp32 MFMA (parity anchor), 'bf16x3' split-bf16 "
@@ -118,6 +124,8 @@ def build_parser():
 
 def parse_args(argv=None):
     args = build_parser().parse_args(argv)
+    if args.text_encoder_path and args.prompt_emb_path:
+        raise ValueError("--text_encoder_path and --prompt_emb_path both give the prompt embeddings: pass one of them")
     if args.max_batch <= 0:
         t2i = any(s in args.model_name for s in ('stable-diffusion', 'DeepFloyd', 'LCM'))
         # sized by what actually shares a pass: the probes of the modify-space and null-space solves when they run as a

@@ -31,6 +31,8 @@ SYMBOLS = [
     "loco_unet_flops", "loco_workspace_bytes", "loco_clock_stamp", "loco_set_side_stream", "loco_timer_start", "loco_timer_stop",
     "loco_profile_enable", "loco_profile_report", "loco_set_precision", "loco_get_precision", "loco_set_streams", "loco_set_chip_share",
     "loco_set_cond", "loco_set_context", "loco_lincomb", "loco_masked_axpby", "loco_latent_sample",
+    "loco_text_create", "loco_text_load_param", "loco_text_params_missing", "loco_text_encode", "loco_text_last_error",
+    "loco_text_destroy",
 ]
 
 
@@ -46,6 +48,11 @@ class LocoCfg(C.Structure):
         ("transformer_depth", C.c_int32),
         ("act", C.c_int32), ("res_scale", C.c_float), ("added_kv", C.c_int32),
     ]
+
+
+class LocoTextCfg(C.Structure):
+    _fields_ = [("vocab", C.c_int32), ("width", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32), ("ffn", C.c_int32),
+                ("positions", C.c_int32), ("act", C.c_int32), ("ln_eps", C.c_float)]
 
 
 def library_path() -> str:
@@ -109,6 +116,15 @@ def load_library():
     lib.loco_lincomb.argtypes = [vp, C.POINTER(vp), C.POINTER(f32), i32, vp, i64, vp]
     lib.loco_profile_enable.argtypes = [vp, i32]
     lib.loco_profile_report.argtypes = [vp, C.c_char_p, i64]
+    if hasattr(lib, "loco_text_create"):
+        lib.loco_text_create.argtypes = [C.POINTER(LocoTextCfg), i32, i32, C.POINTER(vp)]
+        lib.loco_text_load_param.argtypes = [vp, C.c_char_p, vp, C.POINTER(i64), i32]
+        lib.loco_text_params_missing.argtypes = [vp]
+        lib.loco_text_encode.argtypes = [vp, vp, i32, vp, vp]
+        lib.loco_text_last_error.argtypes = [vp]
+        lib.loco_text_last_error.restype = C.c_char_p
+        lib.loco_text_destroy.argtypes = [vp]
+        lib.loco_text_destroy.restype = None
     if hasattr(lib, "loco_bench_conv"):          # diag build only
         lib.loco_bench_conv.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(f32), vp]
         lib.loco_debug_tensor.argtypes = [vp, C.c_char_p, vp, i64, vp]
@@ -532,3 +548,66 @@ class LocoEngine:
         if got < 0:
             raise RuntimeError(f"loco_debug_tensor({name}) failed: {self.lib.loco_last_error(self._ctx).decode()}")
         return dst[:got]
+
+
+class LocoTextEngine:
+    """The CLIP text encoder (= loco_text, include/loco_hip.h): parameters on the device, one batched encode per call.
+    `cfg` is a ``text_encoder.TextConfig``; token ids in, last_hidden_state [n, positions, width] out, exact fp32."""
+
+    def __init__(self, cfg, max_prompts: int = 8, device: Optional[torch.device] = None):
+        self.lib = load_library()
+        if not torch.cuda.is_available() or self.lib.loco_device_count() < 1:
+            raise RuntimeError("loco_hip: no HIP device visible; the text encoder has no CPU fallback")
+        self.device = torch.device(device if device is not None else "cuda:0")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.cfg, self.max_prompts = cfg, int(max_prompts)
+        c = LocoTextCfg(vocab=cfg.vocab, width=cfg.width, layers=cfg.layers, heads=cfg.heads, ffn=cfg.ffn,
+                        positions=cfg.positions, act={"quick_gelu": 0, "gelu": 1}[cfg.act], ln_eps=cfg.ln_eps)
+        self._t = C.c_void_p()
+        rc = self.lib.loco_text_create(C.byref(c), self.device.index, self.max_prompts, C.byref(self._t))
+        if rc != 0:
+            raise RuntimeError(f"loco_text_create failed ({rc}): {self.lib.loco_text_last_error(None).decode()}")
+
+    def __del__(self):
+        try:
+            if getattr(self, "_t", None):
+                self.lib.loco_text_destroy(self._t)
+                self._t = None
+        except Exception:
+            pass
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise RuntimeError(f"{what} failed ({rc}): {self.lib.loco_text_last_error(self._t).decode()}")
+
+    def load_state_dict(self, sd: Dict[str, "np.ndarray | torch.Tensor"]):
+        """Names of CLIPTextTransformer without a prefix (text_encoder.normalize_text_state_dict produces them)."""
+        if any(isinstance(v, torch.Tensor) and v.is_cuda for v in sd.values()):
+            torch.cuda.synchronize()        # the copies below read device values written on torch's streams
+        for name, v in sd.items():
+            t = torch.as_tensor(np.asarray(v) if not isinstance(v, torch.Tensor) else v).detach().to(torch.float32).contiguous()
+            if not t.is_cuda:
+                t = t.cpu()
+            shape = (C.c_int64 * max(t.dim(), 1))(*t.shape)
+            self._check(self.lib.loco_text_load_param(self._t, name.encode(), C.c_void_p(t.data_ptr()), shape, t.dim()),
+                        f"loco_text_load_param({name})")
+        missing = self.lib.loco_text_params_missing(self._t)
+        if missing:
+            raise RuntimeError(f"text encoder: {missing} parameters missing ({self.lib.loco_text_last_error(self._t).decode()})")
+
+    def encode_ids(self, ids: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """ids [n, positions] (any integer dtype, host or device) -> [n, positions, width] fp32 on the device."""
+        ids = torch.as_tensor(ids)
+        if ids.dim() != 2 or ids.shape[1] != self.cfg.positions:
+            raise ValueError(f"ids must be [n, {self.cfg.positions}], got {tuple(ids.shape)}")
+        n = ids.shape[0]
+        ids = ids.to(device=self.device, dtype=torch.int32).contiguous()
+        if out is None:
+            out = torch.empty(n, self.cfg.positions, self.cfg.width, device=self.device, dtype=torch.float32)
+        _chk_dev(out)
+        if tuple(out.shape) != (n, self.cfg.positions, self.cfg.width):
+            raise ValueError(f"out must be [{n}, {self.cfg.positions}, {self.cfg.width}], got {tuple(out.shape)}")
+        with torch.cuda.device(self.device):
+            self._check(self.lib.loco_text_encode(self._t, _ptr(ids), n, _ptr(out), _stream()), "loco_text_encode")
+        return out

@@ -289,7 +289,9 @@ class EditDeepFloydIF(object):
         self.dataset_name = args.dataset_name
         # ---- prompt embeddings: inputs of this path (the T5 encoder is out of scope)
         pe = getattr(args, "prompt_emb", None)
-        if pe is None and getattr(args, "prompt_emb_path", ""):
+        if getattr(args, "text_encoder_path", ""):
+            pe = self._encode_run_prompts(args, cfg)
+        elif pe is None and getattr(args, "prompt_emb_path", ""):
             pe = torch.load(args.prompt_emb_path)
         # text enters through cross-attention stages when the architecture has them (context_dim > 0: tokens
         # [context_len, context_dim] via loco_set_context), otherwise pooled through the time embedding (loco_set_cond)
@@ -395,6 +397,10 @@ class EditDeepFloydIF(object):
 
     def _bind_all(self, for_e, edit_e, null_e):
         self._bind("for", for_e); self._bind("edit", edit_e); self._bind("null", null_e)
+
+    def _encode_run_prompts(self, args, cfg):
+        raise NotImplementedError("--text_encoder_path: the DeepFloyd-IF path needs the T5 text encoder, which is not built "
+                                  "(the CLIP encoder serves the Stable Diffusion path); pass --prompt_emb_path")
 
     def _get_prompt_emb(self, prompt):
         raise NotImplementedError("the T5 text encoder is outside this path: pass prompt embeddings (--prompt_emb_path)")

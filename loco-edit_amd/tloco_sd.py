@@ -104,6 +104,8 @@ class LatentCFGJacobianOperator:
 
 
 class EditStableDiffusion(EditDeepFloydIF):
+    text_encoder = None
+
     def __init__(self, args):
         super().__init__(args)
         # ---- the decoder network (vae.decode, edit.py:498): its own engine context
@@ -139,9 +141,45 @@ class EditStableDiffusion(EditDeepFloydIF):
         self.inv_steps = getattr(args, "inv_steps", 100)
         self.inv_prompt = getattr(args, "inv_prompt", "")
         pe = getattr(args, "prompt_emb", None)
+        if self.text_encoder is not None:
+            # edit.py:524: the run's name keeps the first comma-separated part of a long inversion prompt; its embedding
+            # (:529) encodes the whole argument
+            first = self.inv_prompt.split(',')[0]
+            self.inv_prompt = self.inv_prompt if len(first) <= 3 else first
+            pe = self._text_pe
         self.inv_prompt_emb = pe["inv"] if (pe is not None and "inv" in pe) else self.for_prompt_emb
         self.enc_engine: Optional[LocoEngine] = None
         self.dataset = getattr(args, "dataset", None)
+
+    # ------------------------------------------------------------------ prompts (edit.py:523-538, 1187-1194)
+    def _encode_run_prompts(self, args, cfg):
+        """--text_encoder_path: the CLIP text encoder on the GPU; ONE batched encode of the run's for / edit / null / neg /
+        inv prompts (edit.py:527-538).  Called from the base constructor before the branches bind their prompts."""
+        from .text_encoder import TextEncoder
+        te = TextEncoder(args.text_encoder_path, tokenizer_path=getattr(args, "tokenizer_path", "") or None,
+                         device=args.device, max_prompts=5)
+        if te.width != cfg.context_dim or te.length != cfg.context_len:
+            raise ValueError(f"text encoder states {te.length} x {te.width} do not match the denoiser's cross-attention context "
+                             f"{cfg.context_len} x {cfg.context_dim} (context_len x context_dim)")
+        self.text_encoder = te
+        names = ("for", "edit", "null", "neg", "inv")
+        prompts = [args.for_prompt, args.edit_prompt, "", getattr(args, "neg_prompt", ""), getattr(args, "inv_prompt", "")]
+        states = te.encode(prompts)
+        self._text_pe = {k: states[i:i + 1] for i, k in enumerate(names)}
+        self.neg_prompt_emb = self._text_pe["neg"]
+        return self._text_pe
+
+    def _get_prompt_emb(self, prompt):
+        if self.text_encoder is None:
+            return super()._get_prompt_emb(prompt)
+        return self.text_encoder.encode([prompt])
+
+    def _set_edit_prompt(self, edit_prompt):
+        """edit.py:929-931 / 1055-1057: a driver's edit_prompt argument replaces the constructed one (text encoder runs; the
+        next guidance call binds the new states)."""
+        if edit_prompt is not None and self.text_encoder is not None and edit_prompt != self.edit_prompt:
+            self.edit_prompt = edit_prompt
+            self.edit_prompt_emb = self._get_prompt_emb(edit_prompt)
 
     # ------------------------------------------------------------------ encode (edit.py:594-597)
     def _encoder(self) -> LocoEngine:
@@ -384,6 +422,7 @@ class EditStableDiffusion(EditDeepFloydIF):
     def run_edit_null_space_projection_zt(self, op, block_idx, vis_num, mask_index=0, vis_num_pc=1, vis_vT=False, pca_rank=50,
                                           edit_prompt=None, null_space_projection=False, pca_rank_null=50, non_semantic=False):
         """edit.py:918-1041: unsupervised directions of the decoded x0_hat, null-space projected, +/- walk, decode."""
+        self._set_edit_prompt(edit_prompt)
         prep = self._prepare(mask_index)
         if prep is None:
             return None
@@ -413,6 +452,7 @@ class EditStableDiffusion(EditDeepFloydIF):
                                                    pca_rank_null=50):
         """edit.py:1045-1174: the text-supervised direction through the Jacobian of the decoded image, projected onto the
         null space of the complement-mask Jacobian; ``use_sega`` decodes with the three-branch guidance instead."""
+        self._set_edit_prompt(edit_prompt)
         prep = self._prepare(mask_index)
         if prep is None:
             return None
