@@ -23,14 +23,24 @@ import torch
 import torch.nn.functional as F
 
 
+def _up(x: torch.Tensor) -> torch.Tensor:
+    """At least fp32: the reference's ``.float()`` upcasts, which leave a float64 tensor float64 (tests run the oracle in
+    float64 as the truth that bounds the fp32 arithmetic's own error)."""
+    return x if x.dtype == torch.float64 else x.float()
+
+
+def _up_dtype(w: torch.Tensor) -> torch.dtype:
+    return torch.float64 if w.dtype == torch.float64 else torch.float32
+
+
 # --------------------------------------------------------------------------
 # Denoiser A: Ho-DDPM U-Net (reference src/models/ddpm/diffusion.py)
 # --------------------------------------------------------------------------
-def timestep_embedding(t: torch.Tensor, dim: int) -> torch.Tensor:
+def timestep_embedding(t: torch.Tensor, dim: int, dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """[sin, cos] sinusoid with divisor (half-1) -- diffusion.py:783-804."""
     half = dim // 2
-    freq = torch.exp(torch.arange(half, dtype=torch.float32) * -(math.log(10000) / (half - 1)))
-    arg = t.float()[:, None] * freq[None, :]
+    freq = torch.exp(torch.arange(half, dtype=dtype) * -(math.log(10000) / (half - 1)))
+    arg = t.to(dtype)[:, None] * freq[None, :]
     emb = torch.cat([torch.sin(arg), torch.cos(arg)], dim=1)
     if dim % 2 == 1:
         emb = F.pad(emb, (0, 1, 0, 0))
@@ -85,7 +95,8 @@ def unet_forward(p: Dict[str, torch.Tensor], cfg, x: torch.Tensor, t: torch.Tens
             trace[name] = v.detach().clone()
         return v
     t = t.reshape(1) if t.dim() == 0 else t
-    temb = timestep_embedding(t.to(torch.float32), cfg.ch)
+    dt = _up_dtype(p["temb.dense.0.weight"])
+    temb = timestep_embedding(t.to(dt), cfg.ch, dt)
     temb = F.linear(temb, p["temb.dense.0.weight"], p["temb.dense.0.bias"])
     temb = _swish(temb)
     temb = F.linear(temb, p["temb.dense.1.weight"], p["temb.dense.1.bias"])
@@ -191,19 +202,19 @@ def encoder_forward(p: Dict[str, torch.Tensor], cfg, x: torch.Tensor) -> torch.T
 # --------------------------------------------------------------------------
 # Denoiser B: guided-diffusion / P2 U-Net (reference src/models/guided_diffusion/unet.py, P2_DICT)
 # --------------------------------------------------------------------------
-def timestep_embedding_adm(t: torch.Tensor, dim: int) -> torch.Tensor:
+def timestep_embedding_adm(t: torch.Tensor, dim: int, dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """[cos, sin] sinusoid with divisor half -- guided_diffusion/nn.py:103-121."""
     half = dim // 2
-    freqs = torch.exp(-math.log(10000) * torch.arange(start=0, end=half, dtype=torch.float32) / half)
-    args = t[:, None].float() * freqs[None]
+    freqs = torch.exp(-math.log(10000) * torch.arange(start=0, end=half, dtype=dtype) / half)
+    args = t[:, None].to(dtype) * freqs[None]
     emb = torch.cat([torch.cos(args), torch.sin(args)], dim=-1)
     if dim % 2:
         emb = torch.cat([emb, torch.zeros_like(emb[:, :1])], dim=-1)
     return emb
 
 
-def _adm_gn(p, name, x, cfg):  # GroupNorm32(32, C), eps 1e-5, computed in fp32 -- nn.py:17-19
-    return F.group_norm(x.float(), cfg.gn_groups, p[name + ".weight"], p[name + ".bias"], cfg.gn_eps).type(x.dtype)
+def _adm_gn(p, name, x, cfg):  # GroupNorm32(32, C), eps 1e-5, computed in (at least) fp32 -- nn.py:17-19
+    return F.group_norm(_up(x), cfg.gn_groups, p[name + ".weight"], p[name + ".bias"], cfg.gn_eps).type(x.dtype)
 
 
 def _act(cfg):
@@ -248,7 +259,7 @@ def _adm_attn(p, name, x, cfg):
     q, k, v = qkv.reshape(b * n_heads, ch * 3, hh * ww).split(ch, dim=1)
     scale = 1 / math.sqrt(math.sqrt(ch))
     w = torch.einsum("bct,bcs->bts", q * scale, k * scale)
-    w = torch.softmax(w.float(), dim=-1).type(w.dtype)
+    w = torch.softmax(_up(w), dim=-1).type(w.dtype)
     a = torch.einsum("bts,bcs->bct", w, v).reshape(b, -1, hh * ww)
     h = F.conv1d(a, p[name + ".proj_out.weight"], p[name + ".proj_out.bias"])
     return (xr + h).reshape(b, c, hh, ww)
@@ -267,13 +278,13 @@ def _if_attn(p, name, x, context, cfg):
     ch = c // nh
     q, k, v = qkv.reshape(b * nh, ch * 3, hh * ww).split(ch, dim=1)
     e = context.transpose(1, 2)                                                         # [B, D, L]
-    e = F.group_norm(e.float(), cfg.gn_groups, p[name + ".norm_encoder.weight"], p[name + ".norm_encoder.bias"], cfg.gn_eps)
+    e = F.group_norm(_up(e), cfg.gn_groups, p[name + ".norm_encoder.weight"], p[name + ".norm_encoder.bias"], cfg.gn_eps)
     e = F.conv1d(e, p[name + ".encoder_kv.weight"], p[name + ".encoder_kv.bias"])         # [B, 2C, L]
     ek, ev = e.reshape(b * nh, ch * 2, -1).split(ch, dim=1)
     k = torch.cat([ek, k], dim=-1)
     v = torch.cat([ev, v], dim=-1)
     scale = 1 / math.sqrt(math.sqrt(ch))
-    w = torch.softmax(torch.einsum("bct,bcs->bts", q * scale, k * scale).float(), dim=-1)
+    w = torch.softmax(_up(torch.einsum("bct,bcs->bts", q * scale, k * scale)), dim=-1)
     a = torch.einsum("bts,bcs->bct", w, v).reshape(b, -1, hh * ww)
     h = F.conv1d(a, p[name + ".proj_out.weight"], p[name + ".proj_out.bias"])
     return (xr + h).reshape(b, c, hh, ww)
@@ -285,7 +296,7 @@ def if_text_conditioning(p, cfg, states):
     context = Linear(states) [B, L, D] for the attention blocks, aug = LayerNorm(Linear(AttentionPooling(LayerNorm(states))))
     [B, 4 ch] added to the time embedding.  AttentionPooling: a class token mean(states) + positional_embedding queries
     [token ; states] with `num_heads = E / 64` heads (IF: 64 heads of 64)."""
-    states = states.float()
+    states = _up(states)
     ctx = F.linear(states, p["encoder_proj.weight"], p["encoder_proj.bias"])
     E = states.shape[-1]
     x = F.layer_norm(states, (E,), p["encoder_pooling.0.weight"], p["encoder_pooling.0.bias"], 1e-5)
@@ -301,7 +312,7 @@ def if_text_conditioning(p, cfg, states):
     k = shape(F.linear(xs, p["encoder_pooling.1.k_proj.weight"], p["encoder_pooling.1.k_proj.bias"]))
     v = shape(F.linear(xs, p["encoder_pooling.1.v_proj.weight"], p["encoder_pooling.1.v_proj.bias"]))
     sc = 1 / math.sqrt(math.sqrt(dph))
-    w = torch.softmax(torch.einsum("bct,bcs->bts", q * sc, k * sc).float(), dim=-1)
+    w = torch.softmax(_up(torch.einsum("bct,bcs->bts", q * sc, k * sc)), dim=-1)
     a = torch.einsum("bts,bcs->bct", w, v).reshape(b, -1, 1).transpose(1, 2)[:, 0, :]     # [B, E]
     a = F.linear(a, p["encoder_pooling.2.weight"], p["encoder_pooling.2.bias"])
     aug = F.layer_norm(a, (a.shape[-1],), p["encoder_pooling.3.weight"], p["encoder_pooling.3.bias"], 1e-5)
@@ -387,7 +398,8 @@ def unet_forward_adm(p, cfg, x, t, trace: Optional[dict] = None, emb_add: Option
             h = _adm_xattn(p, name + ".xattn", h, ctx.expand(h.shape[0], -1, -1), cfg)
         return h
     t = t.reshape(1) if t.dim() == 0 else t
-    emb = timestep_embedding_adm(t.to(torch.float32), cfg.ch)
+    dt = _up_dtype(p["time_embed.0.weight"])
+    emb = timestep_embedding_adm(t.to(dt), cfg.ch, dt)
     emb = F.linear(emb, p["time_embed.0.weight"], p["time_embed.0.bias"])
     emb = F.linear(_act(cfg)(emb), p["time_embed.2.weight"], p["time_embed.2.bias"])
     if emb_add is not None:
