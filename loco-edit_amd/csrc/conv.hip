@@ -18,7 +18,6 @@
 // pixels / couts per half wave).  The next chunk's global loads are issued
 // before the MFMA block of the current one (register prefetch).
 #include "kernels.h"
-#include <cstdio>
 
 namespace loco {
 
@@ -288,40 +287,6 @@ __global__ void conv_splitk_reduce(ConvArgs a, long total) {
 }
 
 // ---------------------------------------------------------------------------
-struct TileCfg { int MT, NT; };
-
-static inline int pick_tile(int Cout, int HW) {
-    // 0: 128x128, 1: 128x64, 2: 32x128, 3: 64x64
-    if (HW >= 128) {
-        if (Cout > 64) return 0;
-        if (Cout > 32) return (HW >= 128) ? 0 : 3;
-        return 2;
-    }
-    // HW == 64
-    if (Cout > 64) return 1;
-    return 3;
-}
-int conv_pick_tile(int Cout, int HW) { return pick_tile(Cout, HW); }
-static const TileCfg kTiles[4] = {{128, 128}, {128, 64}, {32, 128}, {64, 64}};
-
-int conv_pick_nsplit(int Cin, int Cout, int Hout, int Wout, int B, int taps) {
-    int t = pick_tile(Cout, Hout * Wout);
-    long blocks = (long)((Hout * Wout) / kTiles[t].NT) * ((Cout + kTiles[t].MT - 1) / kTiles[t].MT) * B;
-    int nchunks = (Cin + BK - 1) / BK;
-    if (blocks >= 384 || nchunks < 8) return 1;
-    int want = (int)((512 + blocks - 1) / blocks);
-    int maxs = nchunks / 4;            // at least 4 chunks (32 channels) per split
-    if (want > maxs) want = maxs;
-    if (want > 32) want = 32;
-    if (want < 1) want = 1;
-    return want;
-}
-
-size_t conv_partial_floats(const ConvArgs& a) {
-    if (a.nsplit <= 1) return 0;
-    return (size_t)a.nsplit * a.B * a.Cout * a.Hout * a.Wout;
-}
-
 template <int TAPS, int WM, int WN, int TM, int TN, int MODE>
 static void launch_one(const ConvArgs& a, hipStream_t st) {
     constexpr int MT = WM * TM * 32, NT = WN * TN * 32;
@@ -336,68 +301,12 @@ static void launch_one(const ConvArgs& a, hipStream_t st) {
 
 template <int TAPS, int MODE>
 static void launch_tile(const ConvArgs& a, hipStream_t st) {
-    switch (pick_tile(a.Cout, a.Hout * a.Wout)) {
+    switch (a.tile) {      // conv_plan.hip: 0: 128x128, 1: 128x64, 2: 32x128, 3: 64x64
         case 0: launch_one<TAPS, 2, 2, 2, 2, MODE>(a, st); break;
         case 1: launch_one<TAPS, 4, 1, 1, 2, MODE>(a, st); break;
         case 2: launch_one<TAPS, 1, 4, 1, 1, MODE>(a, st); break;
         default: launch_one<TAPS, 2, 2, 1, 1, MODE>(a, st); break;
     }
-}
-
-int conv_bf16_pick_tile(int Cout, int HW, int Bsplit);   // conv_bf16.hip
-int bf16_tile_of(const ConvArgs& a);                       // conv_bf16.hip
-static inline int bf16_tile_of_(const ConvArgs& a) { return bf16_tile_of(a); }
-
-const char* conv_variant_name(const ConvArgs& a, int taps, int prec) {
-    static const char* tiles[6] = {"2,2,2,2", "4,1,1,2", "1,4,1,1", "2,2,1,1", "2,2,2,4", "2,4,2,2"};
-    static char names[3][2][6][6][56];
-    int t = prec ? conv_bf16_pick_tile(a.Cout, a.Hout * a.Wout, a.B) : pick_tile(a.Cout, a.Hout * a.Wout);
-    if (prec) { ConvArgs q = a; q.taps = taps; if (bf16_tile_of_(q) == 6) t = 0; }     // the two-per-CU variant is a 128 x 128 tile too
-    if (prec && t == 4) t = 5;
-    if (prec && a.stride == 2 && t == 5) t = 0;
-    if (t < 0 || t > 5) t = 0;
-    if (prec && taps == 9 && a.Cin2 > 0) {
-        static char kn2[3][6][40];
-        const int mm = (a.mode < 0 || a.mode > 5) ? 2 : a.mode;
-        if (!kn2[prec][mm][0]) snprintf(kn2[prec][mm], 40, "%s<2,4,2,2,%d>", prec == 1 ? "conv_kcat_bf16x3" : "conv_kcat_f16", mm);
-        return kn2[prec][mm];
-    }
-    if (prec == 1 && taps == 1 && a.gemm) {
-        static char gn[2][40];
-        char* n = gn[a.gemm_tm == 4];
-        if (!n[0]) snprintf(n, 40, "conv_gemm_bf16x3<%d>", a.gemm_tm);
-        return n;
-    }
-    if (prec == 1 && taps == 9 && a.pers_groups > 0 && !a.dual) {
-        static char pn[6][40];
-        const int mm = (a.mode < 0 || a.mode > 5) ? 2 : a.mode;
-        if (!pn[mm][0]) snprintf(pn[mm], 40, "conv_pers_bf16x3<9,2,4,2,2,%d>", mm);
-        return pn[mm];
-    }
-    {
-        ConvArgs q = a; q.taps = taps;
-        if (prec == 1 && taps == 9 && conv_pair_ok(q)) {      // the 16x16x32 tap-pair kernel (conv_pair_kernel.h)
-            static char pn[5][40];
-            const int mm = (a.mode < 0 || a.mode > 4) ? 0 : a.mode;
-            if (!pn[mm][0]) snprintf(pn[mm], 40, "conv_pair_bf16x3<%d>", mm);
-            return pn[mm];
-        }
-    }
-    if (prec == 1 && taps == 9 && a.dual) {
-        static char dn[5][40];
-        const int mm = (a.mode < 0 || a.mode > 4) ? 2 : a.mode;
-        if (!dn[mm][0]) snprintf(dn[mm], 40, "conv_dual_bf16x3<%d>", mm);
-        return dn[mm];
-    }
-    int ti = taps == 9 ? 0 : 1;
-    int m = a.mode;
-    if (taps != 9 && m != CM_NONE) m = CM_GN;
-    if (!prec && m == CM_GN_GELU) m = CM_GN_SILU;      // the exact-fp32 kernel takes the activation at run time
-    if (m < 0 || m > 5) m = 2;
-    char* n = names[prec][ti][t][m];
-    static const char* kn[3] = {"conv_mfma_f32", "conv_mfma_bf16x3", "conv_mfma_f16"};
-    if (!n[0]) snprintf(n, 56, "%s<%d,%s,%d>", kn[prec], taps, tiles[t], m);
-    return n;
 }
 
 void launch_conv(const ConvArgs& a, int taps, hipStream_t st) {

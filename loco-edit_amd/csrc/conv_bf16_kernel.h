@@ -1646,12 +1646,9 @@ void launch_kcat_b(const ConvArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(kern, grid, dim3(WM * WN * 64), lds, st, a);
 }
 
-int bf16_tile_of(const ConvArgs& a);     // conv_bf16.hip
-
 template <int PR, int TAPS, int MODE>
 void launch_tile_b(const ConvArgs& a, hipStream_t st) {
-    const int tile = bf16_tile_of(a);
-    switch (tile) {
+    switch (a.tile) {      // planned by conv_plan.hip
         case 5:                                                           // 128 x 256, 8 compute waves (64 x 64 each)
             launch_one_b<PR, TAPS, 2, 4, 2, 2, MODE>(a, st);
             break;

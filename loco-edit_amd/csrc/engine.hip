@@ -1315,190 +1315,85 @@ void stats_standalone(loco_ctx* c, const StatReq& rq, const float* x, long xbs, 
     }
 }
 
-// run a conv with automatic split-K selection
+// run a conv as plan_conv (conv_plan.hip) decides: split-K, kernel, tail-probe split, statistics route.
 // `second`: a prepared 1x1 operator on the same output tensor (the ResBlock shortcut, `second->out == a.out`) that `a` then
-// reads as its residual.  Where the launch allows it is K-concatenated into `a`'s kernel (conv_lowp_kcat: one write-out, no
-// read-modify-write of the block output, one launch less); otherwise it runs first and `a` takes its result as residual.
-void run_conv(loco_ctx* c, ConvArgs& a, int taps, hipStream_t st, const StatReq* rq = nullptr, ConvArgs* second = nullptr) {
+// reads as its residual: K-concatenated into `a`'s kernel where the launch allows it, else run first.  Returns whether the
+// norm-cotangent term asked for in a.cot_d rides in the epilogue (false: the caller applies it).
+bool run_conv(loco_ctx* c, const ConvArgs& a0, int taps, hipStream_t st, const StatReq* rq = nullptr,
+              const ConvArgs* second = nullptr) {
+    const size_t span = (size_t)c->cfg.max_batch * c->per_sample;
+    auto padded = [&](const float* p) { return (p >= c->arenaP && p < c->arenaP + span) || (p >= c->arenaT && p < c->arenaT + span); };
+    ConvArgs a = a0, sc;
     a.act = c->cfg.act;
     if (a.mode == CM_GN_SILU && c->cfg.act == ACT_GELU) a.mode = CM_GN_GELU;     // the forward prologue of a GELU network
-    if (second) {
-        const size_t span = (size_t)c->cfg.max_batch * c->per_sample;
-        ConvArgs t = a;
-        t.taps = taps;
-        t.nsplit = c->prec >= 1 ? conv_bf16_pick_nsplit(a.Cin, a.Cout, a.Hout, a.Wout, a.B, c->chip_share, 9, c->lanes_active) : 2;
-        t.in_padded = (a.in >= c->arenaP && a.in < c->arenaP + span) || (a.in >= c->arenaT && a.in < c->arenaT + span);
-        t.in2 = second->in; t.in2_bs = second->in_bs; t.Cin2 = second->Cin;
-        const long per_probe = (long)((a.Hout * a.Wout) / 256) * ((a.Cout + 127) / 128), total = per_probe * a.B;
-        const bool whole_rounds = total <= 256 || total % 256 == 0 || total % 256 > 160;      // no tail-probe split (below)
-        if (c->prec >= 1 && taps == 9 && whole_rounds && !a.bias2 && conv_lowp_can_kcat(t)) {
-            a.in2 = second->in; a.in2_bs = second->in_bs; a.Cin2 = second->Cin;
-            a.in2_padded = (second->in >= c->arenaP && second->in < c->arenaP + span) ||
-                           (second->in >= c->arenaT && second->in < c->arenaT + span);
-            a.wb2 = c->prec == 2 ? second->wh : second->wb;
-            a.bias2 = second->bias; a.bias2_bs = 0;          // the shortcut's bias (the forward pass; tangents carry none)
-            a.res = nullptr;
-        } else {
-            run_conv(c, *second, 1, st);
-            a.res = second->out; a.res_bs = second->out_bs;
-        }
+    a.in_padded = padded(a.in);
+    if (second) { sc = *second; sc.in_padded = padded(sc.in); }
+    ConvEnv e;
+    e.prec = c->prec; e.chip_share = c->chip_share; e.lanes = c->lanes_active; e.lane_s0 = c->lane_s0;
+    e.partial = c->partial; e.partial_floats = c->partial_floats; e.stpart = c->stpart; e.stpart_floats = c->stpart_floats;
+    e.fuse_stats = c->fuse_stats; e.fuse_lin = c->fuse_lin; e.deep1 = c->deep1; e.max_batch = c->cfg.max_batch;
+    StatAsk q;
+    if (rq) {
+        q.kind = rq->kind; q.norm = rq->n != nullptr; q.prim = rq->prim; q.keep = rq->keep; q.keep_floats = rq->keep_floats;
+        if (rq->n && rq->n->sx_off >= 0 && c->sxcache) q.sx = c->sxcache + rq->n->sx_off;
     }
-    if (c->prec == 2) a.wb = a.wh;
-    a.taps = taps;
-    a.no_deep = c->deep1 ? 0 : 1;
-    a.nsplit = c->prec >= 1 ? conv_bf16_pick_nsplit(a.Cin, a.Cout, a.Hout, a.Wout, a.B, c->chip_share, taps, c->lanes_active)
-                            : conv_pick_nsplit(a.Cin, a.Cout, a.Hout, a.Wout, a.B, taps);
-    while (a.nsplit > 1 && (size_t)a.nsplit * a.B * a.Cout * a.Hout * a.Wout > c->partial_floats) a.nsplit >>= 1;
-    if (a.nsplit < 1) a.nsplit = 1;
-    a.partial = c->partial;
-    a.partial_floats = c->partial_floats;
-    a.gemm = 0;
-    // compute-shaped 1x1 operators (the transformer's linear layers): the DMA-fed GEMM with its own split-K choice
-    if (c->prec == 1 && taps == 1) conv_gemm_plan(a);
-    {
-        const size_t span = (size_t)c->cfg.max_batch * c->per_sample;
-        a.in_padded = (a.in >= c->arenaP && a.in < c->arenaP + span) || (a.in >= c->arenaT && a.in < c->arenaT + span);
-    }
-    // 3x3 launches with several probes per (pixel tile, cout tile) workgroup slot: one workgroup walks them (conv_pers_plan)
-    a.pers_groups = 0;
-    if (c->prec == 1 && taps == 9) conv_pers_plan(a);
-    // Tail-probe split (bf16x3): when the workgroups of the launch fill whole rounds of the 256 CUs plus a short
-    // tail made of the last probes (5 probes x 64 tiles = 320 = 256 + 64), those probes are launched separately
-    // with split-K so the tail round is as wide as the chip: 1 + 1/s rounds + a one-sample reduce instead of 2
-    // (measured 331.0 vs 334.1 ms per step).
-    int tail_probes = 0, tail_split = 1;
-    if (c->prec >= 1 && a.nsplit == 1 && a.B >= 2 && !a.gemm && !a.pers_groups) {
-        const long per_probe = (long)((a.Hout * a.Wout) / conv_bf16_tile_pixels(a)) * ((a.Cout + 127) / 128);
-        const long total = per_probe * a.B, r = total % 256;
-        const int nchunks = (a.Cin + 15) / 16;
-        if (total > 256 && r > 0 && r <= 160 && per_probe > 0 && r % per_probe == 0 && r / per_probe < a.B) {
-            int s = (int)(256 / r);
-            if (s > 4) s = 4;
-            while (s > 1 && nchunks / s < 4) --s;
-            const size_t one = (size_t)(r / per_probe) * a.Cout * a.Hout * a.Wout;
-            while (s > 1 && (size_t)s * one > c->partial_floats) --s;
-            if (s > 1) { tail_probes = (int)(r / per_probe); tail_split = s; }
-        }
-    }
-    // one conv kernel (+ its split-K reduce), each timed as its own profile record so the per-kernel averages agree
-    // with rocprofv3's
-    const bool want = rq && rq->kind != ST_NONE && c->prec >= 1 && c->fuse_stats;
+    const ConvPlan p = plan_conv(e, a, taps, rq ? &q : nullptr, second ? &sc : nullptr);
+    if (p.sc_first) run_conv(c, *second, 1, st);
+    if (rq && rq->kind != ST_NONE && rq->n) rq->n->ready = true;
+    if (rq && rq->keep_ntile) *rq->keep_ntile = p.keep_ntile;
     const int HWo = a.Hout * a.Wout, Gn = c->cfg.gn_groups;
     const long SBs = c->stats_per_sample;
-    // statistics of samples [s0, s0 + x.B) of the launch `x`, by the cheapest route that applies
-    auto stats_of = [&](ConvArgs& x, int s0) -> int {      // 0: none asked; 1: in the conv epilogue; 2: in the split-K epilogue; 3: standalone; 4: partials only
-        if (!rq || rq->kind == ST_NONE) return 0;
-        if (rq->keep_ntile) *rq->keep_ntile = 0;
-        if (!want) return rq->n ? 3 : 0;
-        if (x.nsplit > 1) return !rq->n ? 0 : ((HWo % 4 == 0) ? 2 : 3);
-        const int ntile = HWo / conv_bf16_tile_pixels(x);
-        const size_t need = (size_t)x.B * x.Cout * ntile * 2;
-        const bool kept = rq->keep && s0 == 0 && x.B == a.B && need <= rq->keep_floats;      // the whole batch in one launch
-        if (rq->kind == ST_FWD && conv_lowp_can_fuse_stats(x) && (kept || (rq->n && need <= c->stpart_floats))) {
-            x.st_part = kept ? rq->keep : c->stpart; x.st_kind = ST_FWD;
-            if (kept) *rq->keep_ntile = ntile;
-            return rq->n ? 1 : 4;
+    // each kernel (+ its split-K reduce) timed as its own profile record, so the per-kernel averages agree with rocprofv3's
+    auto timed = [&](const char* name, double flops, const ConvArgs& y, auto&& launch) {
+        loco_ctx::ProfRec r;
+        if (c->prof_on) {
+            r.name = name; r.flops = flops;
+            r.cin = y.Cin; r.cout = y.Cout; r.h = y.Hout; r.b = y.B; r.ns = y.nsplit; r.mode = y.mode; r.taps = taps;
+            r.e0 = c->next_event(); r.e1 = c->next_event();
+            (void)hipEventRecord(r.e0, st);
         }
-        // Tangent / cotangent group means in the conv epilogue (round 6, LOCO_FUSE_LIN=0: off): whole cout tiles, no split-K, not the
-        // opt-in persistent / dual-probe kernels (their epilogues take the forward statistics only).  A tangent launch that finishes
-        // one part of a concatenation keeps its (norm-independent) raw sums in the part's buffer, at this lane's samples.
-        const bool cot_cache = rq->kind == ST_COT && rq->n && rq->n->sx_off >= 0 && c->sxcache;      // (its {S, xhat} records exist)
-        // (not next to a norm-cotangent term: the epilogue holds one of the two in its record registers, ConvArgs::cot_d)
-        if ((rq->kind == ST_TAN || cot_cache) && c->fuse_lin && !x.cot_d && conv_lowp_can_fuse_stats(x) && !x.pers_groups && !conv_dual_ok(x)) {
-            const size_t lane_off = (size_t)c->lane_s0 * x.Cout * ntile * 2;
-            const bool keptl = rq->kind == ST_TAN && rq->keep && s0 == 0 && x.B == a.B && lane_off + need <= rq->keep_floats;
-            if (keptl || (rq->n && need <= c->stpart_floats)) {
-                x.st_part = keptl ? rq->keep + lane_off : c->stpart; x.st_kind = rq->kind; x.st_x = rq->prim;
-                if (rq->kind == ST_COT) x.st_sx = c->sxcache + rq->n->sx_off;
-                if (keptl) *rq->keep_ntile = ntile;
-                return rq->n ? 1 : 4;
-            }
-        }
-        return rq->n ? 3 : 0;
+        launch();
+        if (c->prof_on) { (void)hipEventRecord(r.e1, st); c->prof.push_back(r); }
     };
-    auto stats_after = [&](const ConvArgs& x, int s0, int how) {
-        if (how == 0 || how == 2 || how == 4) return;
-        const NormP& n = *rq->n;
-        if (how == 3) { stats_standalone(c, *rq, x.out, x.out_bs, x.B, HWo, s0, st); return; }
-        NS so = nstats(c, rq->stats + (long)s0 * SBs, n);
-        if (rq->kind != ST_FWD) {
-            NS sp = nstats(c, c->statsP, n);
-            launch_gn_lin_fused_finalize(rq->kind, x.st_part, n.C, HWo / conv_bf16_tile_pixels(x), nullptr, 0, x.B, n.C, HWo, Gn,
-                                         sp.mr, so.tst, so.tc, SBs, st);
-            return;
-        }
-        launch_gn_fused_finalize(x.st_part, HWo / conv_bf16_tile_pixels(x), x.B, n.C, HWo, Gn, eps_of(c, n), n.gamma, n.beta,
-                                 so.mr, so.sc, so.sh, SBs, rq->ss_scale, rq->ss_shift, st);
-    };
-    auto reduce_with_stats = [&](const ConvArgs& x, int s0) {
-        const NormP& n = *rq->n;
-        NS sp = nstats(c, c->statsP, n);
-        NS so = nstats(c, rq->stats + (long)s0 * SBs, n);
-        launch_conv_splitk_reduce_stats(x, rq->kind, Gn, eps_of(c, n), n.gamma, n.beta, so.mr, so.sc, so.sh, SBs, rq->ss_scale,
-                                        rq->ss_shift, rq->prim, sp.sc, sp.sh, sp.mr, so.tst, so.tc, SBs, c->red, st);
-    };
-    auto one = [&](ConvArgs& x, int s0) {
-        const int how = stats_of(x, s0);
-        // the launch as the low-precision dispatcher runs it: its even part on the dual-probe tile + an odd last probe on the
-        // 128 x 256 tile (conv_lowp_plan), each kernel with its own profile record
-        ConvArgs parts[2];
-        const int nparts = conv_lowp_plan(x, taps, c->prec, parts);
-        for (int pi = 0; pi < nparts; ++pi) {
-            ConvArgs& y = parts[pi];
-            loco_ctx::ProfRec r;
-            if (c->prof_on) {
-                r.name = conv_variant_name(y, taps, c->prec);
-                r.flops = 2.0 * (y.Cin * taps + y.Cin2) * y.Cout * (double)y.Hout * y.Wout * y.B;
-                if (y.zins) r.flops *= 0.25;     // algorithmic work of the stride-2 data gradient
-                r.cin = y.Cin; r.cout = y.Cout; r.h = y.Hout; r.b = y.B; r.ns = y.nsplit; r.mode = y.mode; r.taps = taps;
-                r.e0 = c->next_event(); r.e1 = c->next_event();
-                (void)hipEventRecord(r.e0, st);
-            }
-            if (c->prec == 1) launch_conv_bf16x3(y, taps, st);
-            else if (c->prec == 2) launch_conv_f16(y, taps, st);
-            else launch_conv(y, taps, st);
-            if (c->prof_on) { (void)hipEventRecord(r.e1, st); c->prof.push_back(r); }
+    for (int li = 0; li < p.nl; ++li) {
+        const ConvLaunch& l = p.l[li];
+        const ConvArgs& x = l.args;
+        for (int pi = 0; pi < l.nparts; ++pi) {
+            const ConvArgs& y = l.parts[pi];
+            double flops = 2.0 * (y.Cin * taps + y.Cin2) * y.Cout * (double)y.Hout * y.Wout * y.B;
+            if (y.zins) flops *= 0.25;     // algorithmic work of the stride-2 data gradient
+            timed(c->prof_on ? conv_variant_name(y, taps, c->prec) : nullptr, flops, y, [&] {
+                if (c->prec == 1) launch_conv_bf16x3(y, taps, st);
+                else if (c->prec == 2) launch_conv_f16(y, taps, st);
+                else launch_conv(y, taps, st);
+            });
         }
         if (x.nsplit > 1) {
-            loco_ctx::ProfRec rr;
-            if (c->prof_on) {
-                rr.name = "conv_splitk_reduce"; rr.flops = 0.0;
-                rr.cin = x.Cin; rr.cout = x.Cout; rr.h = x.Hout; rr.b = x.B; rr.ns = x.nsplit; rr.mode = x.mode; rr.taps = taps;
-                rr.e0 = c->next_event(); rr.e1 = c->next_event();
-                (void)hipEventRecord(rr.e0, st);
-            }
-            if (how == 2) reduce_with_stats(x, s0); else launch_conv_splitk_reduce(x, st);
-            if (c->prof_on) { (void)hipEventRecord(rr.e1, st); c->prof.push_back(rr); }
+            timed("conv_splitk_reduce", 0.0, x, [&] {
+                if (l.stats != SR_SPLITK) { launch_conv_splitk_reduce(x, st); return; }
+                const NormP& n = *rq->n;
+                NS sp = nstats(c, c->statsP, n);
+                NS so = nstats(c, rq->stats + (long)l.s0 * SBs, n);
+                launch_conv_splitk_reduce_stats(x, rq->kind, Gn, eps_of(c, n), n.gamma, n.beta, so.mr, so.sc, so.sh, SBs, rq->ss_scale,
+                                                rq->ss_shift, rq->prim, sp.sc, sp.sh, sp.mr, so.tst, so.tc, SBs, c->red, st);
+            });
         }
-        stats_after(x, s0, how);
-    };
-    if (rq && rq->kind != ST_NONE && rq->n) rq->n->ready = true;
-    if (!tail_probes) { one(a, 0); return; }
-    // tail-probe split: two launches finish the tensor.  Tangent / cotangent statistics are taken once over the whole batch
-    // behind them (separate statistics for the few tail probes would add a reduce-with-statistics and a finalize launch per
-    // conv: LOCO_FUSE_LIN=0).  FORWARD statistics are per sample and come for free with both launches: the main launch's epilogue
-    // partials (+ one merge launch for its samples), the tail's split-K epilogue -- no pass over the finished tensor.
-    // (round 6: the tangent / cotangent means likewise -- they are per probe too: the main launch's epilogue partials + one merge
-    // launch, the tail's split-K epilogue)
-    const bool per_part = want && rq && rq->n && (rq->kind == ST_FWD || (c->fuse_lin && HWo % 4 == 0));
-    const StatReq* rq_all = (!per_part && rq && rq->kind != ST_NONE && rq->n) ? rq : nullptr;
-    if (rq && rq->keep_ntile) *rq->keep_ntile = 0;
-    if (!per_part) rq = nullptr;
-    ConvArgs m = a, t = a;
-    const int nb = a.B - tail_probes;
-    m.B = nb;
-    t.B = tail_probes; t.nsplit = tail_split;
-    t.in += (long)nb * a.in_bs; t.out += (long)nb * a.out_bs;
-    if (t.prim) t.prim += (long)nb * a.prim_bs;
-    if (t.bias2) t.bias2 += (long)nb * a.bias2_bs;
-    if (t.res) t.res += (long)nb * a.res_bs;
-    if (t.sc) { t.sc += (long)nb * a.scsh_bs; t.sh += (long)nb * a.scsh_bs; }
-    if (t.mr) t.mr += (long)nb * a.mr_bs;
-    if (t.tst) t.tst += (long)nb * a.tst_bs;
-    if (t.tc) t.tc += (long)nb * a.tc_bs;
-    one(m, 0);
-    one(t, nb);
-    if (rq_all) stats_standalone(c, *rq_all, a.out, a.out_bs, a.B, HWo, 0, st);
+        if (l.stats == SR_ALONE) stats_standalone(c, *rq, x.out, x.out_bs, x.B, HWo, l.s0, st);
+        if (l.stats == SR_EPI) {
+            const NormP& n = *rq->n;
+            NS so = nstats(c, rq->stats + (long)l.s0 * SBs, n);
+            if (rq->kind != ST_FWD) {
+                NS sp = nstats(c, c->statsP, n);
+                launch_gn_lin_fused_finalize(rq->kind, x.st_part, n.C, l.ntile, nullptr, 0, x.B, n.C, HWo, Gn, sp.mr, so.tst, so.tc,
+                                             SBs, st);
+            } else {
+                launch_gn_fused_finalize(x.st_part, l.ntile, x.B, n.C, HWo, Gn, eps_of(c, n), n.gamma, n.beta, so.mr, so.sc, so.sh,
+                                         SBs, rq->ss_scale, rq->ss_shift, st);
+            }
+        }
+    }
+    if (p.stats_all) stats_standalone(c, *rq, a.out, a.out_bs, a.B, HWo, 0, st);
+    return p.cot;
 }
 
 inline void setw(ConvArgs& a, const ConvP& p, bool dgrad) {
@@ -1541,9 +1436,7 @@ StatReq req_fwd_of(loco_ctx* c, int tid, float* stats) {
 // norm over a concatenation whose two parts both kept their producers' tile partials in this pass: finalise from those
 bool cat_fused_stats(loco_ctx* c, const NormP& n, int tid, float* stats, int B, hipStream_t st) {
     const Tens& q = c->tens[tid];
-    static int on = -1;                      // LOCO_FUSE_CAT=0: A/B switch (the parts' partials are still taken, not used)
-    if (on < 0) { const char* e = getenv("LOCO_FUSE_CAT"); on = e ? (atoi(e) != 0) : 1; }
-    if (q.cat_a < 0 || c->prec < 1 || !c->fuse_stats || !on) return false;
+    if (q.cat_a < 0 || c->prec < 1 || !c->fuse_stats) return false;
     const Tens& A = c->tens[q.cat_a];
     const Tens& Bt = c->tens[q.cat_b];
     if (A.keep_ntile <= 0 || Bt.keep_ntile <= 0) return false;
@@ -1563,8 +1456,9 @@ bool cat_fused_tstats(loco_ctx* c, const NormP& n, int tid, int B, hipStream_t s
     if (A.keep_ntile <= 0 || Bt.keep_ntile <= 0) return false;
     NS sp = nstats(c, c->statsP, n);
     NS stt = nstats(c, c->statsT, n);
-    launch_gn_lin_fused_finalize(ST_TAN, A.keep + (size_t)c->lane_s0 * A.C * A.keep_ntile * 2, A.C, A.keep_ntile,
-                                 Bt.keep + (size_t)c->lane_s0 * Bt.C * Bt.keep_ntile * 2, Bt.keep_ntile, B, q.C, q.H * q.W,
+    const size_t MB = c->cfg.max_batch;      // this lane's rows (conv_plan.hip stats_route: keep_floats / max_batch apart)
+    launch_gn_lin_fused_finalize(ST_TAN, A.keep + c->lane_s0 * (A.keep_floats / MB), A.C, A.keep_ntile,
+                                 Bt.keep + c->lane_s0 * (Bt.keep_floats / MB), Bt.keep_ntile, B, q.C, q.H * q.W,
                                  c->cfg.gn_groups, sp.mr, stt.tst, stt.tc, c->stats_per_sample, st);
     return true;
 }
@@ -2433,23 +2327,14 @@ int cotangent_pass(loco_ctx* c, const float* ge, const float* gx0, float* Aout, 
                     setw(n, op.nin, true); n.pad = 0;
                     n.Cout = ti.C; n.Hout = to.H; n.Wout = to.W; n.B = B; n.out_bs = PS;
                     n.out = TG(op.in); n.accumulate = acc;      // (resampling blocks never change channels: no nin there)
-                    if (op.updown == 0 && c->prec >= 1 && c->fuse_cot) {
-                        // g_in = nin^T g_out + norm1^T g_a1: the norm-cotangent term in the shortcut conv's epilogue instead of
-                        // a read-modify-write pass of gn_apply_kernel<2> over g_in -- one unsplit launch of whole cout tiles only
-                        ConvArgs t = n;
-                        t.taps = 1;
-                        t.nsplit = conv_bf16_pick_nsplit(n.Cin, n.Cout, n.Hout, n.Wout, n.B, c->chip_share, 1, c->lanes_active);
-                        const long per_probe = (long)((n.Hout * n.Wout) / conv_bf16_tile_pixels(t)) * ((n.Cout + 127) / 128);
-                        const long total = per_probe * n.B, r = total % 256;
-                        if (t.nsplit == 1 && (total <= 256 || r == 0 || r > 160) && conv_lowp_can_fuse_stats(t) && op.n1.sx_off >= 0 &&
-                            c->sxcache) {
-                            // (from norm1's {S, xhat} records and the per-channel {rstd m1, rstd m2} its cotangent statistics left)
-                            n.cot_d = TG(op.a1); n.cot_d_bs = PS; n.cot_sx = c->sxcache + op.n1.sx_off;
-                            n.cot_tc = stt.tc; n.cot_tc_bs = c->stats_per_sample;
-                            cot_in_epilogue = true;
-                        }
+                    // g_in = nin^T g_out + norm1^T g_a1: the norm-cotangent term in the shortcut conv's epilogue instead of a
+                    // read-modify-write pass of gn_apply_kernel<2> over g_in where plan_conv takes it (from norm1's {S, xhat}
+                    // records and the per-channel {rstd m1, rstd m2} its cotangent statistics left)
+                    if (op.updown == 0 && c->prec >= 1 && c->fuse_cot && op.n1.sx_off >= 0 && c->sxcache) {
+                        n.cot_d = TG(op.a1); n.cot_d_bs = PS; n.cot_sx = c->sxcache + op.n1.sx_off;
+                        n.cot_tc = stt.tc; n.cot_tc_bs = c->stats_per_sample;
                     }
-                    run_conv(c, n, 1, st);
+                    cot_in_epilogue = run_conv(c, n, 1, st);
                     gsk = nullptr;
                 }
                 if (op.updown == 0) {
@@ -2790,8 +2675,6 @@ int loco_create(const loco_unet_cfg* cfg, loco_ctx** out) {
     {
         const char* e = getenv("LOCO_PRECISION");
         c->prec = (e && std::string(e) == "f32") ? 0 : (e && std::string(e) == "f16") ? 2 : 1;   // default: split-bf16
-        const char* t = getenv("LOCO_BF16_TILE");
-        if (t) g_bf16_tile_override = atoi(t);
     }
     if (dalloc(c, &c->mask2, (size_t)c->n_out)) return -1;
     if (dalloc(c, &c->mask, (size_t)c->n_out) || dalloc(c, &c->mask_idx, (size_t)c->n_out) ||
@@ -3384,13 +3267,10 @@ int loco_bench_conv(loco_ctx* c, int32_t cin, int32_t cout, int32_t H, int32_t W
         a.cot_d = out + out_e * B; a.cot_d_bs = out_e; a.cot_sx = c->sxcache; a.cot_tc = c->statsT; a.cot_tc_bs = c->stats_per_sample;
     }
     if (getenv("LOCO_BENCH_ACC") && atoi(getenv("LOCO_BENCH_ACC"))) a.accumulate = 1;
-    if (c->prec == 1 && taps == 1) conv_gemm_plan(a);
-    if (c->prec == 1 && taps == 9) conv_pers_plan(a);
+    conv_plan_family(a, c->prec);
     if (const char* e = getenv("LOCO_DUAL_WHATIF")) a.no_deep = atoi(e);      // stamp build of the dual tile only (bits 2 / 4)
-    int saved = g_bf16_tile_override;
-    g_bf16_tile_override = tile;
     ConvArgs parts[2];
-    const int nparts = conv_lowp_plan(a, taps, c->prec, parts);
+    const int nparts = conv_plan_parts(a, c->prec, tile, parts);
     auto run = [&]() {
         for (int pi = 0; pi < nparts; ++pi) {
             if (c->prec == 1) launch_conv_bf16x3(parts[pi], taps, st);
@@ -3404,7 +3284,6 @@ int loco_bench_conv(loco_ctx* c, int32_t cin, int32_t cout, int32_t H, int32_t W
     for (int i = 0; i < iters; ++i) run();
     HIPCHK(c, hipEventRecord(c->ev1, st));
     HIPCHK(c, hipEventSynchronize(c->ev1));
-    g_bf16_tile_override = saved;
     c->bench_out = out; c->bench_out_count = (int64_t)out_e * B;
     float ms = 0.f;
     HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));

@@ -112,7 +112,7 @@ struct ConvArgs {
     const float* cot_d; long cot_d_bs; const float2* cot_sx; const float* cot_tc; long cot_tc_bs;
     int act;           // ActKind of the prologue modes (exact-fp32 kernel, split-K statistics epilogue)
     float res_scale;   // out = conv + bias + res_scale * res  (DeepFloyd-IF: (x + h) / sqrt 2 with the conv's weights pre-scaled); conv_defaults: 1
-    int dual;          // 1: run on the dual-probe tile of conv_dual_kernel.h (B even; set by conv_lowp_plan, never by the engine)
+    int dual;          // 1: run on the dual-probe tile of conv_dual_kernel.h (B even; set by conv_plan_parts, never by the engine)
     // 1x1 operator as a DMA-fed GEMM (conv_gemm_kernel.h; set by conv_gemm_plan): gemm_tm = 2 / 4 (128 / 256 couts per
     // workgroup); the activations' split records are written to the END of the workspace `partial` (partial_floats floats)
     int gemm, gemm_tm;
@@ -120,46 +120,84 @@ struct ConvArgs {
     // 3x3 kernel persistent over the probes of a tile (conv_bf16_kernel.h PHASE 3; set by conv_pers_plan): number of workgroups
     // that share one (pixel tile, cout tile), each walking the probes b, b + pers_groups, ...; 0: one workgroup per (tile, probe)
     int pers_groups;
+    // kernel of the launch as planned (conv_plan.hip, read by the dispatchers and conv_variant_name): the tile variant and
+    // whether a 3x3 launch runs the tap-pair kernel of conv_pair_kernel.h
+    int tile, pair;
 };
 
-// the conv kernel only; when a.nsplit > 1 the caller follows with launch_conv_splitk_reduce (run_conv does)
+// the conv kernel of a launch planned by conv_plan.hip; when a.nsplit > 1 the caller follows with launch_conv_splitk_reduce (run_conv does)
 void launch_conv(const ConvArgs& a, int taps, hipStream_t st);
 void launch_conv_bf16x3(const ConvArgs& a, int taps, hipStream_t st);
 void launch_conv_f16(const ConvArgs& a, int taps, hipStream_t st);     // a.wb = the f16 weight records
 void launch_conv_splitk_reduce(const ConvArgs& a, hipStream_t st);
-// Dual-probe tile (conv_dual_kernel.h): a low-precision launch is split into its even part on the dual tile (parts[0], `dual`
-// set) and -- for an odd batch -- the last probe on the 128 x 256 tile (parts[1]); returns the number of parts (1: `a` itself).
-bool conv_dual_ok(const ConvArgs& a);
-int conv_lowp_plan(const ConvArgs& a, int taps, int prec, ConvArgs parts[2]);
-// Compute-shaped 1x1 operators on the DMA-fed GEMM kernel: decides eligibility, the cout tile and the split-K factor (overwrites
-// a.nsplit) and sets a.gemm / a.gemm_tm; false: the launch stays on the per-pixel kernel with the split-K factor it had.
-// LOCO_CONV_GEMM=0 switches it off (A/B).
-bool conv_gemm_plan(ConvArgs& a);
-// 3x3 launches whose (pixel tile, cout tile) grid is at least as wide as the chip, or divides it: persistent over the probes
-// (sets a.pers_groups; opt-in: LOCO_CONV_PERS=1 | 2, see conv_bf16.hip)
-bool conv_pers_plan(ConvArgs& a);
-// does the low-precision 3x3 launch `a` (taps, split-K, pers_groups, dual already decided) run on the 16x16x32 tap-pair kernel?
-bool conv_pair_ok(const ConvArgs& a);
-// can a launch with these arguments feed a.st_part from its epilogue?  (whole cout tiles of the chosen variant, no split-K)
-bool conv_lowp_can_fuse_stats(const ConvArgs& a);
-int conv_bf16_tile_couts(const ConvArgs& a);
-// can the low-precision launch `a` (3x3, its split-K factor already chosen) carry the 1x1 operator a.in2 / a.Cin2 / a.wb2 in the
-// same kernel?  (128 x 256 tiles, stride 1, whole 16-channel chunks of both inputs, no split-K)
-bool conv_lowp_can_kcat(const ConvArgs& a);
-int conv_pick_tile(int Cout, int HW);
-extern int g_bf16_tile_override;
+
+// ---- launch policy of the convolutions (conv_plan.hip, host code only) ----
+// run_conv asks plan_conv for every decision about a conv and executes the plan; the dispatchers and the profile names read
+// what the plan recorded in ConvArgs (tile, pair, dual, gemm, pers_groups, Cin2).  ConvEnv: what the context contributes.
+struct ConvEnv {
+    int prec = 1;                                          // 0: exact fp32, 1: split-bf16, 2: f16
+    int chip_share = 1;                                    // passes enqueued side by side (loco_set_chip_share)
+    int lanes = 1, lane_s0 = 0;                            // probe groups run side by side (run_lanes); first sample of this one
+    float* partial = nullptr; size_t partial_floats = 0;   // this lane's split-K workspace
+    float* stpart = nullptr; size_t stpart_floats = 0;     // this lane's row partials of the epilogue statistics
+    bool fuse_stats = true, fuse_lin = true, deep1 = true; // LOCO_FUSE_STATS / LOCO_FUSE_LIN / LOCO_DEEP1
+    int max_batch = 1;
+};
+
+// the statistics the consumer of a conv's output tensor asks for (engine.hip StatReq, without the norm's arrays)
+struct StatAsk {
+    int kind = ST_NONE;                                // ST_FWD / ST_TAN / ST_COT
+    bool norm = false;                                 // a norm takes them (else: kept partials only)
+    const float2* sx = nullptr;                        // that norm's {S, xhat} records over the output tensor (nullptr: none)
+    const float* prim = nullptr;                       // primal of the output tensor, B = 1 (ST_TAN / ST_COT)
+    float* keep = nullptr; size_t keep_floats = 0;     // one part of a concatenation: its tile partials stay here, [max_batch][...]
+};
+
+// route of the statistics of one launch
+enum StatRoute : int {
+    SR_NONE = 0,      // none asked
+    SR_EPI = 1,       // conv epilogue partials (st_part), merged by a finalize launch
+    SR_SPLITK = 2,    // the split-K epilogue (launch_conv_splitk_reduce_stats)
+    SR_ALONE = 3,     // a standalone statistics pass over the launch's samples
+    SR_KEEP = 4,      // conv epilogue partials kept for the norm over a concatenation, nothing else
+};
+
+// one conv launch and its split-K reduce: samples [s0, s0 + args.B) of the conv.  The kernels it runs are `parts`: the launch
+// itself, or its even part on the dual-probe tile + the odd last probe.
+struct ConvLaunch {
+    ConvArgs args;
+    ConvArgs parts[2]; int nparts = 1;
+    int s0 = 0;
+    int stats = SR_NONE;
+    int ntile = 0;      // pixel tiles per row of args.st_part (SR_EPI / SR_KEEP)
+};
+
+struct ConvPlan {
+    bool sc_first = false;     // the shortcut runs first and `l[0].args` reads its output as the residual (else K-concatenated)
+    int nl = 1;                // 2: tail-probe split, l[1] = the last probes with split-K
+    ConvLaunch l[2];
+    bool stats_all = false;    // a standalone statistics pass over the whole batch follows the launches
+    int keep_ntile = 0;        // tile count of the kept partials (0: none kept)
+    bool cot = false;          // the requested norm-cotangent term (ConvArgs::cot_d) rides in the epilogue
+};
+
+// every decision about conv `a` (`taps` 9 or 1; `ask`: statistics asked for; `shortcut`: the ResBlock's 1x1 operator on the
+// same output tensor).  Pure: reads its arguments (and the process-wide A/B switches of conv_plan.hip) only.
+ConvPlan plan_conv(const ConvEnv& env, const ConvArgs& a, int taps, const StatAsk* ask, const ConvArgs* shortcut);
+// the two steps run_conv and loco_bench_conv share: the kernel family of a conv (DMA-fed GEMM or persistent 3x3; may set
+// a.nsplit), then -- with batch and split-K factor final -- the launch's tile and kernels (returns the number of parts).
+// tile_override >= 0: the tile variant of the big-image case (loco_bench_conv).
+void conv_plan_family(ConvArgs& a, int prec);
+int conv_plan_parts(ConvArgs& a, int prec, int tile_override, ConvArgs parts[2]);
+
+int conv_bf16_tile_couts(const ConvArgs& a);    // couts per workgroup of the planned launch
+// name of the kernel the planned launch runs (the per-kernel profile)
+const char* conv_variant_name(const ConvArgs& a, int taps, int prec);
+
 void launch_fill_random(float* p, long count, unsigned seed, float scale, hipStream_t st);
 // sx[c][hw] = { sc_c * silu'(sc_c*x + sh_c), (x - mean_g) * rstd_g }   (B = 1 primal cache)
 void launch_gn_cache(const float* x, int C, int HW, int cpg, const float* sc, const float* sh, const float* mr,
                      float2* sx, hipStream_t st, int act = 0);
-// name of the kernel variant launch_conv would pick (for the per-kernel profile)
-const char* conv_variant_name(const ConvArgs& a, int taps, int prec);
-// workspace (floats) a conv launch with these args needs for split-K partials
-size_t conv_partial_floats(const ConvArgs& a);
-int conv_pick_nsplit(int Cin, int Cout, int Hout, int Wout, int B, int taps);
-int conv_bf16_pick_nsplit(int Cin, int Cout, int Hout, int Wout, int B, int chip_share = 1, int taps = 9, int lanes = 1);   // chip_share: launches running side by side (loco_set_chip_share)
-int conv_bf16_pick_tile(int Cout, int HW, int Bsplit);
-int conv_bf16_tile_pixels(const ConvArgs& a);
 
 // Generic strided batched GEMM  C[b](m,n) = alpha * sum_k A[b](m,k) B[b](k,n) + beta*C + bias[m] + R[b](m,n)
 struct GemmArgs {
