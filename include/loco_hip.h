@@ -309,6 +309,40 @@ int  loco_text_encode(loco_text* t, const int32_t* ids_dev, int32_t n, float* ou
 const char* loco_text_last_error(loco_text* t);
 void loco_text_destroy(loco_text* t);
 
+/* --- T5 text encoder (DeepFloyd IF prompt embeddings) ---
+ * The encoder of transformers' T5EncoderModel (T5 v1.1) as diffusers' IFPipeline.encode_prompt runs it (reference
+ * src/modules/edit.py:1274-1284): token embedding (no position embedding, no scale), `layers` blocks of
+ * RMS norm -> q / k / v without bias to heads * d_kv channels -> scores q k^T (no 1 / sqrt(d)) + relative position bias
+ * (bidirectional buckets, the table of block 0 serves every block) + key padding mask -> fp32 softmax -> P v -> o -> residual;
+ * RMS norm -> wo(gelu_new(wi_0 x) * (wi_1 x)) -> residual; final RMS norm; output last_hidden_state.  Exact fp32 throughout,
+ * fp32 storage (4.76e9 parameters = 19.0 GB at the XXL geometry).  The handle is a loco_text: loco_text_load_param,
+ * loco_text_params_missing, loco_text_last_error and loco_text_destroy serve it as they serve a CLIP handle. */
+typedef struct loco_t5_cfg {
+    int32_t vocab;         /* rows of shared.weight (32128) */
+    int32_t d_model;       /* 4096 at XXL */
+    int32_t d_kv;          /* channels per head (64); heads * d_kv need not equal d_model */
+    int32_t heads;         /* num_heads (64) */
+    int32_t d_ff;          /* 10240 */
+    int32_t layers;        /* num_layers (24) */
+    int32_t positions;     /* L: the token count every prompt is padded to (77 for IF), <= 128 */
+    int32_t buckets;       /* relative_attention_num_buckets (32) */
+    int32_t max_distance;  /* relative_attention_max_distance (128) */
+    int32_t act;           /* feed_forward_proj: 0 gated-gelu (the only one built) */
+    float   ln_eps;        /* layer_norm_epsilon (1e-6) */
+} loco_t5_cfg;
+/* Parameter names for loco_text_load_param are the T5EncoderModel state_dict names: shared.weight,
+ * encoder.block.{i}.layer.0.SelfAttention.{q,k,v,o}.weight, encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight,
+ * encoder.block.{i}.layer.0.layer_norm.weight, encoder.block.{i}.layer.1.DenseReluDense.{wi_0,wi_1,wo}.weight,
+ * encoder.block.{i}.layer.1.layer_norm.weight, encoder.final_layer_norm.weight. */
+int  loco_t5_create(const loco_t5_cfg* cfg, int32_t device, int32_t max_prompts, loco_text** out);
+/* out_dev[n][positions][d_model] of the n prompts ids_dev[n][positions] (device, padded with any valid id, 0 for IF) whose
+ * first lens[p] tokens are real: keys at positions >= lens[p] are excluded from every softmax of prompt p, the padded query
+ * rows are still computed and returned (as transformers does with an attention mask).  lens: host int32[n], each in
+ * [1, positions], or NULL = every prompt is `positions` long.  ids and lens are checked on the host once per call; each
+ * output row is bit-identical whatever n, its position in the batch and the lengths of the other prompts.  On a CLIP handle
+ * this call is an error; loco_text_encode on a T5 handle means lens == NULL. */
+int  loco_text_encode_masked(loco_text* t, const int32_t* ids_dev, const int32_t* lens, int32_t n, float* out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

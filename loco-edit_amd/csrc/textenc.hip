@@ -9,8 +9,7 @@
 // transpose of the final states to [n][L][D].  Every kernel computes a token column from that column (and, in the
 // attention, from the columns of its own prompt) alone, in a fixed order: a prompt's rows are bit-identical whatever n
 // and its position in the batch.
-#include "kernels.h"
-#include "../../include/loco_hip.h"
+#include "textenc.h"
 
 #include <algorithm>
 #include <cmath>
@@ -109,61 +108,31 @@ __global__ __launch_bounds__(256) void text_transpose_kernel(const float* x, int
 }
 
 }  // namespace
+
+void launch_text_transpose(const float* x, int Tp, int T, int D, float* out, hipStream_t st) {
+    const long TD = (long)T * D;
+    hipLaunchKernelGGL(text_transpose_kernel, dim3((unsigned)((TD + 255) / 256)), dim3(256), 0, st, x, Tp, T, D, out);
+}
 }  // namespace loco
 
 using namespace loco;
 
 namespace {
 thread_local std::string g_text_create_err;
-
-struct TextParam {
-    std::string name;
-    std::vector<int64_t> shape;
-    float* dst;
-    bool loaded;
-};
-struct TextLayer { float *ln1_g, *ln1_b, *wqkv, *bqkv, *wo, *bo, *ln2_g, *ln2_b, *w1, *b1, *w2, *b2; };
+using DeviceGuard = loco::TextDeviceGuard;
 
 size_t attn_lds_bytes(int hd, int L) { return (size_t)(2 * hd * L + TA_WAVES * L) * sizeof(float); }
-}  // namespace
-
-struct loco_text {
-    loco_text_cfg cfg;
-    int device = 0, max_prompts = 0, L = 0, D = 0, hd = 0, Tmax = 0;
-    std::string err;
-    float* params = nullptr;              // one allocation for every parameter
-    float *tok = nullptr, *pos = nullptr, *lnf_g = nullptr, *lnf_b = nullptr;
-    std::vector<TextLayer> layer;
-    std::vector<TextParam> table;
-    // workspace [.][Tmax]
-    float *h = nullptr, *x = nullptr, *qkv = nullptr, *attn = nullptr, *f = nullptr, *stats = nullptr;
-    int* ids = nullptr;
-    std::vector<int> ids_host;
-    int fail(const std::string& m) { err = m; return -1; }
-};
-
-namespace {
-struct DeviceGuard {       // the caller's current device is restored on every return
-    int prev = 0;
-    explicit DeviceGuard(int d) { (void)hipGetDevice(&prev); (void)hipSetDevice(d); }
-    ~DeviceGuard() { (void)hipSetDevice(prev); }
-};
 
 void free_text(loco_text* t) {
     (void)hipFree(t->params); (void)hipFree(t->h); (void)hipFree(t->x); (void)hipFree(t->qkv); (void)hipFree(t->attn);
     (void)hipFree(t->f); (void)hipFree(t->stats); (void)hipFree(t->ids);
-}
-
-GemmArgs linear(const float* W, const float* bias, const float* X, float* Y, const float* R, int M, int K, int Tp) {
-    GemmArgs g; std::memset(&g, 0, sizeof(g));
-    g.A = W; g.sam = K; g.sak = 1;
-    g.Bm = X; g.sbk = Tp; g.sbn = 1;
-    g.C = Y; g.scm = Tp; g.scn = 1;
-    g.bias = bias; g.R = R;
-    g.M = M; g.N = Tp; g.K = K; g.batch = 1; g.alpha = 1.f;
-    return g;
+    t5_free(t);
 }
 }  // namespace
+
+namespace loco {
+void text_set_create_error(const std::string& m) { g_text_create_err = m; }
+}  // namespace loco
 
 extern "C" {
 
@@ -279,7 +248,7 @@ int loco_text_load_param(loco_text* t, const char* name, const float* host, cons
         if (hipMemcpy(p.dst, host, cnt * sizeof(float), hipMemcpyDefault) != hipSuccess)
             return t->fail("loco_text_load_param: copy of " + p.name + " failed");
         p.loaded = true;
-        return 0;
+        return t->kind == TEXT_KIND_T5 ? t5_param_loaded(t, p.dst) : 0;
     }
     return t->fail(std::string("loco_text_load_param: unknown parameter ") + name);
 }
@@ -298,6 +267,7 @@ int loco_text_params_missing(loco_text* t) {
 
 int loco_text_encode(loco_text* t, const int32_t* ids_dev, int32_t n, float* out_dev, void* stream) {
     if (!t) return -1;
+    if (t->kind == TEXT_KIND_T5) return t5_encode(t, ids_dev, nullptr, n, out_dev, (hipStream_t)stream);
     if (!ids_dev || !out_dev) return t->fail("loco_text_encode: null ids or out");
     if (n <= 0 || n > t->max_prompts)
         return t->fail("loco_text_encode: n = " + std::to_string(n) + " outside [1, max_prompts = " + std::to_string(t->max_prompts) + "]");
@@ -325,17 +295,16 @@ int loco_text_encode(loco_text* t, const int32_t* ids_dev, int32_t n, float* out
     const int gact = t->cfg.act == 0 ? GEMM_ACT_QUICK_GELU : GEMM_ACT_GELU;
     for (const TextLayer& ly : t->layer) {
         launch_ln_fwd(t->h, 0, 1, D, Tp, ly.ln1_g, ly.ln1_b, t->cfg.ln_eps, t->x, 0, t->stats, 0, st);
-        launch_gemm_fixed(linear(ly.wqkv, ly.bqkv, t->x, t->qkv, nullptr, 3 * D, D, Tp), GEMM_ACT_NONE, st);
+        launch_gemm_fixed(text_linear(ly.wqkv, ly.bqkv, t->x, t->qkv, nullptr, 3 * D, D, Tp), GEMM_ACT_NONE, st);
         hipLaunchKernelGGL(text_attn_kernel, dim3(n, t->cfg.heads), dim3(TA_THREADS), lds, st, t->qkv, (long)Tp, L, D, t->hd, scale,
                            t->attn);
-        launch_gemm_fixed(linear(ly.wo, ly.bo, t->attn, t->h, t->h, D, D, Tp), GEMM_ACT_NONE, st);
+        launch_gemm_fixed(text_linear(ly.wo, ly.bo, t->attn, t->h, t->h, D, D, Tp), GEMM_ACT_NONE, st);
         launch_ln_fwd(t->h, 0, 1, D, Tp, ly.ln2_g, ly.ln2_b, t->cfg.ln_eps, t->x, 0, t->stats, 0, st);
-        launch_gemm_fixed(linear(ly.w1, ly.b1, t->x, t->f, nullptr, F, D, Tp), gact, st);
-        launch_gemm_fixed(linear(ly.w2, ly.b2, t->f, t->h, t->h, D, F, Tp), GEMM_ACT_NONE, st);
+        launch_gemm_fixed(text_linear(ly.w1, ly.b1, t->x, t->f, nullptr, F, D, Tp), gact, st);
+        launch_gemm_fixed(text_linear(ly.w2, ly.b2, t->f, t->h, t->h, D, F, Tp), GEMM_ACT_NONE, st);
     }
     launch_ln_fwd(t->h, 0, 1, D, Tp, t->lnf_g, t->lnf_b, t->cfg.ln_eps, t->x, 0, t->stats, 0, st);
-    const long TD = (long)T * D;
-    hipLaunchKernelGGL(text_transpose_kernel, dim3((unsigned)((TD + 255) / 256)), dim3(256), 0, st, t->x, Tp, T, D, out_dev);
+    launch_text_transpose(t->x, Tp, T, D, out_dev, st);
     if (hipGetLastError() != hipSuccess) return t->fail("loco_text_encode: kernel launch failed");
     return 0;
 }

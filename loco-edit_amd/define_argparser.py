@@ -106,13 +106,16 @@ def build_parser():
                    help='latent T-LOCO: decoder architecture (default: the Stable Diffusion autoencoder decoder geometry)')
     p.add_argument('--vae_ckpt_path', type=str, default='', help='latent T-LOCO: decoder state_dict in latent-diffusion `Decoder` naming')
     p.add_argument('--prompt_emb_path', type=str, default='',
-                   help="T-LOCO: torch file {'for','edit','null': [1, tokens, D]} of prompt embeddings (Stable Diffusion: or --text_encoder_path)")
+                   help="T-LOCO: torch file {'for','edit','null': [1, tokens, D]} of prompt embeddings (or --text_encoder_path)")
     p.add_argument('--text_encoder_path', type=str, default='',
-                   help='Stable Diffusion: CLIP text encoder that turns --for_prompt / --edit_prompt / ... into prompt states on the '
-                        'GPU: a diffusers pipeline root (text_encoder/ + tokenizer/), a text_encoder/ folder or a single '
-                        'state_dict file (CompVis SD 1.x .ckpt); excludes --prompt_emb_path')
+                   help='text encoder that turns --for_prompt / --edit_prompt / ... into prompt states on the GPU -- Stable '
+                        'Diffusion: CLIP; DeepFloyd IF: T5 (v1.1 encoder, fp32; prompts lower-cased and stripped, 77 tokens). A '
+                        'diffusers pipeline root (text_encoder/ + tokenizer/), a text_encoder/ folder (one file or a sharded '
+                        '*.index.json checkpoint) or a single state_dict file (CompVis SD 1.x .ckpt); the kind is read from the '
+                        'checkpoint and must fit the model; excludes --prompt_emb_path')
     p.add_argument('--tokenizer_path', type=str, default='',
-                   help='CLIP tokenizer folder (vocab.json, merges.txt, configs) when --text_encoder_path is not a pipeline root')
+                   help='tokenizer folder when --text_encoder_path is not a pipeline root: CLIP (vocab.json, merges.txt, configs) '
+                        'or T5 (tokenizer.json with a Unigram model, or spiece.model)')
     p.add_argument('--cond_dim', type=int, default=16, help='T-LOCO stand-in: width of seeded prompt embeddings when no file is given')
     p.add_argument('--precision', type=str, default=None, choices=['f32', 'bf16x3', 'f16'],
                    help="conv arithmetic of the HIP engine: 'f32' exact fp32 MFMA (parity anchor), 'bf16x3' split-bf16 "

@@ -32,7 +32,7 @@ SYMBOLS = [
     "loco_profile_enable", "loco_profile_report", "loco_set_precision", "loco_get_precision", "loco_set_streams", "loco_set_chip_share",
     "loco_set_cond", "loco_set_context", "loco_lincomb", "loco_masked_axpby", "loco_latent_sample",
     "loco_text_create", "loco_text_load_param", "loco_text_params_missing", "loco_text_encode", "loco_text_last_error",
-    "loco_text_destroy",
+    "loco_text_destroy", "loco_t5_create", "loco_text_encode_masked",
 ]
 
 
@@ -53,6 +53,12 @@ class LocoCfg(C.Structure):
 class LocoTextCfg(C.Structure):
     _fields_ = [("vocab", C.c_int32), ("width", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32), ("ffn", C.c_int32),
                 ("positions", C.c_int32), ("act", C.c_int32), ("ln_eps", C.c_float)]
+
+
+class LocoT5Cfg(C.Structure):
+    _fields_ = [("vocab", C.c_int32), ("d_model", C.c_int32), ("d_kv", C.c_int32), ("heads", C.c_int32), ("d_ff", C.c_int32),
+                ("layers", C.c_int32), ("positions", C.c_int32), ("buckets", C.c_int32), ("max_distance", C.c_int32),
+                ("act", C.c_int32), ("ln_eps", C.c_float)]
 
 
 def library_path() -> str:
@@ -125,6 +131,9 @@ def load_library():
         lib.loco_text_last_error.restype = C.c_char_p
         lib.loco_text_destroy.argtypes = [vp]
         lib.loco_text_destroy.restype = None
+    if hasattr(lib, "loco_t5_create"):
+        lib.loco_t5_create.argtypes = [C.POINTER(LocoT5Cfg), i32, i32, C.POINTER(vp)]
+        lib.loco_text_encode_masked.argtypes = [vp, vp, C.POINTER(i32), i32, vp, vp]
     if hasattr(lib, "loco_bench_conv"):          # diag build only
         lib.loco_bench_conv.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(f32), vp]
         lib.loco_debug_tensor.argtypes = [vp, C.c_char_p, vp, i64, vp]
@@ -551,8 +560,9 @@ class LocoEngine:
 
 
 class LocoTextEngine:
-    """The CLIP text encoder (= loco_text, include/loco_hip.h): parameters on the device, one batched encode per call.
-    `cfg` is a ``text_encoder.TextConfig``; token ids in, last_hidden_state [n, positions, width] out, exact fp32."""
+    """A text encoder (= loco_text, include/loco_hip.h): parameters on the device, one batched encode per call.
+    `cfg` is a ``text_encoder.TextConfig`` (CLIP, loco_text_create) or a ``text_encoder.T5Config`` (the T5 encoder of
+    DeepFloyd IF, loco_t5_create); token ids in, last_hidden_state [n, positions, width] out, exact fp32."""
 
     def __init__(self, cfg, max_prompts: int = 8, device: Optional[torch.device] = None):
         self.lib = load_library()
@@ -562,12 +572,20 @@ class LocoTextEngine:
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.cfg, self.max_prompts = cfg, int(max_prompts)
-        c = LocoTextCfg(vocab=cfg.vocab, width=cfg.width, layers=cfg.layers, heads=cfg.heads, ffn=cfg.ffn,
-                        positions=cfg.positions, act={"quick_gelu": 0, "gelu": 1}[cfg.act], ln_eps=cfg.ln_eps)
+        self.is_t5 = hasattr(cfg, "d_kv")
         self._t = C.c_void_p()
-        rc = self.lib.loco_text_create(C.byref(c), self.device.index, self.max_prompts, C.byref(self._t))
+        if self.is_t5:
+            if cfg.act != "gated-gelu":
+                raise ValueError(f"feed_forward_proj {cfg.act!r}: the T5 encoder builds gated-gelu only")
+            c = LocoT5Cfg(vocab=cfg.vocab, d_model=cfg.d_model, d_kv=cfg.d_kv, heads=cfg.heads, d_ff=cfg.d_ff, layers=cfg.layers,
+                          positions=cfg.positions, buckets=cfg.buckets, max_distance=cfg.max_distance, act=0, ln_eps=cfg.ln_eps)
+            rc, what = self.lib.loco_t5_create(C.byref(c), self.device.index, self.max_prompts, C.byref(self._t)), "loco_t5_create"
+        else:
+            c = LocoTextCfg(vocab=cfg.vocab, width=cfg.width, layers=cfg.layers, heads=cfg.heads, ffn=cfg.ffn,
+                            positions=cfg.positions, act={"quick_gelu": 0, "gelu": 1}[cfg.act], ln_eps=cfg.ln_eps)
+            rc, what = self.lib.loco_text_create(C.byref(c), self.device.index, self.max_prompts, C.byref(self._t)), "loco_text_create"
         if rc != 0:
-            raise RuntimeError(f"loco_text_create failed ({rc}): {self.lib.loco_text_last_error(None).decode()}")
+            raise RuntimeError(f"{what} failed ({rc}): {self.lib.loco_text_last_error(None).decode()}")
 
     def __del__(self):
         try:
@@ -581,8 +599,8 @@ class LocoTextEngine:
         if rc != 0:
             raise RuntimeError(f"{what} failed ({rc}): {self.lib.loco_text_last_error(self._t).decode()}")
 
-    def load_state_dict(self, sd: Dict[str, "np.ndarray | torch.Tensor"]):
-        """Names of CLIPTextTransformer without a prefix (text_encoder.normalize_text_state_dict produces them)."""
+    def load_params(self, sd: Dict[str, "np.ndarray | torch.Tensor"]):
+        """Loads the entries of `sd` (a part of the state_dict: a shard, a layer) without asking for completeness."""
         if any(isinstance(v, torch.Tensor) and v.is_cuda for v in sd.values()):
             torch.cuda.synchronize()        # the copies below read device values written on torch's streams
         for name, v in sd.items():
@@ -592,22 +610,45 @@ class LocoTextEngine:
             shape = (C.c_int64 * max(t.dim(), 1))(*t.shape)
             self._check(self.lib.loco_text_load_param(self._t, name.encode(), C.c_void_p(t.data_ptr()), shape, t.dim()),
                         f"loco_text_load_param({name})")
+
+    def check_complete(self):
         missing = self.lib.loco_text_params_missing(self._t)
         if missing:
             raise RuntimeError(f"text encoder: {missing} parameters missing ({self.lib.loco_text_last_error(self._t).decode()})")
 
-    def encode_ids(self, ids: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """ids [n, positions] (any integer dtype, host or device) -> [n, positions, width] fp32 on the device."""
+    def load_state_dict(self, sd: Dict[str, "np.ndarray | torch.Tensor"]):
+        """Names of CLIPTextTransformer without a prefix (text_encoder.normalize_text_state_dict produces them), or of
+        T5EncoderModel (text_encoder.normalize_t5_state_dict)."""
+        self.load_params(sd)
+        self.check_complete()
+
+    @property
+    def width(self) -> int:
+        return self.cfg.d_model if self.is_t5 else self.cfg.width
+
+    def encode_ids(self, ids: torch.Tensor, out: Optional[torch.Tensor] = None, lens=None) -> torch.Tensor:
+        """ids [n, positions] (any integer dtype, host or device) -> [n, positions, width] fp32 on the device.
+        lens (T5 only): the count of real tokens of every prompt, keys beyond it are masked; None = all `positions`."""
         ids = torch.as_tensor(ids)
         if ids.dim() != 2 or ids.shape[1] != self.cfg.positions:
             raise ValueError(f"ids must be [n, {self.cfg.positions}], got {tuple(ids.shape)}")
         n = ids.shape[0]
         ids = ids.to(device=self.device, dtype=torch.int32).contiguous()
         if out is None:
-            out = torch.empty(n, self.cfg.positions, self.cfg.width, device=self.device, dtype=torch.float32)
+            out = torch.empty(n, self.cfg.positions, self.width, device=self.device, dtype=torch.float32)
         _chk_dev(out)
-        if tuple(out.shape) != (n, self.cfg.positions, self.cfg.width):
-            raise ValueError(f"out must be [{n}, {self.cfg.positions}, {self.cfg.width}], got {tuple(out.shape)}")
+        if tuple(out.shape) != (n, self.cfg.positions, self.width):
+            raise ValueError(f"out must be [{n}, {self.cfg.positions}, {self.width}], got {tuple(out.shape)}")
         with torch.cuda.device(self.device):
-            self._check(self.lib.loco_text_encode(self._t, _ptr(ids), n, _ptr(out), _stream()), "loco_text_encode")
+            if lens is None and not self.is_t5:
+                self._check(self.lib.loco_text_encode(self._t, _ptr(ids), n, _ptr(out), _stream()), "loco_text_encode")
+            else:
+                larr = None
+                if lens is not None:
+                    lens = [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+                    if len(lens) != n:
+                        raise ValueError(f"lens must hold {n} lengths, got {len(lens)}")
+                    larr = (C.c_int32 * n)(*lens)
+                self._check(self.lib.loco_text_encode_masked(self._t, _ptr(ids), larr, n, _ptr(out), _stream()),
+                            "loco_text_encode_masked")
         return out

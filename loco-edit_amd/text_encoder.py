@@ -9,12 +9,28 @@ transformer on the HIP engine (``hip.LocoTextEngine``, ``csrc/textenc.hip``).
   (``config.json`` + ``model.safetensors`` or ``pytorch_model.bin``) or one state-dict file (e.g. a CompVis SD 1.x
   ``.ckpt``); keys normalised to the CLIPTextTransformer naming without prefix.
 * ``TextEncoder.encode(list[str]) -> [n, L, D]`` on the device.
+
+The T5 (v1.1) encoder of the DeepFloyd IF path (``IFPipeline.encode_prompt``; reference ``src/modules/edit.py:1274-1284``)
+goes through the same calls (``csrc/t5enc.hip``):
+
+* ``T5Tokenizer``: unigram Viterbi segmentation in pure Python, the ids of ``transformers.T5Tokenizer`` built from the
+  same (piece, score) list: words split on white space, each prefixed with ``▁``, unknown stretches -> ``<unk>``, ``</s>``
+  appended, truncation to L with ``</s>`` kept last, padding with id 0; ids and lengths.  It reads ``tokenizer.json``
+  (Unigram model) or ``spiece.model`` (protobuf wire format, piece list only).  The text is NFKC-normalised with
+  ``unicodedata``: identical to sentencepiece's ``nmt_nfkc`` map for ASCII, approximate beyond.
+* ``load_text_encoder`` recognises a T5 encoder (``model_type`` ``t5`` in ``config.json``, or ``SelfAttention`` keys in a
+  bare file) and returns a ``T5Config``; a sharded checkpoint (``*.index.json``) comes back as ``T5Shards`` and is read
+  one shard at a time.
+* IF's preprocessing (``clean_caption=False``: lower case, strip; 77 tokens, padded, attention mask) is restated from
+  the published diffusers pipeline, which is not pinned by a test here.
 """
 from __future__ import annotations
 
 import json
+import math
 import os
 import re
+import struct
 import unicodedata
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
@@ -281,13 +297,319 @@ def _read_state_dict(path: str) -> Dict[str, torch.Tensor]:
     return torch.load(path, map_location="cpu", weights_only=False)
 
 
-def load_text_encoder(path: str) -> Tuple[TextConfig, Dict[str, torch.Tensor], Optional[str]]:
-    """-> (geometry, normalised state_dict, tokenizer folder of a pipeline root or None)."""
+# ------------------------------------------------------------------------------------------------------------------- T5
+class TextEncoderKindError(NotImplementedError):
+    """The checkpoint holds the other kind of text encoder than the path needs."""
+
+
+@dataclass(frozen=True)
+class T5Config:
+    vocab: int = 32128
+    d_model: int = 4096
+    d_kv: int = 64
+    heads: int = 64
+    d_ff: int = 10240
+    layers: int = 24
+    positions: int = 77             # L: not a property of the checkpoint (no position embedding); IF pads to 77
+    buckets: int = 32
+    max_distance: int = 128
+    act: str = "gated-gelu"         # wo(gelu_new(wi_0 x) * wi_1 x): T5 v1.1
+    ln_eps: float = 1e-6
+
+    @property
+    def inner(self) -> int:
+        return self.heads * self.d_kv
+
+
+T5_XXL = T5Config()
+
+
+def t5_relative_bucket(rel: int, buckets: int = 32, max_distance: int = 128) -> int:
+    """``T5Attention._relative_position_bucket(k - q, bidirectional=True)`` for one offset, in double precision (the
+    same formula as csrc/t5enc.hip t5_bucket)."""
+    nb = buckets // 2
+    ret = nb if rel > 0 else 0
+    n = abs(rel)
+    max_exact = nb // 2
+    if n < max_exact:
+        return ret + n
+    large = max_exact + int(math.log(n / max_exact) / math.log(max_distance / max_exact) * (nb - max_exact))
+    return ret + min(large, nb - 1)
+
+
+def t5_param_shapes(cfg: T5Config) -> Dict[str, Tuple[int, ...]]:
+    D, I, F = cfg.d_model, cfg.inner, cfg.d_ff
+    out = {"shared.weight": (cfg.vocab, D)}
+    for i in range(cfg.layers):
+        p = f"encoder.block.{i}.layer."
+        out[p + "0.layer_norm.weight"] = (D,)
+        for m in "qkv":
+            out[p + f"0.SelfAttention.{m}.weight"] = (I, D)
+        out[p + "0.SelfAttention.o.weight"] = (D, I)
+        if i == 0:
+            out[p + "0.SelfAttention.relative_attention_bias.weight"] = (cfg.buckets, cfg.heads)
+        out[p + "1.layer_norm.weight"] = (D,)
+        out[p + "1.DenseReluDense.wi_0.weight"] = (F, D)
+        out[p + "1.DenseReluDense.wi_1.weight"] = (F, D)
+        out[p + "1.DenseReluDense.wo.weight"] = (D, F)
+    out["encoder.final_layer_norm.weight"] = (D,)
+    return out
+
+
+_T5_EMBED = ("shared.weight", "encoder.embed_tokens.weight")
+
+
+def _t5_name(k: str) -> Optional[str]:
+    """Normalised T5EncoderModel name of a checkpoint key; None for keys that are not the encoder's (decoder, lm_head)."""
+    if k.startswith("text_encoder."):
+        k = k[len("text_encoder."):]
+    if k.startswith(("decoder.", "lm_head.")):
+        return None
+    if k.startswith(("block.", "final_layer_norm.", "embed_tokens.")):      # a bare T5Stack: the `encoder.` level is missing
+        k = "encoder." + k
+    return "shared.weight" if k in _T5_EMBED else k
+
+
+def normalize_t5_state_dict(sd: Dict[str, torch.Tensor], upcast: bool = True) -> Dict[str, torch.Tensor]:
+    """Keys of a T5EncoderModel, of a pipeline (``text_encoder.*``) or of a bare encoder stack (``block.*``) -> the
+    T5EncoderModel naming; the tied embedding under either of its names -> ``shared.weight``; fp16 / bf16 -> fp32
+    (``upcast=False`` leaves that to the engine's loader, which converts one tensor at a time).
+    Keys outside an encoder are refused (a full T5's decoder and lm_head are dropped)."""
+    sd = sd.get("state_dict", sd) if isinstance(sd.get("state_dict", None), dict) else sd
+    out, foreign = {}, []
+    for k, v in sd.items():
+        n = _t5_name(k)
+        if n is None:
+            continue
+        if not (n == "shared.weight" or n.startswith(("encoder.block.", "encoder.final_layer_norm."))):
+            foreign.append(k); continue
+        if n == "shared.weight" and n in out and k.endswith("embed_tokens.weight"):
+            continue                               # the tied copy
+        out[n] = v.to(torch.float32) if upcast and torch.is_tensor(v) and v.is_floating_point() else v
+    if foreign:
+        raise ValueError(f"not a T5 encoder state_dict: foreign keys {sorted(foreign)[:8]}")
+    return out
+
+
+def infer_t5_config(sd: Dict[str, torch.Tensor], config: Optional[dict] = None, positions: int = 77) -> T5Config:
+    """Geometry from a transformers ``config.json`` when given, else from the shapes of the normalised state_dict
+    (max_distance 128 and eps 1e-6, which no shape shows)."""
+    if config is not None:
+        act = config.get("feed_forward_proj", "relu")
+        if act != "gated-gelu":
+            raise ValueError(f"feed_forward_proj {act!r}: the T5 encoder builds gated-gelu (T5 v1.1) only")
+        return T5Config(vocab=int(config["vocab_size"]), d_model=int(config["d_model"]), d_kv=int(config["d_kv"]),
+                        heads=int(config["num_heads"]), d_ff=int(config["d_ff"]), layers=int(config["num_layers"]),
+                        positions=int(positions), buckets=int(config.get("relative_attention_num_buckets", 32)),
+                        max_distance=int(config.get("relative_attention_max_distance", 128)), act=act,
+                        ln_eps=float(config.get("layer_norm_epsilon", 1e-6)))
+    p0 = "encoder.block.0.layer."
+    need = ("shared.weight", p0 + "0.SelfAttention.q.weight", p0 + "0.SelfAttention.relative_attention_bias.weight",
+            p0 + "1.DenseReluDense.wi_0.weight")
+    missing = [k for k in need if k not in sd]
+    if missing:
+        raise ValueError(f"missing keys of the T5 encoder: {missing}")
+    tok, q, rel, wi = (sd[k] for k in need)
+    heads = int(rel.shape[1])
+    if q.shape[0] % heads:
+        raise ValueError(f"q rows {q.shape[0]} are not a multiple of the {heads} heads of relative_attention_bias")
+    layers = 1 + max(int(k.split(".")[2]) for k in sd if k.startswith("encoder.block."))
+    return T5Config(vocab=int(tok.shape[0]), d_model=int(tok.shape[1]), d_kv=int(q.shape[0]) // heads, heads=heads,
+                    d_ff=int(wi.shape[0]), layers=layers, positions=int(positions), buckets=int(rel.shape[0]))
+
+
+def check_t5_names(names, cfg: T5Config):
+    want = set(t5_param_shapes(cfg))
+    missing, foreign = sorted(want - set(names)), sorted(set(names) - want)
+    if foreign:
+        raise ValueError(f"foreign keys for a {cfg.layers}-block T5 encoder: {foreign[:8]}")
+    if missing:
+        raise ValueError(f"missing keys of the T5 encoder: {missing[:8]}" + (" ..." if len(missing) > 8 else ""))
+
+
+def check_t5_state_dict(sd: Dict[str, torch.Tensor], cfg: T5Config):
+    check_t5_names(sd.keys(), cfg)
+    for k, shape in t5_param_shapes(cfg).items():
+        if tuple(sd[k].shape) != shape:
+            raise ValueError(f"{k} has shape {tuple(sd[k].shape)}, the geometry asks for {shape}")
+
+
+class T5Shards:
+    """The state_dict of a sharded checkpoint folder (``*.index.json`` + its shards): ``names`` from the index, the
+    tensors by iterating -- one normalised shard at a time in its stored dtype (the engine's loader upcasts tensor by
+    tensor), so the host never holds the whole encoder, let alone twice."""
+
+    def __init__(self, folder: str, index_file: str):
+        self.folder = folder
+        with open(os.path.join(folder, index_file)) as f:
+            wm = json.load(f)["weight_map"]
+        self.files = sorted(set(wm.values()))
+        self.names = sorted({n for n in map(_t5_name, wm) if n is not None})
+
+    def __iter__(self):
+        for fn in self.files:
+            yield normalize_t5_state_dict(_read_state_dict(os.path.join(self.folder, fn)), upcast=False)
+
+
+def read_spiece_model(path: str) -> List[Tuple[str, float]]:
+    """(piece, score) of every entry of a sentencepiece ``ModelProto`` file: field 1 (repeated SentencePiece: 1 piece
+    string, 2 score float, 3 type), read from the protobuf wire format; everything else is skipped."""
+    with open(path, "rb") as f:
+        buf = f.read()
+
+    def varint(i):
+        v, sh = 0, 0
+        while True:
+            b = buf[i]; i += 1
+            v |= (b & 0x7F) << sh; sh += 7
+            if not b & 0x80:
+                return v, i
+
+    def fields(i, end):
+        while i < end:
+            key, i = varint(i)
+            fno, wt = key >> 3, key & 7
+            if wt == 0:
+                v, i = varint(i)
+            elif wt == 1:
+                v, i = buf[i:i + 8], i + 8
+            elif wt == 2:
+                n, i = varint(i)
+                v, i = (i, i + n), i + n
+            elif wt == 5:
+                v, i = buf[i:i + 4], i + 4
+            else:
+                raise ValueError(f"{path}: wire type {wt} is not that of a sentencepiece model")
+            yield fno, wt, v
+    out = []
+    for fno, wt, v in fields(0, len(buf)):
+        if fno != 1 or wt != 2:
+            continue
+        piece, score = "", 0.0
+        for g, w, x in fields(*v):
+            if g == 1 and w == 2:
+                piece = buf[x[0]:x[1]].decode("utf-8")
+            elif g == 2 and w == 5:
+                score = struct.unpack("<f", x)[0]
+        out.append((piece, score))
+    if not out:
+        raise ValueError(f"{path}: no pieces found")
+    return out
+
+
+class T5Tokenizer:
+    """Unigram segmentation with the (piece, score) list of a T5 ``tokenizer/`` folder; ids 0 / 1 / 2 are
+    ``<pad>`` / ``</s>`` / ``<unk>`` as in every T5 vocabulary."""
+    UNK_PENALTY = 10.0
+
+    def __init__(self, pieces: List[Tuple[str, float]], model_max_length: int = 77, eos_token: str = "</s>",
+                 unk_token: str = "<unk>", pad_token: str = "<pad>"):
+        self.pieces = [(str(p), float(s)) for p, s in pieces]
+        self.encoder: Dict[str, int] = {}
+        for i, (p, _) in enumerate(self.pieces):
+            self.encoder.setdefault(p, i)
+        for name, tok in (("eos", eos_token), ("unk", unk_token), ("pad", pad_token)):
+            if tok not in self.encoder:
+                raise ValueError(f"{name} token {tok!r} is not in the vocabulary")
+        self.eos_token_id, self.unk_token_id, self.pad_token_id = (self.encoder[t] for t in (eos_token, unk_token, pad_token))
+        self.score = {p: s for p, s in reversed(self.pieces)}          # first entry of a repeated piece wins
+        self.max_len = max(len(p) for p, _ in self.pieces)
+        self.unk_score = min(s for _, s in self.pieces) - self.UNK_PENALTY
+        self.model_max_length = int(model_max_length)
+        self.cache: Dict[str, List[int]] = {}
+
+    @classmethod
+    def from_dir(cls, path: str, model_max_length: int = 77) -> "T5Tokenizer":
+        tj, sp = os.path.join(path, "tokenizer.json"), os.path.join(path, "spiece.model")
+        if os.path.exists(tj):
+            with open(tj, encoding="utf-8") as f:
+                model = json.load(f)["model"]
+            if model.get("type", "Unigram") != "Unigram":
+                raise ValueError(f"{tj}: model type {model.get('type')!r}, a Unigram model is needed")
+            pieces = [(p, s) for p, s in model["vocab"]]
+        elif os.path.exists(sp):
+            pieces = read_spiece_model(sp)
+        else:
+            raise FileNotFoundError(f"{path}: no tokenizer.json or spiece.model")
+        return cls(pieces, model_max_length=model_max_length)
+
+    def segment(self, word: str) -> List[int]:
+        """Viterbi over the pieces of one word (``▁`` already prefixed): the best-scoring path, a character no piece
+        covers costs min_score - 10 and consecutive ones fuse into one ``<unk>`` (tokenizers' Unigram, the first of equal
+        candidates is kept)."""
+        if word in self.cache:
+            return self.cache[word]
+        n = len(word)
+        best = [0.0] * (n + 1)
+        start: List[Optional[int]] = [None] * (n + 1)
+        unk = [False] * (n + 1)
+        for s0 in range(n):
+            if s0 > 0 and start[s0] is None:
+                continue
+            base, single = best[s0], False
+            for e in range(s0 + 1, min(n, s0 + self.max_len) + 1):
+                sc = self.score.get(word[s0:e])
+                if sc is None:
+                    continue
+                cand = base + sc
+                if start[e] is None or cand > best[e]:
+                    best[e], start[e], unk[e] = cand, s0, False
+                if e == s0 + 1:
+                    single = True
+            if not single:
+                cand = base + self.unk_score
+                if start[s0 + 1] is None or cand > best[s0 + 1]:
+                    best[s0 + 1], start[s0 + 1], unk[s0 + 1] = cand, s0, True
+        out, e, fused = [], n, False
+        while e > 0:
+            s0 = start[e]
+            if unk[e]:
+                if not fused:
+                    out.append(self.unk_token_id)
+                fused = True
+            else:
+                out.append(self.encoder.get(word[s0:e], self.unk_token_id))
+                fused = False
+            e = s0
+        out.reverse()
+        self.cache[word] = out
+        return out
+
+    def tokenize(self, text: str) -> List[int]:
+        """Ids of the text without ``</s>``."""
+        ids: List[int] = []
+        for w in _WS_RUN.split(unicodedata.normalize("NFKC", text)):
+            if w:
+                ids.extend(self.segment("▁" + w))
+        return ids
+
+    def __call__(self, text: str) -> Tuple[List[int], int]:
+        """``tokenizer(text, padding="max_length", max_length=L, truncation=True)`` -> (input_ids, sum(attention_mask))"""
+        L = self.model_max_length
+        ids = self.tokenize(text)[:L - 1] + [self.eos_token_id]
+        return ids + [self.pad_token_id] * (L - len(ids)), len(ids)
+
+    def batch(self, texts: List[str]) -> Tuple[torch.Tensor, torch.Tensor]:
+        rows = [self(t) for t in texts]
+        return torch.tensor([r[0] for r in rows], dtype=torch.int32), torch.tensor([r[1] for r in rows], dtype=torch.int32)
+
+
+def _is_t5(config: Optional[dict], keys) -> bool:
+    if config is not None and (config.get("model_type") == "t5" or any("T5" in a for a in config.get("architectures") or [])):
+        return True
+    return any(".SelfAttention." in k for k in keys)
+
+
+def load_text_encoder(path: str, positions: int = 77):
+    """-> (geometry, normalised state_dict, tokenizer folder of a pipeline root or None).  The geometry tells the kind:
+    a ``TextConfig`` (CLIP) or a ``T5Config`` (then the state_dict of a sharded checkpoint is a ``T5Shards``, and
+    ``positions`` is the token count L, which a T5 checkpoint does not fix)."""
     tok_dir, config = None, None
     if os.path.isdir(path) and os.path.isdir(os.path.join(path, "text_encoder")):      # pipeline root
         if os.path.isdir(os.path.join(path, "tokenizer")):
             tok_dir = os.path.join(path, "tokenizer")
         path = os.path.join(path, "text_encoder")
+    sd = None
     if os.path.isdir(path):
         cj = os.path.join(path, "config.json")
         if os.path.exists(cj):
@@ -298,11 +620,30 @@ def load_text_encoder(path: str) -> Tuple[TextConfig, Dict[str, torch.Tensor], O
                 sd = _read_state_dict(os.path.join(path, fn))
                 break
         else:
-            raise FileNotFoundError(f"{path}: no model.safetensors or pytorch_model.bin")
+            for fn in ("model.safetensors.index.json", "pytorch_model.bin.index.json"):
+                if os.path.exists(os.path.join(path, fn)):
+                    sd = T5Shards(path, fn)
+                    break
+            else:
+                raise FileNotFoundError(f"{path}: no model.safetensors or pytorch_model.bin (nor a sharded *.index.json)")
     elif os.path.isfile(path):
         sd = _read_state_dict(path)
     else:
         raise FileNotFoundError(path)
+    if isinstance(sd, T5Shards):
+        if not _is_t5(config, sd.names):
+            raise ValueError(f"{path}: sharded checkpoints are read for the T5 encoder only")
+        if config is None:
+            raise ValueError(f"{path}: a sharded T5 checkpoint needs its config.json")
+        cfg = infer_t5_config({}, config, positions=positions)
+        check_t5_names(sd.names, cfg)
+        return cfg, sd, tok_dir
+    inner = sd.get("state_dict", sd) if isinstance(sd.get("state_dict", None), dict) else sd
+    if _is_t5(config, inner.keys()):
+        sd = normalize_t5_state_dict(inner)
+        cfg = infer_t5_config(sd, config, positions=positions)
+        check_t5_state_dict(sd, cfg)
+        return cfg, sd, tok_dir
     sd = normalize_text_state_dict(sd)
     cfg = infer_text_config(sd, config)
     check_text_state_dict(sd, cfg)
@@ -310,32 +651,56 @@ def load_text_encoder(path: str) -> Tuple[TextConfig, Dict[str, torch.Tensor], O
 
 
 class TextEncoder:
-    """Tokenizer + HIP text transformer: ``encode(prompts) -> [n, L, D]`` fp32 on the device."""
+    """Tokenizer + HIP text transformer: ``encode(prompts) -> [n, L, D]`` fp32 on the device.  ``kind`` is ``"clip"`` or
+    ``"t5"`` after the checkpoint; ``positions`` is the token count L of a T5 encoder (CLIP fixes its own)."""
 
-    def __init__(self, path: str, tokenizer_path: Optional[str] = None, device=None, max_prompts: int = 8):
+    def __init__(self, path: str, tokenizer_path: Optional[str] = None, device=None, max_prompts: int = 8, positions: int = 77,
+                 expect: Optional[str] = None):
         from .hip import LocoTextEngine
-        self.cfg, sd, tok_dir = load_text_encoder(path)
+        self.cfg, sd, tok_dir = load_text_encoder(path, positions=positions)
+        self.kind = "t5" if isinstance(self.cfg, T5Config) else "clip"
+        if expect is not None and self.kind != expect:
+            raise TextEncoderKindError(f"{path} holds a {self.kind.upper()} text encoder, a {expect.upper()} encoder is needed here")
         tok_dir = tokenizer_path or tok_dir
         if not tok_dir:
             raise ValueError(f"{path} is not a pipeline root (text_encoder/ + tokenizer/): pass --tokenizer_path")
-        self.tokenizer = CLIPTokenizer.from_dir(tok_dir)
-        if self.tokenizer.model_max_length != self.cfg.positions:
-            raise ValueError(f"tokenizer model_max_length {self.tokenizer.model_max_length} != the encoder's "
-                             f"max_position_embeddings {self.cfg.positions}")
+        if self.kind == "t5":
+            self.tokenizer = T5Tokenizer.from_dir(tok_dir, model_max_length=self.cfg.positions)
+            if len(self.tokenizer.pieces) > self.cfg.vocab:
+                raise ValueError(f"tokenizer has {len(self.tokenizer.pieces)} pieces, the encoder's embedding {self.cfg.vocab} rows")
+        else:
+            self.tokenizer = CLIPTokenizer.from_dir(tok_dir)
+            if self.tokenizer.model_max_length != self.cfg.positions:
+                raise ValueError(f"tokenizer model_max_length {self.tokenizer.model_max_length} != the encoder's "
+                                 f"max_position_embeddings {self.cfg.positions}")
         self.engine = LocoTextEngine(self.cfg, max_prompts=max_prompts, device=device)
-        self.engine.load_state_dict(sd)
+        if isinstance(sd, T5Shards):
+            for part in sd:                      # one shard on the host at a time
+                self.engine.load_params(part)
+            self.engine.check_complete()
+        else:
+            self.engine.load_state_dict(sd)
         self.device = self.engine.device
 
     @property
     def width(self) -> int:
-        return self.cfg.width
+        return self.cfg.d_model if self.kind == "t5" else self.cfg.width
 
     @property
     def length(self) -> int:
         return self.cfg.positions
 
+    @staticmethod
+    def preprocess_if(prompt: str) -> str:
+        """IFPipeline._text_preprocessing with clean_caption=False (the default of encode_prompt)."""
+        return prompt.lower().strip()
+
     def encode(self, prompts: List[str]) -> torch.Tensor:
-        ids = self.tokenizer.batch(list(prompts))
         mp = self.engine.max_prompts
-        outs = [self.engine.encode_ids(ids[i:i + mp]) for i in range(0, ids.shape[0], mp)]
+        if self.kind == "t5":
+            ids, lens = self.tokenizer.batch([self.preprocess_if(p) for p in prompts])
+            outs = [self.engine.encode_ids(ids[i:i + mp], lens=lens[i:i + mp]) for i in range(0, ids.shape[0], mp)]
+        else:
+            ids = self.tokenizer.batch(list(prompts))
+            outs = [self.engine.encode_ids(ids[i:i + mp]) for i in range(0, ids.shape[0], mp)]
         return outs[0] if len(outs) == 1 else torch.cat(outs)

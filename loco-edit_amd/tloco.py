@@ -22,8 +22,10 @@ conditioning (``encoder_proj``, ``encoder_pooling``) runs on the host (``IFTextC
 installed and there are no weights, so the architecture's parity is unpinned, while the orchestration above is pinned
 against the reference's own methods (oracle/make_golden_tloco.py).  The round-2 / 3 stand-ins stay selectable: the
 guided-diffusion U-Net whose time embedding receives ``cond_proj(mean_tokens(prompt_emb))``, and the same with text
-cross-attention stages.  Prompt embeddings are inputs (``--prompt_emb_path``: a dict of [1, tokens, D] tensors; the T5
-encoder is out of scope) or seeded; stages II/III, SAM and the ``diffedit`` ablation are not on this path.
+cross-attention stages.  Prompt embeddings come from the T5 encoder on the GPU (``--text_encoder_path``: ``csrc/t5enc.hip``
+through ``text_encoder.TextEncoder``, the prompts lower-cased and stripped as ``IFPipeline.encode_prompt`` does, one batched
+encode of for / edit / null / neg / inv; a driver's ``edit_prompt`` re-encodes), are inputs (``--prompt_emb_path``: a dict of
+[1, tokens, D] tensors) or seeded; stages II/III, SAM and the ``diffedit`` ablation are not on this path.
 """
 from __future__ import annotations
 
@@ -267,6 +269,8 @@ class CFGJacobianOperator:
 
 
 class EditDeepFloydIF(object):
+    text_encoder = None
+
     def __init__(self, args):
         self.device, self.dtype = args.device, args.dtype
         if self.dtype == torch.float16:
@@ -287,7 +291,7 @@ class EditDeepFloydIF(object):
         self.for_steps, self.use_yh_custom_scheduler = args.for_steps, args.use_yh_custom_scheduler
         self.guidance_scale, self.guidance_scale_edit = args.guidance_scale, args.guidance_scale_edit
         self.dataset_name = args.dataset_name
-        # ---- prompt embeddings: inputs of this path (the T5 encoder is out of scope)
+        # ---- prompt embeddings: inputs (--prompt_emb_path / seeded) or the T5 encoder's states (--text_encoder_path)
         pe = getattr(args, "prompt_emb", None)
         if getattr(args, "text_encoder_path", ""):
             pe = self._encode_run_prompts(args, cfg)
@@ -398,12 +402,48 @@ class EditDeepFloydIF(object):
     def _bind_all(self, for_e, edit_e, null_e):
         self._bind("for", for_e); self._bind("edit", edit_e); self._bind("null", null_e)
 
+    def _build_text_encoder(self, args, cfg):
+        """--text_encoder_path: the T5 encoder on the GPU (csrc/t5enc.hip), the prompts lower-cased and stripped as
+        IFPipeline.encode_prompt does (edit.py:1274-1284)."""
+        from .text_encoder import TextEncoder, TextEncoderKindError
+        try:
+            # the kind of encoder is looked at first, before any geometry: L is the denoiser's context length (77 for IF), not
+            # the tokenizer's model_max_length (512 for T5)
+            te = TextEncoder(args.text_encoder_path, tokenizer_path=getattr(args, "tokenizer_path", "") or None,
+                             device=args.device, max_prompts=5, positions=cfg.context_len or 77, expect="t5")
+        except TextEncoderKindError as e:
+            raise NotImplementedError(f"--text_encoder_path: DeepFloyd IF needs a T5 encoder, this is CLIP ({e}); the CLIP "
+                                      "encoder serves the Stable Diffusion path") from None
+        if cfg.encoder_dim <= 0:
+            raise ValueError("--text_encoder_path: this denoiser takes no text encoder states (encoder_dim 0); choose an IF "
+                             "U-Net (--unet_preset tiny_if / if_i_m_unet) or pass --prompt_emb_path")
+        if te.width != cfg.encoder_dim:
+            raise ValueError(f"text encoder d_model {te.width} does not match the denoiser's encoder_dim {cfg.encoder_dim}")
+        return te
+
     def _encode_run_prompts(self, args, cfg):
-        raise NotImplementedError("--text_encoder_path: the DeepFloyd-IF path needs the T5 text encoder, which is not built "
-                                  "(the CLIP encoder serves the Stable Diffusion path); pass --prompt_emb_path")
+        """ONE batched encode of the run's for / edit / null / neg / inv prompts (edit.py:1242-1253, :527-538).  Called from
+        the constructor before the branches bind their prompts; the encoder stays resident for _get_prompt_emb."""
+        te = self.text_encoder = self._build_text_encoder(args, cfg)
+        names = ("for", "edit", "null", "neg", "inv")
+        prompts = [args.for_prompt, args.edit_prompt, "", getattr(args, "neg_prompt", ""), getattr(args, "inv_prompt", "")]
+        states = te.encode(prompts)
+        self._text_pe = {k: states[i:i + 1] for i, k in enumerate(names)}
+        self.neg_prompt_emb = self._text_pe["neg"]
+        return self._text_pe
 
     def _get_prompt_emb(self, prompt):
-        raise NotImplementedError("the T5 text encoder is outside this path: pass prompt embeddings (--prompt_emb_path)")
+        if self.text_encoder is None:
+            raise NotImplementedError("no text encoder on this run: pass --text_encoder_path (T5) or prompt embeddings "
+                                      "(--prompt_emb_path)")
+        return self.text_encoder.encode([prompt])
+
+    def _set_edit_prompt(self, edit_prompt):
+        """edit.py:1757 / :1886 (IF), :929-931 / :1055-1057 (SD): a driver's edit_prompt argument replaces the constructed
+        one (the text encoder runs; the next guidance call binds the new states)."""
+        if edit_prompt is not None and self.text_encoder is not None and edit_prompt != self.edit_prompt:
+            self.edit_prompt = edit_prompt
+            self.edit_prompt_emb = self._get_prompt_emb(edit_prompt)
 
     # ------------------------------------------------------------------ CFG noise (edit.py:1286-1373)
     def _classifer_free_guidance(self, latents, t, for_prompt_emb, edit_prompt_emb, null_prompt_emb, mode,
@@ -570,6 +610,7 @@ class EditDeepFloydIF(object):
     def run_edit_null_space_projection_xt(self, op, block_idx, vis_num, mask_index=0, vis_num_pc=1, vis_vT=False, pca_rank=50,
                                           edit_prompt=None, null_space_projection=False, pca_rank_null=50):
         """edit.py:1745-1868: unsupervised (non-semantic) directions of the CFG denoiser, null-space projected."""
+        self._set_edit_prompt(edit_prompt)
         self.scheduler.set_timesteps(self.for_steps)
         xT = self._xT()
         self.EXP_NAME = "original"
@@ -621,6 +662,7 @@ class EditDeepFloydIF(object):
                                                    pca_rank_null=50, jacobian=False):
         """edit.py:1871-2018: text-supervised direction (through the Jacobian or directly), projected onto the null
         space of the complement-mask Jacobian; ablations 'null-space-proj' and 'sega'."""
+        self._set_edit_prompt(edit_prompt)
         self.scheduler.set_timesteps(self.for_steps)
         xT = self._xT()
         if self.mask_type != "SAM":

@@ -104,8 +104,6 @@ class LatentCFGJacobianOperator:
 
 
 class EditStableDiffusion(EditDeepFloydIF):
-    text_encoder = None
-
     def __init__(self, args):
         super().__init__(args)
         # ---- the decoder network (vae.decode, edit.py:498): its own engine context
@@ -152,34 +150,16 @@ class EditStableDiffusion(EditDeepFloydIF):
         self.dataset = getattr(args, "dataset", None)
 
     # ------------------------------------------------------------------ prompts (edit.py:523-538, 1187-1194)
-    def _encode_run_prompts(self, args, cfg):
-        """--text_encoder_path: the CLIP text encoder on the GPU; ONE batched encode of the run's for / edit / null / neg /
-        inv prompts (edit.py:527-538).  Called from the base constructor before the branches bind their prompts."""
+    def _build_text_encoder(self, args, cfg):
+        """--text_encoder_path: the CLIP text encoder on the GPU (the base constructor encodes the run's prompts with it,
+        edit.py:527-538).  A T5 checkpoint, the encoder of the DeepFloyd IF path, is refused by its kind."""
         from .text_encoder import TextEncoder
         te = TextEncoder(args.text_encoder_path, tokenizer_path=getattr(args, "tokenizer_path", "") or None,
-                         device=args.device, max_prompts=5)
+                         device=args.device, max_prompts=5, expect="clip")
         if te.width != cfg.context_dim or te.length != cfg.context_len:
             raise ValueError(f"text encoder states {te.length} x {te.width} do not match the denoiser's cross-attention context "
                              f"{cfg.context_len} x {cfg.context_dim} (context_len x context_dim)")
-        self.text_encoder = te
-        names = ("for", "edit", "null", "neg", "inv")
-        prompts = [args.for_prompt, args.edit_prompt, "", getattr(args, "neg_prompt", ""), getattr(args, "inv_prompt", "")]
-        states = te.encode(prompts)
-        self._text_pe = {k: states[i:i + 1] for i, k in enumerate(names)}
-        self.neg_prompt_emb = self._text_pe["neg"]
-        return self._text_pe
-
-    def _get_prompt_emb(self, prompt):
-        if self.text_encoder is None:
-            return super()._get_prompt_emb(prompt)
-        return self.text_encoder.encode([prompt])
-
-    def _set_edit_prompt(self, edit_prompt):
-        """edit.py:929-931 / 1055-1057: a driver's edit_prompt argument replaces the constructed one (text encoder runs; the
-        next guidance call binds the new states)."""
-        if edit_prompt is not None and self.text_encoder is not None and edit_prompt != self.edit_prompt:
-            self.edit_prompt = edit_prompt
-            self.edit_prompt_emb = self._get_prompt_emb(edit_prompt)
+        return te
 
     # ------------------------------------------------------------------ encode (edit.py:594-597)
     def _encoder(self) -> LocoEngine:
