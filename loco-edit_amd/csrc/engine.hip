@@ -1,14 +1,15 @@
-// loco_ctx: the U-Net program (op list), parameter store, activation arenas and
-// the three passes (forward / tangent / cotangent) of the PMP-Jacobian operator,
-// plus the C ABI of include/loco_hip.h.
+// loco_ctx: the device side of the U-Net program (program.h / program.hip build it on the host): parameter store and
+// upload, activation arenas, per-context state, the three passes (forward / tangent / cotangent) of the PMP-Jacobian
+// operator, and the C ABI of include/loco_hip.h.
 //
-// Memory plan (HBM): every logical tensor of the network has a fixed offset in
-// a per-sample layout; an arena holds max_batch samples of that layout, so all
-// tensors share one batch stride.  Skip tensors are placed directly inside the
-// concatenation buffer of the up-block that consumes them (torch.cat of
-// reference diffusion.py:186 is never materialised).  Arena P holds the primal
-// pass (B images for DDIM loops, B=1 cached for the Jacobian), arena T is shared
-// by the tangent and the cotangent pass of a probe batch.
+// Memory plan (HBM): the program gives every logical tensor a fixed offset in a per-sample layout; an arena holds max_batch
+// samples of that layout, so all tensors share one batch stride.  Arena P holds the primal pass (B images for DDIM loops,
+// B=1 cached for the Jacobian), arena T is shared by the tangent and the cotangent pass of a probe batch.
+//
+// Three lifetimes, three places: the Program (immutable, one per configuration, shared by a context and its forks), the
+// Weights (device parameters in kernel layouts, written once by finalize_params of the root context, shared by its forks) and
+// the per-context state (arenas, statistics flags, kept partials, projected prompt states), which lives in the context's own
+// Tens / Op views of the program.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,6 +19,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <thread>
 #include <atomic>
 #include <string>
@@ -28,8 +30,10 @@
 #include "../../include/loco_hip_diag.h"
 #endif
 #include "kernels.h"
+#include "program.h"
 
 using namespace loco;
+
 
 #define HIPCHK(ctx, call)                                                                    \
     do {                                                                                     \
@@ -42,17 +46,6 @@ using namespace loco;
 
 namespace {
 
-struct Tens {
-    long off; int C, H, W;
-    int cons_op = -1, cons_norm = 0;   // op whose norm (1: n1, 2: nx) takes its statistics over exactly this tensor, or -1
-    // channel concatenation [cat_a | cat_b] consumed by a norm (the up-path ResBlocks read torch.cat([h, skip])): the two
-    // parts are tensors of their own, each written by its own conv.  A part keeps the {mean, M2} tile partials its producer's
-    // epilogue took (keep, keep_ntile > 0 in the forward pass that wrote them) so the norm over the concatenation can be
-    // finalised from both parts' partials instead of re-reading the tensor (gn_fused_finalize_cat_kernel).
-    int cat_a = -1, cat_b = -1, cat_of = -1;
-    float* keep = nullptr; size_t keep_floats = 0; int keep_ntile = 0;
-};
-
 struct ConvP {       // one convolution's parameters in kernel layouts
     float* wf = nullptr;    // forward  [Cin][taps][CoutP]
     float* wd = nullptr;    // dgrad    [Cout][taps][CinP]  (flipped taps)
@@ -63,78 +56,61 @@ struct ConvP {       // one convolution's parameters in kernel layouts
     float* bias = nullptr;
     int cin = 0, cout = 0, taps = 0;
 };
-struct NormP {
-    float* gamma = nullptr; float* beta = nullptr; int C = 0;
-    long soff = 0;      // offset into a stats arena
-    long sx_off = -1;   // offset (in float2) into the primal {S, xhat} cache, -1: none
-    bool ready = false; // statistics of the current pass were delivered with the producing conv (run_conv StatReq)
-    float eps = 0.f;    // 0: cfg.gn_eps; the SpatialTransformer's GroupNorm has its own (1e-6)
-};
-inline float eps_of(const loco_ctx* c, const NormP& n);
+struct NormW { float* gamma = nullptr; float* beta = nullptr; };
 
-enum OpKind { OP_CONV_IN, OP_RES, OP_ATTN, OP_DOWN, OP_UP, OP_OUT, OP_CONV, OP_XFMR };   // OP_CONV: plain 3x3 conv, tensor -> tensor
-// OP_XFMR tensors (latent-diffusion SpatialTransformer, depth 1), all [C][T] unless noted
-enum XT { X_G0, X_H0, X_A1, X_QKV, X_S, X_O, X_H1, X_A2, X_XQ, X_XS, X_XO, X_H2, X_A3, X_F, X_GG, X_H3, X_LN1, X_LN2, X_LN3, X_NT };
-
-struct Op {
-    OpKind kind;
-    std::string name;
-    int in = -1, out = -1;        // tensor ids
-    int h1 = -1, a1 = -1;         // RES: conv1 output; cotangent scratch with the input's shape
-    int hn = -1, qkv = -1, S = -1, o = -1;   // ATTN
-    int up = -1;                  // UP: cotangent scratch at the upsampled size
-    int ap = -1, xu = -1;         // ADM up/down ResBlock: pooled activation (down), resampled shortcut input
-    int updown = 0;               // RES: 0 none, 1 down (avg-pool 2x2 on both branches), 2 up (nearest x2)
-    bool scale_shift = false;     // RES: GN(h)*(1+scale)+shift from the embedding (ADM); else conv1 += Linear(temb) (DDPM)
-    int heads = 1;                // ATTN
-    int ksize = 3;                // CONV_IN: 3 (conv_in of the denoisers) or 1 (post_quant_conv of the latent decoder)
-    // ATTN with a text cross-attention stage behind it (cfg.context_dim > 0): xmid = output of the self-attention
-    // stage, xhn = GN(xmid), xq = q projection [C][T], xS = scores / probabilities [heads][T][Lp], xo = attended values
-    bool has_x = false;
-    int xmid = -1, xhn = -1, xq = -1, xS = -1, xo = -1;
-    NormP nx;
-    ConvP xqc, xproj;
-    float *xkw = nullptr, *xkb = nullptr, *xvw = nullptr, *xvb = nullptr;   // key / value projections of the context [C][D], [C]
-    float *xK = nullptr, *xV = nullptr;                                     // projected context [C][Lp] (loco_set_context)
-    // DeepFloyd-IF attention (cfg.added_kv): keys / values = [text ; image] in one softmax.  The text part reuses xkw .. xV
-    // (encoder_kv rows of head h: [k_h | v_h]) behind the block's own GroupNorm of the states (xng / xnb, `norm_encoder`);
-    // S is [heads][T][Lp + T] with the (padded, masked) text columns first
-    bool added_kv = false;
-    float *xng = nullptr, *xnb = nullptr;
-    bool in_is_skip = false;
-    bool has_nin = false;
-    bool has_temb = true;         // RES: false for the embedding-free blocks of the decoder (arch 2)
-    // parameter name stems in the reference state_dict
-    std::string pn_n1, pn_c1, pn_emb, pn_n2, pn_c2, pn_skip, pn_qkv, pn_proj, pn_conv;
+// One op's device parameters: written by finalize_params of the root context, read-only afterwards, copied as one value into
+// the Op views of the root and of every fork (bind_weights).  A field added here reaches the forks without further code.
+struct OpWeights {
     ConvP c1, c2, nin, qkvc, proj, conv;     // conv: CONV_IN / DOWN / UP / OUT
-    NormP n1, n2;                 // RES norm1/norm2, ATTN norm (n1), OUT norm_out (n1)
-    long tproj_off = 0;           // RES: offset into the concatenated temb projections
-    bool sym_down = false;        // DOWN: conv3 stride 2 with symmetric padding 1 (guided-diffusion Downsample) instead of (0,1,0,1)
-    // XFMR: tensors, the three LayerNorms, the linear maps (as 1x1 convs over [C][T])
-    int xt[X_NT] = {};
-    float *lng[3] = {nullptr, nullptr, nullptr}, *lnb[3] = {nullptr, nullptr, nullptr};
-    ConvP pj_in, to_out1, to_out2, ff1, ff2, pj_out;   // qkvc = fused [to_q; to_k; to_v] of attn1 (per-head rows), xqc = attn2.to_q
+    ConvP xqc, xproj;                        // cross-attention q and output projection
+    ConvP pj_in, to_out1, to_out2, ff1, ff2, pj_out;   // XFMR linear maps (as 1x1 convs over [C][T]); qkvc = fused [to_q; to_k; to_v]
+                                                       // of attn1 (per-head rows), xqc = attn2.to_q
+    NormW g1, g2, gx;                        // gamma / beta of the plan's n1 / n2 / nx
+    float *xkw = nullptr, *xkb = nullptr, *xvw = nullptr, *xvb = nullptr;   // key / value projections of the context [C][D], [C]
+    float *xng = nullptr, *xnb = nullptr;    // added_kv: `norm_encoder` of the states
+    float *lng[3] = {nullptr, nullptr, nullptr}, *lnb[3] = {nullptr, nullptr, nullptr};   // XFMR LayerNorms
+    long tproj_off = 0;                      // RES: offset into the concatenated temb projections
+};
+struct Weights {
+    std::vector<OpWeights> op;               // indexed like Program::ops
+    float *freq = nullptr, *td0w = nullptr, *td0b = nullptr, *td1w = nullptr, *td1b = nullptr;   // time embedding
+    float *tp_w = nullptr, *tp_b = nullptr;  // concatenated temb_proj
+    long tproj_total = 0;
+    double flops = 0.0;
+};
+
+// A context's views of the program, indexed like Program::tens / ::ops: the plan (copied), the weights (bound by bind_weights)
+// and the state that belongs to this context alone (allocated by alloc_state).
+struct Tens : TensPlan {
+    // a concatenation part keeps the {mean, M2} tile partials its producer's epilogue took (keep_ntile > 0 in the forward pass
+    // that wrote them) so the norm over the concatenation can be finalised from both parts' partials instead of re-reading the
+    // tensor (gn_fused_finalize_cat_kernel)
+    float* keep = nullptr; size_t keep_floats = 0; int keep_ntile = 0;
+};
+struct NormP : NormPlan, NormW {
+    bool ready = false; // statistics of the current pass were delivered with the producing conv (run_conv StatReq)
+};
+struct Op : OpPlan, OpWeights {
+    NormP n1, n2, nx;                        // OpPlan's norms (hidden by these) + their gamma / beta + this context's flags
+    float *xK = nullptr, *xV = nullptr;      // projected context [C][Lp] (loco_set_context)
 };
 
 struct HostParam { std::vector<float> data; std::vector<int64_t> shape; bool loaded = false; };
 
 }  // namespace
 
+
 struct loco_ctx {
-    loco_unet_cfg cfg;
+    loco_unet_cfg cfg;             // prog->cfg with this context's max_batch
     std::string err;
     std::map<std::string, HostParam> params;
-    std::vector<std::string> param_order;
     bool finalized = false;
 
-    std::vector<Tens> tens;
+    std::shared_ptr<const Program> prog;   // a fork shares its root's (same configuration; max_batch does not enter the layout)
+    std::shared_ptr<Weights> wts;           // the root's; written by its finalize_params only
+    std::vector<Tens> tens;                // this context's views, see Tens / Op
     std::vector<Op> ops;
-    long per_sample = 0;       // floats per sample in an activation arena
-    long stats_per_sample = 0; // floats per sample in a stats arena
-    long tproj_total = 0;
-    int n_in = 0;              // C*H*W of the network input (image / latent)
-    int n_out = 0;             // C*H*W of the network output (= n_in for the denoisers; the decoded image for arch 2)
-    int eps_t = -1;            // tensor id of the network output
+
 
     float *arenaP = nullptr, *arenaT = nullptr;
     float *statsP = nullptr, *statsT = nullptr;
@@ -147,28 +123,22 @@ struct loco_ctx {
     bool deep1 = true;             // LOCO_DEEP1=0: 1x1 operators on the two-buffer stage loop instead of the register ring (A/B)
     bool flash_attn = true;        // LOCO_FLASH_ATTN=0: tangent / cotangent attention on the generic GEMM + softmax-Jacobian path
     float* attn_delta = nullptr;   // [max_batch][heads][tokens] scratch of the flash cotangent (a lane's samples start at its first sample: LaneSwap)
-    long attn_dmax = 0;            // heads * tokens of the largest attention = the per-sample pitch of attn_delta
     float* partial = nullptr;      // split-K workspace
     size_t partial_floats = 0;
     const float* bench_out = nullptr; int64_t bench_out_count = 0;      // diag: output tensor of the last loco_bench_conv
-    float *tact = nullptr, *tproj = nullptr, *freq = nullptr;
-    float *tp_w = nullptr, *tp_b = nullptr;          // concatenated temb_proj
-    float *td0w = nullptr, *td0b = nullptr, *td1w = nullptr, *td1b = nullptr;
+    float *tact = nullptr, *tproj = nullptr;
     float* eps_buf = nullptr;      // [max_batch][n]
     float* gx0 = nullptr;          // [max_batch][n] direct cotangent term
     float* ge = nullptr;           // [max_batch][n] cotangent seed of eps
     float* tmpA = nullptr;         // [64][n] temp for solver rotations
     double *G = nullptr, *Q = nullptr, *W = nullptr, *gscratch = nullptr;
     float* alphas = nullptr;
-    int ctx_Lp = 0;                // context length padded to a multiple of 64 (score row length of the cross-attention)
     float* ctx_colbias = nullptr;  // [Lp]: 0 for real tokens, -1e30 for the padding
     bool has_ctx = false;
     float* cond_add = nullptr;     // [temb_ch] conditioning embedding of the time embedding (loco_set_cond)
     float* ctx_norm = nullptr;     // [context_len][context_dim] scratch: the states behind one block's norm_encoder (added_kv)
-    float res_scale = 1.f;         // cfg.res_scale (0 -> 1): ResBlock output = (shortcut + h) * res_scale
     bool has_cond = false;
     float2* sxcache = nullptr;     // primal {S, xhat} per GroupNorm+SiLU input (bf16x3 path)
-    long sx_total = 0;
     int prec = 0;                  // 0: exact fp32 MFMA, 1: split-bf16 (bf16x3) MFMA, 2: single f16 MFMA
     std::vector<float*> owned;     // everything to hipFree
     size_t bytes = 0;
@@ -186,7 +156,6 @@ struct loco_ctx {
     long mask_L = 0;               // host copy, -1 = not read back yet
     hipStream_t mask_stream = nullptr;
     int primal_B = 0;
-    double flops = 0.0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // second lane (probe groups of one tangent / cotangent pass on two streams, see run_lanes)
     int n_streams = 1;
@@ -245,682 +214,8 @@ int dalloc(loco_ctx* c, T** p, size_t count) {
     return 0;
 }
 
-long align4(long v) { return (v + 63) & ~63L; }
-
-int new_tensor(loco_ctx* c, int C, int H, int W, long off = -1) {
-    Tens t;
-    t.C = C; t.H = H; t.W = W;
-    if (off < 0) {
-        t.off = c->per_sample;
-        c->per_sample += align4((long)C * H * W);
-    } else {
-        t.off = off;
-    }
-    c->tens.push_back(t);
-    return (int)c->tens.size() - 1;
-}
 inline float eps_of(const loco_ctx* c, const NormP& n) { return n.eps > 0.f ? n.eps : c->cfg.gn_eps; }
-NormP new_norm(loco_ctx* c, int C) {
-    NormP n;
-    n.C = C;
-    n.soff = c->stats_per_sample;
-    // layout per norm: sc[C], sh[C], mr[2G], tst[2G], tc[2C]
-    c->stats_per_sample += align4(4L * C + 4L * c->cfg.gn_groups);
-    return n;
-}
-void norm_cache(loco_ctx* c, NormP& n, int HW) {
-    n.sx_off = c->sx_total;
-    c->sx_total += (long)n.C * HW;
-}
-bool attn_at(const loco_unet_cfg& cfg, int res) {
-    for (int i = 0; i < cfg.num_attn_res; ++i)
-        if (cfg.attn_resolutions[i] == res) return true;
-    return false;
-}
 
-int build_program_adm(loco_ctx* c);
-int build_program_dec(loco_ctx* c);
-int build_program_enc(loco_ctx* c);
-
-// Build the op list + memory plan (mirrors DDPM.__init__/forward, reference diffusion.py:22-200)
-int build_program(loco_ctx* c) {
-    if (c->cfg.arch == 1) return build_program_adm(c);
-    if (c->cfg.arch == 2) return build_program_dec(c);
-    if (c->cfg.arch == 3) return build_program_enc(c);
-    const loco_unet_cfg& cfg = c->cfg;
-    const int ch = cfg.ch, nres = cfg.num_levels, R = cfg.resolution;
-    c->n_in = cfg.in_channels * R * R;
-    c->n_out = cfg.out_ch * R * R;
-    auto add_attn = [&](const std::string& name, int in_t, int out_t) {
-        Op a; a.kind = OP_ATTN; a.name = name; a.in = in_t; a.out = out_t;
-        const Tens& t = c->tens[in_t];
-        int T = t.H * t.W;
-        a.hn = new_tensor(c, t.C, t.H, t.W);
-        a.qkv = new_tensor(c, 3 * t.C, t.H, t.W);
-        a.S = new_tensor(c, 1, T, T);
-        a.o = new_tensor(c, t.C, t.H, t.W);
-        a.n1 = new_norm(c, t.C);
-        c->ops.push_back(a);
-    };
-    // ---- pass 1: shapes of the skip stack, to place skips inside concat buffers
-    struct Skip { int C, H; };
-    std::vector<Skip> hs;
-    {
-        int res = R;
-        hs.push_back({ch, res});
-        for (int l = 0; l < nres; ++l) {
-            for (int b = 0; b < cfg.num_res_blocks; ++b) hs.push_back({ch * cfg.ch_mult[l], res});
-            if (l != nres - 1) { res /= 2; hs.push_back({ch * cfg.ch_mult[l], res}); }
-        }
-    }
-    // up path consumption order: pops from the back
-    // concat buffer j (j-th up block) = [h_prev (C1) | skip hs[n-1-j] (C2)]
-    const int nskip = (int)hs.size();
-    std::vector<int> cat_t(nskip), skip_t(nskip), hprev_t(nskip);
-    {
-        int res = hs.back().H;
-        int block_in = ch * cfg.ch_mult[nres - 1];
-        int j = 0;
-        for (int l = nres - 1; l >= 0; --l) {
-            int block_out = ch * cfg.ch_mult[l];
-            for (int b = 0; b < cfg.num_res_blocks + 1; ++b) {
-                const Skip& sk = hs[nskip - 1 - j];
-                int C1 = block_in, C2 = sk.C;
-                if (sk.H != res) { c->err = "internal: skip resolution mismatch"; return -1; }
-                int cat = new_tensor(c, C1 + C2, res, res);
-                long base = c->tens[cat].off;
-                cat_t[j] = cat;
-                hprev_t[j] = new_tensor(c, C1, res, res, base);
-                skip_t[nskip - 1 - j] = new_tensor(c, C2, res, res, base + (long)C1 * res * res);
-                block_in = block_out;
-                ++j;
-            }
-            if (l != 0) res *= 2;
-        }
-    }
-    // ---- pass 2: ops
-    int res = R;
-    int si = 0;   // skip index
-    {
-        Op o; o.kind = OP_CONV_IN; o.name = "conv_in"; o.in = -1; o.out = skip_t[si++];
-        c->ops.push_back(o);
-    }
-    int block_in = ch;
-    int cur = skip_t[0];
-    for (int l = 0; l < nres; ++l) {
-        int block_out = ch * cfg.ch_mult[l];
-        for (int b = 0; b < cfg.num_res_blocks; ++b) {
-            Op r; r.kind = OP_RES; r.name = "down." + std::to_string(l) + ".block." + std::to_string(b);
-            r.in = cur; r.in_is_skip = true;
-            r.has_nin = (block_in != block_out);
-            bool at = attn_at(cfg, res);
-            int out_t = at ? new_tensor(c, block_out, res, res) : skip_t[si];
-            r.out = out_t;
-            r.h1 = new_tensor(c, block_out, res, res);
-            r.a1 = new_tensor(c, block_in, res, res);
-            r.n1 = new_norm(c, block_in); r.n2 = new_norm(c, block_out);
-            c->ops.push_back(r);
-            if (at) add_attn("down." + std::to_string(l) + ".attn." + std::to_string(b), out_t, skip_t[si]);
-            cur = skip_t[si++];
-            block_in = block_out;
-        }
-        if (l != nres - 1) {
-            Op d; d.kind = OP_DOWN; d.name = "down." + std::to_string(l) + ".downsample.conv";
-            d.in = cur; d.in_is_skip = true; d.out = skip_t[si];
-            c->ops.push_back(d);
-            cur = skip_t[si++];
-            res /= 2;
-        }
-    }
-    // middle
-    {
-        Op r; r.kind = OP_RES; r.name = "mid.block_1"; r.in = cur; r.in_is_skip = true; r.has_nin = false;
-        r.out = new_tensor(c, block_in, res, res);
-        r.h1 = new_tensor(c, block_in, res, res); r.a1 = new_tensor(c, block_in, res, res);
-        r.n1 = new_norm(c, block_in); r.n2 = new_norm(c, block_in);
-        c->ops.push_back(r);
-        int a_out = new_tensor(c, block_in, res, res);
-        add_attn("mid.attn_1", r.out, a_out);
-        Op r2; r2.kind = OP_RES; r2.name = "mid.block_2"; r2.in = a_out; r2.has_nin = false;
-        r2.out = hprev_t[0];
-        r2.h1 = new_tensor(c, block_in, res, res); r2.a1 = new_tensor(c, block_in, res, res);
-        r2.n1 = new_norm(c, block_in); r2.n2 = new_norm(c, block_in);
-        c->ops.push_back(r2);
-    }
-    // up path
-    {
-        int j = 0;
-        for (int l = nres - 1; l >= 0; --l) {
-            int block_out = ch * cfg.ch_mult[l];
-            for (int b = 0; b < cfg.num_res_blocks + 1; ++b) {
-                Op r; r.kind = OP_RES; r.name = "up." + std::to_string(l) + ".block." + std::to_string(b);
-                r.in = cat_t[j];
-                int cin = c->tens[cat_t[j]].C;
-                r.has_nin = (cin != block_out);
-                bool at = attn_at(cfg, res);
-                bool last_of_level = (b == cfg.num_res_blocks);
-                bool final_block = (l == 0 && last_of_level);
-                // where does the block's (or its attention's) output go?
-                int dest;
-                if (final_block) dest = new_tensor(c, block_out, res, res);
-                else if (last_of_level) dest = new_tensor(c, block_out, res, res);   // feeds the upsample conv
-                else dest = hprev_t[j + 1];
-                int out_t = at ? new_tensor(c, block_out, res, res) : dest;
-                r.out = out_t;
-                r.h1 = new_tensor(c, block_out, res, res);
-                r.a1 = new_tensor(c, cin, res, res);
-                r.n1 = new_norm(c, cin); r.n2 = new_norm(c, block_out);
-                c->ops.push_back(r);
-                if (at) add_attn("up." + std::to_string(l) + ".attn." + std::to_string(b), out_t, dest);
-                cur = dest;
-                ++j;
-                if (last_of_level && l != 0) {
-                    Op u; u.kind = OP_UP; u.name = "up." + std::to_string(l) + ".upsample.conv";
-                    u.in = cur; u.out = hprev_t[j];
-                    u.up = new_tensor(c, block_out, res * 2, res * 2);
-                    c->ops.push_back(u);
-                    cur = u.out;
-                    res *= 2;
-                }
-            }
-        }
-    }
-    {
-        Op o; o.kind = OP_OUT; o.name = "conv_out"; o.in = cur;
-        o.out = new_tensor(c, cfg.out_ch, R, R);
-        o.a1 = new_tensor(c, c->tens[cur].C, R, R);
-        o.n1 = new_norm(c, c->tens[cur].C);
-        c->ops.push_back(o);
-        c->eps_t = o.out;
-    }
-    for (auto& op : c->ops) {
-        if (op.kind == OP_RES) {
-            const Tens& ti = c->tens[op.in];
-            norm_cache(c, op.n1, ti.H * ti.W);
-            norm_cache(c, op.n2, ti.H * ti.W);
-            op.pn_n1 = op.name + ".norm1"; op.pn_c1 = op.name + ".conv1"; op.pn_emb = op.name + ".temb_proj";
-            op.pn_n2 = op.name + ".norm2"; op.pn_c2 = op.name + ".conv2"; op.pn_skip = op.name + ".nin_shortcut";
-        } else if (op.kind == OP_ATTN) {
-            op.pn_n1 = op.name + ".norm"; op.pn_proj = op.name + ".proj_out";
-        } else if (op.kind == OP_OUT) {
-            const Tens& ti = c->tens[op.in];
-            norm_cache(c, op.n1, ti.H * ti.W);
-            op.pn_n1 = "norm_out"; op.pn_conv = "conv_out";
-        } else {
-            op.pn_conv = op.name;
-        }
-    }
-    return 0;
-}
-
-
-// guided-diffusion / P2 U-Net (reference guided_diffusion/unet.py:398-684 with P2_DICT script_util.py:166-190):
-// input_blocks = conv, then per level {ResBlock [+Attention]} x num_res_blocks and a ResBlock(down) between levels;
-// middle = Res, Attn, Res; output_blocks = {ResBlock(cat) [+Attention] [+ResBlock(up)]}; out = GN, SiLU, conv.
-int build_program_adm(loco_ctx* c) {
-    const loco_unet_cfg& cfg = c->cfg;
-    const int mc = cfg.ch, nlev = cfg.num_levels, R = cfg.resolution;
-    c->n_in = cfg.in_channels * R * R;
-    c->n_out = cfg.out_ch * R * R;
-    c->ctx_Lp = cfg.context_dim > 0 ? ((cfg.context_len + 63) / 64) * 64 : 0;
-    auto heads_of = [&](int C) { return cfg.num_heads > 0 ? cfg.num_heads : (cfg.num_head_channels > 0 ? C / cfg.num_head_channels : 1); };
-    auto add_res = [&](const std::string& name, int in_t, int out_t, int updown, bool in_is_skip) {
-        Op r; r.kind = OP_RES; r.name = name; r.in = in_t; r.out = out_t; r.updown = updown;
-        r.scale_shift = cfg.scale_shift_norm != 0; r.in_is_skip = in_is_skip;
-        const Tens ti = c->tens[in_t];
-        const Tens to = c->tens[out_t];
-        r.has_nin = (ti.C != to.C);
-        r.h1 = new_tensor(c, to.C, to.H, to.W);
-        r.a1 = new_tensor(c, ti.C, ti.H, ti.W);
-        if (updown) { r.xu = new_tensor(c, ti.C, to.H, to.W); }
-        if (updown == 1) { r.ap = new_tensor(c, ti.C, to.H, to.W); }
-        r.n1 = new_norm(c, ti.C); r.n2 = new_norm(c, to.C);
-        r.pn_n1 = name + ".in_layers.0"; r.pn_c1 = name + ".in_layers.2"; r.pn_emb = name + ".emb_layers.1";
-        r.pn_n2 = name + ".out_layers.0"; r.pn_c2 = name + ".out_layers.3"; r.pn_skip = name + ".skip_connection";
-        c->ops.push_back(r);
-    };
-    auto add_xfmr = [&](const std::string& name, int in_t, int out_t) {
-        Op a; a.kind = OP_XFMR; a.name = name; a.in = in_t; a.out = out_t;
-        const Tens t = c->tens[in_t];
-        const int T = t.H * t.W, C = t.C;
-        a.heads = heads_of(C);
-        a.has_x = true;
-        auto ct = [&](int ch) { return new_tensor(c, ch, t.H, t.W); };
-        a.xt[X_G0] = ct(C); a.xt[X_H0] = ct(C); a.xt[X_A1] = ct(C); a.xt[X_QKV] = ct(3 * C);
-        a.xt[X_S] = new_tensor(c, a.heads, T, T); a.xt[X_O] = ct(C); a.xt[X_H1] = ct(C); a.xt[X_A2] = ct(C);
-        a.xt[X_XQ] = ct(C); a.xt[X_XS] = new_tensor(c, a.heads, T, c->ctx_Lp); a.xt[X_XO] = ct(C); a.xt[X_H2] = ct(C);
-        a.xt[X_A3] = ct(C); a.xt[X_F] = ct(8 * C); a.xt[X_GG] = ct(4 * C); a.xt[X_H3] = ct(C);
-        a.xt[X_LN1] = new_tensor(c, 2, 1, T); a.xt[X_LN2] = new_tensor(c, 2, 1, T); a.xt[X_LN3] = new_tensor(c, 2, 1, T);
-        // the attention helpers address the block through the ATTN field names
-        a.qkv = a.xt[X_QKV]; a.S = a.xt[X_S]; a.o = a.xt[X_O]; a.xq = a.xt[X_XQ]; a.xS = a.xt[X_XS]; a.xo = a.xt[X_XO];
-        a.n1 = new_norm(c, C); a.n1.eps = 1e-6f;
-        a.pn_n1 = name + ".norm";
-        c->ops.push_back(a);
-    };
-    auto add_attn = [&](const std::string& name, int in_t, int out_t) {
-        if (cfg.transformer_depth > 0) { add_xfmr(name, in_t, out_t); return; }
-        Op a; a.kind = OP_ATTN; a.name = name; a.in = in_t; a.out = out_t;
-        const Tens t = c->tens[in_t];
-        int T = t.H * t.W;
-        a.heads = heads_of(t.C);
-        a.hn = new_tensor(c, t.C, t.H, t.W);
-        a.qkv = new_tensor(c, 3 * t.C, t.H, t.W);
-        a.added_kv = cfg.added_kv != 0;
-        a.S = new_tensor(c, a.heads, T, a.added_kv ? c->ctx_Lp + T : T);
-        a.o = new_tensor(c, t.C, t.H, t.W);
-        a.n1 = new_norm(c, t.C);
-        a.pn_n1 = name + ".norm"; a.pn_qkv = name + ".qkv"; a.pn_proj = name + ".proj_out";
-        if (cfg.context_dim > 0 && !a.added_kv) {
-            a.has_x = true;
-            a.xmid = new_tensor(c, t.C, t.H, t.W);
-            a.xhn = new_tensor(c, t.C, t.H, t.W);
-            a.xq = new_tensor(c, t.C, t.H, t.W);
-            a.xS = new_tensor(c, a.heads, T, c->ctx_Lp);
-            a.xo = new_tensor(c, t.C, t.H, t.W);
-            a.nx = new_norm(c, t.C);
-        }
-        c->ops.push_back(a);
-    };
-    // pass 1: skip stack (channels, resolution) in push order
-    struct Skip { int C, H; };
-    std::vector<Skip> hs;
-    {
-        int ch = mc * cfg.ch_mult[0], res = R;
-        hs.push_back({ch, res});
-        for (int l = 0; l < nlev; ++l) {
-            for (int b = 0; b < cfg.num_res_blocks; ++b) { ch = mc * cfg.ch_mult[l]; hs.push_back({ch, res}); }
-            if (l != nlev - 1) { res /= 2; hs.push_back({ch, res}); }
-        }
-    }
-    const int nskip = (int)hs.size();
-    std::vector<int> cat_t(nskip), skip_t(nskip), hprev_t(nskip);
-    {
-        int res = hs.back().H, ch = hs.back().C, j = 0;
-        for (int l = nlev - 1; l >= 0; --l) {
-            for (int i = 0; i < cfg.num_res_blocks + 1; ++i) {
-                const Skip& sk = hs[nskip - 1 - j];
-                if (sk.H != res) { c->err = "internal: skip resolution mismatch (adm)"; return -1; }
-                int cat = new_tensor(c, ch + sk.C, res, res);
-                long base = c->tens[cat].off;
-                cat_t[j] = cat;
-                hprev_t[j] = new_tensor(c, ch, res, res, base);
-                skip_t[nskip - 1 - j] = new_tensor(c, sk.C, res, res, base + (long)ch * res * res);
-                ch = mc * cfg.ch_mult[l];
-                if (l && i == cfg.num_res_blocks) res *= 2;
-                ++j;
-            }
-        }
-    }
-    // pass 2: ops
-    int si = 0, res = R, ib = 1;
-    {
-        Op o; o.kind = OP_CONV_IN; o.name = "input_blocks.0.0"; o.out = skip_t[si++]; o.pn_conv = "input_blocks.0.0";
-        c->ops.push_back(o);
-    }
-    int cur = skip_t[0];
-    int ch = mc * cfg.ch_mult[0];
-    for (int l = 0; l < nlev; ++l) {
-        for (int b = 0; b < cfg.num_res_blocks; ++b) {
-            int cout = mc * cfg.ch_mult[l];
-            bool at = attn_at(cfg, res);
-            std::string nm = "input_blocks." + std::to_string(ib);
-            int out_t = at ? new_tensor(c, cout, res, res) : skip_t[si];
-            add_res(nm + ".0", cur, out_t, 0, true);
-            if (at) add_attn(nm + ".1", out_t, skip_t[si]);
-            cur = skip_t[si++]; ch = cout; ++ib;
-        }
-        if (l != nlev - 1) {
-            std::string nm = "input_blocks." + std::to_string(ib);
-            if (cfg.resblock_updown) {
-                add_res(nm + ".0", cur, skip_t[si], 1, true);
-            } else {        // Downsample(use_conv=True): conv3 stride 2 padding 1 (unet.py:113-142)
-                Op d; d.kind = OP_DOWN; d.name = nm + ".0.op"; d.pn_conv = d.name; d.in = cur; d.in_is_skip = true;
-                d.out = skip_t[si]; d.sym_down = true;
-                c->ops.push_back(d);
-            }
-            cur = skip_t[si++]; ++ib; res /= 2;
-        }
-    }
-    {
-        int t0 = new_tensor(c, ch, res, res);
-        add_res("middle_block.0", cur, t0, 0, true);
-        int t1 = new_tensor(c, ch, res, res);
-        add_attn("middle_block.1", t0, t1);
-        add_res("middle_block.2", t1, hprev_t[0], 0, false);
-    }
-    {
-        int j = 0, ob = 0;
-        for (int l = nlev - 1; l >= 0; --l) {
-            for (int i = 0; i < cfg.num_res_blocks + 1; ++i) {
-                int cout = mc * cfg.ch_mult[l];
-                bool at = attn_at(cfg, res);
-                bool has_up = (l != 0 && i == cfg.num_res_blocks);
-                bool final_block = (l == 0 && i == cfg.num_res_blocks);
-                std::string nm = "output_blocks." + std::to_string(ob);
-                // destination of the block's last op
-                int dest = final_block ? new_tensor(c, cout, res, res) : -1;
-                int sub = 1;
-                int res_out = (at || has_up) ? new_tensor(c, cout, res, res) : (final_block ? dest : hprev_t[j + 1]);
-                add_res(nm + ".0", cat_t[j], res_out, 0, false);
-                int last = res_out;
-                if (at) {
-                    int a_out = has_up ? new_tensor(c, cout, res, res) : (final_block ? dest : hprev_t[j + 1]);
-                    add_attn(nm + "." + std::to_string(sub++), last, a_out);
-                    last = a_out;
-                }
-                if (has_up) {
-                    if (cfg.resblock_updown) {
-                        add_res(nm + "." + std::to_string(sub++), last, hprev_t[j + 1], 2, false);
-                    } else {    // Upsample(use_conv=True): nearest x2 + conv3 (unet.py:83-110)
-                        Op u; u.kind = OP_UP; u.name = nm + "." + std::to_string(sub++) + ".conv"; u.pn_conv = u.name;
-                        u.in = last; u.out = hprev_t[j + 1];
-                        u.up = new_tensor(c, cout, res * 2, res * 2);
-                        c->ops.push_back(u);
-                    }
-                    last = hprev_t[j + 1];
-                    res *= 2;
-                }
-                cur = last; ch = cout;
-                ++j; ++ob;
-            }
-        }
-    }
-    {
-        Op o; o.kind = OP_OUT; o.name = "out"; o.in = cur;
-        o.out = new_tensor(c, cfg.out_ch, R, R);
-        o.a1 = new_tensor(c, c->tens[cur].C, R, R);
-        o.n1 = new_norm(c, c->tens[cur].C);
-        o.pn_n1 = "out.0"; o.pn_conv = "out.2";
-        c->ops.push_back(o);
-        c->eps_t = o.out;
-    }
-    for (auto& op : c->ops) {
-        if (op.kind == OP_RES) {
-            const Tens& ti = c->tens[op.in];
-            const Tens& to = c->tens[op.out];
-            norm_cache(c, op.n1, ti.H * ti.W);
-            norm_cache(c, op.n2, to.H * to.W);
-        } else if (op.kind == OP_OUT) {
-            const Tens& ti = c->tens[op.in];
-            norm_cache(c, op.n1, ti.H * ti.W);
-        }
-    }
-    return 0;
-}
-
-// Latent decoder (arch 2): the `Decoder` of the latent-diffusion autoencoder that `vae.decode` runs in the reference's
-// Stable Diffusion path (edit.py:750, 770-771; diffusers AutoencoderKL, un-vendored -- same module tree as the DDPM
-// U-Net's up half without skips and without a time embedding): conv_in (z_channels -> ch*ch_mult[-1]) at the latent
-// resolution R; mid.block_1, mid.attn_1, mid.block_2; for each level from the coarsest: num_res_blocks + 1
-// ResnetBlocks [+ attention at cfg.attn_resolutions] and, except at level 0, nearest x2 + conv3; norm_out, SiLU,
-// conv_out.  Output [out_ch, R * 2^(levels-1), same].
-int build_program_dec(loco_ctx* c) {
-    const loco_unet_cfg& cfg = c->cfg;
-    const int ch = cfg.ch, nlev = cfg.num_levels, R = cfg.resolution;
-    const int Rout = R << (nlev - 1);
-    c->n_in = cfg.in_channels * R * R;
-    c->n_out = cfg.out_ch * Rout * Rout;
-    auto add_res = [&](const std::string& name, int in_t, int cout) {
-        Op r; r.kind = OP_RES; r.name = name; r.in = in_t; r.has_temb = false;
-        const Tens ti = c->tens[in_t];
-        r.has_nin = (ti.C != cout);
-        r.out = new_tensor(c, cout, ti.H, ti.W);
-        r.h1 = new_tensor(c, cout, ti.H, ti.W);
-        r.a1 = new_tensor(c, ti.C, ti.H, ti.W);
-        r.n1 = new_norm(c, ti.C); r.n2 = new_norm(c, cout);
-        c->ops.push_back(r);
-        return r.out;
-    };
-    auto add_attn = [&](const std::string& name, int in_t) {
-        Op a; a.kind = OP_ATTN; a.name = name; a.in = in_t;
-        const Tens t = c->tens[in_t];
-        const int T = t.H * t.W;
-        a.out = new_tensor(c, t.C, t.H, t.W);
-        a.hn = new_tensor(c, t.C, t.H, t.W);
-        a.qkv = new_tensor(c, 3 * t.C, t.H, t.W);
-        a.S = new_tensor(c, 1, T, T);
-        a.o = new_tensor(c, t.C, t.H, t.W);
-        a.n1 = new_norm(c, t.C);
-        c->ops.push_back(a);
-        return a.out;
-    };
-    int res = R, block_in = ch * cfg.ch_mult[nlev - 1];
-    int cur;
-    {   // AutoencoderKL.decode = decoder(post_quant_conv(z)): the 1x1 conv on the latent channels comes first
-        Op o; o.kind = OP_CONV_IN; o.name = "post_quant_conv"; o.in = -1; o.ksize = 1;
-        o.out = new_tensor(c, cfg.in_channels, res, res);
-        c->ops.push_back(o);
-        Op ci; ci.kind = OP_CONV; ci.name = "conv_in"; ci.in = o.out; ci.out = new_tensor(c, block_in, res, res);
-        c->ops.push_back(ci);
-        cur = ci.out;
-    }
-    cur = add_res("mid.block_1", cur, block_in);
-    cur = add_attn("mid.attn_1", cur);
-    cur = add_res("mid.block_2", cur, block_in);
-    for (int l = nlev - 1; l >= 0; --l) {
-        const int block_out = ch * cfg.ch_mult[l];
-        for (int b = 0; b < cfg.num_res_blocks + 1; ++b) {
-            cur = add_res("up." + std::to_string(l) + ".block." + std::to_string(b), cur, block_out);
-            if (attn_at(cfg, res)) cur = add_attn("up." + std::to_string(l) + ".attn." + std::to_string(b), cur);
-            block_in = block_out;
-        }
-        if (l != 0) {
-            Op u; u.kind = OP_UP; u.name = "up." + std::to_string(l) + ".upsample.conv";
-            u.in = cur; u.out = new_tensor(c, block_in, res * 2, res * 2);
-            u.up = new_tensor(c, block_in, res * 2, res * 2);
-            c->ops.push_back(u);
-            cur = u.out;
-            res *= 2;
-        }
-    }
-    {
-        Op o; o.kind = OP_OUT; o.name = "conv_out"; o.in = cur;
-        o.out = new_tensor(c, cfg.out_ch, Rout, Rout);
-        o.a1 = new_tensor(c, c->tens[cur].C, Rout, Rout);
-        o.n1 = new_norm(c, c->tens[cur].C);
-        c->ops.push_back(o);
-        c->eps_t = o.out;
-    }
-    for (auto& op : c->ops) {
-        if (op.kind == OP_RES) {
-            const Tens& ti = c->tens[op.in];
-            norm_cache(c, op.n1, ti.H * ti.W);
-            norm_cache(c, op.n2, ti.H * ti.W);
-            op.pn_n1 = op.name + ".norm1"; op.pn_c1 = op.name + ".conv1";
-            op.pn_n2 = op.name + ".norm2"; op.pn_c2 = op.name + ".conv2"; op.pn_skip = op.name + ".nin_shortcut";
-        } else if (op.kind == OP_ATTN) {
-            op.pn_n1 = op.name + ".norm"; op.pn_proj = op.name + ".proj_out";
-        } else if (op.kind == OP_OUT) {
-            const Tens& ti = c->tens[op.in];
-            norm_cache(c, op.n1, ti.H * ti.W);
-            op.pn_n1 = "norm_out"; op.pn_conv = "conv_out";
-        } else {
-            op.pn_conv = op.name;
-        }
-    }
-    return 0;
-}
-
-// Latent encoder (arch 3): `vae.encode` of the reference's latent inversion (edit.py:594-597; diffusers AutoencoderKL =
-// the latent-diffusion `Encoder` + `quant_conv`, un-vendored): conv_in at the image resolution R; per level num_res_blocks
-// embedding-free ResnetBlocks and, except on the last level, pad (0,1,0,1) + conv3 stride 2; mid block / attention / block;
-// norm_out, SiLU, conv_out (2 z channels: mean | log-variance), 1x1 quant_conv.  Output [out_ch, R >> (levels-1), same].
-int build_program_enc(loco_ctx* c) {
-    const loco_unet_cfg& cfg = c->cfg;
-    const int ch = cfg.ch, nlev = cfg.num_levels, R = cfg.resolution;
-    const int Rout = R >> (nlev - 1);
-    c->n_in = cfg.in_channels * R * R;
-    c->n_out = cfg.out_ch * Rout * Rout;
-    auto add_res = [&](const std::string& name, int in_t, int cout) {
-        Op r; r.kind = OP_RES; r.name = name; r.in = in_t; r.has_temb = false;
-        const Tens ti = c->tens[in_t];
-        r.has_nin = (ti.C != cout);
-        r.out = new_tensor(c, cout, ti.H, ti.W);
-        r.h1 = new_tensor(c, cout, ti.H, ti.W);
-        r.a1 = new_tensor(c, ti.C, ti.H, ti.W);
-        r.n1 = new_norm(c, ti.C); r.n2 = new_norm(c, cout);
-        c->ops.push_back(r);
-        return r.out;
-    };
-    int res = R, cur;
-    {
-        Op o; o.kind = OP_CONV_IN; o.name = "conv_in"; o.in = -1; o.out = new_tensor(c, ch, res, res);
-        c->ops.push_back(o);
-        cur = o.out;
-    }
-    for (int l = 0; l < nlev; ++l) {
-        const int block_out = ch * cfg.ch_mult[l];
-        for (int b = 0; b < cfg.num_res_blocks; ++b)
-            cur = add_res("down." + std::to_string(l) + ".block." + std::to_string(b), cur, block_out);
-        if (l != nlev - 1) {
-            Op d; d.kind = OP_DOWN; d.name = "down." + std::to_string(l) + ".downsample.conv"; d.in = cur;
-            d.out = new_tensor(c, block_out, res / 2, res / 2);
-            c->ops.push_back(d);
-            cur = d.out; res /= 2;
-        }
-    }
-    const int block_in = c->tens[cur].C;
-    cur = add_res("mid.block_1", cur, block_in);
-    {
-        Op a; a.kind = OP_ATTN; a.name = "mid.attn_1"; a.in = cur;
-        const Tens t = c->tens[cur];
-        const int T = t.H * t.W;
-        a.out = new_tensor(c, t.C, t.H, t.W);
-        a.hn = new_tensor(c, t.C, t.H, t.W);
-        a.qkv = new_tensor(c, 3 * t.C, t.H, t.W);
-        a.S = new_tensor(c, 1, T, T);
-        a.o = new_tensor(c, t.C, t.H, t.W);
-        a.n1 = new_norm(c, t.C);
-        c->ops.push_back(a);
-        cur = a.out;
-    }
-    cur = add_res("mid.block_2", cur, block_in);
-    {
-        Op o; o.kind = OP_OUT; o.name = "conv_out"; o.in = cur;
-        o.out = new_tensor(c, cfg.out_ch, Rout, Rout);
-        o.a1 = new_tensor(c, c->tens[cur].C, Rout, Rout);
-        o.n1 = new_norm(c, c->tens[cur].C);
-        c->ops.push_back(o);
-        Op q; q.kind = OP_CONV; q.name = "quant_conv"; q.ksize = 1; q.in = o.out; q.out = new_tensor(c, cfg.out_ch, Rout, Rout);
-        c->ops.push_back(q);
-        c->eps_t = q.out;
-    }
-    for (auto& op : c->ops) {
-        if (op.kind == OP_RES) {
-            const Tens& ti = c->tens[op.in];
-            norm_cache(c, op.n1, ti.H * ti.W);
-            norm_cache(c, op.n2, ti.H * ti.W);
-            op.pn_n1 = op.name + ".norm1"; op.pn_c1 = op.name + ".conv1";
-            op.pn_n2 = op.name + ".norm2"; op.pn_c2 = op.name + ".conv2"; op.pn_skip = op.name + ".nin_shortcut";
-        } else if (op.kind == OP_ATTN) {
-            op.pn_n1 = op.name + ".norm"; op.pn_proj = op.name + ".proj_out";
-        } else if (op.kind == OP_OUT) {
-            const Tens& ti = c->tens[op.in];
-            norm_cache(c, op.n1, ti.H * ti.W);
-            op.pn_n1 = "norm_out"; op.pn_conv = "conv_out";
-        } else {
-            op.pn_conv = op.name;
-        }
-    }
-    return 0;
-}
-
-void declare_param(loco_ctx* c, const std::string& name, std::vector<int64_t> shape) {
-    HostParam hp; hp.shape = shape;
-    c->params[name] = hp;
-    c->param_order.push_back(name);
-}
-void declare_conv(loco_ctx* c, const std::string& n, int cin, int cout, int k) {
-    declare_param(c, n + ".weight", {cout, cin, k, k});
-    declare_param(c, n + ".bias", {cout});
-}
-void declare_norm(loco_ctx* c, const std::string& n, int C) {
-    declare_param(c, n + ".weight", {C});
-    declare_param(c, n + ".bias", {C});
-}
-void declare_lin(loco_ctx* c, const std::string& n, int cin, int cout) {
-    declare_param(c, n + ".weight", {cout, cin});
-    declare_param(c, n + ".bias", {cout});
-}
-
-void declare_all(loco_ctx* c) {
-    const loco_unet_cfg& cfg = c->cfg;
-    const bool adm = cfg.arch == 1;
-    int temb_ch = cfg.ch * 4;
-    if (cfg.arch < 2) {
-        declare_lin(c, adm ? "time_embed.0" : "temb.dense.0", cfg.ch, temb_ch);
-        declare_lin(c, adm ? "time_embed.2" : "temb.dense.1", temb_ch, temb_ch);
-    }
-    for (auto& op : c->ops) {
-        switch (op.kind) {
-            case OP_CONV_IN: declare_conv(c, op.pn_conv, cfg.in_channels, c->tens[op.out].C, op.ksize); break;
-            case OP_CONV: declare_conv(c, op.pn_conv, c->tens[op.in].C, c->tens[op.out].C, op.ksize); break;
-            case OP_RES: {
-                int cin = c->tens[op.in].C, cout = c->tens[op.out].C;
-                declare_norm(c, op.pn_n1, cin);
-                declare_conv(c, op.pn_c1, cin, cout, 3);
-                if (op.has_temb) declare_lin(c, op.pn_emb, temb_ch, op.scale_shift ? 2 * cout : cout);
-                declare_norm(c, op.pn_n2, cout);
-                declare_conv(c, op.pn_c2, cout, cout, 3);
-                if (op.has_nin) declare_conv(c, op.pn_skip, cin, cout, 1);
-                break;
-            }
-            case OP_ATTN: {
-                int C = c->tens[op.in].C;
-                declare_norm(c, op.pn_n1, C);
-                if (adm) {   // Conv1d weights [3C, C, 1] / [C, C, 1] (unet.py:286,296)
-                    declare_param(c, op.pn_qkv + ".weight", {3 * C, C, 1});
-                    declare_param(c, op.pn_qkv + ".bias", {3 * C});
-                    declare_param(c, op.pn_proj + ".weight", {C, C, 1});
-                    declare_param(c, op.pn_proj + ".bias", {C});
-                    if (op.added_kv) {   // deepfloyd_if AttentionBlock: norm_encoder (GroupNorm over the states), encoder_kv Conv1d
-                        declare_norm(c, op.name + ".norm_encoder", cfg.context_dim);
-                        declare_param(c, op.name + ".encoder_kv.weight", {2 * C, cfg.context_dim, 1});
-                        declare_param(c, op.name + ".encoder_kv.bias", {2 * C});
-                    }
-                    if (op.has_x) {
-                        const std::string x = op.name + ".xattn";
-                        declare_norm(c, x + ".norm", C);
-                        declare_param(c, x + ".q.weight", {C, C, 1}); declare_param(c, x + ".q.bias", {C});
-                        declare_lin(c, x + ".k", cfg.context_dim, C);
-                        declare_lin(c, x + ".v", cfg.context_dim, C);
-                        declare_param(c, x + ".proj_out.weight", {C, C, 1}); declare_param(c, x + ".proj_out.bias", {C});
-                    }
-                } else {
-                    for (const char* p : {"q", "k", "v"}) declare_conv(c, op.name + "." + p, C, C, 1);
-                    declare_conv(c, op.pn_proj, C, C, 1);
-                }
-                break;
-            }
-            case OP_DOWN: case OP_UP: {
-                int C = c->tens[op.in].C;
-                declare_conv(c, op.pn_conv, C, C, 3);
-                break;
-            }
-            case OP_XFMR: {      // latent-diffusion SpatialTransformer, depth 1 (ldm/modules/attention.py parameter names)
-                const int C = c->tens[op.in].C, D = cfg.context_dim;
-                const std::string b = op.name + ".transformer_blocks.0";
-                declare_norm(c, op.pn_n1, C);
-                declare_conv(c, op.name + ".proj_in", C, C, 1);
-                for (const char* n : {".norm1", ".norm2", ".norm3"}) declare_norm(c, b + n, C);
-                for (const char* n : {".attn1.to_q", ".attn1.to_k", ".attn1.to_v"}) declare_param(c, b + n + ".weight", {C, C});
-                declare_lin(c, b + ".attn1.to_out.0", C, C);
-                declare_param(c, b + ".attn2.to_q.weight", {C, C});
-                declare_param(c, b + ".attn2.to_k.weight", {C, D});
-                declare_param(c, b + ".attn2.to_v.weight", {C, D});
-                declare_lin(c, b + ".attn2.to_out.0", C, C);
-                declare_lin(c, b + ".ff.net.0.proj", C, 8 * C);
-                declare_lin(c, b + ".ff.net.2", 4 * C, C);
-                declare_conv(c, op.name + ".proj_out", C, C, 1);
-                break;
-            }
-            case OP_OUT:
-                declare_norm(c, op.pn_n1, c->tens[op.in].C);
-                declare_conv(c, op.pn_conv, c->tens[op.in].C, cfg.out_ch * (cfg.learn_sigma ? 2 : 1), 3);
-                break;
-        }
-    }
-}
 
 int upload(loco_ctx* c, float** dst, const std::vector<float>& h) {
     if (dalloc(c, dst, h.size() ? h.size() : 1)) return -1;
@@ -1053,25 +348,40 @@ int make_conv1_scaled(loco_ctx* c, const std::string& name, ConvP* out, float s)
     for (float& v : b.data) v *= s;
     return make_conv(c, {&w}, {&b}, out);
 }
-int make_norm(loco_ctx* c, const std::string& name, NormP* n) {
+int make_norm(loco_ctx* c, const std::string& name, NormW* n) {
     if (upload(c, &n->gamma, c->params[name + ".weight"].data)) return -1;
     if (upload(c, &n->beta, c->params[name + ".bias"].data)) return -1;
     return 0;
 }
 
+// The weights of c->wts enter this context's Op views, and the buffers sized by them are allocated: the end of
+// finalize_params for a created context, all a forked one needs.
+int bind_weights(loco_ctx* c) {
+    const Weights& W = *c->wts;
+    for (size_t i = 0; i < c->ops.size(); ++i) {
+        Op& v = c->ops[i];
+        static_cast<OpWeights&>(v) = W.op[i];
+        static_cast<NormW&>(v.n1) = v.g1; static_cast<NormW&>(v.n2) = v.g2; static_cast<NormW&>(v.nx) = v.gx;
+    }
+    if (dalloc(c, &c->tact, (size_t)c->cfg.ch * 4) || dalloc(c, &c->tproj, (size_t)(W.tproj_total > 0 ? W.tproj_total : 1))) return -1;
+    c->finalized = true;
+    return 0;
+}
+
 int finalize_params(loco_ctx* c) {
     if (c->finalized) return 0;
-    for (auto& n : c->param_order)
-        if (!c->params[n].loaded) { c->err = "parameter not loaded: " + n; return -1; }
+    for (const ParamDecl& d : c->prog->params)
+        if (!c->params[d.name].loaded) { c->err = "parameter not loaded: " + d.name; return -1; }
+    Weights& W = *c->wts;
     const loco_unet_cfg& cfg = c->cfg;
     int temb_ch = cfg.ch * 4;
     const bool adm = cfg.arch == 1;
     const std::string te0 = adm ? "time_embed.0" : "temb.dense.0", te1 = adm ? "time_embed.2" : "temb.dense.1";
     if (cfg.arch < 2) {
-        if (upload(c, &c->td0w, c->params[te0 + ".weight"].data)) return -1;
-        if (upload(c, &c->td0b, c->params[te0 + ".bias"].data)) return -1;
-        if (upload(c, &c->td1w, c->params[te1 + ".weight"].data)) return -1;
-        if (upload(c, &c->td1b, c->params[te1 + ".bias"].data)) return -1;
+        if (upload(c, &W.td0w, c->params[te0 + ".weight"].data)) return -1;
+        if (upload(c, &W.td0b, c->params[te0 + ".bias"].data)) return -1;
+        if (upload(c, &W.td1w, c->params[te1 + ".weight"].data)) return -1;
+        if (upload(c, &W.td1b, c->params[te1 + ".bias"].data)) return -1;
     }
     // sinusoid frequencies exactly as torch computes them in fp32:
     //   DDPM: exp(float32(i) * float32(-ln(1e4)/(half-1)))            (diffusion.py:797-798)
@@ -1085,18 +395,20 @@ int finalize_params(loco_ctx* c) {
             else x = (float)i * (float)(-(std::log(10000.0) / (double)(half - 1)));
             f[i] = (float)std::exp((double)x);
         }
-        if (upload(c, &c->freq, f)) return -1;
+        if (upload(c, &W.freq, f)) return -1;
     }
     std::vector<float> tpw, tpb;
-    for (auto& op : c->ops) {
+    for (size_t oi = 0; oi < W.op.size(); ++oi) {
+        const OpPlan& op = c->prog->ops[oi];
+        OpWeights& ow = W.op[oi];
         switch (op.kind) {
-            case OP_CONV_IN: case OP_CONV: if (make_conv1(c, op.pn_conv, &op.conv)) return -1; break;
+            case OP_CONV_IN: case OP_CONV: if (make_conv1(c, op.pn_conv, &ow.conv)) return -1; break;
             case OP_RES: {
-                if (make_norm(c, op.pn_n1, &op.n1) || make_norm(c, op.pn_n2, &op.n2)) return -1;
-                if (make_conv1(c, op.pn_c1, &op.c1) || make_conv1_scaled(c, op.pn_c2, &op.c2, c->res_scale)) return -1;
-                if (op.has_nin && make_conv1_scaled(c, op.pn_skip, &op.nin, c->res_scale)) return -1;
+                if (make_norm(c, op.pn_n1, &ow.g1) || make_norm(c, op.pn_n2, &ow.g2)) return -1;
+                if (make_conv1(c, op.pn_c1, &ow.c1) || make_conv1_scaled(c, op.pn_c2, &ow.c2, c->prog->res_scale)) return -1;
+                if (op.has_nin && make_conv1_scaled(c, op.pn_skip, &ow.nin, c->prog->res_scale)) return -1;
                 if (!op.has_temb) break;
-                op.tproj_off = (long)tpb.size();
+                ow.tproj_off = (long)tpb.size();
                 auto& w = c->params[op.pn_emb + ".weight"].data;
                 auto& b = c->params[op.pn_emb + ".bias"].data;
                 tpw.insert(tpw.end(), w.begin(), w.end());
@@ -1104,14 +416,14 @@ int finalize_params(loco_ctx* c) {
                 break;
             }
             case OP_ATTN: {
-                if (make_norm(c, op.pn_n1, &op.n1)) return -1;
+                if (make_norm(c, op.pn_n1, &ow.g1)) return -1;
                 if (adm) {
-                    if (make_conv1(c, op.pn_qkv, &op.qkvc)) return -1;
+                    if (make_conv1(c, op.pn_qkv, &ow.qkvc)) return -1;
                 } else if (make_conv(c, {&c->params[op.name + ".q.weight"], &c->params[op.name + ".k.weight"],
                                          &c->params[op.name + ".v.weight"]},
                                      {&c->params[op.name + ".q.bias"], &c->params[op.name + ".k.bias"],
-                                      &c->params[op.name + ".v.bias"]}, &op.qkvc)) return -1;
-                if (make_conv1(c, op.pn_proj, &op.proj)) return -1;
+                                      &c->params[op.name + ".v.bias"]}, &ow.qkvc)) return -1;
+                if (make_conv1(c, op.pn_proj, &ow.proj)) return -1;
                 if (op.added_kv) {
                     // encoder_kv rows of head h are [k_h (CH) | v_h (CH)] (QKVAttention of deepfloyd_if: the states' projection is
                     // split per head like qkv): un-interleave into the key and the value map, rows ordered (head, channel)
@@ -1126,36 +438,32 @@ int finalize_params(loco_ctx* c) {
                             std::copy(w.data.begin() + rv * D, w.data.begin() + (rv + 1) * D, vw.begin() + r * D);
                             kb[r] = b.data[rk]; vb[r] = b.data[rv];
                         }
-                    if (upload(c, &op.xkw, kw) || upload(c, &op.xkb, kb) || upload(c, &op.xvw, vw) || upload(c, &op.xvb, vb) ||
-                        upload(c, &op.xng, c->params[op.name + ".norm_encoder.weight"].data) ||
-                        upload(c, &op.xnb, c->params[op.name + ".norm_encoder.bias"].data)) return -1;
-                    const size_t kv = (size_t)C * c->ctx_Lp;
-                    if (dalloc(c, &op.xK, kv) || dalloc(c, &op.xV, kv)) return -1;
+                    if (upload(c, &ow.xkw, kw) || upload(c, &ow.xkb, kb) || upload(c, &ow.xvw, vw) || upload(c, &ow.xvb, vb) ||
+                        upload(c, &ow.xng, c->params[op.name + ".norm_encoder.weight"].data) ||
+                        upload(c, &ow.xnb, c->params[op.name + ".norm_encoder.bias"].data)) return -1;
                 }
                 if (op.has_x) {
                     const std::string x = op.name + ".xattn";
-                    if (make_norm(c, x + ".norm", &op.nx) || make_conv1(c, x + ".q", &op.xqc) ||
-                        make_conv1(c, x + ".proj_out", &op.xproj)) return -1;
-                    if (upload(c, &op.xkw, c->params[x + ".k.weight"].data) || upload(c, &op.xkb, c->params[x + ".k.bias"].data) ||
-                        upload(c, &op.xvw, c->params[x + ".v.weight"].data) || upload(c, &op.xvb, c->params[x + ".v.bias"].data))
+                    if (make_norm(c, x + ".norm", &ow.gx) || make_conv1(c, x + ".q", &ow.xqc) ||
+                        make_conv1(c, x + ".proj_out", &ow.xproj)) return -1;
+                    if (upload(c, &ow.xkw, c->params[x + ".k.weight"].data) || upload(c, &ow.xkb, c->params[x + ".k.bias"].data) ||
+                        upload(c, &ow.xvw, c->params[x + ".v.weight"].data) || upload(c, &ow.xvb, c->params[x + ".v.bias"].data))
                         return -1;
-                    const size_t kv = (size_t)c->tens[op.in].C * c->ctx_Lp;
-                    if (dalloc(c, &op.xK, kv) || dalloc(c, &op.xV, kv)) return -1;
                 }
                 break;
             }
-            case OP_DOWN: case OP_UP: if (make_conv1(c, op.pn_conv, &op.conv)) return -1; break;
+            case OP_DOWN: case OP_UP: if (make_conv1(c, op.pn_conv, &ow.conv)) return -1; break;
             case OP_XFMR: {
                 const int C = c->tens[op.in].C, NH = op.heads, CH = C / NH;
                 const std::string b = op.name + ".transformer_blocks.0";
                 HostParam zb; zb.shape = {8 * C}; zb.data.assign((size_t)8 * C, 0.f);       // bias of the bias-free maps
                 auto nobias = [&](const std::string& w, ConvP* out) { return make_conv(c, {&c->params[w + ".weight"]}, {&zb}, out); };
-                if (make_norm(c, op.pn_n1, &op.n1) || make_conv1(c, op.name + ".proj_in", &op.pj_in) ||
-                    make_conv1(c, op.name + ".proj_out", &op.pj_out)) return -1;
+                if (make_norm(c, op.pn_n1, &ow.g1) || make_conv1(c, op.name + ".proj_in", &ow.pj_in) ||
+                    make_conv1(c, op.name + ".proj_out", &ow.pj_out)) return -1;
                 const char* lnn[3] = {".norm1", ".norm2", ".norm3"};
                 for (int i = 0; i < 3; ++i)
-                    if (upload(c, &op.lng[i], c->params[b + lnn[i] + ".weight"].data) ||
-                        upload(c, &op.lnb[i], c->params[b + lnn[i] + ".bias"].data)) return -1;
+                    if (upload(c, &ow.lng[i], c->params[b + lnn[i] + ".weight"].data) ||
+                        upload(c, &ow.lnb[i], c->params[b + lnn[i] + ".bias"].data)) return -1;
                 {   // attn1: to_q / to_k / to_v fused into one [3C][C] map whose rows follow the per-head [q_h | k_h | v_h] layout
                     // the attention products address (head h of 'b n (h d)' = channels h*d .. h*d+d-1)
                     HostParam w; w.shape = {3 * C, C}; w.data.resize((size_t)3 * C * C);
@@ -1166,60 +474,58 @@ int finalize_params(loco_ctx* c) {
                             for (int j = 0; j < CH; ++j)
                                 std::memcpy(&w.data[((size_t)(h * 3 + which) * CH + j) * C], &src[(size_t)(h * CH + j) * C], (size_t)C * 4);
                     }
-                    if (make_conv(c, {&w}, {&zb}, &op.qkvc)) return -1;
+                    if (make_conv(c, {&w}, {&zb}, &ow.qkvc)) return -1;
                 }
-                if (make_conv1(c, b + ".attn1.to_out.0", &op.to_out1) || nobias(b + ".attn2.to_q", &op.xqc) ||
-                    make_conv1(c, b + ".attn2.to_out.0", &op.to_out2) || make_conv1(c, b + ".ff.net.0.proj", &op.ff1) ||
-                    make_conv1(c, b + ".ff.net.2", &op.ff2)) return -1;
+                if (make_conv1(c, b + ".attn1.to_out.0", &ow.to_out1) || nobias(b + ".attn2.to_q", &ow.xqc) ||
+                    make_conv1(c, b + ".attn2.to_out.0", &ow.to_out2) || make_conv1(c, b + ".ff.net.0.proj", &ow.ff1) ||
+                    make_conv1(c, b + ".ff.net.2", &ow.ff2)) return -1;
                 std::vector<float> z0((size_t)C, 0.f);
-                if (upload(c, &op.xkw, c->params[b + ".attn2.to_k.weight"].data) || upload(c, &op.xkb, z0) ||
-                    upload(c, &op.xvw, c->params[b + ".attn2.to_v.weight"].data) || upload(c, &op.xvb, z0)) return -1;
-                const size_t kv = (size_t)C * c->ctx_Lp;
-                if (dalloc(c, &op.xK, kv) || dalloc(c, &op.xV, kv)) return -1;
+                if (upload(c, &ow.xkw, c->params[b + ".attn2.to_k.weight"].data) || upload(c, &ow.xkb, z0) ||
+                    upload(c, &ow.xvw, c->params[b + ".attn2.to_v.weight"].data) || upload(c, &ow.xvb, z0)) return -1;
                 break;
             }
             case OP_OUT:
-                if (make_norm(c, op.pn_n1, &op.n1) || make_conv1(c, op.pn_conv, &op.conv, cfg.out_ch)) return -1;
+                if (make_norm(c, op.pn_n1, &ow.g1) || make_conv1(c, op.pn_conv, &ow.conv, cfg.out_ch)) return -1;
                 break;
         }
     }
-    c->tproj_total = (long)tpb.size();
-    if (upload(c, &c->tp_w, tpw) || upload(c, &c->tp_b, tpb)) return -1;
-    if (dalloc(c, &c->tact, (size_t)temb_ch) || dalloc(c, &c->tproj, (size_t)(c->tproj_total > 0 ? c->tproj_total : 1))) return -1;
+    W.tproj_total = (long)tpb.size();
+    if (upload(c, &W.tp_w, tpw) || upload(c, &W.tp_b, tpb)) return -1;
     // FLOP model (2*MAC): convolutions + attention products
     double fl = 0.0;
-    for (auto& op : c->ops) {
+    for (size_t oi = 0; oi < W.op.size(); ++oi) {
+        const OpPlan& op = c->prog->ops[oi];
+        const OpWeights& ow = W.op[oi];
         auto convf = [&](const ConvP& p, int H, int W) { fl += 2.0 * p.cin * p.cout * p.taps * (double)H * W; };
         const Tens& to = c->tens[op.out];
         switch (op.kind) {
-            case OP_CONV_IN: case OP_CONV: case OP_DOWN: case OP_UP: case OP_OUT: convf(op.conv, to.H, to.W); break;
+            case OP_CONV_IN: case OP_CONV: case OP_DOWN: case OP_UP: case OP_OUT: convf(ow.conv, to.H, to.W); break;
             case OP_RES:
-                convf(op.c1, to.H, to.W); convf(op.c2, to.H, to.W);
-                if (op.has_nin) convf(op.nin, to.H, to.W);
+                convf(ow.c1, to.H, to.W); convf(ow.c2, to.H, to.W);
+                if (op.has_nin) convf(ow.nin, to.H, to.W);
                 break;
             case OP_XFMR: {
-                for (const ConvP* p : {&op.pj_in, &op.qkvc, &op.to_out1, &op.xqc, &op.to_out2, &op.ff1, &op.ff2, &op.pj_out}) convf(*p, to.H, to.W);
+                for (const ConvP* p : {&ow.pj_in, &ow.qkvc, &ow.to_out1, &ow.xqc, &ow.to_out2, &ow.ff1, &ow.ff2, &ow.pj_out}) convf(*p, to.H, to.W);
                 double T = (double)to.H * to.W;
                 fl += 2.0 * 2.0 * T * T * to.C + 2.0 * 2.0 * T * c->cfg.context_len * to.C;
                 break;
             }
             case OP_ATTN: {
-                convf(op.qkvc, to.H, to.W); convf(op.proj, to.H, to.W);
+                convf(ow.qkvc, to.H, to.W); convf(ow.proj, to.H, to.W);
                 double T = (double)to.H * to.W;
                 fl += 2.0 * 2.0 * T * T * to.C;
                 if (op.has_x) {
-                    convf(op.xqc, to.H, to.W); convf(op.xproj, to.H, to.W);
+                    convf(ow.xqc, to.H, to.W); convf(ow.xproj, to.H, to.W);
                     fl += 2.0 * 2.0 * T * c->cfg.context_len * to.C;
                 }
                 break;
             }
         }
     }
-    c->flops = fl;
+    W.flops = fl;
     // host copies are no longer needed
     for (auto& kv : c->params) { std::vector<float>().swap(kv.second.data); }
-    c->finalized = true;
-    return 0;
+    return bind_weights(c);
 }
 
 // ---------------------------------------------------------------------------
@@ -1230,7 +536,7 @@ struct Pass {
     float* arena;      // activation arena of this pass
     float* stats;      // stats arena of this pass
     float* T(int id) const { return arena + c->tens[id].off; }
-    long bs() const { return c->per_sample; }
+    long bs() const { return c->prog->per_sample; }
 };
 
 // attention products: exact fp32 MFMA in the f32 mode and for the short / small ones, split-bf16 on the bf16 matrix
@@ -1301,7 +607,7 @@ struct StatReq {
 
 void stats_standalone(loco_ctx* c, const StatReq& rq, const float* x, long xbs, int B, int HW, int s0, hipStream_t st) {
     const NormP& n = *rq.n;
-    const long SB = c->stats_per_sample;
+    const long SB = c->prog->stats_per_sample;
     const int G = c->cfg.gn_groups;
     if (rq.kind == ST_FWD) {
         NS s = nstats(c, rq.stats + (long)s0 * SB, n);
@@ -1321,7 +627,7 @@ void stats_standalone(loco_ctx* c, const StatReq& rq, const float* x, long xbs, 
 // norm-cotangent term asked for in a.cot_d rides in the epilogue (false: the caller applies it).
 bool run_conv(loco_ctx* c, const ConvArgs& a0, int taps, hipStream_t st, const StatReq* rq = nullptr,
               const ConvArgs* second = nullptr) {
-    const size_t span = (size_t)c->cfg.max_batch * c->per_sample;
+    const size_t span = (size_t)c->cfg.max_batch * c->prog->per_sample;
     auto padded = [&](const float* p) { return (p >= c->arenaP && p < c->arenaP + span) || (p >= c->arenaT && p < c->arenaT + span); };
     ConvArgs a = a0, sc;
     a.act = c->cfg.act;
@@ -1342,7 +648,7 @@ bool run_conv(loco_ctx* c, const ConvArgs& a0, int taps, hipStream_t st, const S
     if (rq && rq->kind != ST_NONE && rq->n) rq->n->ready = true;
     if (rq && rq->keep_ntile) *rq->keep_ntile = p.keep_ntile;
     const int HWo = a.Hout * a.Wout, Gn = c->cfg.gn_groups;
-    const long SBs = c->stats_per_sample;
+    const long SBs = c->prog->stats_per_sample;
     // each kernel (+ its split-K reduce) timed as its own profile record, so the per-kernel averages agree with rocprofv3's
     auto timed = [&](const char* name, double flops, const ConvArgs& y, auto&& launch) {
         loco_ctx::ProfRec r;
@@ -1442,7 +748,7 @@ bool cat_fused_stats(loco_ctx* c, const NormP& n, int tid, float* stats, int B, 
     if (A.keep_ntile <= 0 || Bt.keep_ntile <= 0) return false;
     NS s = nstats(c, stats, n);
     launch_gn_fused_finalize_cat(A.keep, A.C, A.keep_ntile, Bt.keep, Bt.keep_ntile, B, q.C, q.H * q.W, c->cfg.gn_groups,
-                                 eps_of(c, n), n.gamma, n.beta, s.mr, s.sc, s.sh, c->stats_per_sample, st);
+                                 eps_of(c, n), n.gamma, n.beta, s.mr, s.sc, s.sh, c->prog->stats_per_sample, st);
     return true;
 }
 
@@ -1459,14 +765,14 @@ bool cat_fused_tstats(loco_ctx* c, const NormP& n, int tid, int B, hipStream_t s
     const size_t MB = c->cfg.max_batch;      // this lane's rows (conv_plan.hip stats_route: keep_floats / max_batch apart)
     launch_gn_lin_fused_finalize(ST_TAN, A.keep + c->lane_s0 * (A.keep_floats / MB), A.C, A.keep_ntile,
                                  Bt.keep + c->lane_s0 * (Bt.keep_floats / MB), Bt.keep_ntile, B, q.C, q.H * q.W,
-                                 c->cfg.gn_groups, sp.mr, stt.tst, stt.tc, c->stats_per_sample, st);
+                                 c->cfg.gn_groups, sp.mr, stt.tst, stt.tc, c->prog->stats_per_sample, st);
     return true;
 }
 
 void gn_forward_stats(const Pass& p, const NormP& n, const float* x, long xbs, int HW) {
     NS s = nstats(p.c, p.stats, n);
     launch_gn_stats(x, xbs, p.B, n.C, HW, p.c->cfg.gn_groups, eps_of(p.c, n), n.gamma, n.beta, s.mr, s.sc, s.sh,
-                    p.c->stats_per_sample, p.c->red, p.st);
+                    p.c->prog->stats_per_sample, p.c->red, p.st);
 }
 
 
@@ -1481,7 +787,7 @@ struct XA {                     // tensors of one pass: `a` = the arena holding 
 XA xa_of(loco_ctx* c, const Op& op, int B, hipStream_t st) {
     XA x; x.c = c; x.op = &op; x.st = st; x.B = B;
     const Tens& t = c->tens[op.in];
-    x.C = t.C; x.T = t.H * t.W; x.NH = op.heads; x.CH = x.C / x.NH; x.Lp = c->ctx_Lp;
+    x.C = t.C; x.T = t.H * t.W; x.NH = op.heads; x.CH = x.C / x.NH; x.Lp = c->prog->ctx_Lp;
     x.scale = 1.0f / std::sqrt((float)x.CH);
     return x;
 }
@@ -1534,7 +840,7 @@ void xa_conv1x1(loco_ctx* c, const ConvP& w, bool dgrad, const float* in, long i
 struct SA { loco_ctx* c; const Op* op; int B, T, NH, CH; hipStream_t st; };
 void sa_forward(const SA& s, float* ar) {
     loco_ctx* c = s.c;
-    const long PS = c->per_sample, HS = 3L * s.CH * s.T, SS = (long)s.T * s.T;
+    const long PS = c->prog->per_sample, HS = 3L * s.CH * s.T, SS = (long)s.T * s.T;
     float* q = ar + c->tens[s.op->qkv].off; float* k = q + (long)s.CH * s.T; float* v = k + (long)s.CH * s.T;
     float* S = ar + c->tens[s.op->S].off; float* o = ar + c->tens[s.op->o].off;
     GemmArgs g; std::memset(&g, 0, sizeof(g));
@@ -1554,7 +860,7 @@ void sa_forward(const SA& s, float* ar) {
 void sa_tangent(const SA& s) {       // dq, dk, dv in arenaT(qkv) -> do in arenaT(o); primal in arenaP (B = 1)
     loco_ctx* c = s.c;
     const int T = s.T, CH = s.CH, NH = s.NH, B = s.B;
-    const long PS = c->per_sample, HS = 3L * CH * T, SS = (long)T * T;
+    const long PS = c->prog->per_sample, HS = 3L * CH * T, SS = (long)T * T;
     float* q = c->arenaP + c->tens[s.op->qkv].off; float* k = q + (long)CH * T; float* v = k + (long)CH * T;
     float* dq = c->arenaT + c->tens[s.op->qkv].off; float* dk = dq + (long)CH * T; float* dv = dk + (long)CH * T;
     float* SP = c->arenaP + c->tens[s.op->S].off; float* ST = c->arenaT + c->tens[s.op->S].off;
@@ -1589,7 +895,7 @@ void sa_tangent(const SA& s) {       // dq, dk, dv in arenaT(qkv) -> do in arena
 void sa_cotangent(const SA& s) {     // g_o in arenaT(o) -> g_q, g_k, g_v in arenaT(qkv)
     loco_ctx* c = s.c;
     const int T = s.T, CH = s.CH, NH = s.NH, B = s.B;
-    const long PS = c->per_sample, HS = 3L * CH * T, SS = (long)T * T, OS = (long)CH * T;
+    const long PS = c->prog->per_sample, HS = 3L * CH * T, SS = (long)T * T, OS = (long)CH * T;
     float* q = c->arenaP + c->tens[s.op->qkv].off; float* k = q + (long)CH * T; float* v = k + (long)CH * T;
     float* gq = c->arenaT + c->tens[s.op->qkv].off; float* gk = gq + (long)CH * T; float* gv = gk + (long)CH * T;
     float* SP = c->arenaP + c->tens[s.op->S].off; float* SG = c->arenaT + c->tens[s.op->S].off;
@@ -1638,7 +944,7 @@ struct AKV {
 AKV akv_of(loco_ctx* c, const Op& op, int B, hipStream_t st) {
     AKV s; s.c = c; s.op = &op; s.B = B; s.st = st;
     const Tens& t = c->tens[op.in];
-    s.T = t.H * t.W; s.NH = op.heads; s.CH = t.C / op.heads; s.Lp = c->ctx_Lp; s.Tk = s.Lp + s.T;
+    s.T = t.H * t.W; s.NH = op.heads; s.CH = t.C / op.heads; s.Lp = c->prog->ctx_Lp; s.Tk = s.Lp + s.T;
     s.HS = 3L * s.CH * s.T; s.SS = (long)s.T * s.Tk; s.KS = (long)s.CH * s.Lp;
     s.scale = 1.0f / std::sqrt((float)s.CH);
     return s;
@@ -1685,7 +991,7 @@ void akv_forward(const AKV& s, float* ar, long bs) {           // q, k, v in ar(
 }
 void akv_tangent(const AKV& s) {        // dq, dk, dv in arenaT(qkv) -> do in arenaT(o); primal in arenaP (B = 1)
     loco_ctx* c = s.c; const Op& op = *s.op;
-    const long PS = c->per_sample, OS = (long)s.CH * s.T;
+    const long PS = c->prog->per_sample, OS = (long)s.CH * s.T;
     float* q = c->arenaP + c->tens[op.qkv].off; float* k = q + OS; float* v = k + OS;
     float* dq = c->arenaT + c->tens[op.qkv].off; float* dk = dq + OS; float* dv = dk + OS;
     float* SP = c->arenaP + c->tens[op.S].off; float* ST = c->arenaT + c->tens[op.S].off;
@@ -1709,7 +1015,7 @@ void akv_tangent(const AKV& s) {        // dq, dk, dv in arenaT(qkv) -> do in ar
 }
 void akv_cotangent(const AKV& s) {      // g_o in arenaT(o) -> g_q, g_k, g_v in arenaT(qkv)
     loco_ctx* c = s.c; const Op& op = *s.op;
-    const long PS = c->per_sample, OS = (long)s.CH * s.T;
+    const long PS = c->prog->per_sample, OS = (long)s.CH * s.T;
     float* q = c->arenaP + c->tens[op.qkv].off; float* k = q + OS; float* v = k + OS;
     float* gq = c->arenaT + c->tens[op.qkv].off; float* gk = gq + OS; float* gv = gk + OS;
     float* SP = c->arenaP + c->tens[op.S].off; float* SG = c->arenaT + c->tens[op.S].off;
@@ -1749,13 +1055,13 @@ int forward_pass(loco_ctx* c, const float* x, float t, int B, float* arena, floa
                  const float* t_ptr = nullptr) {
     const loco_unet_cfg& cfg = c->cfg;
     Pass p{c, st, B, arena, stats};
-    const long SB = c->stats_per_sample;
+    const long SB = c->prog->stats_per_sample;
     clear_ready(c);
     auto next_fwd = [&](int tid) { return req_fwd_of(c, tid, stats); };   // forward statistics for the consumer of `tid` (+ kept partials of a concatenation part)
     if (cfg.arch < 2) {
-        launch_temb(t, cfg.ch, cfg.ch * 4, c->freq, c->td0w, c->td0b, c->td1w, c->td1b, c->tact, st, cfg.arch == 1,
+        launch_temb(t, cfg.ch, cfg.ch * 4, c->wts->freq, c->wts->td0w, c->wts->td0b, c->wts->td1w, c->wts->td1b, c->tact, st, cfg.arch == 1,
                     c->has_cond ? c->cond_add : nullptr, t_ptr, cfg.act);
-        launch_temb_proj(c->tact, cfg.ch * 4, c->tp_w, c->tp_b, (int)c->tproj_total, c->tproj, st);
+        launch_temb_proj(c->tact, cfg.ch * 4, c->wts->tp_w, c->wts->tp_b, (int)c->wts->tproj_total, c->tproj, st);
     }
     for (auto& op : c->ops) {
         const Tens& to = c->tens[op.out];
@@ -1763,7 +1069,7 @@ int forward_pass(loco_ctx* c, const float* x, float t, int B, float* arena, floa
         switch (op.kind) {
             case OP_CONV_IN: {
                 ConvArgs a; conv_defaults(a);
-                a.in = x; a.in_bs = c->n_in; a.Cin = cfg.in_channels; a.Hin = cfg.resolution; a.Win = cfg.resolution;
+                a.in = x; a.in_bs = c->prog->n_in; a.Cin = cfg.in_channels; a.Hin = cfg.resolution; a.Win = cfg.resolution;
                 setw(a, op.conv, false); a.bias = op.conv.bias;
                 a.out = p.T(op.out); a.out_bs = p.bs(); a.Cout = to.C; a.Hout = to.H; a.Wout = to.W; a.B = B;
                 if (op.ksize == 1) a.pad = 0;
@@ -1825,7 +1131,7 @@ int forward_pass(loco_ctx* c, const float* x, float t, int B, float* arena, floa
                 ConvArgs b; conv_defaults(b);
                 b.in = p.T(op.h1); b.in_bs = p.bs(); b.Cin = to.C; b.Hin = to.H; b.Win = to.W;
                 setw(b, op.c2, false); b.bias = op.c2.bias; b.res = xin; b.res_bs = p.bs();
-                b.res_scale = op.has_nin ? 1.f : c->res_scale;        // (shortcut + h) * res_scale: c2 / nin carry it in their weights
+                b.res_scale = op.has_nin ? 1.f : c->prog->res_scale;        // (shortcut + h) * res_scale: c2 / nin carry it in their weights
                 b.mode = CM_GN_SILU; b.sc = s2.sc; b.sh = s2.sh; b.scsh_bs = SB;
                 b.out = p.T(op.out); b.out_bs = p.bs(); b.Cout = to.C; b.Hout = to.H; b.Wout = to.W; b.B = B;
                 const StatReq rq = next_fwd(op.out);
@@ -1974,15 +1280,15 @@ void tangent_stats(loco_ctx* c, const NormP& n, const float* d, long dbs, const 
     NS sp = nstats(c, c->statsP, n);
     NS stt = nstats(c, c->statsT, n);
     launch_gn_tstats(d, dbs, x, 0, B, n.C, HW, c->cfg.gn_groups, sp.sc, sp.sh, sp.mr, 0, 0, 0, stt.tst,
-                     stt.tc, c->stats_per_sample, c->red, st);
+                     stt.tc, c->prog->stats_per_sample, c->red, st);
 }
 void set_tan(loco_ctx* c, ConvArgs& a, const NormP& n, const float* prim) {
     NS sp = nstats(c, c->statsP, n);
     NS stt = nstats(c, c->statsT, n);
     a.mode = CM_TAN_SILU; a.prim = prim; a.prim_bs = 0;
     a.sc = sp.sc; a.sh = sp.sh; a.scsh_bs = 0; a.mr = sp.mr; a.mr_bs = 0; a.gamma_ = n.gamma;
-    a.tst = stt.tst; a.tst_bs = c->stats_per_sample; a.cpg = n.C / c->cfg.gn_groups;
-    a.tc = stt.tc; a.tc_bs = c->stats_per_sample;
+    a.tst = stt.tst; a.tst_bs = c->prog->stats_per_sample; a.cpg = n.C / c->cfg.gn_groups;
+    a.tc = stt.tc; a.tc_bs = c->prog->stats_per_sample;
     a.sx = (n.sx_off >= 0 && c->sxcache) ? c->sxcache + n.sx_off : nullptr;
 }
 
@@ -1990,7 +1296,7 @@ constexpr size_t RED_BYTES = (size_t)4 << 20;   // reduction scratch (GN partial
 
 int tangent_pass(loco_ctx* c, const float* V, int B, hipStream_t st) {
     const loco_unet_cfg& cfg = c->cfg;
-    const long PS = c->per_sample;
+    const long PS = c->prog->per_sample;
     auto TP = [&](int id) { return c->arenaP + c->tens[id].off; };   // primal
     auto TT = [&](int id) { return c->arenaT + c->tens[id].off; };   // tangent
     clear_ready(c);
@@ -2011,7 +1317,7 @@ int tangent_pass(loco_ctx* c, const float* V, int B, hipStream_t st) {
         switch (op.kind) {
             case OP_CONV_IN: {
                 ConvArgs a; conv_defaults(a);
-                a.in = V; a.in_bs = c->n_in; a.Cin = cfg.in_channels; a.Hin = cfg.resolution; a.Win = cfg.resolution;
+                a.in = V; a.in_bs = c->prog->n_in; a.Cin = cfg.in_channels; a.Hin = cfg.resolution; a.Win = cfg.resolution;
                 setw(a, op.conv, false);
                 a.out = TT(op.out); a.out_bs = PS; a.Cout = to.C; a.Hout = to.H; a.Wout = to.W; a.B = B;
                 if (op.ksize == 1) a.pad = 0;
@@ -2042,7 +1348,7 @@ int tangent_pass(loco_ctx* c, const float* V, int B, hipStream_t st) {
                     NS sp = nstats(c, c->statsP, op.n1);
                     NS stt = nstats(c, c->statsT, op.n1);
                     launch_gn_apply(5, TT(op.in), PS, TP(op.in), 0, nullptr, 0, TT(op.a1), PS, 0, B, ti.C, HWi,
-                                    cfg.gn_groups, sp.sc, sp.sh, sp.mr, 0, 0, stt.tst, c->stats_per_sample, st, cfg.act);
+                                    cfg.gn_groups, sp.sc, sp.sh, sp.mr, 0, 0, stt.tst, c->prog->stats_per_sample, st, cfg.act);
                     launch_pool2x2_sum(TT(op.a1), PS, TT(op.ap), PS, 0, B, ti.C, to.H, to.W, st, 0.25f);
                     launch_pool2x2_sum(TT(op.in), PS, TT(op.xu), PS, 0, B, ti.C, to.H, to.W, st, 0.25f);
                     a.in = TT(op.ap); a.in_bs = PS; a.Hin = to.H; a.Win = to.W;
@@ -2070,7 +1376,7 @@ int tangent_pass(loco_ctx* c, const float* V, int B, hipStream_t st) {
                 ConvArgs b; conv_defaults(b);
                 b.in = TT(op.h1); b.in_bs = PS; b.Cin = to.C; b.Hin = to.H; b.Win = to.W;
                 setw(b, op.c2, false); b.res = xin; b.res_bs = PS;
-                b.res_scale = op.has_nin ? 1.f : c->res_scale;
+                b.res_scale = op.has_nin ? 1.f : c->prog->res_scale;
                 set_tan(c, b, op.n2, TP(op.h1));
                 b.out = TT(op.out); b.out_bs = PS; b.Cout = to.C; b.Hout = to.H; b.Wout = to.W; b.B = B;
                 const StatReq rq = next_tan(op.out);
@@ -2084,7 +1390,7 @@ int tangent_pass(loco_ctx* c, const float* V, int B, hipStream_t st) {
                 NS sp = nstats(c, c->statsP, op.n1);
                 NS stt = nstats(c, c->statsT, op.n1);
                 launch_gn_apply(1, TT(op.in), PS, TP(op.in), 0, nullptr, 0, TT(op.hn), PS, 0, B, C, HW,
-                                cfg.gn_groups, sp.sc, sp.sh, sp.mr, 0, 0, stt.tst, c->stats_per_sample, st);
+                                cfg.gn_groups, sp.sc, sp.sh, sp.mr, 0, 0, stt.tst, c->prog->stats_per_sample, st);
                 ConvArgs a; conv_defaults(a);
                 a.in = TT(op.hn); a.in_bs = PS; a.Cin = C; a.Hin = to.H; a.Win = to.W;
                 setw(a, op.qkvc, false); a.pad = 0;
@@ -2146,7 +1452,7 @@ int tangent_pass(loco_ctx* c, const float* V, int B, hipStream_t st) {
                     NS spx = nstats(c, c->statsP, op.nx);
                     NS stx = nstats(c, c->statsT, op.nx);
                     launch_gn_apply(1, TT(op.xmid), PS, TP(op.xmid), 0, nullptr, 0, TT(op.xhn), PS, 0, B, C, HW,
-                                    cfg.gn_groups, spx.sc, spx.sh, spx.mr, 0, 0, stx.tst, c->stats_per_sample, st);
+                                    cfg.gn_groups, spx.sc, spx.sh, spx.mr, 0, 0, stx.tst, c->prog->stats_per_sample, st);
                     xa_conv1x1(c, op.xqc, false, TT(op.xhn), PS, TT(op.xq), PS, C, to.H, to.W, B, nullptr, 0, false, st);
                     if (!xa_fused(x, 1, TT(op.xq), PS, op.xK, op.xV, TP(op.xS), 0, TT(op.xo), PS)) {
                         xa_scores(x, TT(op.xq), PS, op.xK, TT(op.xS), PS, 1.f, false);                  // dS = dq^T K
@@ -2167,7 +1473,7 @@ int tangent_pass(loco_ctx* c, const float* V, int B, hipStream_t st) {
                 NS sp = nstats(c, c->statsP, op.n1);
                 NS stt = nstats(c, c->statsT, op.n1);
                 launch_gn_apply(1, TT(op.in), PS, TP(op.in), 0, nullptr, 0, XT_(X_G0), PS, 0, B, C, HW,
-                                cfg.gn_groups, sp.sc, sp.sh, sp.mr, 0, 0, stt.tst, c->stats_per_sample, st);
+                                cfg.gn_groups, sp.sc, sp.sh, sp.mr, 0, 0, stt.tst, c->prog->stats_per_sample, st);
                 lin1x1(c, op.pj_in, false, XT_(X_G0), PS, C, XT_(X_H0), PS, C, H, W, B, nullptr, 0, false, st);
                 const SA sa{c, &op, B, T, NH, C / NH, st};
                 const XA xa = xa_of(c, op, B, st);
@@ -2225,19 +1531,19 @@ void cot_stats(loco_ctx* c, const NormP& n, const float* d, long dbs, const floa
     NS sp = nstats(c, c->statsP, n);
     NS stt = nstats(c, c->statsT, n);
     launch_gn_tstats(d, dbs, x, 0, B, n.C, HW, c->cfg.gn_groups, sp.sc, sp.sh, sp.mr, 0, 0, kind, stt.tst,
-                     stt.tc, c->stats_per_sample, c->red, st, c->cfg.act);
+                     stt.tc, c->prog->stats_per_sample, c->red, st, c->cfg.act);
 }
 
 // ge: cotangent of eps [B][n]; result A[B][n] = conv_in^T(...) + gx0
 int cotangent_pass(loco_ctx* c, const float* ge, const float* gx0, float* Aout, int B, hipStream_t st) {
     const loco_unet_cfg& cfg = c->cfg;
-    const long PS = c->per_sample;
+    const long PS = c->prog->per_sample;
     const int G = cfg.gn_groups;
     auto TP = [&](int id) { return c->arenaP + c->tens[id].off; };
     auto TG = [&](int id) { return c->arenaT + c->tens[id].off; };   // cotangent of tensor id
     // the op that produces the network output takes the caller's cotangent (conv_out; the encoder's quant_conv)
-    auto GO = [&](const Op& o) -> const float* { return o.out == c->eps_t ? ge : TG(o.out); };
-    auto GOS = [&](const Op& o) -> long { return o.out == c->eps_t ? (long)c->n_out : PS; };
+    auto GO = [&](const Op& o) -> const float* { return o.out == c->prog->eps_t ? ge : TG(o.out); };
+    auto GOS = [&](const Op& o) -> long { return o.out == c->prog->eps_t ? (long)c->prog->n_out : PS; };
     clear_ready(c);
     for (int oi = (int)c->ops.size() - 1; oi >= 0; --oi) {
         Op& op = c->ops[oi];
@@ -2258,7 +1564,7 @@ int cotangent_pass(loco_ctx* c, const float* ge, const float* gx0, float* Aout, 
                 NS sp = nstats(c, c->statsP, op.n1);
                 NS stt = nstats(c, c->statsT, op.n1);
                 launch_gn_apply(2, TG(op.a1), PS, TP(op.in), 0, nullptr, 0, TG(op.in), PS, 0, B, ti.C, ti.H * ti.W, G,
-                                sp.sc, sp.sh, sp.mr, 0, 0, stt.tst, c->stats_per_sample, st, cfg.act);
+                                sp.sc, sp.sh, sp.mr, 0, 0, stt.tst, c->prog->stats_per_sample, st, cfg.act);
                 break;
             }
             case OP_UP: {
@@ -2332,7 +1638,7 @@ int cotangent_pass(loco_ctx* c, const float* ge, const float* gx0, float* Aout, 
                     // records and the per-channel {rstd m1, rstd m2} its cotangent statistics left)
                     if (op.updown == 0 && c->prec >= 1 && c->fuse_cot && op.n1.sx_off >= 0 && c->sxcache) {
                         n.cot_d = TG(op.a1); n.cot_d_bs = PS; n.cot_sx = c->sxcache + op.n1.sx_off;
-                        n.cot_tc = stt.tc; n.cot_tc_bs = c->stats_per_sample;
+                        n.cot_tc = stt.tc; n.cot_tc_bs = c->prog->stats_per_sample;
                     }
                     cot_in_epilogue = run_conv(c, n, 1, st);
                     gsk = nullptr;
@@ -2341,15 +1647,15 @@ int cotangent_pass(loco_ctx* c, const float* ge, const float* gx0, float* Aout, 
                     if (cot_in_epilogue) { /* done by the shortcut conv */ }
                     else if (op.has_nin)
                         launch_gn_apply(2, TG(op.a1), PS, TP(op.in), 0, nullptr, 0, TG(op.in), PS, 1, B, ti.C, HWi, G,
-                                        sp.sc, sp.sh, sp.mr, 0, 0, stt.tst, c->stats_per_sample, st, cfg.act);
+                                        sp.sc, sp.sh, sp.mr, 0, 0, stt.tst, c->prog->stats_per_sample, st, cfg.act);
                     else        // identity shortcut: g_in = res_scale * g_out + norm1^T g_a1
                         launch_gn_apply(2, TG(op.a1), PS, TP(op.in), 0, gsk, PS, TG(op.in), PS, acc, B, ti.C, HWi, G,
-                                        sp.sc, sp.sh, sp.mr, 0, 0, stt.tst, c->stats_per_sample, st, cfg.act, c->res_scale);
+                                        sp.sc, sp.sh, sp.mr, 0, 0, stt.tst, c->prog->stats_per_sample, st, cfg.act, c->prog->res_scale);
                 } else {
                     launch_gn_apply(2, TG(op.a1), PS, TP(op.in), 0, nullptr, 0, TG(op.in), PS, acc, B, ti.C, HWi, G,
-                                    sp.sc, sp.sh, sp.mr, 0, 0, stt.tst, c->stats_per_sample, st, cfg.act);
-                    if (op.updown == 1) launch_upsample2x(gsk, PS, TG(op.in), PS, 1, 0.25f * c->res_scale, B, ti.C, to.H, to.W, st);
-                    else launch_pool2x2_sum(gsk, PS, TG(op.in), PS, 1, B, ti.C, ti.H, ti.W, st, c->res_scale);
+                                    sp.sc, sp.sh, sp.mr, 0, 0, stt.tst, c->prog->stats_per_sample, st, cfg.act);
+                    if (op.updown == 1) launch_upsample2x(gsk, PS, TG(op.in), PS, 1, 0.25f * c->prog->res_scale, B, ti.C, to.H, to.W, st);
+                    else launch_pool2x2_sum(gsk, PS, TG(op.in), PS, 1, B, ti.C, ti.H, ti.W, st, c->prog->res_scale);
                 }
                 break;
             }
@@ -2373,7 +1679,7 @@ int cotangent_pass(loco_ctx* c, const float* ge, const float* gx0, float* Aout, 
                     NS spx = nstats(c, c->statsP, op.nx);
                     NS stx = nstats(c, c->statsT, op.nx);
                     launch_gn_apply(3, TG(op.xhn), PS, TP(op.xmid), 0, TG(op.out), PS, TG(op.xmid), PS, 0, B, C, HW, G,
-                                    spx.sc, spx.sh, spx.mr, 0, 0, stx.tst, c->stats_per_sample, st);
+                                    spx.sc, spx.sh, spx.mr, 0, 0, stx.tst, c->prog->stats_per_sample, st);
                 }
                 // g_o = proj^T g_out
                 ConvArgs pr; conv_defaults(pr);
@@ -2429,7 +1735,7 @@ int cotangent_pass(loco_ctx* c, const float* ge, const float* gx0, float* Aout, 
                 NS sp = nstats(c, c->statsP, op.n1);
                 NS stt = nstats(c, c->statsT, op.n1);
                 launch_gn_apply(3, TG(op.hn), PS, TP(op.in), 0, TG(so), PS, TG(op.in), PS,
-                                op.in_is_skip ? 1 : 0, B, C, HW, G, sp.sc, sp.sh, sp.mr, 0, 0, stt.tst, c->stats_per_sample, st);
+                                op.in_is_skip ? 1 : 0, B, C, HW, G, sp.sc, sp.sh, sp.mr, 0, 0, stt.tst, c->prog->stats_per_sample, st);
                 break;
             }
             case OP_XFMR: {      // transposes of the forward chain, last map first
@@ -2464,14 +1770,14 @@ int cotangent_pass(loco_ctx* c, const float* ge, const float* gx0, float* Aout, 
                 NS sp = nstats(c, c->statsP, op.n1);
                 NS stt = nstats(c, c->statsT, op.n1);
                 launch_gn_apply(3, XG(X_G0), PS, TP(op.in), 0, TG(op.out), PS, TG(op.in), PS,
-                                op.in_is_skip ? 1 : 0, B, C, HW, G, sp.sc, sp.sh, sp.mr, 0, 0, stt.tst, c->stats_per_sample, st);
+                                op.in_is_skip ? 1 : 0, B, C, HW, G, sp.sc, sp.sh, sp.mr, 0, 0, stt.tst, c->prog->stats_per_sample, st);
                 break;
             }
             case OP_CONV_IN: {
                 ConvArgs a; conv_defaults(a);
                 a.in = TG(op.out); a.in_bs = PS; a.Cin = to.C; a.Hin = to.H; a.Win = to.W;
-                setw(a, op.conv, true); a.res = gx0; a.res_bs = c->n_in;
-                a.out = Aout; a.out_bs = c->n_in; a.Cout = cfg.in_channels; a.Hout = cfg.resolution;
+                setw(a, op.conv, true); a.res = gx0; a.res_bs = c->prog->n_in;
+                a.out = Aout; a.out_bs = c->prog->n_in; a.Cout = cfg.in_channels; a.Hout = cfg.resolution;
                 a.Wout = cfg.resolution; a.B = B;
                 if (op.ksize == 1) a.pad = 0;
                 run_conv(c, a, op.ksize == 1 ? 1 : 9, st);
@@ -2505,10 +1811,10 @@ struct LaneSwap {
     LaneSwap(loco_ctx* c_, int s0) : c(c_) {
         arenaT = c->arenaT; statsT = c->statsT; partial = c->partial; eps_buf = c->eps_buf; ge = c->ge; gx0 = c->gx0;
         // the flash cotangent indexes its delta scratch by the lane-local sample: lane 1 gets the slots of ITS samples
-        attn_delta = c->attn_delta; c->attn_delta += (long)s0 * c->attn_dmax;
+        attn_delta = c->attn_delta; c->attn_delta += (long)s0 * c->prog->attn_dmax;
         red = c->red; partial_floats = c->partial_floats; stpart = c->stpart; c->stpart = c->stpart2;
-        c->arenaT += (long)s0 * c->per_sample; c->statsT += (long)s0 * c->stats_per_sample;
-        c->eps_buf += (long)s0 * c->n_out; c->ge += (long)s0 * c->n_out; c->gx0 += (long)s0 * c->n_in;
+        c->arenaT += (long)s0 * c->prog->per_sample; c->statsT += (long)s0 * c->prog->stats_per_sample;
+        c->eps_buf += (long)s0 * c->prog->n_out; c->ge += (long)s0 * c->prog->n_out; c->gx0 += (long)s0 * c->prog->n_in;
         c->partial += partial_floats / 2; c->partial_floats = partial_floats / 2;
         c->red = c->red2;
         c->lane = 1; c->lane_s0 = s0;
@@ -2542,6 +1848,103 @@ int run_lanes(loco_ctx* c, int B, hipStream_t st, F body) {      // body(first s
     HIPCHK(c, hipStreamWaitEvent(st, c->ev_join, 0));
     return 0;
 }
+// Per-context state of the program's tensors and ops, in this context's views of them: the one place that allocates it, for a
+// created and a forked context alike.
+int alloc_state(loco_ctx* c) {
+    const Program& P = *c->prog;
+    const size_t MB = (size_t)c->cfg.max_batch;
+    c->tens.resize(P.tens.size());
+    c->ops.resize(P.ops.size());
+    for (size_t i = 0; i < P.tens.size(); ++i) {
+        Tens& t = c->tens[i];
+        static_cast<TensPlan&>(t) = P.tens[i];
+        if (t.cat_of < 0) continue;      // kept tile partials of the concatenation parts: [B][C][<= HW / 64 tiles][2]
+        t.keep_floats = MB * (size_t)t.C * ((size_t)t.H * t.W / 64 + 1) * 2;
+        if (dalloc(c, &t.keep, t.keep_floats)) return -1;
+    }
+    for (size_t i = 0; i < P.ops.size(); ++i) {
+        const OpPlan& plan = P.ops[i];
+        Op& v = c->ops[i];
+        static_cast<OpPlan&>(v) = plan;
+        static_cast<NormPlan&>(v.n1) = plan.n1; static_cast<NormPlan&>(v.n2) = plan.n2; static_cast<NormPlan&>(v.nx) = plan.nx;
+        if (!plan.has_ctx_kv()) continue;      // the projected prompt states are per context (loco_set_context)
+        const size_t kv = (size_t)P.tens[plan.in].C * P.ctx_Lp;
+        if (dalloc(c, &v.xK, kv) || dalloc(c, &v.xV, kv)) return -1;
+    }
+    return 0;
+}
+
+// Everything a context owns, for the program `prog` (its own for loco_create, the root's for loco_fork)
+int create_ctx(loco_ctx* c, const loco_unet_cfg* cfg, std::shared_ptr<const Program> prog) {
+    c->cfg = *cfg;
+    c->prog = std::move(prog);
+    const size_t MB = (size_t)cfg->max_batch;
+    {   // 64-float guard bands: the vector halo loads of the convs may touch 1 float before / 3 after a tensor
+        float *p0 = nullptr, *p1 = nullptr;
+        if (dalloc(c, &p0, MB * c->prog->per_sample + 128) || dalloc(c, &p1, MB * c->prog->per_sample + 128)) return -1;
+        c->arenaP = p0 + 64; c->arenaT = p1 + 64;
+    }
+    if (dalloc(c, &c->statsP, MB * c->prog->stats_per_sample) || dalloc(c, &c->statsT, MB * c->prog->stats_per_sample)) return -1;
+    if (dalloc(c, &c->red, RED_BYTES) || dalloc(c, &c->red2, RED_BYTES)) return -1;
+    if (alloc_state(c)) return -1;
+    {   // row partials of the epilogue statistics: [B][C][pixel tiles >= HW / 64][2] of the largest tensor
+        c->stpart_floats = MB * (size_t)(c->prog->max_tensor / 64 + 1) * 2;
+        if (dalloc(c, &c->stpart, c->stpart_floats) || dalloc(c, &c->stpart2, c->stpart_floats)) return -1;
+        const char* e = getenv("LOCO_FUSE_STATS");
+        c->fuse_stats = !(e && atoi(e) == 0);
+        e = getenv("LOCO_FUSE_LIN");
+        c->fuse_lin = !(e && atoi(e) == 0);
+        e = getenv("LOCO_FUSE_COT");
+        c->fuse_cot = !(e && atoi(e) == 0) && cfg->act == ACT_SILU;     // the epilogue term is written for SiLU
+        e = getenv("LOCO_DEEP1");
+        c->deep1 = !(e && atoi(e) == 0);
+        e = getenv("LOCO_FUSE_XATTN");
+        c->fuse_xattn = !(e && atoi(e) == 0);
+        const char* fa = getenv("LOCO_FLASH_ATTN");
+        c->flash_attn = !(fa && atoi(fa) == 0);
+        if (dalloc(c, &c->attn_delta, MB * (size_t)c->prog->attn_dmax)) return -1;
+    }
+    c->partial_floats = (size_t)64 << 20;   // 256 MB split-K workspace
+    if (dalloc(c, &c->partial, c->partial_floats)) return -1;
+    if (dalloc(c, &c->xin_buf, MB * c->prog->n_in) || dalloc(c, &c->t_dev, 4)) return -1;
+    if (dalloc(c, &c->eps_buf, MB * c->prog->n_out) || dalloc(c, &c->gx0, MB * c->prog->n_in) || dalloc(c, &c->ge, MB * c->prog->n_out))
+        return -1;
+    if (dalloc(c, &c->tmpA, (size_t)64 * c->prog->n_in)) return -1;
+    if (dalloc(c, &c->G, 64 * 64) || dalloc(c, &c->Q, 64 * 64) || dalloc(c, &c->W, 64)) return -1;
+    {
+        size_t nblk = ((size_t)c->prog->n_in + 255) / 256;
+        if (dalloc(c, &c->gscratch, nblk * 64 * 64 + 4096)) return -1;
+    }
+    if (dalloc(c, &c->alphas, 256) || dalloc(c, &c->cond_add, (size_t)cfg->ch * 4)) return -1;
+    {
+        float2* sx0 = nullptr;
+        if (dalloc(c, &sx0, (size_t)c->prog->sx_total + 64)) return -1;
+        c->sxcache = sx0 + 32;
+    }
+    {
+        const char* e = getenv("LOCO_PRECISION");
+        c->prec = (e && std::string(e) == "f32") ? 0 : (e && std::string(e) == "f16") ? 2 : 1;   // default: split-bf16
+    }
+    if (dalloc(c, &c->mask2, (size_t)c->prog->n_out)) return -1;
+    if (dalloc(c, &c->mask, (size_t)c->prog->n_out) || dalloc(c, &c->mask_idx, (size_t)c->prog->n_out) ||
+        dalloc(c, &c->mask_L_dev, 4)) return -1;
+    HIPCHK(c, hipEventCreate(&c->ev0));
+    HIPCHK(c, hipEventCreate(&c->ev1));
+    {
+        const char* e = getenv("LOCO_STREAMS");
+        c->n_streams = (e && atoi(e) == 2) ? 2 : 1;
+        HIPCHK(c, hipStreamCreateWithFlags(&c->st2, hipStreamNonBlocking));
+        HIPCHK(c, hipStreamCreateWithFlags(&c->cap_st, hipStreamNonBlocking));
+        const char* gl = getenv("LOCO_GEMM_LOWP");
+        if (gl) c->gemm_lowp = atoi(gl) != 0;
+        const char* gr = getenv("LOCO_GRAPH");
+        c->graph_on = gr && atoi(gr) == 1;
+        HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+        HIPCHK(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
+    }
+    return 0;
+}
+
 }  // namespace
 
 // =============================== C ABI =======================================
@@ -2565,137 +1968,13 @@ int loco_create(const loco_unet_cfg* cfg, loco_ctx** out) {
                  std::to_string(sizeof(loco_unet_cfg)) + " (binding and library built from different headers)";
         return -2;
     }
-    c->cfg = *cfg;
-    if (cfg->max_batch < 1 || cfg->num_levels < 1 || cfg->num_levels > 8) { c->err = "bad config"; return -2; }
-    {
-        int r = cfg->resolution;
-        for (int l = 0; l < cfg->num_levels - 1; ++l) r /= 2;
-        if (cfg->arch == 2) r = cfg->resolution;      // decoder: `resolution` is the coarsest (latent) level
-        if (cfg->arch > 3 || cfg->arch < 0) { c->err = "arch must be 0 (Ho-DDPM), 1 (guided-diffusion family), 2 (latent decoder) or 3 (latent encoder)"; return -2; }
-        if (r < 8 || (cfg->resolution & (cfg->resolution - 1))) {
-            c->err = "resolution must be a power of two with >= 8x8 at the coarsest level";
-            return -2;
-        }
-        if (cfg->ch % 32) { c->err = "ch must be a multiple of 32"; return -2; }
-    }
-    if (cfg->act != ACT_SILU && cfg->act != ACT_GELU) { c->err = "act must be 0 (SiLU) or 1 (GELU)"; return -2; }
-    c->res_scale = cfg->res_scale == 0.f ? 1.f : cfg->res_scale;
-    if ((cfg->act != ACT_SILU || c->res_scale != 1.f || cfg->added_kv) && cfg->arch != 1) {
-        c->err = "act / res_scale / added_kv belong to the guided-diffusion family (arch 1)"; return -2;
-    }
-    if (cfg->added_kv && (cfg->context_dim <= 0 || cfg->context_len <= 0 || cfg->transformer_depth != 0 ||
-                          cfg->context_dim % cfg->gn_groups)) {
-        c->err = "added_kv needs context_dim (a multiple of gn_groups) and context_len > 0 and transformer_depth = 0"; return -2;
-    }
-    if (build_program(c)) return -2;
-    for (auto& op : c->ops)
-        if (op.kind == OP_RES && op.updown && op.has_nin) { c->err = "resampling ResBlock with a channel change is not supported"; return -2; }
-    // which norm takes its statistics over exactly which tensor: the conv that finishes that tensor delivers them
-    for (size_t i = 0; i < c->ops.size(); ++i) {
-        const Op& op = c->ops[i];
-        if ((op.kind == OP_RES || op.kind == OP_ATTN || op.kind == OP_OUT || op.kind == OP_XFMR) && op.in >= 0) {
-            c->tens[op.in].cons_op = (int)i; c->tens[op.in].cons_norm = 1;
-        }
-        if (op.kind == OP_ATTN && op.has_x) { c->tens[op.xmid].cons_op = (int)i; c->tens[op.xmid].cons_norm = 2; }
-    }
-    // concatenations consumed by a norm: Q = [P1 | P2] with P1, P2 tensors of their own inside Q's storage
-    for (size_t q = 0; q < c->tens.size(); ++q) {
-        Tens& Q = c->tens[q];
-        if (Q.cons_op < 0) continue;
-        int p1 = -1, p2 = -1;
-        for (size_t i = 0; i < c->tens.size(); ++i) {
-            const Tens& P = c->tens[i];
-            if (i == q || P.H != Q.H || P.W != Q.W || P.C >= Q.C) continue;
-            if (P.off == Q.off) p1 = (int)i;
-        }
-        if (p1 < 0) continue;
-        for (size_t i = 0; i < c->tens.size(); ++i) {
-            const Tens& P = c->tens[i];
-            if (i != q && P.H == Q.H && P.W == Q.W && P.C == Q.C - c->tens[p1].C &&
-                P.off == Q.off + (long)c->tens[p1].C * Q.H * Q.W) p2 = (int)i;
-        }
-        if (p2 < 0) continue;
-        Q.cat_a = p1; Q.cat_b = p2;
-        c->tens[p1].cat_of = (int)q; c->tens[p2].cat_of = (int)q;
-    }
-    declare_all(c);
-    const size_t MB = (size_t)cfg->max_batch;
-    {   // 64-float guard bands: the vector halo loads of the convs may touch 1 float before / 3 after a tensor
-        float *p0 = nullptr, *p1 = nullptr;
-        if (dalloc(c, &p0, MB * c->per_sample + 128) || dalloc(c, &p1, MB * c->per_sample + 128)) return -1;
-        c->arenaP = p0 + 64; c->arenaT = p1 + 64;
-    }
-    if (dalloc(c, &c->statsP, MB * c->stats_per_sample) || dalloc(c, &c->statsT, MB * c->stats_per_sample)) return -1;
-    if (dalloc(c, &c->red, RED_BYTES) || dalloc(c, &c->red2, RED_BYTES)) return -1;
-    {   // row partials of the epilogue statistics: [B][C][pixel tiles >= HW / 64][2] of the largest tensor
-        long big = 0;
-        for (const Tens& t : c->tens) big = std::max(big, (long)t.C * t.H * t.W);
-        c->stpart_floats = MB * (size_t)(big / 64 + 1) * 2;
-        if (dalloc(c, &c->stpart, c->stpart_floats) || dalloc(c, &c->stpart2, c->stpart_floats)) return -1;
-        for (Tens& t : c->tens)          // kept tile partials of the concatenation parts: [B][C][<= HW / 64 tiles][2]
-            if (t.cat_of >= 0) {
-                t.keep_floats = MB * (size_t)t.C * ((size_t)t.H * t.W / 64 + 1) * 2;
-                if (dalloc(c, &t.keep, t.keep_floats)) return -1;
-            }
-        const char* e = getenv("LOCO_FUSE_STATS");
-        c->fuse_stats = !(e && atoi(e) == 0);
-        e = getenv("LOCO_FUSE_LIN");
-        c->fuse_lin = !(e && atoi(e) == 0);
-        e = getenv("LOCO_FUSE_COT");
-        c->fuse_cot = !(e && atoi(e) == 0) && cfg->act == ACT_SILU;     // the epilogue term is written for SiLU
-        e = getenv("LOCO_DEEP1");
-        c->deep1 = !(e && atoi(e) == 0);
-        e = getenv("LOCO_FUSE_XATTN");
-        c->fuse_xattn = !(e && atoi(e) == 0);
-        const char* fa = getenv("LOCO_FLASH_ATTN");
-        c->flash_attn = !(fa && atoi(fa) == 0);
-        long dmax = 1;
-        for (const Op& op : c->ops)
-            if (op.kind == OP_ATTN || op.kind == OP_XFMR) dmax = std::max(dmax, (long)op.heads * c->tens[op.in].H * c->tens[op.in].W);
-        c->attn_dmax = dmax;
-        if (dalloc(c, &c->attn_delta, MB * (size_t)dmax)) return -1;
-    }
-    c->partial_floats = (size_t)64 << 20;   // 256 MB split-K workspace
-    if (dalloc(c, &c->partial, c->partial_floats)) return -1;
-    if (dalloc(c, &c->xin_buf, MB * c->n_in) || dalloc(c, &c->t_dev, 4)) return -1;
-    if (dalloc(c, &c->eps_buf, MB * c->n_out) || dalloc(c, &c->gx0, MB * c->n_in) || dalloc(c, &c->ge, MB * c->n_out))
-        return -1;
-    if (dalloc(c, &c->tmpA, (size_t)64 * c->n_in)) return -1;
-    if (dalloc(c, &c->G, 64 * 64) || dalloc(c, &c->Q, 64 * 64) || dalloc(c, &c->W, 64)) return -1;
-    {
-        size_t nblk = ((size_t)c->n_in + 255) / 256;
-        if (dalloc(c, &c->gscratch, nblk * 64 * 64 + 4096)) return -1;
-    }
-    if (dalloc(c, &c->alphas, 256) || dalloc(c, &c->cond_add, (size_t)cfg->ch * 4)) return -1;
-    {
-        float2* sx0 = nullptr;
-        if (dalloc(c, &sx0, (size_t)c->sx_total + 64)) return -1;
-        c->sxcache = sx0 + 32;
-    }
-    {
-        const char* e = getenv("LOCO_PRECISION");
-        c->prec = (e && std::string(e) == "f32") ? 0 : (e && std::string(e) == "f16") ? 2 : 1;   // default: split-bf16
-    }
-    if (dalloc(c, &c->mask2, (size_t)c->n_out)) return -1;
-    if (dalloc(c, &c->mask, (size_t)c->n_out) || dalloc(c, &c->mask_idx, (size_t)c->n_out) ||
-        dalloc(c, &c->mask_L_dev, 4)) return -1;
-    HIPCHK(c, hipEventCreate(&c->ev0));
-    HIPCHK(c, hipEventCreate(&c->ev1));
-    {
-        const char* e = getenv("LOCO_STREAMS");
-        c->n_streams = (e && atoi(e) == 2) ? 2 : 1;
-        HIPCHK(c, hipStreamCreateWithFlags(&c->st2, hipStreamNonBlocking));
-        HIPCHK(c, hipStreamCreateWithFlags(&c->cap_st, hipStreamNonBlocking));
-        const char* gl = getenv("LOCO_GEMM_LOWP");
-        if (gl) c->gemm_lowp = atoi(gl) != 0;
-        const char* gr = getenv("LOCO_GRAPH");
-        c->graph_on = gr && atoi(gr) == 1;
-        HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-        HIPCHK(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-    }
-    return 0;
+    auto prog = std::make_shared<Program>();
+    if (const int rc = build_program(*cfg, prog.get(), &c->err)) return rc;
+    for (const ParamDecl& d : prog->params) c->params[d.name].shape = d.shape;
+    c->wts = std::make_shared<Weights>();
+    c->wts->op.resize(prog->ops.size());
+    return create_ctx(c, cfg, std::move(prog));
 }
-
 
 int loco_fork(loco_ctx* parent, int32_t max_batch, loco_ctx** out) {
     if (!parent || !out) return -2;
@@ -2704,36 +1983,12 @@ int loco_fork(loco_ctx* parent, int32_t max_batch, loco_ctx** out) {
     loco_ctx* root = parent->weights_of ? parent->weights_of : parent;      // forks of a fork share the root's store
     loco_unet_cfg cfg = parent->cfg;
     if (max_batch > 0) cfg.max_batch = max_batch;
-    loco_ctx* c = nullptr;
-    const int rc = loco_create(&cfg, &c);
+    loco_ctx* c = new loco_ctx();
     *out = c;
-    if (rc) return rc;
-    if (c->ops.size() != root->ops.size()) { c->err = "loco_fork: programs differ"; return -2; }
-    // the parameter pointers of every operator (program-dependent fields -- tensor ids, statistics offsets -- are the child's own,
-    // identical by construction: same configuration, same build_program)
-    for (size_t i = 0; i < c->ops.size(); ++i) {
-        Op& d = c->ops[i];
-        const Op& s_ = root->ops[i];
-        d.c1 = s_.c1; d.c2 = s_.c2; d.nin = s_.nin; d.qkvc = s_.qkvc; d.proj = s_.proj; d.conv = s_.conv;
-        d.xqc = s_.xqc; d.xproj = s_.xproj;
-        d.pj_in = s_.pj_in; d.to_out1 = s_.to_out1; d.to_out2 = s_.to_out2; d.ff1 = s_.ff1; d.ff2 = s_.ff2; d.pj_out = s_.pj_out;
-        d.n1.gamma = s_.n1.gamma; d.n1.beta = s_.n1.beta; d.n2.gamma = s_.n2.gamma; d.n2.beta = s_.n2.beta;
-        d.nx.gamma = s_.nx.gamma; d.nx.beta = s_.nx.beta;
-        d.xkw = s_.xkw; d.xkb = s_.xkb; d.xvw = s_.xvw; d.xvb = s_.xvb; d.xng = s_.xng; d.xnb = s_.xnb;
-        for (int k = 0; k < 3; ++k) { d.lng[k] = s_.lng[k]; d.lnb[k] = s_.lnb[k]; }
-        d.tproj_off = s_.tproj_off;
-        if (s_.xK) {      // the projected prompt states are per context (loco_set_context)
-            const size_t kv = (size_t)c->tens[d.in].C * c->ctx_Lp;
-            if (dalloc(c, &d.xK, kv) || dalloc(c, &d.xV, kv)) return -1;
-        }
-    }
-    c->td0w = root->td0w; c->td0b = root->td0b; c->td1w = root->td1w; c->td1b = root->td1b; c->freq = root->freq;
-    c->tp_w = root->tp_w; c->tp_b = root->tp_b; c->tproj_total = root->tproj_total;
-    if (dalloc(c, &c->tact, (size_t)cfg.ch * 4) || dalloc(c, &c->tproj, (size_t)(c->tproj_total > 0 ? c->tproj_total : 1))) return -1;
-    c->flops = root->flops;
+    if (const int rc = create_ctx(c, &cfg, root->prog)) return rc;
+    c->wts = root->wts;
+    if (bind_weights(c)) return -1;
     c->prec = parent->prec;
-    c->params.clear(); c->param_order.clear();
-    c->finalized = true;
     c->weights_of = root;
     ++root->forks;
     return 0;
@@ -2787,8 +2042,8 @@ int loco_params_missing(loco_ctx* c) {
     if (!c) return -2;
     if (c->finalized) return 0;
     int miss = 0;
-    for (auto& n : c->param_order)
-        if (!c->params[n].loaded) { if (!miss) c->err = "missing parameter: " + n; ++miss; }
+    for (const ParamDecl& d : c->prog->params)
+        if (!c->params[d.name].loaded) { if (!miss) c->err = "missing parameter: " + d.name; ++miss; }
     return miss;
 }
 
@@ -2816,18 +2071,18 @@ int loco_unet_forward(loco_ctx* c, const float* x, float t, int32_t B, float* ep
         // the first evaluation of a key runs eagerly (one-time lazy setup inside the launchers), the second is captured
         if (!g.exec && g.calls++ >= 1 && capture_forward(c, B, g)) return -1;
         if (g.exec) {
-            launch_copy(x, c->n_in, c->xin_buf, c->n_in, 0, B, c->n_in, st);
+            launch_copy(x, c->prog->n_in, c->xin_buf, c->prog->n_in, 0, B, c->prog->n_in, st);
             launch_set_scalar(c->t_dev, t, st);
             HIPCHK(c, hipGraphLaunch(g.exec, st));
             c->primal_B = B;
-            launch_copy(c->arenaP + c->tens[c->eps_t].off, c->per_sample, eps, c->n_out, 0, B, c->n_out, st);
+            launch_copy(c->arenaP + c->tens[c->prog->eps_t].off, c->prog->per_sample, eps, c->prog->n_out, 0, B, c->prog->n_out, st);
             HIPCHK(c, hipGetLastError());
             return 0;
         }
     }
     if (forward_pass(c, x, t, B, c->arenaP, c->statsP, st)) return -1;
     c->primal_B = B;
-    launch_copy(c->arenaP + c->tens[c->eps_t].off, c->per_sample, eps, c->n_out, 0, B, c->n_out, st);
+    launch_copy(c->arenaP + c->tens[c->prog->eps_t].off, c->prog->per_sample, eps, c->prog->n_out, 0, B, c->prog->n_out, st);
     HIPCHK(c, hipGetLastError());
     return 0;
 }
@@ -2861,17 +2116,17 @@ int loco_ddim_step(loco_ctx* c, const float* x, float t, float at, float at_next
                    int32_t B, float* x_next, void* stream) {
     if (!c) return -2;
     if (eta != 0.f && !noise) { c->err = "eta != 0 needs a noise tensor"; return -2; }
-    if (c->n_out != c->n_in) { c->err = "loco_ddim_step: this network is not a denoiser (output and input sizes differ)"; return -2; }
+    if (c->prog->n_out != c->prog->n_in) { c->err = "loco_ddim_step: this network is not a denoiser (output and input sizes differ)"; return -2; }
     int rc = loco_unet_forward(c, x, t, B, c->eps_buf, stream);
     if (rc) return rc;
-    return loco_sched_step(c, x, c->eps_buf, at, at_next, eta, noise, (int64_t)B * c->n_in, x_next, nullptr, stream);
+    return loco_sched_step(c, x, c->eps_buf, at, at_next, eta, noise, (int64_t)B * c->prog->n_in, x_next, nullptr, stream);
 }
 
 int loco_pmp_primal(loco_ctx* c, const float* x, float t, float at, const uint8_t* mask, int32_t use_et,
                     void* stream) {
     if (!c) return -2;
     if (finalize_params(c)) return -3;
-    if (c->n_out != c->n_in && !use_et) {
+    if (c->prog->n_out != c->prog->n_in && !use_et) {
         c->err = "loco_pmp_primal: a network whose output size differs from its input has no x0 combination; use_et = 1 "
                  "(raw network Jacobian)";
         return -2;
@@ -2900,12 +2155,12 @@ int loco_pmp_primal(loco_ctx* c, const float* x, float t, float at, const uint8_
     else { c->p_cv = 1.0f / std::sqrt(at); c->p_ce = -std::sqrt(1.0f - at) / std::sqrt(at); }
     c->has_mask = (mask != nullptr);
     c->has_mask2 = false;
-    c->mask_L = c->n_out;
+    c->mask_L = c->prog->n_out;
     if (mask) {
         // masked-latent gather list built on the device (ordered prefix-sum compaction, one launch, no host sync);
         // L is read back lazily by loco_mask_count / loco_mask_gather
-        HIPCHK(c, hipMemcpyAsync(c->mask, mask, (size_t)c->n_out, hipMemcpyDeviceToDevice, st));
-        launch_mask_compact(c->mask, c->n_out, c->mask_idx, c->mask_L_dev, st);
+        HIPCHK(c, hipMemcpyAsync(c->mask, mask, (size_t)c->prog->n_out, hipMemcpyDeviceToDevice, st));
+        launch_mask_compact(c->mask, c->prog->n_out, c->mask_idx, c->mask_L_dev, st);
         c->mask_L = -1;
         c->mask_stream = st;
     }
@@ -2920,7 +2175,7 @@ int loco_pmp_set_second_mask(loco_ctx* c, const uint8_t* mask2, int32_t from_row
     if (!mask2) { c->has_mask2 = false; return 0; }
     if (!c->has_mask) { c->err = "a second mask needs a first one (loco_pmp_primal with mask)"; return -2; }
     if (from_row < 0) { c->err = "from_row must be >= 0"; return -2; }
-    HIPCHK(c, hipMemcpyAsync(c->mask2, mask2, (size_t)c->n_out, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    HIPCHK(c, hipMemcpyAsync(c->mask2, mask2, (size_t)c->prog->n_out, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     c->has_mask2 = true;
     c->mask2_from = from_row;
     return 0;
@@ -2934,12 +2189,12 @@ int loco_pmp_jvp(loco_ctx* c, const float* V, int32_t k, float* U, void* stream)
     for (int b0 = 0; b0 < k; b0 += MB) {
         int B = (k - b0 < MB) ? k - b0 : MB;
         int rc = run_lanes(c, B, st, [&](int s0, int nb, hipStream_t ls) -> int {
-            const float* Vc = V + (long)(b0 + s0) * c->n_in;
+            const float* Vc = V + (long)(b0 + s0) * c->prog->n_in;
             if (tangent_pass(c, Vc, nb, ls)) return -1;
             // U = mask * (cv*V + ce*dEps); dEps lives strided in arena T -> gather through eps_buf
-            launch_copy(c->arenaT + c->tens[c->eps_t].off, c->per_sample, c->eps_buf, c->n_out, 0, nb, c->n_out, ls);
-            launch_masked_axpby(c->n_out == c->n_in ? Vc : nullptr, c->eps_buf, c->has_mask ? c->mask : nullptr, c->p_cv,
-                                c->p_ce, U + (long)(b0 + s0) * c->n_out, nb, c->n_out, ls,
+            launch_copy(c->arenaT + c->tens[c->prog->eps_t].off, c->prog->per_sample, c->eps_buf, c->prog->n_out, 0, nb, c->prog->n_out, ls);
+            launch_masked_axpby(c->prog->n_out == c->prog->n_in ? Vc : nullptr, c->eps_buf, c->has_mask ? c->mask : nullptr, c->p_cv,
+                                c->p_ce, U + (long)(b0 + s0) * c->prog->n_out, nb, c->prog->n_out, ls,
                                 c->has_mask2 ? c->mask2 : nullptr, (long)c->mask2_from - (b0 + s0));
             return 0;
         });
@@ -2957,11 +2212,11 @@ int loco_pmp_vjp(loco_ctx* c, const float* U, int32_t k, float* A, void* stream)
     for (int b0 = 0; b0 < k; b0 += MB) {
         int B = (k - b0 < MB) ? k - b0 : MB;
         int rc = run_lanes(c, B, st, [&](int s0, int nb, hipStream_t ls) -> int {
-            const bool same = c->n_out == c->n_in;
-            launch_cot_seed(U + (long)(b0 + s0) * c->n_out, c->has_mask ? c->mask : nullptr, c->p_cv, c->p_ce, c->ge,
-                            same ? c->gx0 : nullptr, nb, c->n_out, ls, c->has_mask2 ? c->mask2 : nullptr,
+            const bool same = c->prog->n_out == c->prog->n_in;
+            launch_cot_seed(U + (long)(b0 + s0) * c->prog->n_out, c->has_mask ? c->mask : nullptr, c->p_cv, c->p_ce, c->ge,
+                            same ? c->gx0 : nullptr, nb, c->prog->n_out, ls, c->has_mask2 ? c->mask2 : nullptr,
                             (long)c->mask2_from - (b0 + s0));
-            return cotangent_pass(c, c->ge, same ? c->gx0 : nullptr, A + (long)(b0 + s0) * c->n_in, nb, ls);
+            return cotangent_pass(c, c->ge, same ? c->gx0 : nullptr, A + (long)(b0 + s0) * c->prog->n_in, nb, ls);
         });
         if (rc) return rc;
     }
@@ -2971,7 +2226,7 @@ int loco_pmp_vjp(loco_ctx* c, const float* U, int32_t k, float* A, void* stream)
 
 int loco_orthonormalize(loco_ctx* c, float* A, int32_t k, int64_t n, float* s, void* stream) {
     if (!c) return -2;
-    if (k < 1 || k > 64 || n > c->n_in) { c->err = "orthonormalize: need k <= 64 and n <= C*H*W"; return -2; }
+    if (k < 1 || k > 64 || n > c->prog->n_in) { c->err = "orthonormalize: need k <= 64 and n <= C*H*W"; return -2; }
     hipStream_t st = (hipStream_t)stream;
     launch_gram(A, k, n, c->G, c->gscratch, st);
     launch_jacobi_eig(c->G, k, c->W, c->Q, st);
@@ -2985,7 +2240,7 @@ int loco_orthonormalize(loco_ctx* c, float* A, int32_t k, int64_t n, float* s, v
 
 int loco_qr_rows(loco_ctx* c, float* A, int32_t k, int64_t n, void* stream) {
     if (!c) return -2;
-    if (k < 1 || k > 64 || n > c->n_in) { c->err = "qr_rows: need k <= 64 and n <= C*H*W"; return -2; }
+    if (k < 1 || k > 64 || n > c->prog->n_in) { c->err = "qr_rows: need k <= 64 and n <= C*H*W"; return -2; }
     hipStream_t st = (hipStream_t)stream;
     for (int rep = 0; rep < 2; ++rep) {   // CholeskyQR2
         launch_gram(A, k, n, c->G, c->gscratch, st);
@@ -3010,10 +2265,10 @@ int loco_convergence_rows(loco_ctx* c, const float* Vprev, const float* V, int32
     if (!c) return -2;
     if (k < 1 || k > 64 || n < 1) { c->err = "convergence_rows: need 1 <= k <= 64"; return -2; }
     // the kernel leaves k * min(64, ceil(n / 256)) * 4 doubles in gscratch, which is sized for rows of the context's own width
-    if (n > c->n_in) { c->err = "convergence_rows: rows longer than the context's input"; return -2; }
+    if (n > c->prog->n_in) { c->err = "convergence_rows: rows longer than the context's input"; return -2; }
     {
         const size_t nseg = (size_t)((n + 255) / 256) < 64 ? (size_t)((n + 255) / 256) : 64;
-        const size_t cap = (((size_t)c->n_in + 255) / 256) * 64 * 64 + 4096;       // doubles in gscratch (finalize_params)
+        const size_t cap = (((size_t)c->prog->n_in + 255) / 256) * 64 * 64 + 4096;       // doubles in gscratch (finalize_params)
         if ((size_t)k * nseg * 4 > cap) { c->err = "convergence_rows: k rows of this length exceed the reduction workspace"; return -2; }
     }
     launch_convergence_rows(Vprev, V, k, n, atol, 1e-5f, out2, c->gscratch, (hipStream_t)stream);
@@ -3024,7 +2279,7 @@ int loco_convergence_rows(loco_ctx* c, const float* Vprev, const float* V, int32
 int loco_null_project(loco_ctx* c, const float* Vm, int32_t k, const float* Vn, int32_t k0, int64_t n, float* out,
                       void* stream) {
     if (!c) return -2;
-    if (k < 1 || k > 64 || k0 > 64 || n > c->n_in) { c->err = "null_project: bad sizes"; return -2; }
+    if (k < 1 || k > 64 || k0 > 64 || n > c->prog->n_in) { c->err = "null_project: bad sizes"; return -2; }
     hipStream_t st = (hipStream_t)stream;
     if (Vn && k0 > 0) {
         launch_cross_gram(Vn, k0, Vm, k, n, c->G, c->gscratch, st);
@@ -3064,12 +2319,12 @@ int loco_mask_gather(loco_ctx* c, const float* U, int32_t k, float* out, void* s
     if (!c->primal_ok) { c->err = "loco_pmp_primal has not been called"; return -2; }
     hipStream_t st = (hipStream_t)stream;
     if (!c->has_mask) {
-        HIPCHK(c, hipMemcpyAsync(out, U, (size_t)k * c->n_out * sizeof(float), hipMemcpyDeviceToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(out, U, (size_t)k * c->prog->n_out * sizeof(float), hipMemcpyDeviceToDevice, st));
         return 0;
     }
     const long L = mask_count_lazy(c);
     if (L < 0) { c->err = "mask count readback failed"; return -1; }
-    if (L > 0) launch_mask_gather(U, c->mask_idx, L, c->n_out, k, out, st);
+    if (L > 0) launch_mask_gather(U, c->mask_idx, L, c->prog->n_out, k, out, st);
     HIPCHK(c, hipGetLastError());
     return 0;
 }
@@ -3084,7 +2339,7 @@ int loco_clock_stamp(loco_ctx* c, uint64_t* out2, void* stream) {
 double loco_unet_flops(loco_ctx* c) {
     if (!c) return 0.0;
     if (!c->finalized && finalize_params(c)) return 0.0;
-    return c->flops;
+    return c->wts->flops;
 }
 int64_t loco_workspace_bytes(loco_ctx* c) { return c ? (int64_t)c->bytes : 0; }
 
@@ -3127,7 +2382,7 @@ int loco_set_context(loco_ctx* c, const float* tokens, void* stream) {
     if (finalize_params(c)) return -3;
     hipStream_t st = (hipStream_t)stream;
     c->primal_ok = false;
-    const int L = c->cfg.context_len, D = c->cfg.context_dim, Lp = c->ctx_Lp;
+    const int L = c->cfg.context_len, D = c->cfg.context_dim, Lp = c->prog->ctx_Lp;
     if (!c->ctx_colbias) {
         std::vector<float> cb(Lp, -1e30f);
         for (int l = 0; l < L; ++l) cb[l] = 0.f;
@@ -3135,7 +2390,7 @@ int loco_set_context(loco_ctx* c, const float* tokens, void* stream) {
     }
     if (c->cfg.added_kv && !c->ctx_norm && dalloc(c, &c->ctx_norm, (size_t)L * D)) return -1;
     for (auto& op : c->ops) {
-        if (!((op.kind == OP_ATTN && (op.has_x || op.added_kv)) || op.kind == OP_XFMR)) continue;
+        if (!op.has_ctx_kv()) continue;
         const int C = c->tens[op.in].C;
         const float* tok = tokens;
         if (op.added_kv) {      // the block's own GroupNorm over the states [D][L] (norm_encoder), then encoder_kv
@@ -3164,7 +2419,7 @@ int loco_masked_axpby(loco_ctx* c, const float* V, const float* E, float cv, flo
                       void* stream) {
     if (!c) return -2;
     if (!c->primal_ok) { c->err = "loco_pmp_primal has not been called"; return -2; }
-    launch_masked_axpby(V, E, c->has_mask ? c->mask : nullptr, cv, ce, out, k, c->n_out, (hipStream_t)stream);
+    launch_masked_axpby(V, E, c->has_mask ? c->mask : nullptr, cv, ce, out, k, c->prog->n_out, (hipStream_t)stream);
     HIPCHK(c, hipGetLastError());
     return 0;
 }
@@ -3173,7 +2428,7 @@ int loco_latent_sample(loco_ctx* c, const float* moments, const float* noise, fl
     if (!c) return -2;
     if (c->cfg.arch != 3 || (c->cfg.out_ch & 1)) { c->err = "latent_sample: the context must be a latent encoder (arch 3) with out_ch = 2 z"; return -2; }
     if (B < 1 || !moments || !z) { c->err = "latent_sample: bad arguments"; return -2; }
-    launch_latent_sample(moments, noise, scale, z, B, c->n_out / 2, (hipStream_t)stream);
+    launch_latent_sample(moments, noise, scale, z, B, c->prog->n_out / 2, (hipStream_t)stream);
     HIPCHK(c, hipGetLastError());
     return 0;
 }
@@ -3223,8 +2478,8 @@ int loco_bench_conv(loco_ctx* c, int32_t cin, int32_t cout, int32_t H, int32_t W
     hipStream_t st = (hipStream_t)stream;
     const long HW = (long)H * W;
     const long in_e = (long)cin * HW, out_e = (long)cout * HW;
-    if ((in_e + out_e) * B > (long)c->cfg.max_batch * c->per_sample || 2 * in_e > (long)c->per_sample ||
-        in_e > c->sx_total) { c->err = "bench_conv: shape exceeds the arenas"; return -2; }
+    if ((in_e + out_e) * B > (long)c->cfg.max_batch * c->prog->per_sample || 2 * in_e > (long)c->prog->per_sample ||
+        in_e > c->prog->sx_total) { c->err = "bench_conv: shape exceeds the arenas"; return -2; }
     float* in = c->arenaT;
     float* out = c->arenaT + in_e * B;
     // LOCO_BENCH_ZERO (bit 1: activations, bit 2: weights): all-zero operands draw less power in the matrix pipe -- the time
@@ -3234,8 +2489,8 @@ int loco_bench_conv(loco_ctx* c, int32_t cin, int32_t cout, int32_t H, int32_t W
     launch_fill_random(in, in_e * B, 1u, zs, st);
     launch_fill_random(c->arenaP, in_e, 2u, zs, st);
     launch_fill_random(reinterpret_cast<float*>(c->sxcache), 2 * in_e, 3u, zs, st);
-    launch_fill_random(c->statsP, c->stats_per_sample, 4u, 1.0f, st);
-    launch_fill_random(c->statsT, c->stats_per_sample * B, 5u, 0.01f, st);
+    launch_fill_random(c->statsP, c->prog->stats_per_sample, 4u, 1.0f, st);
+    launch_fill_random(c->statsT, c->prog->stats_per_sample * B, 5u, 0.01f, st);
     // weights: any conv of matching size is fine for timing; synthesise records in the split-K workspace
     size_t wfl = (size_t)((cin + 15) / 16) * 16 * taps * ((cout + 31) & ~31);
     if (wfl * 2 > c->partial_floats) { c->err = "bench_conv: weights exceed workspace"; return -2; }
@@ -3253,18 +2508,18 @@ int loco_bench_conv(loco_ctx* c, int32_t cin, int32_t cout, int32_t H, int32_t W
     a.out = out; a.out_bs = out_e; a.Cout = cout; a.Hout = H; a.Wout = W; a.B = B;
     a.mode = mode; a.pad = taps == 9 ? 1 : 0; a.in_padded = 1; a.taps = taps;
     a.sc = c->statsP; a.sh = c->statsP + cin; a.scsh_bs = 0; a.mr = c->statsP + 2 * cin; a.mr_bs = 0;
-    a.gamma_ = c->statsP; a.tst = c->statsT; a.tst_bs = c->stats_per_sample; a.cpg = cin / c->cfg.gn_groups;
-    a.tc = c->statsT + 64; a.tc_bs = c->stats_per_sample;
+    a.gamma_ = c->statsP; a.tst = c->statsT; a.tst_bs = c->prog->stats_per_sample; a.cpg = cin / c->cfg.gn_groups;
+    a.tc = c->statsT + 64; a.tc_bs = c->prog->stats_per_sample;
     if (a.cpg < 1) a.cpg = 1;
     a.nsplit = 1; a.partial = c->partial;
     a.partial_floats = c->partial_floats - wfl * 2;                            // (the synthetic weights sit at the end of the workspace)
     if (getenv("LOCO_BENCH_COT") && atoi(getenv("LOCO_BENCH_COT")) && taps == 1) {
         // the ResBlock shortcut's cotangent form: norm-cotangent term in the epilogue (synthetic operands behind the output tensor)
-        if ((in_e + 2 * out_e) * B > (long)c->cfg.max_batch * c->per_sample || out_e > c->sx_total ||
-            2L * cout > c->stats_per_sample) { c->err = "bench_conv: cot operands exceed the arenas"; return -2; }
+        if ((in_e + 2 * out_e) * B > (long)c->cfg.max_batch * c->prog->per_sample || out_e > c->prog->sx_total ||
+            2L * cout > c->prog->stats_per_sample) { c->err = "bench_conv: cot operands exceed the arenas"; return -2; }
         launch_fill_random(out + out_e * B, out_e * B, 8u, zs, st);
         if (out_e > in_e) launch_fill_random(reinterpret_cast<float*>(c->sxcache), 2 * out_e, 3u, zs, st);
-        a.cot_d = out + out_e * B; a.cot_d_bs = out_e; a.cot_sx = c->sxcache; a.cot_tc = c->statsT; a.cot_tc_bs = c->stats_per_sample;
+        a.cot_d = out + out_e * B; a.cot_d_bs = out_e; a.cot_sx = c->sxcache; a.cot_tc = c->statsT; a.cot_tc_bs = c->prog->stats_per_sample;
     }
     if (getenv("LOCO_BENCH_ACC") && atoi(getenv("LOCO_BENCH_ACC"))) a.accumulate = 1;
     conv_plan_family(a, c->prec);
@@ -3375,7 +2630,7 @@ int64_t loco_debug_tensor(loco_ctx* c, const char* name, float* dst, int64_t cap
         int B = arena ? 1 : (c->primal_B > 0 ? c->primal_B : 1);
         if (cnt * B > cap) { c->err = "debug buffer too small"; return -4; }
         float* base = (arena ? c->arenaT : c->arenaP) + t.off;
-        launch_copy(base, c->per_sample, dst, cnt, 0, B, cnt, (hipStream_t)stream);
+        launch_copy(base, c->prog->per_sample, dst, cnt, 0, B, cnt, (hipStream_t)stream);
         return cnt * B;
     }
     c->err = "no such op: " + nm;

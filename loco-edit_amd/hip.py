@@ -159,6 +159,28 @@ def _chk_dev(t: torch.Tensor, dtype=torch.float32):
         raise ValueError("tensor must be contiguous")
 
 
+def c_cfg(cfg: UNetConfig, max_batch: int) -> LocoCfg:
+    """The loco_unet_cfg that loco_create receives for `cfg` (also what the host-side program check is fed)."""
+    c = LocoCfg()
+    c.struct_size = C.sizeof(LocoCfg)
+    c.resolution, c.in_channels, c.out_ch, c.ch = cfg.resolution, cfg.in_channels, cfg.out_ch, cfg.ch
+    c.num_levels = len(cfg.ch_mult)
+    for i, m in enumerate(cfg.ch_mult):
+        c.ch_mult[i] = m
+    c.num_res_blocks = cfg.num_res_blocks
+    c.num_attn_res = len(cfg.attn_resolutions)
+    for i, r in enumerate(cfg.attn_resolutions):
+        c.attn_resolutions[i] = r
+    c.gn_groups, c.gn_eps, c.max_batch = cfg.gn_groups, cfg.gn_eps, int(max_batch)
+    c.arch = {"ddpm": 0, "adm": 1, "dec": 2, "enc": 3}[cfg.arch]
+    c.num_head_channels, c.learn_sigma = cfg.num_head_channels, int(cfg.learn_sigma)
+    c.context_dim, c.context_len = cfg.context_dim, cfg.context_len
+    c.scale_shift_norm, c.resblock_updown = int(cfg.scale_shift_norm), int(cfg.resblock_updown)
+    c.num_heads, c.transformer_depth = cfg.num_heads, cfg.transformer_depth
+    c.act, c.res_scale, c.added_kv = {"silu": 0, "gelu": 1}[cfg.act], float(cfg.res_scale), int(cfg.added_kv)
+    return c
+
+
 class LocoEngine:
     """One engine (= loco_ctx) per process and GPU."""
 
@@ -170,23 +192,7 @@ class LocoEngine:
         torch.cuda.set_device(self.device)
         self.cfg = cfg
         self.max_batch = int(max_batch)
-        c = LocoCfg()
-        c.struct_size = C.sizeof(LocoCfg)
-        c.resolution, c.in_channels, c.out_ch, c.ch = cfg.resolution, cfg.in_channels, cfg.out_ch, cfg.ch
-        c.num_levels = len(cfg.ch_mult)
-        for i, m in enumerate(cfg.ch_mult):
-            c.ch_mult[i] = m
-        c.num_res_blocks = cfg.num_res_blocks
-        c.num_attn_res = len(cfg.attn_resolutions)
-        for i, r in enumerate(cfg.attn_resolutions):
-            c.attn_resolutions[i] = r
-        c.gn_groups, c.gn_eps, c.max_batch = cfg.gn_groups, cfg.gn_eps, self.max_batch
-        c.arch = {"ddpm": 0, "adm": 1, "dec": 2, "enc": 3}[cfg.arch]
-        c.num_head_channels, c.learn_sigma = cfg.num_head_channels, int(cfg.learn_sigma)
-        c.context_dim, c.context_len = cfg.context_dim, cfg.context_len
-        c.scale_shift_norm, c.resblock_updown = int(cfg.scale_shift_norm), int(cfg.resblock_updown)
-        c.num_heads, c.transformer_depth = cfg.num_heads, cfg.transformer_depth
-        c.act, c.res_scale, c.added_kv = {"silu": 0, "gelu": 1}[cfg.act], float(cfg.res_scale), int(cfg.added_kv)
+        c = c_cfg(cfg, self.max_batch)
         self._ctx = C.c_void_p()
         rc = self.lib.loco_create(C.byref(c), C.byref(self._ctx))
         if rc != 0:

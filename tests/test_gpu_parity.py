@@ -754,13 +754,17 @@ def test_bench_two_ranks_headline_is_two_replicas_of_the_metrics_unit():
     assert d["scaling"] == "weak" and len(d["singular_values"]) == 5
 
 
-@pytest.mark.parametrize("cfg", [TINY_DDPM, TINY_ADM], ids=["tiny", "tiny_adm"])
-def test_forked_context_shares_the_parameters_and_computes_the_same_bits(cfg):
+@pytest.mark.parametrize("which", ["tiny", "tiny_adm", "tiny_adm_xattn", "tiny_ldm", "tiny_if"])
+def test_forked_context_shares_the_parameters_and_computes_the_same_bits(which):
     """loco_fork (round 6): a second context on the parent's device parameters (all six layouts shared; own arenas, statistics,
     scratch, prompt constants) -- what the reference does with ONE U-Net object for all guidance branches (edit.py:1319-1322,
     :655-667).  Forward batch, J V and U^T J of the fork are bit-identical to an independently loaded context, its workspace is
-    smaller by the parameter store, and it outlives its parent."""
+    smaller by the parameter store, and it outlives its parent.  The prompt-conditioned configs (cross-attention stage,
+    SpatialTransformer, DeepFloyd-IF added keys / values) cover the per-context projected prompt states of a fork: every
+    context is given the same context / conditioning."""
+    from loco_edit_amd.config import TINY_ADM_XATTN, TINY_IF, TINY_LDM
     from loco_edit_amd.hip import LocoEngine
+    cfg = {"tiny": TINY_DDPM, "tiny_adm": TINY_ADM, "tiny_adm_xattn": TINY_ADM_XATTN, "tiny_ldm": TINY_LDM, "tiny_if": TINY_IF}[which]
     s_ = _sched()
     t = float(s_.timesteps[40]); at = float(s_.alpha_at(s_.timesteps[40]))
     gen = torch.Generator().manual_seed(11)
@@ -769,6 +773,12 @@ def test_forked_context_shares_the_parameters_and_computes_the_same_bits(cfg):
     mask = torch.zeros(cfg.out_ch, R, R, dtype=torch.bool); mask[:, R // 3:R // 2, R // 4:R // 2] = True
     V = torch.randn(3, cfg.n, generator=gen).to(DEV)
     params = synth_params(cfg, 0)
+    context = aug = None
+    if cfg.added_kv:
+        from loco_edit_amd.tloco import IFTextConditioner
+        context, aug = IFTextConditioner(params, cfg, DEV)(torch.randn(1, cfg.context_len, cfg.encoder_dim, generator=gen))
+    elif cfg.context_dim:
+        context = torch.randn(cfg.context_len, cfg.context_dim, generator=gen).to(DEV).contiguous()
 
     def run(eng):
         out = [eng.unet_forward(xs, t).clone()]
@@ -780,6 +790,11 @@ def test_forked_context_shares_the_parameters_and_computes_the_same_bits(cfg):
     b = LocoEngine(cfg, max_batch=4, device=torch.device(DEV)); b.load_state_dict(params)
     f = a.fork()
     f2 = f.fork(max_batch=3)                     # a fork of a fork shares the root's store
+    for e in (a, b, f, f2):
+        if context is not None:
+            e.set_context(context)
+        if aug is not None:
+            e.set_cond(aug)
     ref = run(b)
     assert a.workspace_bytes() == b.workspace_bytes() and f.workspace_bytes() < a.workspace_bytes()
     for prec in ("bf16x3", "f32"):
