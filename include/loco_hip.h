@@ -270,6 +270,26 @@ int  loco_set_context(loco_ctx* ctx, const float* tokens, void* stream);
 int  loco_lincomb(loco_ctx* ctx, const float* const* src, const float* coef, int32_t n, float* out, int64_t count,
                   void* stream);
 
+/* DiffEdit mask from two guided noise predictions: the body of EditDeepFloydIF.mask_diffedit after its denoiser calls
+ * (edit.py:1401-1402).  eps_a, eps_b: [B, C, HW] device tensors;
+ *   m[p] = mean_c( mean_b( scale * (eps_a[b,c,p] - eps_b[b,c,p]) ) )     (batch first, then channels, as the reference)
+ * rule 0 ("reference"): mask = round(m - min / (max - min)) != 0 with round-half-to-even, i.e. |m - min/(max - min)| > 0.5
+ *                       -- edit.py:1402 as its parentheses stand;
+ * rule 1 ("intended"):  mask = (m - min) / (max - min) > 0.5.
+ * m_out: [HW] floats or NULL, mask_out: [HW] uint8.  Two launches; min and max stay on the device, the call ends with one
+ * read-back of a status word (it synchronises the stream): a constant map (max == min, where the reference divides by zero
+ * and returns an all-True mask out of NaN) returns -4, a non-finite map -5, the cause in loco_last_error. */
+int  loco_diffedit_mask(loco_ctx* ctx, const float* eps_a, const float* eps_b, float scale, int32_t B, int32_t C,
+                        int64_t HW, int32_t rule, float* m_out, uint8_t* mask_out, void* stream);
+/* One step of EditDeepFloydIF.MaskedDDPMforwardsteps after the denoiser calls (edit.py:1540-1548), fused:
+ *   eF = n + g (f - n), eE = n + g (e - n)          (edit.py:1336, 1341: guidance_scale for both)
+ *   x_next = mask ? step(x, eE) : step(x, eF)        step = the eta = 0 update of loco_sched_step
+ * x, eps_for, eps_edit, eps_null, x_next: [B, n]; mask: uint8 [n] (the format loco_pmp_primal takes), broadcast over B.
+ * A select, so a non-finite value of the half not taken does not reach x_next.  x_next may alias x. */
+int  loco_cfg_masked_step(loco_ctx* ctx, const float* x, const float* eps_for, const float* eps_edit,
+                          const float* eps_null, float g, float at, float at_next, const uint8_t* mask, int32_t B,
+                          int64_t n, float* x_next, void* stream);
+
 /* Per-kernel HIP-event profile of the convolution launches (bench.py roofline
  * leg).  While enabled every conv launch is bracketed by two events on the
  * caller's stream; loco_profile_report synchronises, then writes one line per

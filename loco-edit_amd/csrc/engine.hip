@@ -2442,6 +2442,49 @@ int loco_lincomb(loco_ctx* c, const float* const* src, const float* coef, int32_
     return 0;
 }
 
+int loco_diffedit_mask(loco_ctx* c, const float* eps_a, const float* eps_b, float scale, int32_t B, int32_t C, int64_t HW,
+                       int32_t rule, float* m_out, uint8_t* mask_out, void* stream) {
+    if (!c) return -2;
+    if (!eps_a || !eps_b || !mask_out || B < 1 || C < 1 || HW < 1) { c->err = "diffedit_mask: bad arguments"; return -2; }
+    if (rule != 0 && rule != 1) { c->err = "diffedit_mask: rule is 0 (reference) or 1 (intended)"; return -2; }
+    // reduction workspace (doubles, create_ctx) read as floats: [0, 768) block partials, [768, 772) status, [1024, ..) the map
+    // when the caller does not ask for it
+    float* ws = reinterpret_cast<float*>(c->gscratch);
+    const size_t cap = 2 * ((((size_t)c->prog->n_in + 255) / 256) * 64 * 64 + 4096);
+    float* m = m_out;
+    if (!m) {
+        if (1024 + (size_t)HW > cap) { c->err = "diffedit_mask: map larger than the reduction workspace; pass m_out"; return -2; }
+        m = ws + 1024;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    launch_diffedit_mask(eps_a, eps_b, scale, B, C, (long)HW, rule, m, mask_out, ws, ws + 768, st);
+    HIPCHK(c, hipGetLastError());
+    float status[3] = {0.f, 0.f, 0.f};      // the one read-back, after both launches: a constant map is an error, not a mask
+    HIPCHK(c, hipMemcpyAsync(status, ws + 768, sizeof(status), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (status[0] == 1.f) {
+        c->err = "diffedit_mask: constant map (max == min = " + std::to_string(status[1]) + "): the two noise predictions do not differ";
+        return -4;
+    }
+    if (status[0] != 0.f) { c->err = "diffedit_mask: non-finite map"; return -5; }
+    return 0;
+}
+
+int loco_cfg_masked_step(loco_ctx* c, const float* x, const float* eps_for, const float* eps_edit, const float* eps_null,
+                         float g, float at, float at_next, const uint8_t* mask, int32_t B, int64_t n, float* x_next,
+                         void* stream) {
+    if (!c) return -2;
+    if (!x || !eps_for || !eps_edit || !eps_null || !mask || !x_next || B < 1 || n < 1) {
+        c->err = "cfg_masked_step: bad arguments";
+        return -2;
+    }
+    float s1, s2, s3, ce, cn;
+    sched_coeffs(at, at_next, 0.f, &s1, &s2, &s3, &ce, &cn);
+    launch_cfg_masked_step(x, eps_for, eps_edit, eps_null, mask, x_next, B, (long)n, g, s2, s1, s3, ce, (hipStream_t)stream);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
 // Tuning hook: time one convolution shape on scratch data (random inputs), avg ms over `iters` launches.
 #ifdef LOCO_DIAG     /* include/loco_hip_diag.h: tuning / bring-up hooks, only in the diag build */
 }  // extern "C"

@@ -374,6 +374,17 @@ void launch_cot_seed(const float* U, const uint8_t* mask, float cv, float ce, fl
 void launch_add(const float* a, const float* b, float* out, long count, hipStream_t st);
 // out = sum_{i<n} coef[i] * src[i]   (n <= 4, 16-byte aligned tensors of `count` floats; CFG combination of Jacobian products)
 void launch_lincomb(const float* const* src, const float* coef, int n, float* out, long count, hipStream_t st);
+// ---- DiffEdit (diffedit.hip) -----------------------------------------------------
+// m[HW] = mean_c mean_b scale (a - b) over [B][C][HW] tensors, then mask[HW] (uint8) by `rule` (0: |m - min/(max-min)| > 0.5,
+// the reference's line as written; 1: (m - min)/(max - min) > 0.5).  Two launches, min / max stay on the device.
+// part: 3 * 256 floats, status: 3 floats {0 fine | 1 constant map | 2 non-finite map, min, max}
+void launch_diffedit_mask(const float* eps_a, const float* eps_b, float scale, int B, int C, long HW, int rule, float* m,
+                          uint8_t* mask, float* part, float* status, hipStream_t st);
+// out = mask ? ddim(x, n + g (e - n)) : ddim(x, n + g (f - n)), eta = 0, coefficients as launch_ddim_step; mask uint8 [n]
+// broadcast over the B frames; out may alias x
+void launch_cfg_masked_step(const float* x, const float* ef, const float* ee, const float* en, const uint8_t* mask, float* out,
+                            int B, long n, float g, float c_x0_x, float c_x0_e, float c_next_x0, float c_next_e,
+                            hipStream_t st);
 
 // ---- solver --------------------------------------------------------------------
 // G[k][k] (double) = A A^T, A: [k][n] fp32

@@ -33,7 +33,11 @@ SYMBOLS = [
     "loco_set_cond", "loco_set_context", "loco_lincomb", "loco_masked_axpby", "loco_latent_sample",
     "loco_text_create", "loco_text_load_param", "loco_text_params_missing", "loco_text_encode", "loco_text_last_error",
     "loco_text_destroy", "loco_t5_create", "loco_text_encode_masked",
+    "loco_diffedit_mask", "loco_cfg_masked_step",
 ]
+
+# threshold rules of loco_diffedit_mask (include/loco_hip.h)
+DIFFEDIT_RULES = {"reference": 0, "intended": 1}
 
 
 class LocoCfg(C.Structure):
@@ -120,6 +124,8 @@ def load_library():
     lib.loco_masked_axpby.argtypes = [vp, vp, vp, f32, f32, i32, vp, vp]
     lib.loco_latent_sample.argtypes = [vp, vp, vp, f32, i32, vp, vp]
     lib.loco_lincomb.argtypes = [vp, C.POINTER(vp), C.POINTER(f32), i32, vp, i64, vp]
+    lib.loco_diffedit_mask.argtypes = [vp, vp, vp, f32, i32, i32, i64, i32, vp, vp, vp]
+    lib.loco_cfg_masked_step.argtypes = [vp, vp, vp, vp, vp, f32, f32, f32, vp, i32, i64, vp, vp]
     lib.loco_profile_enable.argtypes = [vp, i32]
     lib.loco_profile_report.argtypes = [vp, C.c_char_p, i64]
     if hasattr(lib, "loco_text_create"):
@@ -458,6 +464,54 @@ class LocoEngine:
         ptrs = (C.c_void_p * n)(*[t.data_ptr() for _, t in terms])
         coef = (C.c_float * n)(*[float(c) for c, _ in terms])
         self._check(self.lib.loco_lincomb(self._ctx, ptrs, coef, n, _ptr(out), out.numel(), _stream()), "loco_lincomb")
+        return out
+
+    # ---- DiffEdit (edit.py:1395-1407, :1486-1563)
+    def diffedit_mask(self, eps_a: torch.Tensor, eps_b: torch.Tensor, scale: float, rule: str = "reference",
+                      want_map: bool = False):
+        """uint8 mask [HW] from the two guided noise predictions [B, C, H, W] (or [B, C, HW]): the map
+        m = mean_c mean_b scale (eps_a - eps_b), thresholded by `rule` ("reference": |m - min/(max-min)| > 0.5, edit.py:1402
+        as written; "intended": (m - min)/(max - min) > 0.5).  A constant map raises ValueError (the reference divides by
+        zero there).  want_map: returns (mask, m)."""
+        _chk_dev(eps_a)
+        _chk_dev(eps_b)
+        if eps_a.shape != eps_b.shape or eps_a.dim() < 3:
+            raise ValueError(f"two [B, C, ...] tensors of one shape, got {tuple(eps_a.shape)} and {tuple(eps_b.shape)}")
+        if rule not in DIFFEDIT_RULES:
+            raise ValueError(f"rule must be one of {sorted(DIFFEDIT_RULES)}, got {rule!r}")
+        B, Cc = eps_a.shape[0], eps_a.shape[1]
+        HW = eps_a.numel() // (B * Cc)
+        mask = torch.empty(HW, device=eps_a.device, dtype=torch.uint8)
+        m = torch.empty(HW, device=eps_a.device, dtype=torch.float32) if want_map else None
+        rc = self.lib.loco_diffedit_mask(self._ctx, _ptr(eps_a), _ptr(eps_b), float(scale), B, Cc, HW, DIFFEDIT_RULES[rule],
+                                         _ptr(m), _ptr(mask), _stream())
+        if rc in (-4, -5):
+            raise ValueError(self.lib.loco_last_error(self._ctx).decode())
+        self._check(rc, "loco_diffedit_mask")
+        return (mask, m) if want_map else mask
+
+    def cfg_masked_step(self, x, ef, ee, en, g: float, at: float, at_next: float, mask: torch.Tensor,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One masked-sampler step: mask ? ddim(x, en + g (ee - en)) : ddim(x, en + g (ef - en)), eta = 0.  x, ef, ee, en:
+        [B, ...] of one shape; mask: uint8 with the elements of one frame, broadcast over B; out may be x."""
+        for t_ in (x, ef, ee, en):
+            _chk_dev(t_)
+            if t_.shape != x.shape:
+                raise ValueError(f"x and the three noise predictions must share a shape, got {tuple(t_.shape)} vs {tuple(x.shape)}")
+        _chk_dev(mask, torch.uint8)
+        B = x.shape[0]
+        n = x.numel() // B
+        if mask.numel() != n:
+            raise ValueError(f"mask must hold the {n} elements of one frame, got {tuple(mask.shape)}")
+        if out is None:
+            out = torch.empty_like(x)
+        else:
+            _chk_dev(out)
+            if out.shape != x.shape:
+                raise ValueError(f"out must be {tuple(x.shape)}, got {tuple(out.shape)}")
+        self._check(self.lib.loco_cfg_masked_step(self._ctx, _ptr(x), _ptr(ef), _ptr(ee), _ptr(en), float(g), float(at),
+                                                  float(at_next), _ptr(mask), B, n, _ptr(out), _stream()),
+                    "loco_cfg_masked_step")
         return out
 
     # ---- introspection

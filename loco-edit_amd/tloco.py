@@ -7,7 +7,10 @@ conditional noise predictions (``_classifer_free_guidance`` :1286-1373), ``get_x
 PMP-Jacobian subspace solver (``local_encoder_decoder_pullback_xt`` :1589-1676), the edit direction through the
 Jacobian and directly in noise space (``get_delta_xt_via_grad`` :1680-1717, ``get_v_modify`` :1720-1741), the sampler
 (``DDPMforwardsteps`` :1412-1481) and the two drivers (``run_edit_null_space_projection_xt`` :1745-1868,
-``..._xt_semantic`` :1871-2018, ablations ``null-space-proj`` and ``sega``).
+``..._xt_semantic`` :1871-2018, ablations ``null-space-proj``, ``sega`` and ``diffedit``), the mask derived from the two
+prompts (``mask_diffedit`` :1395-1407, ``--mask_type diffedit``) and the masked sampler behind the ``diffedit`` ablation
+(``MaskedDDPMforwardsteps`` :1486-1563): the reductions / updates around the denoiser calls are the two kernels of
+``csrc/diffedit.hip`` (``loco_diffedit_mask``, ``loco_cfg_masked_step``).
 
 Why several engines: J = d x0_hat / d x_t with eps = sum_c w_c eps_c(x, t | prompt_c) is the same linear combination of
 the per-prompt Jacobians, J V = mask (V/sqrt(at) - sqrt(1-at)/sqrt(at) sum_c w_c dEps_c V).  Each prompt gets its own
@@ -25,7 +28,7 @@ guided-diffusion U-Net whose time embedding receives ``cond_proj(mean_tokens(pro
 cross-attention stages.  Prompt embeddings come from the T5 encoder on the GPU (``--text_encoder_path``: ``csrc/t5enc.hip``
 through ``text_encoder.TextEncoder``, the prompts lower-cased and stripped as ``IFPipeline.encode_prompt`` does, one batched
 encode of for / edit / null / neg / inv; a driver's ``edit_prompt`` re-encodes), are inputs (``--prompt_emb_path``: a dict of
-[1, tokens, D] tensors) or seeded; stages II/III, SAM and the ``diffedit`` ablation are not on this path.
+[1, tokens, D] tensors) or seeded; stages II/III and SAM are not on this path (``--mask_type SAM`` reads ``mask/mask.pt``).
 """
 from __future__ import annotations
 
@@ -139,6 +142,18 @@ class IFScheduler(object):
         nxt, x0 = self.engine.sched_step(xt.contiguous(), et.contiguous(), self.alpha_at(t), self.alpha_at(t_next), 0.0,
                                          None, want_x0=True)
         return SchedulerOutput(nxt, x0)
+
+
+def diffedit_rule() -> str:
+    """How edit.py:1402 is applied (``LOCO_DIFFEDIT_RULE``, default ``reference``).
+
+    ``reference``: ``round(m - min / (max - min))`` as the line's parentheses stand -- ``min`` is divided by the range before
+    it is subtracted, so the mask is ``|m - c| > 0.5`` with the constant ``c = min / (max - min)``; what a drop-in has to
+    reproduce.  ``intended``: ``(m - min) / (max - min) > 0.5``, the min-max normalisation the line was meant to be."""
+    rule = os.environ.get("LOCO_DIFFEDIT_RULE", "reference")
+    if rule not in ("reference", "intended"):
+        raise ValueError(f"LOCO_DIFFEDIT_RULE must be 'reference' or 'intended', got {rule!r}")
+    return rule
 
 
 def cfg_weights(mode: str, g: float, ge: float, do_cfg: bool = True) -> List[Tuple[str, float]]:
@@ -559,6 +574,101 @@ class EditDeepFloydIF(object):
             _save_image(xt, os.path.join(self.result_folder, f'{self.EXP_NAME}_stage1.png'), nrow=xt.size(0))
         return (xt * 255).to(torch.uint8).permute(0, 2, 3, 1)
 
+    # ------------------------------------------------------------------ DiffEdit mask (edit.py:1395-1407)
+    def _branch_eps(self, x, t, names):
+        """eps_c(x, t) of the named prompt branches for a batch of any size: chunks of ``max_batch``, the branches side by
+        side (as ``_classifer_free_guidance`` evaluates them, without the combination).  -> [len(names)][B, C, H, W]."""
+        mb = self.engine.max_batch
+        outs = [torch.empty_like(x) for _ in names]
+        for b0 in range(0, x.shape[0], mb):
+            xs = x[b0:b0 + mb].contiguous()
+            bufs = [torch.empty_like(xs) for _ in names]            # allocated here: nothing is allocated under a side stream
+            res = self.branch_streams.run([(lambda n=name, o=o: self.branches[n].unet_forward(xs, float(t), out=o))
+                                           for name, o in zip(names, bufs)])
+            for o, r in zip(outs, res):
+                o[b0:b0 + mb] = r
+        return outs
+
+    @torch.no_grad()
+    def mask_diffedit(self, x0, for_prompt_emb, edit_prompt_emb, null_prompt_emb, noise=None):
+        """edit.py:1395-1407: x0 noised ten times at t = 500, the guided noise under the `for` and under the `edit` prompt,
+        the averaged difference thresholded -> bool [1, H, W] on the device, `mask/mask_diffedit_t_500.png` from the main rank.
+        eps_1 - eps_2 = g (eps_for - eps_edit): the null branch cancels, so two branches are evaluated (the reference runs
+        four batches).  `noise` [10, C, H, W] replaces the draw (tests).  The threshold rule: ``diffedit_rule``.  A constant
+        map (e.g. identical prompts) raises ValueError where the reference returns an all-True mask out of 0 / 0."""
+        self._bind_all(for_prompt_emb, edit_prompt_emb, null_prompt_emb)
+        t = 500
+        R = self.image_size
+        if noise is None:
+            noise = torch.randn(10, self.c_in, R, R, dtype=self.dtype, device=self.device)
+        noise = noise.to(self.device, torch.float32).contiguous()
+        x0 = x0.to(self.device, torch.float32)
+        if x0.dim() == 3:
+            x0 = x0[None]
+        if tuple(x0.shape) != (1, self.c_in, R, R):
+            raise ValueError(f"x0 must be [1, {self.c_in}, {R}, {R}] in [-1, 1], got {tuple(x0.shape)}")
+        at = np.float32(self.scheduler.alphas_cumprod[t])
+        xt = self.engine.lincomb([(float(np.sqrt(at)), x0.expand_as(noise).contiguous()),
+                                  (float(np.sqrt(np.float32(1.0) - at)), noise)])
+        e_for, e_edit = self._branch_eps(xt, t, ("for", "edit"))
+        try:
+            m8, m = self.engine.diffedit_mask(e_for, e_edit, self.guidance_scale, rule=diffedit_rule(), want_map=True)
+        except ValueError as ex:
+            raise ValueError(f"mask_diffedit: {ex} (for prompt {self.for_prompt!r}, edit prompt {self.edit_prompt!r})") from None
+        self.diffedit_map = m.view(1, R, R)          # the real-valued map, kept for inspection
+        mask = m8.view(1, R, R).to(torch.bool)
+        if self.sharder.is_main:
+            _save_image(mask.float(), os.path.join(self.result_folder, "mask", f"mask_diffedit_t_{t}.png"))
+        return mask
+
+    def _frame_mask(self, mask) -> torch.Tensor:
+        """[H, W], [1, H, W] or [C, H, W] -> bool [C, H, W] on the device."""
+        R, Cn = self.image_size, self.c_in
+        m = torch.as_tensor(mask).to(self.device) != 0
+        if m.dim() == 2:
+            m = m[None]
+        if m.dim() != 3 or tuple(m.shape[1:]) != (R, R) or m.shape[0] not in (1, Cn):
+            raise ValueError(f"mask must be [{R}, {R}], [1, {R}, {R}] or [{Cn}, {R}, {R}], got {tuple(torch.as_tensor(mask).shape)}")
+        return m.expand(Cn, R, R).contiguous()
+
+    # ------------------------------------------------------------------ masked sampler (edit.py:1486-1563)
+    @torch.no_grad()
+    def MaskedDDPMforwardsteps(self, xt, t_start_idx, t_end_idx, for_prompt_emb, edit_prompt_emb, null_prompt_emb, mask,
+                               **kwargs):
+        """The loop of DDPMforwardsteps with, per step, the `for`, `edit` and `null` evaluations (the reference evaluates
+        `null` twice, once per guided prediction) and one fused launch: both guided predictions, both DDIM updates and the
+        select by `mask` (loco_cfg_masked_step).  Same return contract as DDPMforwardsteps.  guidance_scale <= 1: the
+        reference's guidance ignores the mode and predicts under the `for` prompt alone (edit.py:1315-1317), both halves of
+        its blend are one update -- one evaluation and the plain scheduler step."""
+        do_cfg = self.guidance_scale > 1.0
+        self.scheduler.set_timesteps(self.for_steps, device=self.device)
+        self._bind_all(for_prompt_emb, edit_prompt_emb, null_prompt_emb)
+        m8 = self._frame_mask(mask).to(torch.uint8).view(-1)
+        xt = xt.to(self.device, torch.float32).contiguous()
+        own = False
+        for t_idx, t in enumerate(self.scheduler.timesteps):
+            if t_idx < t_start_idx:
+                continue
+            elif t_start_idx == t_idx:
+                pass
+            elif t_idx == t_end_idx:
+                return xt, t, t_idx
+            xt = self.scheduler.scale_model_input(xt, t)
+            if not do_cfg:
+                (e_for,) = self._branch_eps(xt, t, ("for",))
+                xt = self.scheduler.step(e_for, t, xt, eta=0).prev_sample
+                continue
+            e_for, e_edit, e_null = self._branch_eps(xt, t, ("for", "edit", "null"))
+            t_next = self.scheduler.timesteps_next[t_idx]
+            # in place from the second step on: the first input is the caller's tensor
+            xt = self.engine.cfg_masked_step(xt, e_for, e_edit, e_null, self.guidance_scale, self.scheduler.alpha_at(t),
+                                             self.scheduler.alpha_at(t_next), m8, out=xt if own else None)
+            own = True
+        xt = (xt / 2 + 0.5).clamp(0, 1)
+        if self.sharder.is_main:
+            _save_image(xt, os.path.join(self.result_folder, f'{self.EXP_NAME}_stage1.png'), nrow=xt.size(0))
+        return (xt * 255).to(torch.uint8).permute(0, 2, 3, 1)
+
     @torch.no_grad()
     def x_space_guidance_direct(self, xt, t_idx, vk, single_edit_step):
         return self.engine.edit_axpy(xt.contiguous(), vk.contiguous().view(-1), [self.x_space_guidance_scale * single_edit_step])
@@ -661,17 +771,31 @@ class EditDeepFloydIF(object):
                                                    pca_rank=50, edit_prompt=None, null_space_projection=False,
                                                    pca_rank_null=50, jacobian=False):
         """edit.py:1871-2018: text-supervised direction (through the Jacobian or directly), projected onto the null
-        space of the complement-mask Jacobian; ablations 'null-space-proj' and 'sega'."""
+        space of the complement-mask Jacobian; ablations 'null-space-proj', 'sega' and 'diffedit'; the mask from
+        mask/mask.pt (mask_type 'SAM') or from the two prompts (mask_type 'diffedit': nothing from outside the run).
+        The reference converts the generated image to fp16 before it is noised for the DiffEdit mask (edit.py:1919); tensors
+        are fp32 on this path."""
         self._set_edit_prompt(edit_prompt)
         self.scheduler.set_timesteps(self.for_steps)
         xT = self._xT()
-        if self.mask_type != "SAM":
-            raise NotImplementedError("mask_type 'diffedit' (edit.py:1395-1409) is not on this path")
-        masks = self._masks()
-        mask = masks[mask_index].squeeze(dim=0).repeat(3, 1, 1)
+        F, E, N = self.for_prompt_emb, self.edit_prompt_emb, self.null_prompt_emb
+        if self.mask_type == "SAM":
+            masks = self._masks()
+            mask = masks[mask_index].squeeze(dim=0).repeat(3, 1, 1)
+        elif self.mask_type == "diffedit":
+            # edit.py:1911-1919: the full sample under the `for` prompt, then the mask from the two prompts.  No mask.pt is
+            # looked for or written (that name is the SAM cache).  Stage-II super-resolution stays off this path, as for SAM
+            self.EXP_NAME = "original"
+            x0 = self.DDPMforwardsteps(xT, t_start_idx=0, t_end_idx=-1, for_prompt_emb=F, edit_prompt_emb=E, null_prompt_emb=N,
+                                       mode="null+(for-null)")
+            mask = self.mask_diffedit((x0.to(torch.float32) * 2 / 255 - 1).permute(0, 3, 1, 2), F, E, N)
+            # the reference keeps [1, H, W] here and fails in get_x0's P[:, mask] on a [1, 3, H, W] tensor (IndexError) as soon as
+            # 'null-space-proj' reaches it; repeated over the channels as the SAM branch repeats its masks, that ablation runs
+            mask = mask.repeat(self.c_in, 1, 1)
+        else:
+            raise NotImplementedError(f"mask_type {self.mask_type!r}: 'SAM' (mask/mask.pt) or 'diffedit'")
         if self.sampling_mode:
             return None
-        F, E, N = self.for_prompt_emb, self.edit_prompt_emb, self.null_prompt_emb
         xt, t, t_idx = self.DDPMforwardsteps(xT, t_start_idx=0, t_end_idx=self.edit_t_idx, for_prompt_emb=F,
                                              edit_prompt_emb=E, null_prompt_emb=N, mode="null+(for-null)")
         assert t_idx == self.edit_t_idx
@@ -710,6 +834,10 @@ class EditDeepFloydIF(object):
             self.EXP_NAME = f'sega-edit_prompt-{self.edit_prompt}-mask_type-{self.mask_type}-select_mask{mask_index}'
             x0 = self.DDPMforwardsteps(xt, t_start_idx=self.edit_t_idx, t_end_idx=-1, for_prompt_emb=F, edit_prompt_emb=E,
                                        null_prompt_emb=N, mode="null+(for-null)+(edit-null)")
+        elif self.ablation_method == "diffedit":
+            self.EXP_NAME = f'diffedit-edit_prompt-{self.edit_prompt}-mask_type-{self.mask_type}-select_mask{mask_index}'
+            x0 = self.MaskedDDPMforwardsteps(xt, t_start_idx=self.edit_t_idx, t_end_idx=-1, for_prompt_emb=F, edit_prompt_emb=E,
+                                             null_prompt_emb=N, mask=mask)
         else:
-            raise NotImplementedError(f"ablation_method {self.ablation_method!r} (diffedit needs MaskedDDPMforwardsteps)")
+            raise NotImplementedError(f"ablation_method {self.ablation_method!r}")
         return x0
