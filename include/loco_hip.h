@@ -363,6 +363,50 @@ int  loco_t5_create(const loco_t5_cfg* cfg, int32_t device, int32_t max_prompts,
  * this call is an error; loco_text_encode on a T5 handle means lens == NULL. */
 int  loco_text_encode_masked(loco_text* t, const int32_t* ids_dev, const int32_t* lens, int32_t n, float* out_dev, void* stream);
 
+/* --- Segment Anything image encoder (edit masks) ---
+ * The SamVisionEncoder of transformers, which the reference's mask_segmentation.py runs inside the mask-generation pipeline:
+ * 16 x 16 patch embedding + learned absolute position embedding; `depth` pre-LN blocks whose attention runs inside
+ * window_size x window_size windows (the normalised map zero-padded at the bottom and right to a multiple of the window; the
+ * padded tokens take part as keys and queries, unmasked) or, at the layers listed in global_attn, over the whole map; scores
+ * (q scale) k^T + rel_h[q, row(k)] + rel_w[q, col(k)] with rel_h[q, j] = q . rel_pos_h[row(q) - j + size - 1] from the unscaled
+ * query (decomposed relative position bias), fp32 softmax; erf-GELU MLP; neck: 1x1 conv -> channel LayerNorm (eps 1e-6) ->
+ * 3x3 conv pad 1 -> channel LayerNorm.  Exact fp32 throughout (independent of loco_set_precision / LOCO_PRECISION), sums in
+ * a fixed order, no host synchronisation inside a call.  Its own handle; the workspace for one image is allocated at create. */
+#define LOCO_SAM_MAX_GLOBAL 16
+typedef struct loco_sam loco_sam;
+typedef struct loco_sam_cfg {
+    int32_t image_size;    /* S: side of pixel_values (1024) */
+    int32_t patch_size;    /* 16; the token grid is G = S / patch_size */
+    int32_t width;         /* hidden_size D: 768 (ViT-B), 1024 (ViT-L), 1280 (ViT-H) */
+    int32_t depth;         /* num_hidden_layers: 12 / 24 / 32 */
+    int32_t heads;         /* num_attention_heads: 12 / 16 / 16; head width hd = D / heads.  The attention kernel's LDS,
+                            * 4 (144 hd + 32 max(G, window_size) + 1088) bytes, must fit 64 KiB: hd <= 92 at G 64 (ViT-H has 80),
+                            * hd <= 106 at the smallest grid; loco_sam_create refuses the rest */
+    int32_t mlp_dim;       /* 4 D */
+    int32_t window_size;   /* 14 */
+    int32_t num_global;    /* entries of global_attn, <= LOCO_SAM_MAX_GLOBAL */
+    int32_t global_attn[LOCO_SAM_MAX_GLOBAL];   /* global_attn_indexes: [2,5,8,11] / [5,11,17,23] / [7,15,23,31] */
+    int32_t out_channels;  /* output_channels C_out of the neck (256) */
+    float   ln_eps;        /* layer_norm_eps of the blocks (1e-6) */
+} loco_sam_cfg;
+int  loco_sam_create(const loco_sam_cfg* cfg, int32_t device, loco_sam** out);
+/* One call per state_dict entry in SamVisionEncoder naming, without a `vision_encoder.` prefix (patch_embed.projection.weight,
+ * pos_embed, layers.{i}.attn.qkv.weight, layers.{i}.attn.rel_pos_h, ..., neck.layer_norm2.bias).  rel_pos_h / rel_pos_w must
+ * have 2 window_size - 1 rows in a windowed layer and 2 G - 1 in a global one (transformers would interpolate another
+ * length; here it is a shape error).  `host`: fp32 values, a host or a device pointer. */
+int  loco_sam_load_param(loco_sam* t, const char* name, const float* host, const int64_t* shape, int32_t ndim);
+int  loco_sam_params_missing(loco_sam* t);
+/* out_dev[C_out][G][G] = image embeddings of pixel_values[3][S][S] (device, preprocessed: normalised and zero-padded). */
+int  loco_sam_encode(loco_sam* t, const float* pixel_values, float* out_dev, void* stream);
+/* on != 0: the following encodes bracket their launches with events; loco_sam_profile_read waits for the last one and returns
+ * its milliseconds in ms4 = { GEMMs, windowed attention, global attention, everything else } (the attention entries include
+ * the relative position tables). */
+int  loco_sam_profile(loco_sam* t, int32_t on);
+int  loco_sam_profile_read(loco_sam* t, float* ms4);
+/* Message of the last failed call on t; t == NULL: of the last failed loco_sam_create. */
+const char* loco_sam_last_error(loco_sam* t);
+void loco_sam_destroy(loco_sam* t);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,562 @@
+// Image encoder of Segment Anything (include/loco_hip.h loco_sam_*): the SamVisionEncoder of transformers (a ViT with
+// windowed and global attention, decomposed relative position bias and a convolutional neck) that the reference's
+// mask_segmentation.py runs through the mask-generation pipeline.  Exact fp32 throughout, fp32 storage.
+//
+// Layout: that of the text encoders (textenc.hip) -- the G x G tokens of the one image channel-major in [D][Tp], token
+// column row * G + col, Tp = G * G rounded up to 16.  A windowed layer works on a second column order, [D][Twp]: column
+// w * ws^2 + r * ws + c of window w, the map zero-padded at the bottom and right to a multiple of ws AFTER the LayerNorm (so
+// the padded tokens' k and v are the qkv biases, as in transformers); its attention output goes through proj in that
+// order and is scattered back (cropped) with the residual.  The linear layers, the 1x1 neck conv and the 3x3 neck conv
+// (im2col) are launch_gemm_fixed, the LayerNorms -- the per-pixel channel LayerNorm of the neck included -- xfmr.hip's
+// launch_ln_fwd.  New here: the patch gather, the partition / un-partition, the relative position tables
+// rel_h / rel_w [heads][T][size] from the unscaled queries, the im2col, and one attention kernel for both regimes: a
+// workgroup owns 16 queries of one (window, head) and streams the keys in order in chunks of 64 through LDS with a running
+// max and sum, so the T x T scores never reach memory.  Every sum runs in a fixed order set by compile-time constants.
+#include "textenc.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+struct SamLayer {
+    float *ln1_g, *ln1_b, *wqkv, *bqkv, *rel_h, *rel_w, *wo, *bo, *ln2_g, *ln2_b, *w1, *b1, *w2, *b2;
+    bool global;
+};
+struct SamTimed { int cat; hipEvent_t a, b; };
+
+struct loco_sam {
+    loco_sam_cfg cfg;
+    int device = 0;
+    int G = 0, T = 0, Tp = 0, hd = 0;
+    int nwx = 0, Tw = 0, Twp = 0, ld = 0;        // windows per side, tokens of the padded windowed order, max(Tp, Twp)
+    long frows = 0;                                // rows of f: max(mlp_dim, 9 out_channels, 3 patch^2)
+    std::string err;
+    float* params = nullptr;
+    float *patch_w = nullptr, *patch_b = nullptr, *pos = nullptr, *neck_w1 = nullptr, *neck_g1 = nullptr, *neck_b1 = nullptr,
+          *neck_w2 = nullptr, *neck_g2 = nullptr, *neck_b2 = nullptr;
+    std::vector<SamLayer> layer;
+    std::vector<TextParam> table;
+    float *h = nullptr, *x = nullptr, *xw = nullptr, *qkv = nullptr, *attn = nullptr, *y = nullptr, *f = nullptr, *stats = nullptr,
+          *relh = nullptr, *relw = nullptr, *n1 = nullptr, *n2 = nullptr;
+    bool profile = false;
+    std::vector<SamTimed> timed;                   // event pairs of the last profiled encode
+    std::vector<hipEvent_t> pool;
+    int fail(const std::string& m) { err = m; return -1; }
+};
+
+namespace loco {
+namespace {
+
+constexpr int SA_THREADS = 256, SA_WAVES = SA_THREADS / 64, SA_QW = 4, SA_QB = SA_WAVES * SA_QW, SA_KC = 64;
+
+// P[(ci ps + ky) ps + kx][col] = pix[ci][ty ps + ky][tx ps + kx] for token col = ty G + tx < T, 0 for the padding columns
+__global__ __launch_bounds__(256) void sam_patch_kernel(const float* pix, int S, int ps, int G, int T, int Tp, float* P) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (long)3 * ps * ps * Tp) return;
+    const int r = (int)(e / Tp), col = (int)(e % Tp);
+    float v = 0.f;
+    if (col < T) {
+        const int ci = r / (ps * ps), ky = (r / ps) % ps, kx = r % ps, ty = col / G, tx = col % G;
+        v = pix[((long)ci * S + ty * ps + ky) * S + tx * ps + kx];
+    }
+    P[e] = v;
+}
+
+// h[c][t] += pos[t][c] (pos_embed is stored token-major [G][G][D])
+__global__ __launch_bounds__(256) void sam_add_pos_kernel(float* h, const float* pos, int D, int T, int Tp) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (long)D * T) return;
+    const int c = (int)(e / T), t = (int)(e % T);
+    h[(long)c * Tp + t] += pos[(long)t * D + c];
+}
+
+// xw[c][w ws^2 + r ws + cc] = x[c][(wr ws + r) G + wc ws + cc] inside the map, 0 in the padding and in the columns >= Tw
+__global__ __launch_bounds__(256) void sam_partition_kernel(const float* x, int D, int G, int Tp, int ws, int nwx, int Tw, int Twp,
+                                                            float* xw) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (long)D * Twp) return;
+    const int c = (int)(e / Twp), col = (int)(e % Twp);
+    float v = 0.f;
+    if (col < Tw) {
+        const int w = col / (ws * ws), l = col % (ws * ws);
+        const int row = (w / nwx) * ws + l / ws, cc = (w % nwx) * ws + l % ws;
+        if (row < G && cc < G) v = x[(long)c * Tp + row * G + cc];
+    }
+    xw[e] = v;
+}
+
+// h[c][t] += y[c][column of token t in the windowed order]: un-partition, crop and residual in one pass
+__global__ __launch_bounds__(256) void sam_unpartition_kernel(const float* y, int D, int G, int T, int Tp, int ws, int nwx, int Twp,
+                                                              float* h) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (long)D * T) return;
+    const int c = (int)(e / T), t = (int)(e % T);
+    const int row = t / G, cc = t % G;
+    const int col = ((row / ws) * nwx + cc / ws) * ws * ws + (row % ws) * ws + cc % ws;
+    h[(long)c * Tp + t] += y[(long)c * Twp + col];
+}
+
+// rel_h[h][t][j] = sum_c q[h hd + c][t] Rh[row(t) - j + size - 1][c], rel_w likewise with the column of t; t runs over the
+// Tall tokens of the layer's column order, row / column inside its window (size = ws) or the map (size = G); c in order
+__global__ __launch_bounds__(256) void sam_relpos_kernel(const float* q, long ld, int hd, int heads, long Tall, int size,
+                                                         const float* Rh, const float* Rw, float* relh, float* relw) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (long)heads * Tall * size) return;
+    const int j = (int)(e % size);
+    const long ht = e / size;
+    const int h = (int)(ht / Tall);
+    const long t = ht % Tall;
+    const int l = (int)(t % ((long)size * size)), qr = l / size, qc = l % size;
+    const float* qp = q + (long)(h * hd) * ld + t;
+    const float* rh = Rh + (long)(qr - j + size - 1) * hd;
+    const float* rw = Rw + (long)(qc - j + size - 1) * hd;
+    float ah = 0.f, aw = 0.f;
+    for (int c = 0; c < hd; ++c) {
+        const float qv = qp[(long)c * ld];
+        ah = fmaf(qv, rh[c], ah);
+        aw = fmaf(qv, rw[c], aw);
+    }
+    relh[e] = ah;
+    relw[e] = aw;
+}
+
+// parts of sam_attn_kernel's LDS start at multiples of 4 floats (float4 reads of Qs and Ps)
+__host__ __device__ constexpr size_t sam_r4(size_t n) { return (n + 3) / 4 * 4; }
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// One workgroup per (query block of 16, head, window): the nk = size^2 keys of the window (size = ws) or of the map
+// (size = G, one "window") are streamed in order in chunks of 64 -- K [hd][64] and V [64][hd + 1] of the chunk in LDS.  A wave
+// owns 4 queries; lane j scores key k0 + j against them: (q scale) . k + rel_h[q][row(k)] + rel_w[q][col(k)], then the
+// running max / sum update (fp32, max and sum over the chunk by shuffles), then lane c (and c + 64) adds P V of the chunk to
+// its output channel in key order.  qkv: [3 D][ld] = q | k | v channel rows, out [D][ld]; hd <= 128.
+__global__ __launch_bounds__(SA_THREADS) void sam_attn_kernel(const float* qkv, long ld, int D, int hd, int nk, int size, float scale,
+                                                              const float* relh, const float* relw, long Tall, float* out) {
+    extern __shared__ __align__(16) float sam_sm[];
+    const int hdp = hd + 1;
+    float* Ks = sam_sm;                                    // [hd][64]
+    float* Vs = Ks + sam_r4(hd * SA_KC);                   // [64][hd + 1]
+    float* Qs = Vs + sam_r4(SA_KC * hdp);                  // [hd][16]
+    float* Bh = Qs + sam_r4(hd * SA_QB);                   // [16][size]
+    float* Bw = Bh + SA_QB * size;                         // [16][size]
+    float* Ps = Bh + sam_r4(2 * SA_QB * size);             // [waves][64][4]
+    const int qb = blockIdx.x, h = blockIdx.y, w = blockIdx.z;
+    const long col0 = (long)w * nk;
+    const int q0 = qb * SA_QB;
+    const float* q = qkv + (long)(h * hd) * ld + col0;
+    const float* k = qkv + (long)(D + h * hd) * ld + col0;
+    const float* v = qkv + (long)(2 * D + h * hd) * ld + col0;
+    for (int e = threadIdx.x; e < hd * SA_QB; e += SA_THREADS) {
+        const int c = e / SA_QB, ql = min(q0 + e % SA_QB, nk - 1);
+        Qs[e] = q[(long)c * ld + ql] * scale;
+    }
+    for (int e = threadIdx.x; e < SA_QB * size; e += SA_THREADS) {
+        const int ql = min(q0 + e / size, nk - 1), j = e % size;
+        const long o = ((long)h * Tall + col0 + ql) * size + j;
+        Bh[e] = relh[o];
+        Bw[e] = relw[o];
+    }
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int c0 = lane < hd ? lane : 0, c1 = lane + 64 < hd ? lane + 64 : 0;
+    float* pw = Ps + wv * (SA_KC * SA_QW);
+    float m[SA_QW], l[SA_QW], o0[SA_QW], o1[SA_QW];
+#pragma unroll
+    for (int u = 0; u < SA_QW; ++u) { m[u] = -INFINITY; l[u] = 0.f; o0[u] = 0.f; o1[u] = 0.f; }
+    for (int k0 = 0; k0 < nk; k0 += SA_KC) {
+        __syncthreads();
+        for (int e = threadIdx.x; e < hd * SA_KC; e += SA_THREADS) {
+            const int c = e / SA_KC, j = e % SA_KC, kj = k0 + j;
+            const bool ok = kj < nk;
+            Ks[e] = ok ? k[(long)c * ld + kj] : 0.f;
+            Vs[j * hdp + c] = ok ? v[(long)c * ld + kj] : 0.f;
+        }
+        __syncthreads();
+        const int kj = k0 + lane;
+        const bool valid = kj < nk;
+        const int kr = valid ? kj / size : 0, kc = valid ? kj - kr * size : 0;
+        float s[SA_QW];
+#pragma unroll
+        for (int u = 0; u < SA_QW; ++u) s[u] = 0.f;
+        for (int c = 0; c < hd; ++c) {
+            const float kv = Ks[c * SA_KC + lane];
+            const float4 qv = *reinterpret_cast<const float4*>(Qs + c * SA_QB + wv * SA_QW);
+            s[0] = fmaf(qv.x, kv, s[0]);
+            s[1] = fmaf(qv.y, kv, s[1]);
+            s[2] = fmaf(qv.z, kv, s[2]);
+            s[3] = fmaf(qv.w, kv, s[3]);
+        }
+#pragma unroll
+        for (int u = 0; u < SA_QW; ++u) {
+            const int qi = wv * SA_QW + u;
+            const float sc = valid ? s[u] + Bh[qi * size + kr] + Bw[qi * size + kc] : -INFINITY;
+            const float mn = fmaxf(m[u], wave_max(sc));
+            const float corr = expf(m[u] - mn);
+            const float p = valid ? expf(sc - mn) : 0.f;
+            l[u] = l[u] * corr + wave_sum(p);
+            o0[u] *= corr;
+            o1[u] *= corr;
+            m[u] = mn;
+            pw[lane * SA_QW + u] = p;
+        }
+        __syncthreads();
+        for (int j = 0; j < SA_KC; ++j) {
+            const float4 pv = *reinterpret_cast<const float4*>(pw + j * SA_QW);
+            const float v0 = Vs[j * hdp + c0];
+            o0[0] = fmaf(pv.x, v0, o0[0]);
+            o0[1] = fmaf(pv.y, v0, o0[1]);
+            o0[2] = fmaf(pv.z, v0, o0[2]);
+            o0[3] = fmaf(pv.w, v0, o0[3]);
+            if (hd > 64) {                                 // uniform
+                const float v1 = Vs[j * hdp + c1];
+                o1[0] = fmaf(pv.x, v1, o1[0]);
+                o1[1] = fmaf(pv.y, v1, o1[1]);
+                o1[2] = fmaf(pv.z, v1, o1[2]);
+                o1[3] = fmaf(pv.w, v1, o1[3]);
+            }
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < SA_QW; ++u) {
+        const int ql = q0 + wv * SA_QW + u;
+        if (ql >= nk) continue;
+        const float inv = 1.0f / l[u];
+        if (lane < hd) out[(long)(h * hd + lane) * ld + col0 + ql] = o0[u] * inv;
+        if (lane + 64 < hd) out[(long)(h * hd + lane + 64) * ld + col0 + ql] = o1[u] * inv;
+    }
+}
+
+// col[(ci 9 + ky 3 + kx)][t] = x[ci][(row + ky - 1) G + col + kx - 1] inside the map, 0 outside and in the padding columns
+__global__ __launch_bounds__(256) void sam_im2col3_kernel(const float* x, int C, int G, int T, int Tp, float* colbuf) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (long)C * 9 * Tp) return;
+    const int r = (int)(e / Tp), t = (int)(e % Tp);
+    float v = 0.f;
+    if (t < T) {
+        const int ci = r / 9, ky = (r % 9) / 3, kx = r % 3, row = t / G + ky - 1, cc = t % G + kx - 1;
+        if (row >= 0 && row < G && cc >= 0 && cc < G) v = x[(long)ci * Tp + row * G + cc];
+    }
+    colbuf[e] = v;
+}
+
+// out[c][t] = x[c][t] for the T real columns of x [C][Tp]
+__global__ __launch_bounds__(256) void sam_crop_kernel(const float* x, int C, int T, int Tp, float* out) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (long)C * T) return;
+    out[e] = x[(e / T) * Tp + e % T];
+}
+
+}  // namespace
+}  // namespace loco
+
+using namespace loco;
+
+namespace {
+thread_local std::string g_sam_create_err;
+using DeviceGuard = loco::TextDeviceGuard;
+
+inline unsigned blocks256(long n) { return (unsigned)((n + 255) / 256); }
+
+}  // namespace
+namespace loco { namespace {
+// the carve-up of sam_attn_kernel's LDS
+size_t sam_attn_lds_floats(int hd, int size) {
+    return sam_r4((size_t)hd * SA_KC) + sam_r4((size_t)SA_KC * (hd + 1)) + sam_r4((size_t)hd * SA_QB) + sam_r4((size_t)2 * SA_QB * size) +
+           (size_t)SA_WAVES * SA_KC * SA_QW;
+}
+} }
+namespace {
+
+void free_sam(loco_sam* t) {
+    (void)hipFree(t->params); (void)hipFree(t->h); (void)hipFree(t->x); (void)hipFree(t->xw); (void)hipFree(t->qkv);
+    (void)hipFree(t->attn); (void)hipFree(t->y); (void)hipFree(t->f); (void)hipFree(t->stats); (void)hipFree(t->relh);
+    (void)hipFree(t->relw); (void)hipFree(t->n1); (void)hipFree(t->n2);
+    for (hipEvent_t e : t->pool) (void)hipEventDestroy(e);
+}
+
+struct SamTimer {             // brackets a run of launches with two events while the profile is on
+    loco_sam* t; hipStream_t st; int at = -1;
+    SamTimer(loco_sam* t_, hipStream_t st_, int cat) : t(t_), st(st_) {
+        if (!t->profile) return;
+        hipEvent_t a = nullptr, b = nullptr;
+        if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return;
+        t->pool.push_back(a); t->pool.push_back(b);
+        (void)hipEventRecord(a, st);
+        at = (int)t->timed.size();
+        t->timed.push_back({cat, a, b});
+    }
+    ~SamTimer() { if (at >= 0) (void)hipEventRecord(t->timed[at].b, st); }
+};
+enum { SAM_CAT_GEMM = 0, SAM_CAT_WIN_ATTN = 1, SAM_CAT_GLOBAL_ATTN = 2, SAM_CAT_OTHER = 3 };
+}  // namespace
+
+extern "C" {
+
+int loco_sam_create(const loco_sam_cfg* cfg, int32_t device, loco_sam** out) {
+    auto report = [](const std::string& m) { g_sam_create_err = m; return -1; };
+    if (!out) return report("loco_sam_create: out is NULL");
+    *out = nullptr;
+    if (!cfg) return report("loco_sam_create: cfg is NULL");
+    const loco_sam_cfg c = *cfg;
+    if (c.image_size <= 0 || c.patch_size <= 0 || c.width <= 0 || c.depth <= 0 || c.heads <= 0 || c.mlp_dim <= 0 ||
+        c.window_size <= 0 || c.out_channels <= 0)
+        return report("loco_sam_create: image_size, patch_size, width, depth, heads, mlp_dim, window_size and out_channels must be positive");
+    if (c.image_size % c.patch_size) return report("loco_sam_create: image_size is not a multiple of patch_size");
+    if (c.width % c.heads) return report("loco_sam_create: width is not a multiple of heads");
+    if (c.num_global < 0 || c.num_global > LOCO_SAM_MAX_GLOBAL) return report("loco_sam_create: num_global outside [0, 16]");
+    for (int i = 0; i < c.num_global; ++i)
+        if (c.global_attn[i] < 0 || c.global_attn[i] >= c.depth) return report("loco_sam_create: a global attention index is outside [0, depth)");
+    if (!(c.ln_eps > 0.f)) return report("loco_sam_create: ln_eps must be positive");
+    const int G = c.image_size / c.patch_size, hd = c.width / c.heads, ws = c.window_size;
+    if (hd > 128) return report("loco_sam_create: head width > 128 (the attention kernel holds 2 channels per lane)");
+    if (sam_attn_lds_floats(hd, std::max(G, ws)) * sizeof(float) > 65536)
+        return report("loco_sam_create: head width x grid too large for the attention kernel's LDS (64 KiB)");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return report("loco_sam_create: no such HIP device");
+    DeviceGuard dg(device);
+    loco_sam* t = new loco_sam();
+    t->cfg = c; t->device = device;
+    t->G = G; t->T = G * G; t->Tp = (t->T + 15) / 16 * 16; t->hd = hd;
+    t->nwx = (G + ws - 1) / ws; t->Tw = t->nwx * t->nwx * ws * ws; t->Twp = (t->Tw + 15) / 16 * 16;
+    t->ld = std::max(t->Tp, t->Twp);
+    const long D = c.width, F = c.mlp_dim, Co = c.out_channels, ps = c.patch_size;
+    t->frows = std::max(std::max(F, 9 * Co), 3 * ps * ps);
+    size_t total = 0;
+    struct Spec { std::string name; std::vector<int64_t> shape; size_t off; };
+    std::vector<Spec> specs;
+    auto add = [&](const std::string& n, std::vector<int64_t> s) {
+        size_t cnt = 1;
+        for (auto d : s) cnt *= (size_t)d;
+        specs.push_back({n, s, total});
+        total += (cnt + 63) / 64 * 64;
+        return specs.back().off;
+    };
+    // names of transformers' SamVisionEncoder, without a `vision_encoder.` prefix
+    const size_t o_pw = add("patch_embed.projection.weight", {D, 3, ps, ps});
+    const size_t o_pb = add("patch_embed.projection.bias", {D});
+    const size_t o_pos = add("pos_embed", {1, G, G, D});
+    std::vector<bool> global(c.depth, false);
+    for (int i = 0; i < c.num_global; ++i) global[c.global_attn[i]] = true;
+    struct LOff { size_t v[14]; };
+    std::vector<LOff> loff(c.depth);
+    for (int l = 0; l < c.depth; ++l) {
+        const std::string p = "layers." + std::to_string(l) + ".";
+        const long rel = 2 * (global[l] ? G : ws) - 1;       // transformers would interpolate another length: refused by the shape
+        size_t* v = loff[l].v;
+        v[0] = add(p + "layer_norm1.weight", {D});
+        v[1] = add(p + "layer_norm1.bias", {D});
+        v[2] = add(p + "attn.qkv.weight", {3 * D, D});
+        v[3] = add(p + "attn.qkv.bias", {3 * D});
+        v[4] = add(p + "attn.rel_pos_h", {rel, hd});
+        v[5] = add(p + "attn.rel_pos_w", {rel, hd});
+        v[6] = add(p + "attn.proj.weight", {D, D});
+        v[7] = add(p + "attn.proj.bias", {D});
+        v[8] = add(p + "layer_norm2.weight", {D});
+        v[9] = add(p + "layer_norm2.bias", {D});
+        v[10] = add(p + "mlp.lin1.weight", {F, D});
+        v[11] = add(p + "mlp.lin1.bias", {F});
+        v[12] = add(p + "mlp.lin2.weight", {D, F});
+        v[13] = add(p + "mlp.lin2.bias", {D});
+    }
+    const size_t o_n1 = add("neck.conv1.weight", {Co, D, 1, 1});
+    const size_t o_g1 = add("neck.layer_norm1.weight", {Co});
+    const size_t o_b1 = add("neck.layer_norm1.bias", {Co});
+    const size_t o_n2 = add("neck.conv2.weight", {Co, Co, 3, 3});
+    const size_t o_g2 = add("neck.layer_norm2.weight", {Co});
+    const size_t o_b2 = add("neck.layer_norm2.bias", {Co});
+    const long Tp = t->Tp, Twp = t->Twp, ld = t->ld;
+    const size_t rel_floats = (size_t)c.heads * std::max((long)t->Tw * ws, (long)t->T * G);
+    struct Buf { float** p; size_t n; };
+    const Buf bufs[] = {{&t->params, total}, {&t->h, (size_t)(D * Tp)}, {&t->x, (size_t)(D * Tp)}, {&t->xw, (size_t)(D * Twp)},
+                        {&t->qkv, (size_t)(3 * D * ld)}, {&t->attn, (size_t)(D * ld)}, {&t->y, (size_t)(D * Twp)},
+                        {&t->f, (size_t)(t->frows * Tp)}, {&t->stats, (size_t)(2 * ld)}, {&t->relh, rel_floats}, {&t->relw, rel_floats},
+                        {&t->n1, (size_t)(Co * Tp)}, {&t->n2, (size_t)(Co * Tp)}};
+    bool ok = true;
+    // zeroed: the padding columns of every buffer hold finite values from the first call on
+    for (const Buf& b : bufs) ok = ok && hipMalloc(b.p, b.n * sizeof(float)) == hipSuccess && hipMemset(*b.p, 0, b.n * sizeof(float)) == hipSuccess;
+    if (!ok) {
+        free_sam(t);
+        delete t;
+        return report("loco_sam_create: hipMalloc failed");
+    }
+    for (const Spec& s : specs) t->table.push_back({s.name, s.shape, t->params + s.off, false});
+    float* P = t->params;
+    t->patch_w = P + o_pw; t->patch_b = P + o_pb; t->pos = P + o_pos;
+    t->neck_w1 = P + o_n1; t->neck_g1 = P + o_g1; t->neck_b1 = P + o_b1;
+    t->neck_w2 = P + o_n2; t->neck_g2 = P + o_g2; t->neck_b2 = P + o_b2;
+    for (int l = 0; l < c.depth; ++l) {
+        const size_t* v = loff[l].v;
+        t->layer.push_back({P + v[0], P + v[1], P + v[2], P + v[3], P + v[4], P + v[5], P + v[6], P + v[7], P + v[8], P + v[9],
+                            P + v[10], P + v[11], P + v[12], P + v[13], (bool)global[l]});
+    }
+    *out = t;
+    return 0;
+}
+
+int loco_sam_load_param(loco_sam* t, const char* name, const float* host, const int64_t* shape, int32_t ndim) {
+    if (!t) return -1;
+    if (!name || !host || (ndim > 0 && !shape) || ndim < 0) return t->fail("loco_sam_load_param: null argument");
+    for (TextParam& p : t->table) {
+        if (p.name != name) continue;
+        if ((size_t)ndim != p.shape.size() || !std::equal(p.shape.begin(), p.shape.end(), shape)) {
+            std::string m = "loco_sam_load_param: " + p.name + " has shape [";
+            for (size_t i = 0; i < p.shape.size(); ++i) m += (i ? ", " : "") + std::to_string(p.shape[i]);
+            return t->fail(m + "], got another");
+        }
+        size_t cnt = 1;
+        for (auto d : p.shape) cnt *= (size_t)d;
+        DeviceGuard dg(t->device);
+        if (hipMemcpy(p.dst, host, cnt * sizeof(float), hipMemcpyDefault) != hipSuccess)
+            return t->fail("loco_sam_load_param: copy of " + p.name + " failed");
+        p.loaded = true;
+        return 0;
+    }
+    return t->fail(std::string("loco_sam_load_param: unknown parameter ") + name);
+}
+
+int loco_sam_params_missing(loco_sam* t) {
+    if (!t) return -1;
+    int miss = 0;
+    for (const TextParam& p : t->table) {
+        if (!p.loaded) {
+            if (!miss) t->err = "missing parameter " + p.name;
+            ++miss;
+        }
+    }
+    return miss;
+}
+
+int loco_sam_encode(loco_sam* t, const float* pixel_values, float* out_dev, void* stream) {
+    if (!t) return -1;
+    if (!pixel_values || !out_dev) return t->fail("loco_sam_encode: null pixel_values or out");
+    if (loco_sam_params_missing(t)) return -1;
+    DeviceGuard dg(t->device);
+    hipStream_t st = (hipStream_t)stream;
+    const loco_sam_cfg& c = t->cfg;
+    const int D = c.width, F = c.mlp_dim, Co = c.out_channels, ps = c.patch_size, ws = c.window_size, heads = c.heads;
+    const int G = t->G, T = t->T, Tp = t->Tp, Tw = t->Tw, Twp = t->Twp, hd = t->hd, PK = 3 * ps * ps;
+    const float scale = 1.0f / std::sqrt((float)hd);
+    if (t->profile) {
+        for (hipEvent_t e : t->pool) (void)hipEventDestroy(e);
+        t->pool.clear();
+        t->timed.clear();
+    }
+    {
+        SamTimer tm(t, st, SAM_CAT_OTHER);
+        hipLaunchKernelGGL(sam_patch_kernel, dim3(blocks256((long)PK * Tp)), dim3(256), 0, st, pixel_values, c.image_size, ps, G, T, Tp, t->f);
+    }
+    {
+        SamTimer tm(t, st, SAM_CAT_GEMM);
+        launch_gemm_fixed(text_linear(t->patch_w, t->patch_b, t->f, t->h, nullptr, D, PK, Tp), GEMM_ACT_NONE, st);
+    }
+    {
+        SamTimer tm(t, st, SAM_CAT_OTHER);
+        hipLaunchKernelGGL(sam_add_pos_kernel, dim3(blocks256((long)D * T)), dim3(256), 0, st, t->h, t->pos, D, T, Tp);
+    }
+    for (const SamLayer& ly : t->layer) {
+        const bool gl = ly.global;
+        const int ldl = gl ? Tp : Twp, size = gl ? G : ws, nk = size * size, nwin = gl ? 1 : t->nwx * t->nwx;
+        const long Tall = gl ? T : Tw;
+        const float* xin = gl ? t->x : t->xw;
+        const int acat = gl ? SAM_CAT_GLOBAL_ATTN : SAM_CAT_WIN_ATTN;
+        {
+            SamTimer tm(t, st, SAM_CAT_OTHER);
+            launch_ln_fwd(t->h, 0, 1, D, Tp, ly.ln1_g, ly.ln1_b, c.ln_eps, t->x, 0, t->stats, 0, st);
+            if (!gl) hipLaunchKernelGGL(sam_partition_kernel, dim3(blocks256((long)D * Twp)), dim3(256), 0, st, t->x, D, G, Tp, ws, t->nwx, Tw, Twp, t->xw);
+        }
+        {
+            SamTimer tm(t, st, SAM_CAT_GEMM);
+            launch_gemm_fixed(text_linear(ly.wqkv, ly.bqkv, xin, t->qkv, nullptr, 3 * D, D, ldl), GEMM_ACT_NONE, st);
+        }
+        {
+            SamTimer tm(t, st, acat);
+            hipLaunchKernelGGL(sam_relpos_kernel, dim3(blocks256((long)heads * Tall * size)), dim3(256), 0, st, t->qkv, (long)ldl, hd, heads,
+                               Tall, size, ly.rel_h, ly.rel_w, t->relh, t->relw);
+            hipLaunchKernelGGL(sam_attn_kernel, dim3((nk + SA_QB - 1) / SA_QB, heads, nwin), dim3(SA_THREADS),
+                               sam_attn_lds_floats(hd, size) * sizeof(float), st, t->qkv, (long)ldl, D, hd, nk, size, scale, t->relh, t->relw,
+                               Tall, t->attn);
+        }
+        if (gl) {
+            SamTimer tm(t, st, SAM_CAT_GEMM);
+            launch_gemm_fixed(text_linear(ly.wo, ly.bo, t->attn, t->h, t->h, D, D, Tp), GEMM_ACT_NONE, st);
+        } else {
+            {
+                SamTimer tm(t, st, SAM_CAT_GEMM);
+                launch_gemm_fixed(text_linear(ly.wo, ly.bo, t->attn, t->y, nullptr, D, D, Twp), GEMM_ACT_NONE, st);
+            }
+            SamTimer tm(t, st, SAM_CAT_OTHER);
+            hipLaunchKernelGGL(sam_unpartition_kernel, dim3(blocks256((long)D * T)), dim3(256), 0, st, t->y, D, G, T, Tp, ws, t->nwx, Twp, t->h);
+        }
+        {
+            SamTimer tm(t, st, SAM_CAT_OTHER);
+            launch_ln_fwd(t->h, 0, 1, D, Tp, ly.ln2_g, ly.ln2_b, c.ln_eps, t->x, 0, t->stats, 0, st);
+        }
+        SamTimer tm(t, st, SAM_CAT_GEMM);
+        launch_gemm_fixed(text_linear(ly.w1, ly.b1, t->x, t->f, nullptr, F, D, Tp), GEMM_ACT_GELU, st);
+        launch_gemm_fixed(text_linear(ly.w2, ly.b2, t->f, t->h, t->h, D, F, Tp), GEMM_ACT_NONE, st);
+    }
+    // neck: 1x1 conv -> LayerNorm over channels -> 3x3 conv (im2col) -> LayerNorm, eps 1e-6 as SamLayerNorm's default
+    {
+        SamTimer tm(t, st, SAM_CAT_GEMM);
+        launch_gemm_fixed(text_linear(t->neck_w1, nullptr, t->h, t->n1, nullptr, Co, D, Tp), GEMM_ACT_NONE, st);
+    }
+    {
+        SamTimer tm(t, st, SAM_CAT_OTHER);
+        launch_ln_fwd(t->n1, 0, 1, Co, Tp, t->neck_g1, t->neck_b1, 1e-6f, t->n2, 0, t->stats, 0, st);
+        hipLaunchKernelGGL(sam_im2col3_kernel, dim3(blocks256((long)Co * 9 * Tp)), dim3(256), 0, st, t->n2, Co, G, T, Tp, t->f);
+    }
+    {
+        SamTimer tm(t, st, SAM_CAT_GEMM);
+        launch_gemm_fixed(text_linear(t->neck_w2, nullptr, t->f, t->n1, nullptr, Co, 9 * Co, Tp), GEMM_ACT_NONE, st);
+    }
+    {
+        SamTimer tm(t, st, SAM_CAT_OTHER);
+        launch_ln_fwd(t->n1, 0, 1, Co, Tp, t->neck_g2, t->neck_b2, 1e-6f, t->n2, 0, t->stats, 0, st);
+        hipLaunchKernelGGL(sam_crop_kernel, dim3(blocks256((long)Co * T)), dim3(256), 0, st, t->n2, Co, T, Tp, out_dev);
+    }
+    if (hipGetLastError() != hipSuccess) return t->fail("loco_sam_encode: kernel launch failed");
+    return 0;
+}
+
+int loco_sam_profile(loco_sam* t, int32_t on) {
+    if (!t) return -1;
+    t->profile = on != 0;
+    return 0;
+}
+
+int loco_sam_profile_read(loco_sam* t, float* ms4) {
+    if (!t) return -1;
+    if (!ms4) return t->fail("loco_sam_profile_read: ms4 is NULL");
+    DeviceGuard dg(t->device);
+    for (int i = 0; i < 4; ++i) ms4[i] = 0.f;
+    for (const SamTimed& e : t->timed) {
+        float ms = 0.f;
+        if (hipEventSynchronize(e.b) != hipSuccess || hipEventElapsedTime(&ms, e.a, e.b) != hipSuccess)
+            return t->fail("loco_sam_profile_read: reading an event failed");
+        ms4[e.cat] += ms;
+    }
+    return 0;
+}
+
+const char* loco_sam_last_error(loco_sam* t) { return t ? t->err.c_str() : g_sam_create_err.c_str(); }
+
+void loco_sam_destroy(loco_sam* t) {
+    if (!t) return;
+    {
+        DeviceGuard dg(t->device);
+        free_sam(t);
+    }
+    delete t;
+}
+
+}  // extern "C"

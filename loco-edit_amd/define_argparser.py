@@ -116,6 +116,10 @@ def build_parser():
     p.add_argument('--tokenizer_path', type=str, default='',
                    help='tokenizer folder when --text_encoder_path is not a pipeline root: CLIP (vocab.json, merges.txt, configs) '
                         'or T5 (tokenizer.json with a Unigram model, or spiece.model)')
+    p.add_argument('--mask_model_path', type=str, default='',
+                   help='Segment Anything model that produces mask/mask.pt on the GPU when it is missing: a local SamModel '
+                        'folder (config.json + model.safetensors or pytorch_model.bin) or a checkpoint file in SamModel naming. '
+                        'Nothing is downloaded (--mask_model_name stays a name only). Empty: mask/mask.pt must exist')
     p.add_argument('--cond_dim', type=int, default=16, help='T-LOCO stand-in: width of seeded prompt embeddings when no file is given')
     p.add_argument('--precision', type=str, default=None, choices=['f32', 'bf16x3', 'f16'],
                    help="conv arithmetic of the HIP engine: 'f32' exact fp32 MFMA (parity anchor), 'bf16x3' split-bf16 "

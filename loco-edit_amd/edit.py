@@ -237,16 +237,30 @@ class EditUncondDiffusion(object):
         self.DDIMforwardsteps(xt_vis, t_start_idx=self.edit_t_idx, t_end_idx=-1, performance_boosting=True)
         return xt
 
+    def _segment(self, x0_fn):
+        """SAM masks of the image `x0_fn()` ([1, 3, R, R] in [-1, 1]) at the model's resolution, cached as mask/mask.pt."""
+        from .mask_segmentation import segment_for_driver
+
+        def image():
+            x0 = x0_fn()
+            return ((x0 / 2 + 0.5).clamp(0, 1) * 255).to(torch.uint8).permute(0, 2, 3, 1)[0].detach().cpu().numpy()
+        print("Creating masks......")
+        return segment_for_driver(self.args, self.result_folder, self.sharder, image, self.image_size)
+
     def _get_xT_and_mask(self, idx, use_mask):
         """edit.py:2234-2267."""
         if self.dataset_name == 'Random':
             xT = torch.randn(1, self.c_in, self.image_size, self.image_size, dtype=self.dtype, device=self.device)
             mpath = os.path.join(self.result_folder, "mask/mask.pt")
-            if not os.path.exists(mpath):
-                raise FileNotFoundError(
-                    f"{mpath} missing: SAM mask generation is outside the hot path (SURVEY.md 2.1 #9); "
-                    "provide mask.pt (bool [N,res,res])")
-            masks = torch.load(mpath)
+            if getattr(self.args, "mask_model_path", "") and not self._exists(mpath):
+                self.EXP_NAME = "original"                     # edit.py:2236-2241: sample, then segment the sample
+                masks = self._segment(lambda: self.DDIMforwardsteps(xT, t_start_idx=0, t_end_idx=-1))
+            else:
+                if not os.path.exists(mpath):
+                    raise FileNotFoundError(
+                        f"{mpath} missing: SAM mask generation is outside the hot path (SURVEY.md 2.1 #9); "
+                        "provide mask.pt (bool [N,res,res])")
+                masks = torch.load(mpath)
             if self.args.sampling_mode:
                 return None, None
             mask = masks[self.args.mask_index].squeeze(dim=0).repeat(3, 1, 1)
@@ -257,12 +271,15 @@ class EditUncondDiffusion(object):
             return xT, (mask if use_mask or self.dataset_name == "CelebA_HQ_mask" else None)
         # FFHQ / AFHQ / ... : SAM masks cached as mask/mask.pt, bool [N,res,res] (edit.py:2252-2267)
         mpath = os.path.join(self.result_folder, "mask/mask.pt")
-        if not os.path.exists(mpath):
-            raise FileNotFoundError(
-                f"{mpath} missing: SAM mask generation is outside the hot path (SURVEY.md 2.1 #9); "
-                "provide mask.pt (bool [N,res,res]) as the reference's mask_segmentation.py writes it")
-        print("loading masks")
-        masks = torch.load(mpath)
+        if getattr(self.args, "mask_model_path", "") and not self._exists(mpath):
+            masks = self._segment(lambda: self.dataset[idx])    # edit.py:2253-2257: the dataset image
+        else:
+            if not os.path.exists(mpath):
+                raise FileNotFoundError(
+                    f"{mpath} missing: SAM mask generation is outside the hot path (SURVEY.md 2.1 #9); "
+                    "provide mask.pt (bool [N,res,res]) as the reference's mask_segmentation.py writes it")
+            print("loading masks")
+            masks = torch.load(mpath)
         if self.args.sampling_mode:
             return None, None
         xT = self.run_DDIMinversion(idx=idx)

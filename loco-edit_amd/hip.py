@@ -34,6 +34,8 @@ SYMBOLS = [
     "loco_text_create", "loco_text_load_param", "loco_text_params_missing", "loco_text_encode", "loco_text_last_error",
     "loco_text_destroy", "loco_t5_create", "loco_text_encode_masked",
     "loco_diffedit_mask", "loco_cfg_masked_step",
+    "loco_sam_create", "loco_sam_load_param", "loco_sam_params_missing", "loco_sam_encode", "loco_sam_profile",
+    "loco_sam_profile_read", "loco_sam_last_error", "loco_sam_destroy",
 ]
 
 # threshold rules of loco_diffedit_mask (include/loco_hip.h)
@@ -63,6 +65,15 @@ class LocoT5Cfg(C.Structure):
     _fields_ = [("vocab", C.c_int32), ("d_model", C.c_int32), ("d_kv", C.c_int32), ("heads", C.c_int32), ("d_ff", C.c_int32),
                 ("layers", C.c_int32), ("positions", C.c_int32), ("buckets", C.c_int32), ("max_distance", C.c_int32),
                 ("act", C.c_int32), ("ln_eps", C.c_float)]
+
+
+SAM_MAX_GLOBAL = 16
+
+
+class LocoSamCfg(C.Structure):
+    _fields_ = [("image_size", C.c_int32), ("patch_size", C.c_int32), ("width", C.c_int32), ("depth", C.c_int32),
+                ("heads", C.c_int32), ("mlp_dim", C.c_int32), ("window_size", C.c_int32), ("num_global", C.c_int32),
+                ("global_attn", C.c_int32 * SAM_MAX_GLOBAL), ("out_channels", C.c_int32), ("ln_eps", C.c_float)]
 
 
 def library_path() -> str:
@@ -140,6 +151,17 @@ def load_library():
     if hasattr(lib, "loco_t5_create"):
         lib.loco_t5_create.argtypes = [C.POINTER(LocoT5Cfg), i32, i32, C.POINTER(vp)]
         lib.loco_text_encode_masked.argtypes = [vp, vp, C.POINTER(i32), i32, vp, vp]
+    if hasattr(lib, "loco_sam_create"):
+        lib.loco_sam_create.argtypes = [C.POINTER(LocoSamCfg), i32, C.POINTER(vp)]
+        lib.loco_sam_load_param.argtypes = [vp, C.c_char_p, vp, C.POINTER(i64), i32]
+        lib.loco_sam_params_missing.argtypes = [vp]
+        lib.loco_sam_encode.argtypes = [vp, vp, vp, vp]
+        lib.loco_sam_profile.argtypes = [vp, i32]
+        lib.loco_sam_profile_read.argtypes = [vp, C.POINTER(f32)]
+        lib.loco_sam_last_error.argtypes = [vp]
+        lib.loco_sam_last_error.restype = C.c_char_p
+        lib.loco_sam_destroy.argtypes = [vp]
+        lib.loco_sam_destroy.restype = None
     if hasattr(lib, "loco_bench_conv"):          # diag build only
         lib.loco_bench_conv.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(f32), vp]
         lib.loco_debug_tensor.argtypes = [vp, C.c_char_p, vp, i64, vp]
@@ -712,3 +734,92 @@ class LocoTextEngine:
                 self._check(self.lib.loco_text_encode_masked(self._t, _ptr(ids), larr, n, _ptr(out), _stream()),
                             "loco_text_encode_masked")
         return out
+
+
+class LocoSamEngine:
+    """The image encoder of Segment Anything (= loco_sam, include/loco_hip.h): parameters and the workspace of one image on
+    the device.  `cfg` is a ``mask_segmentation.SamVisionConfig``; preprocessed pixel_values [3, S, S] in, image embeddings
+    [1, C_out, G, G] out, exact fp32."""
+
+    def __init__(self, cfg, device: Optional[torch.device] = None):
+        self.lib = load_library()
+        if not torch.cuda.is_available() or self.lib.loco_device_count() < 1:
+            raise RuntimeError("loco_hip: no HIP device visible; the SAM image encoder has no CPU fallback")
+        self.device = torch.device(device if device is not None else "cuda:0")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.cfg = cfg
+        glob = [int(i) for i in cfg.global_attn_indexes]
+        if len(glob) > SAM_MAX_GLOBAL:
+            raise ValueError(f"at most {SAM_MAX_GLOBAL} global attention layers, got {len(glob)}")
+        c = LocoSamCfg(image_size=cfg.image_size, patch_size=cfg.patch_size, width=cfg.hidden_size, depth=cfg.num_hidden_layers,
+                       heads=cfg.num_attention_heads, mlp_dim=cfg.mlp_dim, window_size=cfg.window_size, num_global=len(glob),
+                       out_channels=cfg.output_channels, ln_eps=cfg.layer_norm_eps)
+        for i, g in enumerate(glob):
+            c.global_attn[i] = g
+        self.grid = cfg.image_size // cfg.patch_size
+        self._t = C.c_void_p()
+        rc = self.lib.loco_sam_create(C.byref(c), self.device.index, C.byref(self._t))
+        if rc != 0:
+            raise RuntimeError(f"loco_sam_create failed ({rc}): {self.lib.loco_sam_last_error(None).decode()}")
+
+    def __del__(self):
+        try:
+            if getattr(self, "_t", None):
+                self.lib.loco_sam_destroy(self._t)
+                self._t = None
+        except Exception:
+            pass
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise RuntimeError(f"{what} failed ({rc}): {self.lib.loco_sam_last_error(self._t).decode()}")
+
+    def load_params(self, sd: Dict[str, "np.ndarray | torch.Tensor"]):
+        """Loads the entries of `sd` (a part of the state_dict) without asking for completeness."""
+        if any(isinstance(v, torch.Tensor) and v.is_cuda for v in sd.values()):
+            torch.cuda.synchronize()
+        for name, v in sd.items():
+            t = torch.as_tensor(np.asarray(v) if not isinstance(v, torch.Tensor) else v).detach().to(torch.float32).contiguous()
+            if not t.is_cuda:
+                t = t.cpu()
+            shape = (C.c_int64 * max(t.dim(), 1))(*t.shape)
+            self._check(self.lib.loco_sam_load_param(self._t, name.encode(), C.c_void_p(t.data_ptr()), shape, t.dim()),
+                        f"loco_sam_load_param({name})")
+
+    def check_complete(self):
+        missing = self.lib.loco_sam_params_missing(self._t)
+        if missing:
+            raise RuntimeError(f"SAM image encoder: {missing} parameters missing ({self.lib.loco_sam_last_error(self._t).decode()})")
+
+    def load_state_dict(self, sd: Dict[str, "np.ndarray | torch.Tensor"]):
+        """Names of SamVisionEncoder without a prefix (mask_segmentation.vision_state_dict produces them)."""
+        self.load_params(sd)
+        self.check_complete()
+
+    def encode(self, pixel_values: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """pixel_values [3, S, S] or [1, 3, S, S] (fp32, host or device) -> [1, C_out, G, G] fp32 on the device."""
+        S, G, Co = self.cfg.image_size, self.grid, self.cfg.output_channels
+        pv = torch.as_tensor(pixel_values)
+        if tuple(pv.shape) == (1, 3, S, S):
+            pv = pv[0]
+        if tuple(pv.shape) != (3, S, S):
+            raise ValueError(f"pixel_values must be [3, {S}, {S}] (one image per call), got {tuple(pv.shape)}")
+        pv = pv.to(device=self.device, dtype=torch.float32).contiguous()
+        if out is None:
+            out = torch.empty(1, Co, G, G, device=self.device, dtype=torch.float32)
+        _chk_dev(out)
+        if tuple(out.shape) != (1, Co, G, G):
+            raise ValueError(f"out must be [1, {Co}, {G}, {G}], got {tuple(out.shape)}")
+        with torch.cuda.device(self.device):
+            self._check(self.lib.loco_sam_encode(self._t, _ptr(pv), _ptr(out), _stream()), "loco_sam_encode")
+        return out
+
+    def profile(self, on: bool):
+        self._check(self.lib.loco_sam_profile(self._t, int(bool(on))), "loco_sam_profile")
+
+    def profile_read(self) -> Dict[str, float]:
+        """Milliseconds of the last profiled encode by kind of launch (waits for it)."""
+        ms = (C.c_float * 4)()
+        self._check(self.lib.loco_sam_profile_read(self._t, ms), "loco_sam_profile_read")
+        return dict(zip(("gemm", "window_attn", "global_attn", "other"), [float(v) for v in ms]))

@@ -695,13 +695,26 @@ class EditDeepFloydIF(object):
         return obj
 
     # ------------------------------------------------------------------ drivers
-    def _masks(self):
+    def _masks(self, image_fn=None, resolution=None):
+        """The cached SAM masks; without a cache and with --mask_model_path, `image_fn()` (uint8 [H, W, 3]) is segmented."""
         mpath = os.path.join(self.result_folder, "mask/mask.pt")
         if not self._exists(mpath):
+            if getattr(self.args, "mask_model_path", "") and image_fn is not None:
+                from .mask_segmentation import segment_for_driver
+                print("Creating masks......")
+                return segment_for_driver(self.args, self.result_folder, self.sharder, image_fn, resolution)
             raise FileNotFoundError(f"{mpath} missing: stage-II super-resolution + SAM (edit.py:1768-1776) are outside this "
                                     "path; provide mask.pt (bool [N,res,res])")
         print("Loading masks......")
         return self._load(mpath)
+
+    def _stage1_sample(self, xT):
+        """The 64 x 64 stage-I sample under the `for` prompt as uint8 [H, W, 3]: what SAM segments on this path (the
+        reference segments the stage-II output, edit.py:1768-1776; stage II is not built)."""
+        self.EXP_NAME = "original"
+        x0 = self.DDPMforwardsteps(xT, t_start_idx=0, t_end_idx=-1, for_prompt_emb=self.for_prompt_emb,
+                                   edit_prompt_emb=self.edit_prompt_emb, null_prompt_emb=self.null_prompt_emb, mode="null+(for-null)")
+        return x0[0].detach().cpu().numpy()
 
     def _walk(self, original_xt, v_row, vis_num):
         """+/- walk of edit.py:1840-1860 in one kernel (frames x + j*scale*step*v)."""
@@ -724,7 +737,7 @@ class EditDeepFloydIF(object):
         self.scheduler.set_timesteps(self.for_steps)
         xT = self._xT()
         self.EXP_NAME = "original"
-        masks = self._masks()
+        masks = self._masks(lambda: self._stage1_sample(xT), self.image_size)
         if self.sampling_mode:
             return None
         mask = masks[mask_index].squeeze(dim=0).repeat(3, 1, 1)
@@ -780,7 +793,7 @@ class EditDeepFloydIF(object):
         xT = self._xT()
         F, E, N = self.for_prompt_emb, self.edit_prompt_emb, self.null_prompt_emb
         if self.mask_type == "SAM":
-            masks = self._masks()
+            masks = self._masks(lambda: self._stage1_sample(xT), self.image_size)
             mask = masks[mask_index].squeeze(dim=0).repeat(3, 1, 1)
         elif self.mask_type == "diffedit":
             # edit.py:1911-1919: the full sample under the `for` prompt, then the mask from the two prompts.  No mask.pt is

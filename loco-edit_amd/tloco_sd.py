@@ -386,10 +386,13 @@ class EditStableDiffusion(EditDeepFloydIF):
         zT = self._zT()
         self.EXP_NAME = "original"
         F, E, N = self.for_prompt_emb, self.edit_prompt_emb, self.null_prompt_emb
-        if self.sharder.agree(not os.path.exists(os.path.join(self.result_folder, "original.png"))):
-            self.DDIMforwardsteps(zT, t_start_idx=0, t_end_idx=-1, for_prompt_emb=F, edit_prompt_emb=E, null_prompt_emb=N,
-                                  mode="null+(for-null)")                 # the image SAM would segment (edit.py:942-948)
-        masks = self._masks()
+        x0 = None
+        segment = bool(getattr(self.args, "mask_model_path", "")) and not self._exists(os.path.join(self.result_folder, "mask/mask.pt"))
+        if self.sharder.agree(not os.path.exists(os.path.join(self.result_folder, "original.png"))) or segment:
+            _, x0 = self.DDIMforwardsteps(zT, t_start_idx=0, t_end_idx=-1, for_prompt_emb=F, edit_prompt_emb=E, null_prompt_emb=N,
+                                          mode="null+(for-null)")         # the image SAM segments (edit.py:942-948)
+        # masks at the size of the decoded sample (512 for Stable Diffusion)
+        masks = self._masks((lambda: x0[0].detach().cpu().numpy()) if segment else None, x0.shape[1] if segment else None)
         if self.sampling_mode:
             return None
         mask = masks[mask_index].squeeze(dim=0).repeat(3, 1, 1)
