@@ -93,6 +93,11 @@ typedef struct loco_unet_cfg {
     int32_t act;
     float   res_scale;
     int32_t added_kv;
+    /* arch 1, latent-consistency distilled denoisers (diffusers UNet2DConditionModel `time_cond_proj_dim`; LCM_Dreamshaper_v7:
+     * 256): P > 0 adds the parameter `time_embed.cond_proj.weight` [ch][P] (no bias) and the call loco_set_time_cond, whose
+     * result is added to the sinusoid before the first dense layer of the time embedding
+     * (`t_emb + cond_proj(timestep_cond)` ahead of `linear_1`).  0: neither exists. */
+    int32_t time_cond_proj_dim;
 } loco_unet_cfg;
 
 /* Library / device probes (no ctx). */
@@ -246,6 +251,14 @@ int  loco_get_precision(loco_ctx* ctx);
  * SiLU -- the slot guided-diffusion uses for `label_emb(y)` (unet.py:660-662) and diffusers' UNet2DConditionModel for
  * `addition_embed_type="text"`.  NULL clears it.  Invalidates the cached primal. */
 int  loco_set_cond(loco_ctx* ctx, const float* emb_add, void* stream);
+/* Guidance-scale embedding of a latent-consistency denoiser (cfg.time_cond_proj_dim = P > 0; the `timestep_cond` of
+ * `self.unet(latents, t, timestep_cond=w_embedding, ...)`, src/modules/edit.py:126-132): w_emb = device pointer to P floats.
+ * Computes cond_in[ch] = cond_proj.weight . w_emb once (exact fp32, one wave per row) into a buffer this context owns; every
+ * later time embedding adds it to the sinusoid.  Per context, not per parameter store: forks of one store keep their own
+ * (a fork starts without one).  The buffer's address never changes, so a captured forward graph stays valid across calls.
+ * NULL clears it (evaluations are then bit-identical to a context that never had one).  Constant in x: the tangent and
+ * cotangent passes are unchanged.  Invalidates the cached primal; refused when time_cond_proj_dim == 0. */
+int  loco_set_time_cond(loco_ctx* ctx, const float* w_emb, void* stream);
 /* out[k, n] = mask * (cv * V + ce * E) with the mask of the last loco_pmp_primal (all ones without one): the
  * x0_hat = (x - eps sqrt(1-at)) / sqrt(at) algebra of edit.py:1574 / 2385 applied to tangents or cotangents when eps is a
  * CFG combination assembled by the caller.  V, E: [k, n]; out may alias either. */
@@ -289,6 +302,16 @@ int  loco_diffedit_mask(loco_ctx* ctx, const float* eps_a, const float* eps_b, f
 int  loco_cfg_masked_step(loco_ctx* ctx, const float* x, const float* eps_for, const float* eps_edit,
                           const float* eps_null, float g, float at, float at_next, const uint8_t* mask, int32_t B,
                           int64_t n, float* x_next, void* stream);
+
+/* One step of the latent-consistency scheduler after the denoiser call (LCMScheduler.step as src/modules/edit.py:135, 194, 235
+ * use it), one launch, per element in fp32:
+ *   x0       = (x - sqrt(1 - at) eps) / sqrt(at)
+ *   denoised = c_out x0 + c_skip x                                  (boundary-condition scalings)
+ *   x_prev   = noise ? sqrt(at_prev) denoised + sqrt(1 - at_prev) noise : denoised
+ * x, eps, noise, x_prev, denoised: `count` floats; noise NULL on the last step; x_prev and denoised may each be NULL (not
+ * written), x_prev may alias x.  No scratch.  Replaces loco_sched_step + two loco_lincomb (three launches, two intermediates). */
+int  loco_lcm_step(loco_ctx* ctx, const float* x, const float* eps, float at, float at_prev, float c_skip, float c_out,
+                   const float* noise, int64_t count, float* x_prev, float* denoised, void* stream);
 
 /* Per-kernel HIP-event profile of the convolution launches (bench.py roofline
  * leg).  While enabled every conv launch is bracketed by two events on the

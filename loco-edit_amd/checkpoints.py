@@ -330,7 +330,15 @@ def hf_unet2d_condition_to_ldm(sd: Dict[str, torch.Tensor], cfg: UNetConfig) -> 
     out: Dict[str, torch.Tensor] = {}
     for k, v in sd.items():
         p = k.split(".")
-        if p[0] == "time_embedding":
+        if p[0] == "time_embedding" and p[1] == "cond_proj":
+            # the guidance-scale input of a latent-consistency distilled U-Net (`time_cond_proj_dim`): its own parameter.  An
+            # architecture without it refuses the file -- the model would run with its guidance silently dropped
+            if cfg.time_cond_proj_dim <= 0:
+                raise ValueError(f"{k}: this is an LCM-distilled U-Net (time_cond_proj_dim = {tuple(v.shape)[-1]}), the "
+                                 "configuration has time_cond_proj_dim = 0; choose an LCM architecture "
+                                 "(config.LCM_DREAMSHAPER_V7_UNET)")
+            out[f"time_embed.cond_proj.{p[-1]}"] = v
+        elif p[0] == "time_embedding":
             out[f"time_embed.{0 if p[1] == 'linear_1' else 2}.{p[-1]}"] = v
         elif p[0] == "conv_in":
             out[f"input_blocks.0.0.{p[-1]}"] = v
@@ -383,7 +391,9 @@ def ldm_to_hf_unet2d_condition(sd: Dict[str, torch.Tensor], cfg: UNetConfig) -> 
 
     for k, v in sd.items():
         p = k.split(".")
-        if p[0] == "time_embed":
+        if p[0] == "time_embed" and p[1] == "cond_proj":
+            out[f"time_embedding.cond_proj.{p[-1]}"] = v
+        elif p[0] == "time_embed":
             out[f"time_embedding.linear_{1 if p[1] == '0' else 2}.{p[-1]}"] = v
         elif p[0] == "out":
             out[f"{'conv_norm_out' if p[1] == '0' else 'conv_out'}.{p[-1]}"] = v

@@ -62,6 +62,10 @@ class UNetConfig:
     res_scale: float = 1.0
     added_kv: bool = False
     encoder_dim: int = 0
+    # adm, latent-consistency distilled denoisers (diffusers `time_cond_proj_dim`; LCM_Dreamshaper_v7: 256): P > 0 adds
+    # `time_embed.cond_proj.weight` [ch, P] (no bias); the guidance-scale embedding w_emb [P] given to
+    # `LocoEngine.set_time_cond` enters as t_emb + cond_proj(w_emb) ahead of the first dense layer
+    time_cond_proj_dim: int = 0
 
     @property
     def temb_ch(self) -> int:
@@ -156,6 +160,22 @@ SD21_BASE_UNET = UNetConfig(resolution=64, in_channels=4, out_ch=4, ch=320, ch_m
 TINY_LDM = UNetConfig(resolution=16, in_channels=4, out_ch=4, ch=32, ch_mult=(1, 2), num_res_blocks=1,
                       attn_resolutions=(16, 8), gn_eps=1e-5, arch="adm", learn_sigma=False, context_dim=16, context_len=7,
                       scale_shift_norm=False, resblock_updown=False, num_heads=4, transformer_depth=1)
+# SimianLuo/LCM_Dreamshaper_v7 (the id of scripts/main_T2I_LCM_null_space_projection*.sh:4): the Stable Diffusion v1 denoiser
+# with a 256-wide guidance-scale embedding in front of the time embedding; 859 520 964 + 320 * 256 = 859 602 884 parameters.
+# The test size takes 10: no multiple of 4 or 64, so the projection's tail lanes are exercised
+# Reached as `config.LCM_DREAMSHAPER_V7_UNET` / `config.TINY_LCM` through the module's __getattr__ below, not bound as module
+# globals: tests/test_program_host.py sweeps every UNetConfig global against tests/golden/program_digest.json, which holds the
+# programs recorded when the program moved into its own unit; these two are recorded in tests/golden/program_digest_lcm.json
+# and swept the same way by tests/test_program_host_lcm.py
+_LCM_PRESETS = {"LCM_DREAMSHAPER_V7_UNET": UNetConfig(**{**SD15_UNET.__dict__, "time_cond_proj_dim": 256}),
+                "TINY_LCM": UNetConfig(**{**TINY_LDM.__dict__, "time_cond_proj_dim": 10})}
+
+
+def __getattr__(name):
+    try:
+        return _LCM_PRESETS[name]
+    except KeyError:
+        raise AttributeError(f"module {__name__!r} has no attribute {name!r}") from None
 # a SpatialTransformer with 40-channel heads (Stable Diffusion's width at its 4096-token level) over 256 tokens
 FLASH_LDM = UNetConfig(resolution=16, in_channels=4, out_ch=4, ch=160, ch_mult=(1,), num_res_blocks=1, attn_resolutions=(16,),
                        gn_eps=1e-5, arch="adm", learn_sigma=False, context_dim=16, context_len=7, scale_shift_norm=False,
@@ -266,6 +286,8 @@ def adm_param_shapes(cfg: UNetConfig) -> "OrderedDict[str, Tuple[int, ...]]":
 
     shapes["time_embed.0.weight"] = (ted, mc); shapes["time_embed.0.bias"] = (ted,)
     shapes["time_embed.2.weight"] = (ted, ted); shapes["time_embed.2.bias"] = (ted,)
+    if cfg.time_cond_proj_dim > 0:      # guidance-scale embedding of the LCM-distilled U-Nets (Linear without bias)
+        shapes["time_embed.cond_proj.weight"] = (mc, cfg.time_cond_proj_dim)
     if cfg.encoder_dim > 0:
         # host-side text conditioning of the IF U-Net (tloco.IFTextConditioner; diffusers `encoder_hid_proj` and
         # `add_embedding` = TextTimeEmbedding: LayerNorm, AttentionPooling, Linear, LayerNorm)

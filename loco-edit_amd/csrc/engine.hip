@@ -74,6 +74,7 @@ struct OpWeights {
 struct Weights {
     std::vector<OpWeights> op;               // indexed like Program::ops
     float *freq = nullptr, *td0w = nullptr, *td0b = nullptr, *td1w = nullptr, *td1b = nullptr;   // time embedding
+    float* tcw = nullptr;          // time_embed.cond_proj.weight [ch][time_cond_proj_dim] (cfg.time_cond_proj_dim > 0)
     float *tp_w = nullptr, *tp_b = nullptr;  // concatenated temb_proj
     long tproj_total = 0;
     double flops = 0.0;
@@ -138,6 +139,8 @@ struct loco_ctx {
     float* cond_add = nullptr;     // [temb_ch] conditioning embedding of the time embedding (loco_set_cond)
     float* ctx_norm = nullptr;     // [context_len][context_dim] scratch: the states behind one block's norm_encoder (added_kv)
     bool has_cond = false;
+    float* cond_in = nullptr;      // [ch] cond_proj(w_emb), added to the sinusoid of the time embedding (loco_set_time_cond); this context's own
+    bool has_tcond = false;
     float2* sxcache = nullptr;     // primal {S, xhat} per GroupNorm+SiLU input (bf16x3 path)
     int prec = 0;                  // 0: exact fp32 MFMA, 1: split-bf16 (bf16x3) MFMA, 2: single f16 MFMA
     std::vector<float*> owned;     // everything to hipFree
@@ -382,6 +385,7 @@ int finalize_params(loco_ctx* c) {
         if (upload(c, &W.td0b, c->params[te0 + ".bias"].data)) return -1;
         if (upload(c, &W.td1w, c->params[te1 + ".weight"].data)) return -1;
         if (upload(c, &W.td1b, c->params[te1 + ".bias"].data)) return -1;
+        if (cfg.time_cond_proj_dim > 0 && upload(c, &W.tcw, c->params["time_embed.cond_proj.weight"].data)) return -1;
     }
     // sinusoid frequencies exactly as torch computes them in fp32:
     //   DDPM: exp(float32(i) * float32(-ln(1e4)/(half-1)))            (diffusion.py:797-798)
@@ -1060,7 +1064,7 @@ int forward_pass(loco_ctx* c, const float* x, float t, int B, float* arena, floa
     auto next_fwd = [&](int tid) { return req_fwd_of(c, tid, stats); };   // forward statistics for the consumer of `tid` (+ kept partials of a concatenation part)
     if (cfg.arch < 2) {
         launch_temb(t, cfg.ch, cfg.ch * 4, c->wts->freq, c->wts->td0w, c->wts->td0b, c->wts->td1w, c->wts->td1b, c->tact, st, cfg.arch == 1,
-                    c->has_cond ? c->cond_add : nullptr, t_ptr, cfg.act);
+                    c->has_cond ? c->cond_add : nullptr, t_ptr, cfg.act, c->has_tcond ? c->cond_in : nullptr);
         launch_temb_proj(c->tact, cfg.ch * 4, c->wts->tp_w, c->wts->tp_b, (int)c->wts->tproj_total, c->tproj, st);
     }
     for (auto& op : c->ops) {
@@ -1916,6 +1920,7 @@ int create_ctx(loco_ctx* c, const loco_unet_cfg* cfg, std::shared_ptr<const Prog
         if (dalloc(c, &c->gscratch, nblk * 64 * 64 + 4096)) return -1;
     }
     if (dalloc(c, &c->alphas, 256) || dalloc(c, &c->cond_add, (size_t)cfg->ch * 4)) return -1;
+    if (dalloc(c, &c->cond_in, (size_t)cfg->ch)) return -1;
     {
         float2* sx0 = nullptr;
         if (dalloc(c, &sx0, (size_t)c->prog->sx_total + 64)) return -1;
@@ -2066,8 +2071,8 @@ int loco_unet_forward(loco_ctx* c, const float* x, float t, int32_t B, float* ep
     hipStream_t st = (hipStream_t)stream;
     c->primal_ok = false;
     if (c->graph_on && !c->prof_on) {
-        // key: batch, condition on/off, arithmetic (all three change the launch list)
-        loco_ctx::FwdGraph& g = c->fwd_graphs[(B << 3) | (c->has_cond ? 4 : 0) | c->prec];
+        // key: batch, conditions on/off, arithmetic (all change the launch list; the contents of cond_add / cond_in do not)
+        loco_ctx::FwdGraph& g = c->fwd_graphs[(B << 4) | (c->has_tcond ? 8 : 0) | (c->has_cond ? 4 : 0) | c->prec];
         // the first evaluation of a key runs eagerly (one-time lazy setup inside the launchers), the second is captured
         if (!g.exec && g.calls++ >= 1 && capture_forward(c, B, g)) return -1;
         if (g.exec) {
@@ -2375,6 +2380,20 @@ int loco_set_cond(loco_ctx* c, const float* emb_add, void* stream) {
     return 0;
 }
 
+int loco_set_time_cond(loco_ctx* c, const float* w_emb, void* stream) {
+    if (!c) return -2;
+    const int P = c->cfg.time_cond_proj_dim;
+    if (P <= 0) { c->err = "loco_set_time_cond: this architecture has no guidance-scale embedding (time_cond_proj_dim = 0)"; return -2; }
+    c->primal_ok = false;           // cached activations belong to the previous embedding
+    if (!w_emb) { c->has_tcond = false; return 0; }
+    if (finalize_params(c)) return -3;
+    // cond_in[ch] = cond_proj.weight [ch][P] . w_emb [P]: the per-block projection kernel without a bias
+    launch_temb_proj(w_emb, P, c->wts->tcw, nullptr, c->cfg.ch, c->cond_in, (hipStream_t)stream);
+    HIPCHK(c, hipGetLastError());
+    c->has_tcond = true;
+    return 0;
+}
+
 int loco_set_context(loco_ctx* c, const float* tokens, void* stream) {
     if (!c) return -2;
     if (c->cfg.context_dim <= 0) { c->err = "this architecture has no cross-attention stages (context_dim = 0)"; return -2; }
@@ -2481,6 +2500,17 @@ int loco_cfg_masked_step(loco_ctx* c, const float* x, const float* eps_for, cons
     float s1, s2, s3, ce, cn;
     sched_coeffs(at, at_next, 0.f, &s1, &s2, &s3, &ce, &cn);
     launch_cfg_masked_step(x, eps_for, eps_edit, eps_null, mask, x_next, B, (long)n, g, s2, s1, s3, ce, (hipStream_t)stream);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+int loco_lcm_step(loco_ctx* c, const float* x, const float* eps, float at, float at_prev, float c_skip, float c_out,
+                  const float* noise, int64_t count, float* x_prev, float* denoised, void* stream) {
+    if (!c) return -2;
+    if (!x || !eps || count < 1 || (!x_prev && !denoised)) { c->err = "lcm_step: bad arguments"; return -2; }
+    if (!(at > 0.f && at <= 1.f) || !(at_prev >= 0.f && at_prev <= 1.f)) { c->err = "lcm_step: alpha-bar outside (0, 1]"; return -2; }
+    launch_lcm_step(x, eps, noise, x_prev, denoised, (long)count, std::sqrt(at), std::sqrt(1.0f - at), std::sqrt(at_prev),
+                    std::sqrt(1.0f - at_prev), c_skip, c_out, (hipStream_t)stream);
     HIPCHK(c, hipGetLastError());
     return 0;
 }

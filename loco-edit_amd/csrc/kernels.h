@@ -346,11 +346,12 @@ void launch_temb(float t, int ch, int temb_ch, const float* freq, const float* w
                  const float* w1, const float* b1, float* scratch, hipStream_t st, int cos_first = 0,
                  const float* add = nullptr,      // add[temb_ch]: conditioning embedding added to emb before the SiLU
                  const float* t_ptr = nullptr,    // non-null: read the timestep from device memory (graph replay)
-                 int act = 0);
+                 int act = 0,
+                 const float* add_in = nullptr);  // add_in[ch]: added to the sinusoid before dense0 (loco_set_time_cond)
 void launch_set_scalar(float* p, float v, hipStream_t st);
 void launch_clock_stamp(unsigned long long* out2, hipStream_t st);   // {s_memtime, s_memrealtime}
 void launch_temb_proj(const float* tact, int temb_ch, const float* w, const float* b, int cout,
-                      float* out, hipStream_t st);
+                      float* out, hipStream_t st);      // b may be nullptr (no bias)
 // out[b][c][y][x] = sum of the 2x2 block of in[b][c][2y..][2x..]   (adjoint of nearest x2)
 void launch_pool2x2_sum(const float* in, long in_bs, float* out, long out_bs, int accumulate,
                         int B, int C, int Hout, int Wout, hipStream_t st, float scale = 1.0f);
@@ -385,6 +386,11 @@ void launch_diffedit_mask(const float* eps_a, const float* eps_b, float scale, i
 void launch_cfg_masked_step(const float* x, const float* ef, const float* ee, const float* en, const uint8_t* mask, float* out,
                             int B, long n, float g, float c_x0_x, float c_x0_e, float c_next_x0, float c_next_e,
                             hipStream_t st);
+// ---- latent-consistency scheduler (lcm.hip) --------------------------------------
+// x0 = (x - s1mat eps) / sat; den = c_out x0 + c_skip x; prev = noise ? satp den + s1matp noise : den.  prev / den may be
+// nullptr (not written); prev may alias x
+void launch_lcm_step(const float* x, const float* eps, const float* noise, float* prev, float* den, long count, float sat,
+                     float s1mat, float satp, float s1matp, float c_skip, float c_out, hipStream_t st);
 
 // ---- solver --------------------------------------------------------------------
 // G[k][k] (double) = A A^T, A: [k][n] fp32

@@ -784,7 +784,7 @@ void launch_softmax_jac(float* dS, const float* P, long rows, int T, long p_rows
 // (reference diffusion.py:783-804, 154-157, and the nonlinearity(temb) of :899)
 __global__ void temb_kernel(float t, int ch, int temb_ch, const float* freq, const float* w0, const float* b0,
                             const float* w1, const float* b1, float* out, int cos_first, const float* add,
-                            const float* t_ptr, int act) {
+                            const float* t_ptr, int act, const float* add_in) {
     extern __shared__ float sm[];
     if (t_ptr) t = *t_ptr;     // timestep from device memory: the launch is a node of a replayed HIP graph
     float* emb = sm;           // [ch]
@@ -798,6 +798,10 @@ __global__ void temb_kernel(float t, int ch, int temb_ch, const float* freq, con
     }
     if ((ch & 1) && threadIdx.x == 0) emb[ch - 1] = 0.f;
     __syncthreads();
+    if (add_in) {              // guidance-scale embedding (loco_set_time_cond): t_emb + cond_proj(timestep_cond) before dense0
+        for (int i = threadIdx.x; i < ch; i += blockDim.x) emb[i] += add_in[i];
+        __syncthreads();
+    }
     for (int o = threadIdx.x; o < temb_ch; o += blockDim.x) {
         float acc = b0[o];
         for (int i = 0; i < ch; ++i) acc = fmaf(w0[(long)o * ch + i], emb[i], acc);
@@ -813,9 +817,9 @@ __global__ void temb_kernel(float t, int ch, int temb_ch, const float* freq, con
 }
 void launch_temb(float t, int ch, int temb_ch, const float* freq, const float* w0, const float* b0, const float* w1,
                  const float* b1, float* scratch, hipStream_t st, int cos_first, const float* add,
-                 const float* t_ptr, int act) {
+                 const float* t_ptr, int act, const float* add_in) {
     hipLaunchKernelGGL(temb_kernel, dim3(1), dim3(512), (ch + temb_ch) * sizeof(float), st, t, ch, temb_ch, freq,
-                       w0, b0, w1, b1, scratch, cos_first, add, t_ptr, act);
+                       w0, b0, w1, b1, scratch, cos_first, add, t_ptr, act, add_in);
 }
 __global__ void set_scalar_kernel(float* p, float v) { *p = v; }
 // {shader-clock counter, 100 MHz wall counter} of the CU this one-lane launch lands on: two of these around a timed
@@ -831,7 +835,7 @@ void launch_clock_stamp(unsigned long long* out2, hipStream_t st) {
 void launch_set_scalar(float* p, float v, hipStream_t st) {
     hipLaunchKernelGGL(set_scalar_kernel, dim3(1), dim3(1), 0, st, p, v);
 }
-// out[o] = b[o] + sum_i w[o][i]*tact[i]; one wave per output row
+// out[o] = b[o] + sum_i w[o][i]*tact[i]; one wave per output row (b == nullptr: no bias, the cond_proj of loco_set_time_cond)
 __global__ __launch_bounds__(256) void temb_proj_kernel(const float* tact, int temb_ch, const float* w,
                                                         const float* b, int cout, float* out) {
     int o = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -840,7 +844,7 @@ __global__ __launch_bounds__(256) void temb_proj_kernel(const float* tact, int t
     float acc = 0.f;
     for (int i = lane; i < temb_ch; i += 64) acc = fmaf(w[(long)o * temb_ch + i], tact[i], acc);
     acc = wave_sumf(acc);
-    if (lane == 0) out[o] = acc + b[o];
+    if (lane == 0) out[o] = b ? acc + b[o] : acc;
 }
 void launch_temb_proj(const float* tact, int temb_ch, const float* w, const float* b, int cout, float* out,
                       hipStream_t st) {

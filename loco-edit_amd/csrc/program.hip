@@ -389,6 +389,7 @@ void Builder::declare() {
     if (cfg.arch < 2) {
         lin(nm.te0, cfg.ch, temb_ch);
         lin(nm.te1, temb_ch, temb_ch);
+        if (cfg.time_cond_proj_dim > 0) param("time_embed.cond_proj.weight", {cfg.ch, cfg.time_cond_proj_dim});   // no bias
     }
     for (const OpPlan& op : p.ops) {
         const int cin = op.in >= 0 ? p.tens[op.in].C : cfg.in_channels, cout = p.tens[op.out].C, C = cin;
@@ -462,6 +463,8 @@ const char* refuse(const loco_unet_cfg& cfg) {
     if ((cfg.act != 0 || scaled || cfg.added_kv) && cfg.arch != 1) return "act / res_scale / added_kv belong to the guided-diffusion family (arch 1)";
     if (cfg.added_kv && (cfg.context_dim <= 0 || cfg.context_len <= 0 || cfg.transformer_depth != 0 || cfg.context_dim % cfg.gn_groups))
         return "added_kv needs context_dim (a multiple of gn_groups) and context_len > 0 and transformer_depth = 0";
+    if (cfg.time_cond_proj_dim < 0 || (cfg.time_cond_proj_dim > 0 && cfg.arch != 1))
+        return "time_cond_proj_dim must be >= 0 and belongs to the guided-diffusion family (arch 1)";
     return nullptr;
 }
 

@@ -78,7 +78,8 @@ _UNET_PRESETS = {'celeba_ddpm': 'CELEBA_DDPM', 'ffhq_p2': 'FFHQ_P2', 'tiny_ddpm'
                  'tiny_adm': 'TINY_ADM', 'if64_standin': 'IF64_STANDIN', 'sd64_standin': 'SD64_STANDIN',
                  'sd64_xattn_standin': 'SD64_XATTN_STANDIN', 'tiny_latent': 'TINY_LATENT', 'tiny_latent_xattn': 'TINY_LATENT_XATTN',
                  'if64_xattn_standin': 'IF64_XATTN_STANDIN', 'tiny_adm_xattn': 'TINY_ADM_XATTN', 'sd15_unet': 'SD15_UNET', 'sd21_base_unet': 'SD21_BASE_UNET',
-                 'tiny_ldm': 'TINY_LDM', 'if_i_m_unet': 'IF_I_M_UNET', 'tiny_if': 'TINY_IF', 'mid_if': 'MID_IF'}
+                 'tiny_ldm': 'TINY_LDM', 'if_i_m_unet': 'IF_I_M_UNET', 'tiny_if': 'TINY_IF', 'mid_if': 'MID_IF',
+                 'lcm_dreamshaper_v7_unet': 'LCM_DREAMSHAPER_V7_UNET', 'tiny_lcm': 'TINY_LCM'}
 _VAE_PRESETS = {'sd_vae_decoder': 'SD_VAE_DECODER', 'tiny_decoder': 'TINY_DECODER'}
 _TILDA_V = ["proj_null[for-null](edit-null)-direct", "(for-edit)-direct", "(edit-null)-direct",
             "null+(for-null)+(edit-null)", "null+(for-null)", "null+(edit-null)", "(for-edit)",
@@ -120,6 +121,11 @@ def build_parser():
                    help='Segment Anything model that produces mask/mask.pt on the GPU when it is missing: a local SamModel '
                         'folder (config.json + model.safetensors or pytorch_model.bin) or a checkpoint file in SamModel naming. '
                         'Nothing is downloaded (--mask_model_name stays a name only). Empty: mask/mask.pt must exist')
+    p.add_argument('--lcm_timesteps', type=str, default=None, choices=['linspace', 'stride'],
+                   help='latent-consistency models (required for them): which published LCMScheduler.set_timesteps rule picks the '
+                        "N sampling timesteps out of the 50 training ones -- 'linspace' (current diffusers: N = 4 gives "
+                        "[999, 759, 499, 259]) or 'stride' (LCMScheduler as first released: [999, 759, 519, 279]); the reference "
+                        'does not pin a diffusers version that has the scheduler')
     p.add_argument('--cond_dim', type=int, default=16, help='T-LOCO stand-in: width of seeded prompt embeddings when no file is given')
     p.add_argument('--precision', type=str, default=None, choices=['f32', 'bf16x3', 'f16'],
                    help="conv arithmetic of the HIP engine: 'f32' exact fp32 MFMA (parity anchor), 'bf16x3' split-bf16 "
@@ -165,9 +171,15 @@ def preset(args):
     args.is_DeepFloyd_IF_diffusion = (not args.is_stable_diffusion) and 'DeepFloyd' in args.model_name
     args.is_LCM = (not args.is_stable_diffusion) and (not args.is_DeepFloyd_IF_diffusion) and 'LCM' in args.model_name
     if args.is_LCM:
-        raise NotImplementedError('the latent-consistency path (EditLatentConsistency, edit.py:42-481: LCM scheduler, guidance '
-                                  'embedding) is outside this build; Stable Diffusion is loco_edit_amd.tloco_sd, DeepFloyd-IF '
-                                  'loco_edit_amd.tloco')
+        if not getattr(args, 'lcm_timesteps', None):
+            # the two published rules give different timestep tables, and the shipped scripts edit at one of the entries that
+            # differ (--num_inference_steps 4 --edit_t_idx 2: t = 499 against 519): a drop-in cannot choose silently
+            raise NotImplementedError('the latent-consistency path (loco_edit_amd.tloco_lcm, edit.py:42-481) needs '
+                                      '--lcm_timesteps {linspace,stride}: the reference pins no diffusers version that has '
+                                      'LCMScheduler, and its two published set_timesteps rules differ -- linspace (current '
+                                      'diffusers) gives [999, 759, 499, 259] for 4 steps, stride (as first released) '
+                                      '[999, 759, 519, 279]')
+        return _preset_t2i(args, 'LCM')
     if args.is_stable_diffusion:
         return _preset_t2i(args, 'Stable_Diffusion')
     if args.is_DeepFloyd_IF_diffusion:
@@ -222,6 +234,17 @@ def _preset_t2i(args, family):
     args.dtype = torch.float32 if args.dtype == 'fp32' else torch.float16
     print(f'device : {args.device}, dtype : {args.dtype}')
     from . import config
+    if getattr(args, 'is_LCM', False):
+        # SimianLuo/LCM_Dreamshaper_v7: the SD v1 denoiser with the guidance-scale embedding, the SD autoencoder's decoder; none of
+        # the Stable Diffusion asserts below (define_argparser.py:242-243 of the reference: `elif args.is_LCM: pass`)
+        if getattr(args, 'unet_config', None) is None:
+            args.unet_config = config.LCM_DREAMSHAPER_V7_UNET
+        if getattr(args, 'vae_config', None) is None:
+            args.vae_config = config.SD_VAE_DECODER
+        args.c_in = args.unet_config.in_channels
+        args.image_size = args.unet_config.resolution
+        args.memory_bound = 5
+        return args
     if args.is_stable_diffusion:
         if getattr(args, 'unet_config', None) is None:
             # the Stable Diffusion v1.x denoiser (latent-diffusion UNetModel with SpatialTransformer blocks, 859.5 M

@@ -33,7 +33,7 @@ SYMBOLS = [
     "loco_set_cond", "loco_set_context", "loco_lincomb", "loco_masked_axpby", "loco_latent_sample",
     "loco_text_create", "loco_text_load_param", "loco_text_params_missing", "loco_text_encode", "loco_text_last_error",
     "loco_text_destroy", "loco_t5_create", "loco_text_encode_masked",
-    "loco_diffedit_mask", "loco_cfg_masked_step",
+    "loco_diffedit_mask", "loco_cfg_masked_step", "loco_set_time_cond", "loco_lcm_step",
     "loco_sam_create", "loco_sam_load_param", "loco_sam_params_missing", "loco_sam_encode", "loco_sam_profile",
     "loco_sam_profile_read", "loco_sam_last_error", "loco_sam_destroy",
 ]
@@ -53,6 +53,7 @@ class LocoCfg(C.Structure):
         ("scale_shift_norm", C.c_int32), ("resblock_updown", C.c_int32), ("num_heads", C.c_int32),
         ("transformer_depth", C.c_int32),
         ("act", C.c_int32), ("res_scale", C.c_float), ("added_kv", C.c_int32),
+        ("time_cond_proj_dim", C.c_int32),
     ]
 
 
@@ -137,6 +138,8 @@ def load_library():
     lib.loco_lincomb.argtypes = [vp, C.POINTER(vp), C.POINTER(f32), i32, vp, i64, vp]
     lib.loco_diffedit_mask.argtypes = [vp, vp, vp, f32, i32, i32, i64, i32, vp, vp, vp]
     lib.loco_cfg_masked_step.argtypes = [vp, vp, vp, vp, vp, f32, f32, f32, vp, i32, i64, vp, vp]
+    lib.loco_set_time_cond.argtypes = [vp, vp, vp]
+    lib.loco_lcm_step.argtypes = [vp, vp, vp, f32, f32, f32, f32, vp, i64, vp, vp, vp]
     lib.loco_profile_enable.argtypes = [vp, i32]
     lib.loco_profile_report.argtypes = [vp, C.c_char_p, i64]
     if hasattr(lib, "loco_text_create"):
@@ -206,6 +209,7 @@ def c_cfg(cfg: UNetConfig, max_batch: int) -> LocoCfg:
     c.scale_shift_norm, c.resblock_updown = int(cfg.scale_shift_norm), int(cfg.resblock_updown)
     c.num_heads, c.transformer_depth = cfg.num_heads, cfg.transformer_depth
     c.act, c.res_scale, c.added_kv = {"silu": 0, "gelu": 1}[cfg.act], float(cfg.res_scale), int(cfg.added_kv)
+    c.time_cond_proj_dim = int(cfg.time_cond_proj_dim)
     return c
 
 
@@ -444,6 +448,19 @@ class LocoEngine:
                 raise ValueError("conditioning embedding must have 4*ch elements")
         self._check(self.lib.loco_set_cond(self._ctx, _ptr(emb_add), _stream()), "loco_set_cond")
 
+    def set_time_cond(self, w_emb: Optional[torch.Tensor]):
+        """Guidance-scale embedding [time_cond_proj_dim] of a latent-consistency denoiser (``timestep_cond`` of
+        ``self.unet(...)``, edit.py:126-132): cond_proj(w_emb) is added to the sinusoid of every later time embedding of THIS
+        context (forks keep their own).  None clears it."""
+        if w_emb is not None:
+            _chk_dev(w_emb)
+            if self.cfg.time_cond_proj_dim > 0 and w_emb.numel() != self.cfg.time_cond_proj_dim:      # (0: the engine refuses)
+                raise ValueError(f"guidance-scale embedding must have time_cond_proj_dim = {self.cfg.time_cond_proj_dim} "
+                                 f"elements, got {tuple(w_emb.shape)}")
+        self._check(self.lib.loco_set_time_cond(self._ctx, _ptr(w_emb), _stream()), "loco_set_time_cond")
+        if w_emb is not None:
+            torch.cuda.current_stream().synchronize()     # `w_emb` may be a temporary
+
     def set_context(self, tokens: torch.Tensor):
         """Encoder states of the prompt [context_len, context_dim] for the cross-attention stages (the
         ``encoder_hidden_states`` of ``self.unet(...)``, edit.py:664-667); projected to keys / values once."""
@@ -535,6 +552,34 @@ class LocoEngine:
                                                   float(at_next), _ptr(mask), B, n, _ptr(out), _stream()),
                     "loco_cfg_masked_step")
         return out
+
+    # ---- latent-consistency scheduler (edit.py:135, 194, 235)
+    def lcm_step(self, x, eps, at: float, at_prev: float, c_skip: float, c_out: float, noise: Optional[torch.Tensor] = None,
+                 want_prev: bool = True, want_denoised: bool = True, out: Optional[torch.Tensor] = None):
+        """One LCMScheduler step after the denoiser call, one launch: denoised = c_out (x - sqrt(1-at) eps) / sqrt(at) +
+        c_skip x, prev = sqrt(at_prev) denoised + sqrt(1-at_prev) noise (noise None: prev = denoised).  -> (prev, denoised),
+        None for the one not asked for; ``out``: the tensor prev is written into (may be x)."""
+        _chk_dev(x)
+        _chk_dev(eps)
+        if eps.shape != x.shape:
+            raise ValueError(f"x and eps must share a shape, got {tuple(x.shape)} and {tuple(eps.shape)}")
+        if noise is not None:
+            _chk_dev(noise)
+            if noise.shape != x.shape:
+                raise ValueError(f"noise must be {tuple(x.shape)}, got {tuple(noise.shape)}")
+        if not (want_prev or want_denoised):
+            raise ValueError("lcm_step: ask for prev, denoised or both")
+        prev = None
+        if want_prev:
+            prev = torch.empty_like(x) if out is None else out
+            if out is not None:
+                _chk_dev(out)
+                if out.shape != x.shape:
+                    raise ValueError(f"out must be {tuple(x.shape)}, got {tuple(out.shape)}")
+        den = torch.empty_like(x) if want_denoised else None
+        self._check(self.lib.loco_lcm_step(self._ctx, _ptr(x), _ptr(eps), float(at), float(at_prev), float(c_skip), float(c_out),
+                                           _ptr(noise), x.numel(), _ptr(prev), _ptr(den), _stream()), "loco_lcm_step")
+        return prev, den
 
     # ---- introspection
     def version(self) -> str:

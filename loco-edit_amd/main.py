@@ -1,6 +1,6 @@
 """CLI entry: ``python -m loco_edit_amd.main <flags>`` -- dispatch of reference
-``src/main.py:12-103`` for the unconditional (DDPM) models, the pixel-space DeepFloyd-IF and the latent-space
-Stable Diffusion T-LOCO paths.
+``src/main.py:12-103`` for the unconditional (DDPM) models, the pixel-space DeepFloyd-IF, the latent-space
+Stable Diffusion and the latent-consistency (LCM) T-LOCO paths.
 
 Multi-GPU: ``torchrun --nproc-per-node N -m loco_edit_amd.main <flags>`` runs one
 process per GPU; the Jacobian probes of each subspace solve are sharded over the
@@ -31,6 +31,10 @@ def main(argv=None):
         from .tloco import EditDeepFloydIF
         print('is DeepFloyd-IF')
         edit = EditDeepFloydIF(args)
+    elif args.is_LCM:                            # main.py:29-31
+        from .tloco_lcm import EditLatentConsistency
+        print('is LCM')
+        edit = EditLatentConsistency(args)
     else:
         from .edit import EditUncondDiffusion
         print('is custmized diffusion model')

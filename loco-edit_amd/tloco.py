@@ -285,6 +285,7 @@ class CFGJacobianOperator:
 
 class EditDeepFloydIF(object):
     text_encoder = None
+    BRANCH_NAMES = ("for", "edit", "null")      # one engine context per prompt of the guidance (a subclass may run fewer)
 
     def __init__(self, args):
         self.device, self.dtype = args.device, args.dtype
@@ -351,7 +352,7 @@ class EditDeepFloydIF(object):
         # context loads the parameters (six device layouts), the others are forks of it (loco_fork: own arenas, statistics and
         # prompt constants only; bit-identical to independently loaded contexts).  LOCO_CFG_FORK=0: three independent contexts
         share_weights = os.environ.get("LOCO_CFG_FORK", "1") != "0"
-        for name in ("for", "edit", "null"):
+        for name in self.BRANCH_NAMES:
             if share_weights and self.branches:
                 eng = self.branches["for"].fork()
             else:
@@ -370,8 +371,9 @@ class EditDeepFloydIF(object):
                 eng.set_chip_share(share)
         self._cond_of: Dict[str, int] = {}
         for name, e in (("for", self.for_prompt_emb), ("edit", self.edit_prompt_emb), ("null", self.null_prompt_emb)):
-            self._bind(name, e)
-        print(f'engine : {self.engine.version()}, conv arithmetic : {self.engine.get_precision()}, branches : for / edit / null')
+            if name in self.branches:
+                self._bind(name, e)
+        print(f'engine : {self.engine.version()}, conv arithmetic : {self.engine.get_precision()}, branches : {" / ".join(self.branches)}')
         self.scheduler = IFScheduler(engine=self.engine)
         self.scheduler.set_timesteps(self.for_steps, device=self.device)
         self.edit_t = args.edit_t
@@ -388,13 +390,17 @@ class EditDeepFloydIF(object):
         # path (edit.py:1205-1208)
         # the reference ends the name with the model size of "DeepFloyd/IF-I-<size>-v1.0" (edit.py:1204-1206); the stand-in
         # denoisers (no IF architecture behind the name) say so instead
-        parts = str(getattr(args, "model_name", "")).split("-")
-        size = (parts[2] if len(parts) > 2 else "M") if self.use_text_cond else "standin"
-        self.result_folder = os.path.join(args.result_folder, f"for_prompt_{args.for_prompt}_cfg{args.guidance_scale}_seed{args.seed}_{size}")
+        self.result_folder = os.path.join(args.result_folder, f"for_prompt_{args.for_prompt}_cfg{args.guidance_scale}_seed{args.seed}"
+                                          + self._result_suffix(args))
         os.makedirs(self.result_folder, exist_ok=True)
         self.sharder = ProbeSharder("world")
         self.EXP_NAME = "exp"
         self.args = args
+
+    def _result_suffix(self, args) -> str:
+        parts = str(getattr(args, "model_name", "")).split("-")
+        size = (parts[2] if len(parts) > 2 else "M") if self.use_text_cond else "standin"
+        return f"_{size}"
 
     # ------------------------------------------------------------------ conditioning
     def cond_embedding(self, prompt_emb: torch.Tensor) -> torch.Tensor:

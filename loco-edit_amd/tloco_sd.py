@@ -67,7 +67,10 @@ class SDScheduler(IFScheduler):
 class LatentCFGJacobianOperator:
     """J and J^T of the decoded x0_hat(z_t) under classifier-free guidance: per-prompt denoiser engines + decoder engine."""
 
-    def __init__(self, branches: Dict[str, LocoEngine], weights, decoder: LocoEngine, z, t, at, z0_scaled, mask, streams=None):
+    def __init__(self, branches: Dict[str, LocoEngine], weights, decoder: LocoEngine, z, t, at, z0_scaled, mask, streams=None,
+                 scalars=None):
+        """J = J_dec(z0_scaled) . (a I - b sum_c w_c J_eps,c).  DDIM's x0 (default): a = s, b = s sigma; ``scalars`` = (a, b)
+        for another map from (z, eps) to the decoder's input (tloco_lcm: the consistency function)."""
         self.streams = streams or BranchStreams(1, "cpu")
         self.w = [(branches[name], w) for name, w in weights if w != 0.0]
         self.lead = self.w[0][0]
@@ -78,6 +81,7 @@ class LatentCFGJacobianOperator:
         a32 = np.float32(at)
         self.s = float(np.float32(1.0) / (np.float32(LATENT_SCALE) * np.sqrt(a32)))
         self.sigma = float(np.sqrt(np.float32(1.0) - a32))
+        self.a, self.b = (self.s, self.s * self.sigma) if scalars is None else (float(scalars[0]), float(scalars[1]))
         zc = z.contiguous()
         self.streams.run([(lambda e=eng: e.pmp_primal(zc, float(t), at, None, use_et=True)) for eng, _ in self.w])   # dEps products in latent space
         decoder.pmp_primal(z0_scaled.contiguous(), 0.0, 1.0, mask, use_et=True)   # raw decoder Jacobian, mask on the image
@@ -89,14 +93,14 @@ class LatentCFGJacobianOperator:
     def jvp(self, V):              # [k, n_z] -> dense masked [k, n_image]
         bufs = [torch.empty(V.shape[0], self.lead.n_out, device=V.device, dtype=torch.float32) for _ in self.w]
         outs = self.streams.run([(lambda e=eng, o=o: e.pmp_jvp(V, out=o)) for (eng, _), o in zip(self.w, bufs)])
-        terms = [(self.s, V)] + [(-self.s * self.sigma * w, o) for (_, w), o in zip(self.w, outs)]
+        terms = [(self.a, V)] + [(-self.b * w, o) for (_, w), o in zip(self.w, outs)]
         return self.dec.pmp_jvp(self.lead.lincomb(terms))
 
     def vjp(self, U):              # dense [k, n_image] -> [k, n_z]
         g = self.dec.pmp_vjp(U)
         bufs = [torch.empty(g.shape[0], self.n, device=g.device, dtype=torch.float32) for _ in self.w]
         outs = self.streams.run([(lambda e=eng, o=o: e.pmp_vjp(g, out=o)) for (eng, _), o in zip(self.w, bufs)])
-        terms = [(self.s, g)] + [(-self.s * self.sigma * w, o) for (_, w), o in zip(self.w, outs)]
+        terms = [(self.a, g)] + [(-self.b * w, o) for (_, w), o in zip(self.w, outs)]
         return self.lead.lincomb(terms)
 
     def gather(self, U):
