@@ -12,38 +12,33 @@
 // rel_h / rel_w [heads][T][size] from the unscaled queries, the im2col, and one attention kernel for both regimes: a
 // workgroup owns 16 queries of one (window, head) and streams the keys in order in chunks of 64 through LDS with a running
 // max and sum, so the T x T scores never reach memory.  Every sum runs in a fixed order set by compile-time constants.
-#include "textenc.h"
+#include "encoder_common.h"
 
-#include <algorithm>
 #include <cmath>
-#include <cstring>
-#include <string>
-#include <vector>
 
 struct SamLayer {
     float *ln1_g, *ln1_b, *wqkv, *bqkv, *rel_h, *rel_w, *wo, *bo, *ln2_g, *ln2_b, *w1, *b1, *w2, *b2;
-    bool global;
+    bool global = false;
 };
 struct SamTimed { int cat; hipEvent_t a, b; };
 
-struct loco_sam {
+struct loco_sam : loco::EncoderBase {
     loco_sam_cfg cfg;
-    int device = 0;
     int G = 0, T = 0, Tp = 0, hd = 0;
     int nwx = 0, Tw = 0, Twp = 0, ld = 0;        // windows per side, tokens of the padded windowed order, max(Tp, Twp)
     long frows = 0;                                // rows of f: max(mlp_dim, 9 out_channels, 3 patch^2)
-    std::string err;
-    float* params = nullptr;
     float *patch_w = nullptr, *patch_b = nullptr, *pos = nullptr, *neck_w1 = nullptr, *neck_g1 = nullptr, *neck_b1 = nullptr,
           *neck_w2 = nullptr, *neck_g2 = nullptr, *neck_b2 = nullptr;
     std::vector<SamLayer> layer;
-    std::vector<TextParam> table;
     float *h = nullptr, *x = nullptr, *xw = nullptr, *qkv = nullptr, *attn = nullptr, *y = nullptr, *f = nullptr, *stats = nullptr,
           *relh = nullptr, *relw = nullptr, *n1 = nullptr, *n2 = nullptr;
     bool profile = false;
     std::vector<SamTimed> timed;                   // event pairs of the last profiled encode
     std::vector<hipEvent_t> pool;
-    int fail(const std::string& m) { err = m; return -1; }
+    ~loco_sam() override {
+        loco::DeviceGuard dg(device);
+        for (hipEvent_t e : pool) (void)hipEventDestroy(e);
+    }
 };
 
 namespace loco {
@@ -124,17 +119,6 @@ __global__ __launch_bounds__(256) void sam_relpos_kernel(const float* q, long ld
 
 // parts of sam_attn_kernel's LDS start at multiples of 4 floats (float4 reads of Qs and Ps)
 __host__ __device__ constexpr size_t sam_r4(size_t n) { return (n + 3) / 4 * 4; }
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // One workgroup per (query block of 16, head, window): the nk = size^2 keys of the window (size = ws) or of the map
 // (size = G, one "window") are streamed in order in chunks of 64 -- K [hd][64] and V [64][hd + 1] of the chunk in LDS.  A wave
@@ -263,25 +247,11 @@ using namespace loco;
 
 namespace {
 thread_local std::string g_sam_create_err;
-using DeviceGuard = loco::TextDeviceGuard;
 
-inline unsigned blocks256(long n) { return (unsigned)((n + 255) / 256); }
-
-}  // namespace
-namespace loco { namespace {
 // the carve-up of sam_attn_kernel's LDS
 size_t sam_attn_lds_floats(int hd, int size) {
     return sam_r4((size_t)hd * SA_KC) + sam_r4((size_t)SA_KC * (hd + 1)) + sam_r4((size_t)hd * SA_QB) + sam_r4((size_t)2 * SA_QB * size) +
            (size_t)SA_WAVES * SA_KC * SA_QW;
-}
-} }
-namespace {
-
-void free_sam(loco_sam* t) {
-    (void)hipFree(t->params); (void)hipFree(t->h); (void)hipFree(t->x); (void)hipFree(t->xw); (void)hipFree(t->qkv);
-    (void)hipFree(t->attn); (void)hipFree(t->y); (void)hipFree(t->f); (void)hipFree(t->stats); (void)hipFree(t->relh);
-    (void)hipFree(t->relw); (void)hipFree(t->n1); (void)hipFree(t->n2);
-    for (hipEvent_t e : t->pool) (void)hipEventDestroy(e);
 }
 
 struct SamTimer {             // brackets a run of launches with two events while the profile is on
@@ -303,143 +273,83 @@ enum { SAM_CAT_GEMM = 0, SAM_CAT_WIN_ATTN = 1, SAM_CAT_GLOBAL_ATTN = 2, SAM_CAT_
 extern "C" {
 
 int loco_sam_create(const loco_sam_cfg* cfg, int32_t device, loco_sam** out) {
-    auto report = [](const std::string& m) { g_sam_create_err = m; return -1; };
-    if (!out) return report("loco_sam_create: out is NULL");
-    *out = nullptr;
-    if (!cfg) return report("loco_sam_create: cfg is NULL");
-    const loco_sam_cfg c = *cfg;
-    if (c.image_size <= 0 || c.patch_size <= 0 || c.width <= 0 || c.depth <= 0 || c.heads <= 0 || c.mlp_dim <= 0 ||
-        c.window_size <= 0 || c.out_channels <= 0)
-        return report("loco_sam_create: image_size, patch_size, width, depth, heads, mlp_dim, window_size and out_channels must be positive");
-    if (c.image_size % c.patch_size) return report("loco_sam_create: image_size is not a multiple of patch_size");
-    if (c.width % c.heads) return report("loco_sam_create: width is not a multiple of heads");
-    if (c.num_global < 0 || c.num_global > LOCO_SAM_MAX_GLOBAL) return report("loco_sam_create: num_global outside [0, 16]");
-    for (int i = 0; i < c.num_global; ++i)
-        if (c.global_attn[i] < 0 || c.global_attn[i] >= c.depth) return report("loco_sam_create: a global attention index is outside [0, depth)");
-    if (!(c.ln_eps > 0.f)) return report("loco_sam_create: ln_eps must be positive");
-    const int G = c.image_size / c.patch_size, hd = c.width / c.heads, ws = c.window_size;
-    if (hd > 128) return report("loco_sam_create: head width > 128 (the attention kernel holds 2 channels per lane)");
-    if (sam_attn_lds_floats(hd, std::max(G, ws)) * sizeof(float) > 65536)
-        return report("loco_sam_create: head width x grid too large for the attention kernel's LDS (64 KiB)");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return report("loco_sam_create: no such HIP device");
-    DeviceGuard dg(device);
-    loco_sam* t = new loco_sam();
-    t->cfg = c; t->device = device;
-    t->G = G; t->T = G * G; t->Tp = (t->T + 15) / 16 * 16; t->hd = hd;
-    t->nwx = (G + ws - 1) / ws; t->Tw = t->nwx * t->nwx * ws * ws; t->Twp = (t->Tw + 15) / 16 * 16;
-    t->ld = std::max(t->Tp, t->Twp);
-    const long D = c.width, F = c.mlp_dim, Co = c.out_channels, ps = c.patch_size;
-    t->frows = std::max(std::max(F, 9 * Co), 3 * ps * ps);
-    size_t total = 0;
-    struct Spec { std::string name; std::vector<int64_t> shape; size_t off; };
-    std::vector<Spec> specs;
-    auto add = [&](const std::string& n, std::vector<int64_t> s) {
-        size_t cnt = 1;
-        for (auto d : s) cnt *= (size_t)d;
-        specs.push_back({n, s, total});
-        total += (cnt + 63) / 64 * 64;
-        return specs.back().off;
+    auto refuse = [](const loco_sam_cfg& c) -> std::string {
+        if (c.image_size <= 0 || c.patch_size <= 0 || c.width <= 0 || c.depth <= 0 || c.heads <= 0 || c.mlp_dim <= 0 ||
+            c.window_size <= 0 || c.out_channels <= 0)
+            return "image_size, patch_size, width, depth, heads, mlp_dim, window_size and out_channels must be positive";
+        if (c.image_size % c.patch_size) return "image_size is not a multiple of patch_size";
+        if (c.width % c.heads) return "width is not a multiple of heads";
+        if (c.num_global < 0 || c.num_global > LOCO_SAM_MAX_GLOBAL) return "num_global outside [0, 16]";
+        for (int i = 0; i < c.num_global; ++i)
+            if (c.global_attn[i] < 0 || c.global_attn[i] >= c.depth) return "a global attention index is outside [0, depth)";
+        if (!(c.ln_eps > 0.f)) return "ln_eps must be positive";
+        const int G = c.image_size / c.patch_size, hd = c.width / c.heads;
+        if (hd > 128) return "head width > 128 (the attention kernel holds 2 channels per lane)";
+        if (sam_attn_lds_floats(hd, std::max(G, c.window_size)) * sizeof(float) > 65536)
+            return "head width x grid too large for the attention kernel's LDS (64 KiB)";
+        return "";
     };
-    // names of transformers' SamVisionEncoder, without a `vision_encoder.` prefix
-    const size_t o_pw = add("patch_embed.projection.weight", {D, 3, ps, ps});
-    const size_t o_pb = add("patch_embed.projection.bias", {D});
-    const size_t o_pos = add("pos_embed", {1, G, G, D});
-    std::vector<bool> global(c.depth, false);
-    for (int i = 0; i < c.num_global; ++i) global[c.global_attn[i]] = true;
-    struct LOff { size_t v[14]; };
-    std::vector<LOff> loff(c.depth);
-    for (int l = 0; l < c.depth; ++l) {
-        const std::string p = "layers." + std::to_string(l) + ".";
-        const long rel = 2 * (global[l] ? G : ws) - 1;       // transformers would interpolate another length: refused by the shape
-        size_t* v = loff[l].v;
-        v[0] = add(p + "layer_norm1.weight", {D});
-        v[1] = add(p + "layer_norm1.bias", {D});
-        v[2] = add(p + "attn.qkv.weight", {3 * D, D});
-        v[3] = add(p + "attn.qkv.bias", {3 * D});
-        v[4] = add(p + "attn.rel_pos_h", {rel, hd});
-        v[5] = add(p + "attn.rel_pos_w", {rel, hd});
-        v[6] = add(p + "attn.proj.weight", {D, D});
-        v[7] = add(p + "attn.proj.bias", {D});
-        v[8] = add(p + "layer_norm2.weight", {D});
-        v[9] = add(p + "layer_norm2.bias", {D});
-        v[10] = add(p + "mlp.lin1.weight", {F, D});
-        v[11] = add(p + "mlp.lin1.bias", {F});
-        v[12] = add(p + "mlp.lin2.weight", {D, F});
-        v[13] = add(p + "mlp.lin2.bias", {D});
-    }
-    const size_t o_n1 = add("neck.conv1.weight", {Co, D, 1, 1});
-    const size_t o_g1 = add("neck.layer_norm1.weight", {Co});
-    const size_t o_b1 = add("neck.layer_norm1.bias", {Co});
-    const size_t o_n2 = add("neck.conv2.weight", {Co, Co, 3, 3});
-    const size_t o_g2 = add("neck.layer_norm2.weight", {Co});
-    const size_t o_b2 = add("neck.layer_norm2.bias", {Co});
-    const long Tp = t->Tp, Twp = t->Twp, ld = t->ld;
-    const size_t rel_floats = (size_t)c.heads * std::max((long)t->Tw * ws, (long)t->T * G);
-    struct Buf { float** p; size_t n; };
-    const Buf bufs[] = {{&t->params, total}, {&t->h, (size_t)(D * Tp)}, {&t->x, (size_t)(D * Tp)}, {&t->xw, (size_t)(D * Twp)},
-                        {&t->qkv, (size_t)(3 * D * ld)}, {&t->attn, (size_t)(D * ld)}, {&t->y, (size_t)(D * Twp)},
-                        {&t->f, (size_t)(t->frows * Tp)}, {&t->stats, (size_t)(2 * ld)}, {&t->relh, rel_floats}, {&t->relw, rel_floats},
-                        {&t->n1, (size_t)(Co * Tp)}, {&t->n2, (size_t)(Co * Tp)}};
-    bool ok = true;
-    // zeroed: the padding columns of every buffer hold finite values from the first call on
-    for (const Buf& b : bufs) ok = ok && hipMalloc(b.p, b.n * sizeof(float)) == hipSuccess && hipMemset(*b.p, 0, b.n * sizeof(float)) == hipSuccess;
-    if (!ok) {
-        free_sam(t);
-        delete t;
-        return report("loco_sam_create: hipMalloc failed");
-    }
-    for (const Spec& s : specs) t->table.push_back({s.name, s.shape, t->params + s.off, false});
-    float* P = t->params;
-    t->patch_w = P + o_pw; t->patch_b = P + o_pb; t->pos = P + o_pos;
-    t->neck_w1 = P + o_n1; t->neck_g1 = P + o_g1; t->neck_b1 = P + o_b1;
-    t->neck_w2 = P + o_n2; t->neck_g2 = P + o_g2; t->neck_b2 = P + o_b2;
-    for (int l = 0; l < c.depth; ++l) {
-        const size_t* v = loff[l].v;
-        t->layer.push_back({P + v[0], P + v[1], P + v[2], P + v[3], P + v[4], P + v[5], P + v[6], P + v[7], P + v[8], P + v[9],
-                            P + v[10], P + v[11], P + v[12], P + v[13], (bool)global[l]});
-    }
-    *out = t;
-    return 0;
+    return encoder_create<loco_sam>("loco_sam_create", g_sam_create_err, cfg, device, out, refuse, [&](loco_sam& t) {
+        const loco_sam_cfg& c = t.cfg = *cfg;
+        const int G = c.image_size / c.patch_size, hd = c.width / c.heads, ws = c.window_size;
+        t.G = G; t.T = G * G; t.Tp = (t.T + 15) / 16 * 16; t.hd = hd;
+        t.nwx = (G + ws - 1) / ws; t.Tw = t.nwx * t.nwx * ws * ws; t.Twp = (t.Tw + 15) / 16 * 16;
+        t.ld = std::max(t.Tp, t.Twp);
+        const long D = c.width, F = c.mlp_dim, Co = c.out_channels, ps = c.patch_size;
+        t.frows = std::max(std::max(F, 9 * Co), 3 * ps * ps);
+        // names of transformers' SamVisionEncoder, without a `vision_encoder.` prefix
+        ParamTable& pt = t.table;
+        pt.add("patch_embed.projection.weight", {D, 3, ps, ps}, &t.patch_w);
+        pt.add("patch_embed.projection.bias", {D}, &t.patch_b);
+        pt.add("pos_embed", {1, G, G, D}, &t.pos);
+        t.layer.resize(c.depth);
+        for (int i = 0; i < c.num_global; ++i) t.layer[c.global_attn[i]].global = true;
+        for (int l = 0; l < c.depth; ++l) {
+            const std::string p = "layers." + std::to_string(l) + ".";
+            SamLayer& ly = t.layer[l];
+            const long rel = 2 * (ly.global ? G : ws) - 1;       // transformers would interpolate another length: refused by the shape
+            pt.add(p + "layer_norm1.weight", {D}, &ly.ln1_g);
+            pt.add(p + "layer_norm1.bias", {D}, &ly.ln1_b);
+            pt.add(p + "attn.qkv.weight", {3 * D, D}, &ly.wqkv);
+            pt.add(p + "attn.qkv.bias", {3 * D}, &ly.bqkv);
+            pt.add(p + "attn.rel_pos_h", {rel, hd}, &ly.rel_h);
+            pt.add(p + "attn.rel_pos_w", {rel, hd}, &ly.rel_w);
+            pt.add(p + "attn.proj.weight", {D, D}, &ly.wo);
+            pt.add(p + "attn.proj.bias", {D}, &ly.bo);
+            pt.add(p + "layer_norm2.weight", {D}, &ly.ln2_g);
+            pt.add(p + "layer_norm2.bias", {D}, &ly.ln2_b);
+            pt.add(p + "mlp.lin1.weight", {F, D}, &ly.w1);
+            pt.add(p + "mlp.lin1.bias", {F}, &ly.b1);
+            pt.add(p + "mlp.lin2.weight", {D, F}, &ly.w2);
+            pt.add(p + "mlp.lin2.bias", {D}, &ly.b2);
+        }
+        pt.add("neck.conv1.weight", {Co, D, 1, 1}, &t.neck_w1);
+        pt.add("neck.layer_norm1.weight", {Co}, &t.neck_g1);
+        pt.add("neck.layer_norm1.bias", {Co}, &t.neck_b1);
+        pt.add("neck.conv2.weight", {Co, Co, 3, 3}, &t.neck_w2);
+        pt.add("neck.layer_norm2.weight", {Co}, &t.neck_g2);
+        pt.add("neck.layer_norm2.bias", {Co}, &t.neck_b2);
+        const long Tp = t.Tp, Twp = t.Twp, ld = t.ld;
+        const size_t rel_floats = (size_t)c.heads * std::max((long)t.Tw * ws, (long)t.T * G);
+        using B = EncoderBase;
+        // zeroed: the padding columns of every buffer hold finite values from the first call on
+        return t.alloc({B::buf(&t.h, D * Tp, true), B::buf(&t.x, D * Tp, true), B::buf(&t.xw, D * Twp, true), B::buf(&t.qkv, 3 * D * ld, true),
+                        B::buf(&t.attn, D * ld, true), B::buf(&t.y, D * Twp, true), B::buf(&t.f, t.frows * Tp, true),
+                        B::buf(&t.stats, 2 * ld, true), B::buf(&t.relh, rel_floats, true), B::buf(&t.relw, rel_floats, true),
+                        B::buf(&t.n1, Co * Tp, true), B::buf(&t.n2, Co * Tp, true)});
+    });
 }
 
 int loco_sam_load_param(loco_sam* t, const char* name, const float* host, const int64_t* shape, int32_t ndim) {
-    if (!t) return -1;
-    if (!name || !host || (ndim > 0 && !shape) || ndim < 0) return t->fail("loco_sam_load_param: null argument");
-    for (TextParam& p : t->table) {
-        if (p.name != name) continue;
-        if ((size_t)ndim != p.shape.size() || !std::equal(p.shape.begin(), p.shape.end(), shape)) {
-            std::string m = "loco_sam_load_param: " + p.name + " has shape [";
-            for (size_t i = 0; i < p.shape.size(); ++i) m += (i ? ", " : "") + std::to_string(p.shape[i]);
-            return t->fail(m + "], got another");
-        }
-        size_t cnt = 1;
-        for (auto d : p.shape) cnt *= (size_t)d;
-        DeviceGuard dg(t->device);
-        if (hipMemcpy(p.dst, host, cnt * sizeof(float), hipMemcpyDefault) != hipSuccess)
-            return t->fail("loco_sam_load_param: copy of " + p.name + " failed");
-        p.loaded = true;
-        return 0;
-    }
-    return t->fail(std::string("loco_sam_load_param: unknown parameter ") + name);
+    return t ? t->table.load(name, host, shape, ndim, t->device, "loco_sam_load_param", t->err) : -1;
 }
 
-int loco_sam_params_missing(loco_sam* t) {
-    if (!t) return -1;
-    int miss = 0;
-    for (const TextParam& p : t->table) {
-        if (!p.loaded) {
-            if (!miss) t->err = "missing parameter " + p.name;
-            ++miss;
-        }
-    }
-    return miss;
-}
+int loco_sam_params_missing(loco_sam* t) { return t ? t->table.missing(t->err) : -1; }
 
 int loco_sam_encode(loco_sam* t, const float* pixel_values, float* out_dev, void* stream) {
     if (!t) return -1;
     if (!pixel_values || !out_dev) return t->fail("loco_sam_encode: null pixel_values or out");
-    if (loco_sam_params_missing(t)) return -1;
+    if (t->table.missing(t->err)) return -1;
     DeviceGuard dg(t->device);
     hipStream_t st = (hipStream_t)stream;
     const loco_sam_cfg& c = t->cfg;
@@ -457,7 +367,7 @@ int loco_sam_encode(loco_sam* t, const float* pixel_values, float* out_dev, void
     }
     {
         SamTimer tm(t, st, SAM_CAT_GEMM);
-        launch_gemm_fixed(text_linear(t->patch_w, t->patch_b, t->f, t->h, nullptr, D, PK, Tp), GEMM_ACT_NONE, st);
+        launch_gemm_fixed(enc_linear(t->patch_w, t->patch_b, t->f, t->h, nullptr, D, PK, Tp), GEMM_ACT_NONE, st);
     }
     {
         SamTimer tm(t, st, SAM_CAT_OTHER);
@@ -476,7 +386,7 @@ int loco_sam_encode(loco_sam* t, const float* pixel_values, float* out_dev, void
         }
         {
             SamTimer tm(t, st, SAM_CAT_GEMM);
-            launch_gemm_fixed(text_linear(ly.wqkv, ly.bqkv, xin, t->qkv, nullptr, 3 * D, D, ldl), GEMM_ACT_NONE, st);
+            launch_gemm_fixed(enc_linear(ly.wqkv, ly.bqkv, xin, t->qkv, nullptr, 3 * D, D, ldl), GEMM_ACT_NONE, st);
         }
         {
             SamTimer tm(t, st, acat);
@@ -488,11 +398,11 @@ int loco_sam_encode(loco_sam* t, const float* pixel_values, float* out_dev, void
         }
         if (gl) {
             SamTimer tm(t, st, SAM_CAT_GEMM);
-            launch_gemm_fixed(text_linear(ly.wo, ly.bo, t->attn, t->h, t->h, D, D, Tp), GEMM_ACT_NONE, st);
+            launch_gemm_fixed(enc_linear(ly.wo, ly.bo, t->attn, t->h, t->h, D, D, Tp), GEMM_ACT_NONE, st);
         } else {
             {
                 SamTimer tm(t, st, SAM_CAT_GEMM);
-                launch_gemm_fixed(text_linear(ly.wo, ly.bo, t->attn, t->y, nullptr, D, D, Twp), GEMM_ACT_NONE, st);
+                launch_gemm_fixed(enc_linear(ly.wo, ly.bo, t->attn, t->y, nullptr, D, D, Twp), GEMM_ACT_NONE, st);
             }
             SamTimer tm(t, st, SAM_CAT_OTHER);
             hipLaunchKernelGGL(sam_unpartition_kernel, dim3(blocks256((long)D * T)), dim3(256), 0, st, t->y, D, G, T, Tp, ws, t->nwx, Twp, t->h);
@@ -502,13 +412,13 @@ int loco_sam_encode(loco_sam* t, const float* pixel_values, float* out_dev, void
             launch_ln_fwd(t->h, 0, 1, D, Tp, ly.ln2_g, ly.ln2_b, c.ln_eps, t->x, 0, t->stats, 0, st);
         }
         SamTimer tm(t, st, SAM_CAT_GEMM);
-        launch_gemm_fixed(text_linear(ly.w1, ly.b1, t->x, t->f, nullptr, F, D, Tp), GEMM_ACT_GELU, st);
-        launch_gemm_fixed(text_linear(ly.w2, ly.b2, t->f, t->h, t->h, D, F, Tp), GEMM_ACT_NONE, st);
+        launch_gemm_fixed(enc_linear(ly.w1, ly.b1, t->x, t->f, nullptr, F, D, Tp), GEMM_ACT_GELU, st);
+        launch_gemm_fixed(enc_linear(ly.w2, ly.b2, t->f, t->h, t->h, D, F, Tp), GEMM_ACT_NONE, st);
     }
     // neck: 1x1 conv -> LayerNorm over channels -> 3x3 conv (im2col) -> LayerNorm, eps 1e-6 as SamLayerNorm's default
     {
         SamTimer tm(t, st, SAM_CAT_GEMM);
-        launch_gemm_fixed(text_linear(t->neck_w1, nullptr, t->h, t->n1, nullptr, Co, D, Tp), GEMM_ACT_NONE, st);
+        launch_gemm_fixed(enc_linear(t->neck_w1, nullptr, t->h, t->n1, nullptr, Co, D, Tp), GEMM_ACT_NONE, st);
     }
     {
         SamTimer tm(t, st, SAM_CAT_OTHER);
@@ -517,7 +427,7 @@ int loco_sam_encode(loco_sam* t, const float* pixel_values, float* out_dev, void
     }
     {
         SamTimer tm(t, st, SAM_CAT_GEMM);
-        launch_gemm_fixed(text_linear(t->neck_w2, nullptr, t->f, t->n1, nullptr, Co, 9 * Co, Tp), GEMM_ACT_NONE, st);
+        launch_gemm_fixed(enc_linear(t->neck_w2, nullptr, t->f, t->n1, nullptr, Co, 9 * Co, Tp), GEMM_ACT_NONE, st);
     }
     {
         SamTimer tm(t, st, SAM_CAT_OTHER);
@@ -550,13 +460,6 @@ int loco_sam_profile_read(loco_sam* t, float* ms4) {
 
 const char* loco_sam_last_error(loco_sam* t) { return t ? t->err.c_str() : g_sam_create_err.c_str(); }
 
-void loco_sam_destroy(loco_sam* t) {
-    if (!t) return;
-    {
-        DeviceGuard dg(t->device);
-        free_sam(t);
-    }
-    delete t;
-}
+void loco_sam_destroy(loco_sam* t) { delete t; }
 
 }  // extern "C"

@@ -1,79 +1,41 @@
-// The handle behind include/loco_hip.h's loco_text, shared by the two text encoders: CLIP (textenc.hip, loco_text_create)
-// and the T5 encoder of DeepFloyd IF (t5enc.hip, loco_t5_create).  loco_text_load_param / _params_missing / _last_error /
-// _destroy (textenc.hip) work on the parameter table and the allocations alone, so they serve both kinds; loco_text_encode
-// and loco_text_encode_masked look at `kind`.
+// The handle behind include/loco_hip.h's loco_text: the base of the two text encoders, CLIP (textenc.hip,
+// loco_text_create) and the T5 encoder of DeepFloyd IF (t5enc.hip, loco_t5_create), and the kernels both launch.  The six
+// loco_text_* functions (textenc.hip) work on this base alone: what differs between the encoders is behind its virtuals.
 #pragma once
-#include "kernels.h"
-#include "../../include/loco_hip.h"
+#include "encoder_common.h"
 
-#include <cstring>
-#include <string>
-#include <vector>
-
-struct TextParam {
-    std::string name;
-    std::vector<int64_t> shape;
-    float* dst;
-    bool loaded;
-};
-struct TextLayer { float *ln1_g, *ln1_b, *wqkv, *bqkv, *wo, *bo, *ln2_g, *ln2_b, *w1, *b1, *w2, *b2; };
-// T5 block: RMS-norm weights, q | k | v packed [3 inner][D], o [D][inner], wi_0 | wi_1 packed [2 F][D], wo [D][F]
-struct T5Layer { float *ln1, *wqkv, *wo, *ln2, *wi, *wff; };
-
-enum TextKind : int { TEXT_KIND_CLIP = 0, TEXT_KIND_T5 = 1 };
-
-struct loco_text {
-    int kind = TEXT_KIND_CLIP;
-    loco_text_cfg cfg;
-    int device = 0, max_prompts = 0, L = 0, D = 0, hd = 0, Tmax = 0;
-    std::string err;
-    float* params = nullptr;              // one allocation for every parameter
-    float *tok = nullptr, *pos = nullptr, *lnf_g = nullptr, *lnf_b = nullptr;
-    std::vector<TextLayer> layer;
-    std::vector<TextParam> table;
+struct loco_text : loco::EncoderBase {
+    int max_prompts = 0, L = 0, D = 0, hd = 0, Tmax = 0;
+    float *tok = nullptr, *lnf_g = nullptr;
     // workspace [.][Tmax]
-    float *h = nullptr, *x = nullptr, *qkv = nullptr, *attn = nullptr, *f = nullptr, *stats = nullptr;
+    float *h = nullptr, *x = nullptr, *qkv = nullptr, *attn = nullptr, *f = nullptr;
     int* ids = nullptr;
     std::vector<int> ids_host;
-    // ---- T5 only (t5enc.hip)
-    loco_t5_cfg t5;
-    int inner = 0;                        // heads * d_kv
-    float* relw = nullptr;                // relative_attention_bias.weight [buckets][heads] (inside params)
-    float* bias_tab = nullptr;            // [heads][2 L - 1]: the bias of key offset k - q + L - 1, built when relw is loaded
-    std::vector<int> bucket;              // [2 L - 1] bucket of every offset
-    std::vector<T5Layer> t5layer;
-    int* lens = nullptr;                  // device [max_prompts]
-    std::vector<int> lens_host;
-    int fail(const std::string& m) { err = m; return -1; }
+
+    // lens: host [n] or NULL = every prompt is L long
+    virtual int encode(const int32_t* ids_dev, const int32_t* lens, int32_t n, float* out_dev, hipStream_t st) = 0;
+    virtual int encode_masked(const int32_t* ids_dev, const int32_t* lens, int32_t n, float* out_dev, hipStream_t st) {
+        return encode(ids_dev, lens, n, out_dev, st);
+    }
+    virtual int param_loaded(const float* /*dst*/) { return 0; }      // after loco_text_load_param has copied a parameter to dst
 };
 
 namespace loco {
 
-struct TextDeviceGuard {       // the caller's current device is restored on every return
-    int prev = 0;
-    explicit TextDeviceGuard(int d) { (void)hipGetDevice(&prev); (void)hipSetDevice(d); }
-    ~TextDeviceGuard() { (void)hipSetDevice(prev); }
-};
+extern thread_local std::string g_text_create_err;        // what loco_text_last_error(NULL) returns (textenc.hip)
 
-// Y [M][Tp] = W [M][K] X [K][Tp] (+ bias per row) (+ R), channel-major activations
-inline GemmArgs text_linear(const float* W, const float* bias, const float* X, float* Y, const float* R, int M, int K, int Tp) {
-    GemmArgs g; std::memset(&g, 0, sizeof(g));
-    g.A = W; g.sam = K; g.sak = 1;
-    g.Bm = X; g.sbk = Tp; g.sbn = 1;
-    g.C = Y; g.scm = Tp; g.scn = 1;
-    g.bias = bias; g.R = R;
-    g.M = M; g.N = Tp; g.K = K; g.batch = 1; g.alpha = 1.f;
-    return g;
-}
-
-// out[col][c] = x[c][col] for the T real columns of x [D][Tp] (textenc.hip)
+// the head of every encode: the arguments, n against max_prompts, the parameters complete
+int text_check_call(loco_text* t, const int32_t* ids_dev, int32_t n, const float* out_dev);
+// t->ids = the T = n * L ids behind ids_dev, each checked against [0, vocab) on the host: the one host synchronisation of a call
+int stage_ids(loco_text* t, const int32_t* ids_dev, int T, int L, int vocab, hipStream_t st);
+// h[c][col] = tok[ids[col]][c] (+ pos[col % L][c] unless pos is NULL) for col < T, 0 for the padding columns T <= col < Tp
+void launch_text_embed(const int* ids, int T, int Tp, int L, int D, const float* tok, const float* pos, float* h, hipStream_t st);
+// Self-attention of one (prompt, head) per workgroup over qkv [3 inner][ld] = q | k | v channel rows, out [inner][ld].
+// causal_scaled: keys j <= i, score q_i . k_j * scale (CLIP); else keys j < lens[p], score q_i . k_j + bias_tab[h][j - i + L - 1] (T5)
+size_t prompt_attn_lds_bytes(int hd, int L);
+void launch_prompt_attn(bool causal_scaled, const float* qkv, long ld, int n, int heads, int L, int inner, int hd, float scale,
+                        const float* bias_tab, const int* lens, float* out, hipStream_t st);
+// out[col][c] = x[c][col] for the T real columns of x [D][Tp]
 void launch_text_transpose(const float* x, int Tp, int T, int D, float* out, hipStream_t st);
-
-void text_set_create_error(const std::string& m);         // what loco_text_last_error(NULL) returns (textenc.hip)
-
-// t5enc.hip
-int t5_encode(loco_text* t, const int32_t* ids_dev, const int32_t* lens, int32_t n, float* out_dev, hipStream_t st);
-int t5_param_loaded(loco_text* t, const float* dst);      // hook of loco_text_load_param: builds the bias table
-void t5_free(loco_text* t);
 
 }  // namespace loco

@@ -686,45 +686,41 @@ class LocoEngine:
         return dst[:got]
 
 
-class LocoTextEngine:
-    """A text encoder (= loco_text, include/loco_hip.h): parameters on the device, one batched encode per call.
-    `cfg` is a ``text_encoder.TextConfig`` (CLIP, loco_text_create) or a ``text_encoder.T5Config`` (the T5 encoder of
-    DeepFloyd IF, loco_t5_create); token ids in, last_hidden_state [n, positions, width] out, exact fp32."""
+class _EncoderEngine:
+    """What the encoder handles of include/loco_hip.h share on this side: `_prefix` is the symbol prefix of the handle's
+    functions (``{prefix}_load_param``, ``_params_missing``, ``_last_error``, ``_destroy``), `_label` names the encoder in
+    messages.  A subclass creates the handle with ``_create``."""
+    _prefix = ""
+    _label = ""
 
-    def __init__(self, cfg, max_prompts: int = 8, device: Optional[torch.device] = None):
+    def _open(self, device: Optional[torch.device]):
         self.lib = load_library()
         if not torch.cuda.is_available() or self.lib.loco_device_count() < 1:
-            raise RuntimeError("loco_hip: no HIP device visible; the text encoder has no CPU fallback")
+            raise RuntimeError(f"loco_hip: no HIP device visible; the {self._label} has no CPU fallback")
         self.device = torch.device(device if device is not None else "cuda:0")
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
-        self.cfg, self.max_prompts = cfg, int(max_prompts)
-        self.is_t5 = hasattr(cfg, "d_kv")
         self._t = C.c_void_p()
-        if self.is_t5:
-            if cfg.act != "gated-gelu":
-                raise ValueError(f"feed_forward_proj {cfg.act!r}: the T5 encoder builds gated-gelu only")
-            c = LocoT5Cfg(vocab=cfg.vocab, d_model=cfg.d_model, d_kv=cfg.d_kv, heads=cfg.heads, d_ff=cfg.d_ff, layers=cfg.layers,
-                          positions=cfg.positions, buckets=cfg.buckets, max_distance=cfg.max_distance, act=0, ln_eps=cfg.ln_eps)
-            rc, what = self.lib.loco_t5_create(C.byref(c), self.device.index, self.max_prompts, C.byref(self._t)), "loco_t5_create"
-        else:
-            c = LocoTextCfg(vocab=cfg.vocab, width=cfg.width, layers=cfg.layers, heads=cfg.heads, ffn=cfg.ffn,
-                            positions=cfg.positions, act={"quick_gelu": 0, "gelu": 1}[cfg.act], ln_eps=cfg.ln_eps)
-            rc, what = self.lib.loco_text_create(C.byref(c), self.device.index, self.max_prompts, C.byref(self._t)), "loco_text_create"
+
+    def _fn(self, name):
+        return getattr(self.lib, f"{self._prefix}_{name}")
+
+    def _create(self, what, c_cfg, *args):
+        rc = getattr(self.lib, what)(C.byref(c_cfg), self.device.index, *args, C.byref(self._t))
         if rc != 0:
-            raise RuntimeError(f"{what} failed ({rc}): {self.lib.loco_text_last_error(None).decode()}")
+            raise RuntimeError(f"{what} failed ({rc}): {self._fn('last_error')(None).decode()}")
 
     def __del__(self):
         try:
             if getattr(self, "_t", None):
-                self.lib.loco_text_destroy(self._t)
+                self._fn("destroy")(self._t)
                 self._t = None
         except Exception:
             pass
 
     def _check(self, rc, what):
         if rc != 0:
-            raise RuntimeError(f"{what} failed ({rc}): {self.lib.loco_text_last_error(self._t).decode()}")
+            raise RuntimeError(f"{what} failed ({rc}): {self._fn('last_error')(self._t).decode()}")
 
     def load_params(self, sd: Dict[str, "np.ndarray | torch.Tensor"]):
         """Loads the entries of `sd` (a part of the state_dict: a shard, a layer) without asking for completeness."""
@@ -735,19 +731,42 @@ class LocoTextEngine:
             if not t.is_cuda:
                 t = t.cpu()
             shape = (C.c_int64 * max(t.dim(), 1))(*t.shape)
-            self._check(self.lib.loco_text_load_param(self._t, name.encode(), C.c_void_p(t.data_ptr()), shape, t.dim()),
-                        f"loco_text_load_param({name})")
+            self._check(self._fn("load_param")(self._t, name.encode(), C.c_void_p(t.data_ptr()), shape, t.dim()),
+                        f"{self._prefix}_load_param({name})")
 
     def check_complete(self):
-        missing = self.lib.loco_text_params_missing(self._t)
+        missing = self._fn("params_missing")(self._t)
         if missing:
-            raise RuntimeError(f"text encoder: {missing} parameters missing ({self.lib.loco_text_last_error(self._t).decode()})")
+            raise RuntimeError(f"{self._label}: {missing} parameters missing ({self._fn('last_error')(self._t).decode()})")
 
     def load_state_dict(self, sd: Dict[str, "np.ndarray | torch.Tensor"]):
-        """Names of CLIPTextTransformer without a prefix (text_encoder.normalize_text_state_dict produces them), or of
-        T5EncoderModel (text_encoder.normalize_t5_state_dict)."""
+        """The state_dict of the encoder under the names of its *_load_param (include/loco_hip.h), all of it."""
         self.load_params(sd)
         self.check_complete()
+
+
+class LocoTextEngine(_EncoderEngine):
+    """A text encoder (= loco_text, include/loco_hip.h): parameters on the device, one batched encode per call.
+    `cfg` is a ``text_encoder.TextConfig`` (CLIP, loco_text_create) or a ``text_encoder.T5Config`` (the T5 encoder of
+    DeepFloyd IF, loco_t5_create); token ids in, last_hidden_state [n, positions, width] out, exact fp32.
+    ``load_state_dict`` takes the names of CLIPTextTransformer without a prefix (text_encoder.normalize_text_state_dict
+    produces them), or of T5EncoderModel (text_encoder.normalize_t5_state_dict)."""
+    _prefix, _label = "loco_text", "text encoder"
+
+    def __init__(self, cfg, max_prompts: int = 8, device: Optional[torch.device] = None):
+        self._open(device)
+        self.cfg, self.max_prompts = cfg, int(max_prompts)
+        self.is_t5 = hasattr(cfg, "d_kv")
+        if self.is_t5:
+            if cfg.act != "gated-gelu":
+                raise ValueError(f"feed_forward_proj {cfg.act!r}: the T5 encoder builds gated-gelu only")
+            c = LocoT5Cfg(vocab=cfg.vocab, d_model=cfg.d_model, d_kv=cfg.d_kv, heads=cfg.heads, d_ff=cfg.d_ff, layers=cfg.layers,
+                          positions=cfg.positions, buckets=cfg.buckets, max_distance=cfg.max_distance, act=0, ln_eps=cfg.ln_eps)
+            self._create("loco_t5_create", c, self.max_prompts)
+        else:
+            c = LocoTextCfg(vocab=cfg.vocab, width=cfg.width, layers=cfg.layers, heads=cfg.heads, ffn=cfg.ffn,
+                            positions=cfg.positions, act={"quick_gelu": 0, "gelu": 1}[cfg.act], ln_eps=cfg.ln_eps)
+            self._create("loco_text_create", c, self.max_prompts)
 
     @property
     def width(self) -> int:
@@ -781,18 +800,15 @@ class LocoTextEngine:
         return out
 
 
-class LocoSamEngine:
+class LocoSamEngine(_EncoderEngine):
     """The image encoder of Segment Anything (= loco_sam, include/loco_hip.h): parameters and the workspace of one image on
     the device.  `cfg` is a ``mask_segmentation.SamVisionConfig``; preprocessed pixel_values [3, S, S] in, image embeddings
-    [1, C_out, G, G] out, exact fp32."""
+    [1, C_out, G, G] out, exact fp32.  ``load_state_dict`` takes the names of SamVisionEncoder without a prefix
+    (mask_segmentation.vision_state_dict produces them)."""
+    _prefix, _label = "loco_sam", "SAM image encoder"
 
     def __init__(self, cfg, device: Optional[torch.device] = None):
-        self.lib = load_library()
-        if not torch.cuda.is_available() or self.lib.loco_device_count() < 1:
-            raise RuntimeError("loco_hip: no HIP device visible; the SAM image encoder has no CPU fallback")
-        self.device = torch.device(device if device is not None else "cuda:0")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._open(device)
         self.cfg = cfg
         glob = [int(i) for i in cfg.global_attn_indexes]
         if len(glob) > SAM_MAX_GLOBAL:
@@ -803,44 +819,7 @@ class LocoSamEngine:
         for i, g in enumerate(glob):
             c.global_attn[i] = g
         self.grid = cfg.image_size // cfg.patch_size
-        self._t = C.c_void_p()
-        rc = self.lib.loco_sam_create(C.byref(c), self.device.index, C.byref(self._t))
-        if rc != 0:
-            raise RuntimeError(f"loco_sam_create failed ({rc}): {self.lib.loco_sam_last_error(None).decode()}")
-
-    def __del__(self):
-        try:
-            if getattr(self, "_t", None):
-                self.lib.loco_sam_destroy(self._t)
-                self._t = None
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise RuntimeError(f"{what} failed ({rc}): {self.lib.loco_sam_last_error(self._t).decode()}")
-
-    def load_params(self, sd: Dict[str, "np.ndarray | torch.Tensor"]):
-        """Loads the entries of `sd` (a part of the state_dict) without asking for completeness."""
-        if any(isinstance(v, torch.Tensor) and v.is_cuda for v in sd.values()):
-            torch.cuda.synchronize()
-        for name, v in sd.items():
-            t = torch.as_tensor(np.asarray(v) if not isinstance(v, torch.Tensor) else v).detach().to(torch.float32).contiguous()
-            if not t.is_cuda:
-                t = t.cpu()
-            shape = (C.c_int64 * max(t.dim(), 1))(*t.shape)
-            self._check(self.lib.loco_sam_load_param(self._t, name.encode(), C.c_void_p(t.data_ptr()), shape, t.dim()),
-                        f"loco_sam_load_param({name})")
-
-    def check_complete(self):
-        missing = self.lib.loco_sam_params_missing(self._t)
-        if missing:
-            raise RuntimeError(f"SAM image encoder: {missing} parameters missing ({self.lib.loco_sam_last_error(self._t).decode()})")
-
-    def load_state_dict(self, sd: Dict[str, "np.ndarray | torch.Tensor"]):
-        """Names of SamVisionEncoder without a prefix (mask_segmentation.vision_state_dict produces them)."""
-        self.load_params(sd)
-        self.check_complete()
+        self._create("loco_sam_create", c)
 
     def encode(self, pixel_values: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """pixel_values [3, S, S] or [1, 3, S, S] (fp32, host or device) -> [1, C_out, G, G] fp32 on the device."""

@@ -211,6 +211,35 @@ def test_t5_at_size_vs_float64_restatement(which):
           "(the restatement; the engine's own allocations are outside it)")
 
 
+def test_t5_heads_wider_than_a_wave_vs_restatement():
+    """d_kv = 80 > 64: a lane of the attention kernel owns a second output channel (c = lane + 64), inner = 160 != d_model;
+    L = 70 keeps the second key slot live for the full-length prompt and leaves the last round of the 4 waves partly empty;
+    lens 70 / 1 / 37 are a full, a one-key and a first-slot-only prompt.  Bound: the file's rel-L2 <= 1e-4 against the
+    float64 restatement."""
+    from loco_edit_amd.hip import LocoTextEngine
+    cfg = te.T5Config(d_model=48, d_kv=80, heads=2, d_ff=64, layers=1, positions=70)
+    assert cfg.inner != cfg.d_model
+    sd = SeededT5(cfg, 5)
+    eng = LocoTextEngine(cfg, max_prompts=3, device=torch.device(DEV))
+    eng.load_state_dict({k: sd[k] for k in sd.keys()})
+    ids = torch.randint(2, cfg.vocab, (3, cfg.positions), generator=torch.Generator().manual_seed(11))
+    lens = torch.tensor([70, 1, 37])
+    for p, ln in enumerate(lens.tolist()):
+        ids[p, ln - 1] = 1
+        ids[p, ln:] = 0
+    out = eng.encode_ids(ids, lens=lens)
+    with torch.no_grad():
+        ref = restated_t5(sd, cfg, ids.to(DEV), lens, dtype=torch.float64)
+        r32 = restated_t5(sd, cfg, ids.to(DEV), lens, dtype=torch.float32)
+    errs, eref = rel_rows(out, ref), rel_rows(r32, ref)
+    for p in range(3):
+        print(f"d_kv 80 prompt {p} (len {int(lens[p])}): HIP vs float64 restatement {errs[p]:.2e}   e_ref (torch fp32 restatement vs "
+              f"float64) {eref[p]:.2e}   ratio {errs[p] / eref[p]:.2f}")
+    assert max(errs) <= 1e-4
+    for i in range(3):
+        assert torch.equal(eng.encode_ids(ids[i:i + 1], lens=lens[i:i + 1])[0], out[i])
+
+
 # ---------------------------------------------------------------------------------------------------------- end to end
 def _write_pipeline(root, name="tiny_a"):
     """A diffusers-layout IF text encoder from a fixture: text_encoder/ (config.json + model.safetensors) + tokenizer/."""

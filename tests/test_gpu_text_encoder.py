@@ -141,6 +141,29 @@ def test_encoder_at_stable_diffusion_size_vs_restatement(which):
     assert max(errs) <= 1e-4
 
 
+def test_heads_wider_than_a_wave_vs_restatement():
+    """hd = 80 > 64: a lane of the attention kernel owns a second output channel (c = lane + 64); L = 70 keeps the second
+    key slot live (keys 64..69) and leaves the last round of the 4 waves partly empty (70 = 17 * 4 + 2).  3 prompts: T = 210
+    pads to Tp = 224.  Bound: the file's rel-L2 <= 1e-4 against the float64 restatement."""
+    from loco_edit_amd.hip import LocoTextEngine
+    cfg = te.TextConfig(vocab=50, width=160, layers=1, heads=2, ffn=64, positions=70)
+    sd = _synth_clip(cfg, 5)
+    eng = LocoTextEngine(cfg, max_prompts=3, device=torch.device(DEV))
+    eng.load_state_dict(sd)
+    ids = torch.randint(0, cfg.vocab, (3, cfg.positions), generator=torch.Generator().manual_seed(11))
+    out = eng.encode_ids(ids)
+    with torch.no_grad():
+        ref = restated_clip_text(sd, cfg, ids.to(DEV), dtype=torch.float64)
+        r32 = restated_clip_text(sd, cfg, ids.to(DEV), dtype=torch.float32)
+    errs, eref = rel_rows(out, ref), rel_rows(r32, ref)
+    for p in range(3):
+        print(f"hd 80 prompt {p}: HIP vs float64 restatement {errs[p]:.2e}   e_ref (torch fp32 restatement vs float64) {eref[p]:.2e}"
+              f"   ratio {errs[p] / eref[p]:.2f}")
+    assert max(errs) <= 1e-4
+    for i in range(3):
+        assert torch.equal(eng.encode_ids(ids[i:i + 1])[0], out[i])
+
+
 # ---------------------------------------------------------------------------------------------------------- end to end
 def _write_pipeline(root, seed=0):
     """A diffusers-layout text encoder of the tiny_ldm geometry (context 16 x 7): text_encoder/ + tokenizer/."""
