@@ -170,7 +170,13 @@ int  loco_pmp_vjp(loco_ctx* ctx, const float* U, int32_t k, float* A, void* stre
 /* Thin SVD re-orthonormalisation of the k x n block (replaces torch.linalg.svd
  * at edit.py:2482): on return A holds Vh (orthonormal rows, descending
  * singular value, sign: largest-|.| entry of each row positive), s[k] the
- * singular values of the input. k <= 64. */
+ * singular values of the input. k <= 64.
+ * Rows are found through the double-precision Gram A A^T, which resolves singular values down to about 1e-7 of
+ * the largest.  A row whose s_i >= 1e-6 s_0 is determined: unit norm, orthogonal to the others to fp32 rounding,
+ * the singular vector of the input.  Below that a row is either a unit vector orthogonal to every row before it
+ * (its direction is then not meaningful) or, when its eigenvalue is at the Gram's rounding floor (2^-47 of the
+ * largest: rank-deficient input, more probes than directions, A = 0), exactly zero with s_i = 0.  No row is ever
+ * longer than a unit vector and no output is non-finite for finite input. */
 int  loco_orthonormalize(loco_ctx* ctx, float* A, int32_t k, int64_t n, float* s, void* stream);
 /* Q = thin-QR orthonormal basis of the rows of A (replaces torch.linalg.qr at
  * edit.py:2436 on the transposed layout): A [k,n] in, orthonormal rows out,

@@ -1914,7 +1914,7 @@ int create_ctx(loco_ctx* c, const loco_unet_cfg* cfg, std::shared_ptr<const Prog
     if (dalloc(c, &c->eps_buf, MB * c->prog->n_out) || dalloc(c, &c->gx0, MB * c->prog->n_in) || dalloc(c, &c->ge, MB * c->prog->n_out))
         return -1;
     if (dalloc(c, &c->tmpA, (size_t)64 * c->prog->n_in)) return -1;
-    if (dalloc(c, &c->G, 64 * 64) || dalloc(c, &c->Q, 64 * 64) || dalloc(c, &c->W, 64)) return -1;
+    if (dalloc(c, &c->G, 64 * 64) || dalloc(c, &c->Q, 64 * 64) || dalloc(c, &c->W, SOLVER_W_GATE + 1)) return -1;
     {
         size_t nblk = ((size_t)c->prog->n_in + 255) / 256;
         if (dalloc(c, &c->gscratch, nblk * 64 * 64 + 4096)) return -1;
@@ -2236,8 +2236,17 @@ int loco_orthonormalize(loco_ctx* c, float* A, int32_t k, int64_t n, float* s, v
     launch_gram(A, k, n, c->G, c->gscratch, st);
     launch_jacobi_eig(c->G, k, c->W, c->Q, st);
     launch_rotate_rows(A, c->tmpA, k, n, c->Q, c->W, 0, st);
+    // The Gram squares the condition number: rows rotated by its eigenvectors are orthonormal to about
+    // k 2^-53 w_max / (s_i s_j), which on a graded spectrum is far from fp32 rounding.  The eigensolver raises
+    // W[SOLVER_W_GATE] for such a spectrum and the rows then take one Cholesky pass, in the order of descending singular
+    // value so that each row is corrected against the better determined ones only; a row with less than a quarter of
+    // its norm left after that has no direction of its own and is dropped (zero row, s = 0).  With the gate down these
+    // launches return at once and the last one only copies tmpA back: decided on the device, nothing is read back.
+    const double* gate = c->W + SOLVER_W_GATE;
+    launch_gram(c->tmpA, k, n, c->G, c->gscratch, st, gate);
+    launch_cholesky(c->G, k, st, 0.25, c->W, gate);
+    launch_trsm_rows(c->tmpA, A, k, n, c->G, st, gate);
     // singular values of the input = sqrt(eigenvalues of A A^T)
-    HIPCHK(c, hipMemcpyAsync(A, c->tmpA, (size_t)k * n * sizeof(float), hipMemcpyDeviceToDevice, st));
     launch_sign_fix(A, k, n, s, c->W, reinterpret_cast<float*>(c->red), st);
     HIPCHK(c, hipGetLastError());
     return 0;

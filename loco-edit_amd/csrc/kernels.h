@@ -393,21 +393,40 @@ void launch_lcm_step(const float* x, const float* eps, const float* noise, float
                      float s1mat, float satp, float s1matp, float c_skip, float c_out, hipStream_t st);
 
 // ---- solver --------------------------------------------------------------------
-// G[k][k] (double) = A A^T, A: [k][n] fp32
-void launch_gram(const float* A, int k, long n, double* G, double* scratch, hipStream_t st);
+// G[k][k] (double) = A A^T, A: [k][n] fp32.
+// `gate` (here and below): a device double or nullptr.  With a gate that holds 0 the launch leaves its output untouched
+// (launch_trsm_rows: copies Ain to Aout): a data-dependent pass decided on the device, so the sequence stays capturable.
+void launch_gram(const float* A, int k, long n, double* G, double* scratch, hipStream_t st, const double* gate = nullptr);
 // cross Gram C[k1][k2] (double) = A B^T
 void launch_cross_gram(const float* A, int k1, const float* B, int k2, long n, double* C, double* scratch,
-                       hipStream_t st);
+                       hipStream_t st, const double* gate = nullptr);
 // symmetric eigen-decomposition of G (k<=64, double, cyclic Jacobi in one workgroup):
-// evals descending in w[k], eigenvectors as rows of Q[k][k]
+// evals descending in w[k], eigenvectors as rows of Q[k][k]; w[SOLVER_W_GATE] = 1 when the spectrum is graded enough
+// (w_min < SOLVER_REORTHO_RATIO * w_max) for the rotated rows to need one Cholesky re-orthonormalisation, else 0
+constexpr int SOLVER_W_GATE = 64;               // w has SOLVER_W_GATE + 1 doubles
+// An eigenvalue of the double Gram at or below SOLVER_W_FLOOR * w_max is rounding: the Gram's entries carry errors of
+// order 2^-53 w_max from their summation and the k-by-k Jacobi adds k of them, so for every k <= 64 a direction below
+// 64 * 2^-53 = 2^-47 of w_max counts as absent (s = 0, a zero row) and nothing divides by it.
+constexpr double SOLVER_W_FLOOR = 0x1p-47;
+// Orthonormality of rows rotated by the Gram's eigenvectors is off by about k 2^-53 w_max / (s_i s_j); at
+// w_min / w_max = 1e-7 that is 7e-8 for k = 64, the rounding of the fp32 rows themselves.  Below the ratio the
+// rows get one Cholesky pass (Gram, Cholesky, triangular solve), above it they are taken as they are.
+constexpr double SOLVER_REORTHO_RATIO = 1e-7;
 void launch_jacobi_eig(double* G, int k, double* w, double* Q, hipStream_t st);
-// A <- diag(scale) * Q * A   (k x n, in place, via temp copy), scale from w: mode 0: 1/sqrt(max(w,tiny)); mode 1: none
+// Aout = diag(scale) * Q * Ain   (k x n), scale from w: mode 0: 1/sqrt(w_i), 0 for w_i <= SOLVER_W_FLOOR * w[0]; mode 1: none
 void launch_rotate_rows(const float* Ain, float* Aout, int k, long n, const double* Q, const double* w,
                         int mode, hipStream_t st);
+// s_out[i] = sqrt(w_i), 0 for w_i <= SOLVER_W_FLOOR * w[0]
 void launch_sign_fix(float* A, int k, long n, float* s_out, const double* w, float* scratch, hipStream_t st);   // scratch: k * ceil(n/4096) floats
-// Cholesky factor of G (k x k double, lower) in one workgroup, then A <- L^{-1} A
-void launch_cholesky(double* G, int k, hipStream_t st);
-void launch_trsm_rows(const float* Ain, float* Aout, int k, long n, const double* L, hipStream_t st);
+// Cholesky factor of G (k x k double, lower) in one workgroup, then A <- L^{-1} A.
+// drop_below = 0: pivots are clamped to 1e-300 (CholeskyQR of independent rows).  drop_below > 0 (the Gram of rows that
+// are unit vectors up to rounding, or zero): a row whose pivot -- what is left of its squared norm after the rows
+// before it -- is below drop_below has no direction of its own: L[i][i] = 0, which launch_trsm_rows turns into a
+// zero row, its column of L is zero, and w[i] = 0; a kept row's w[i] is multiplied by G[i][i] (w may be nullptr).
+void launch_cholesky(double* G, int k, hipStream_t st, double drop_below = 0.0, double* w = nullptr,
+                     const double* gate = nullptr);
+void launch_trsm_rows(const float* Ain, float* Aout, int k, long n, const double* L, hipStream_t st,
+                      const double* gate = nullptr);
 void launch_convergence(const float* a, const float* b, long count, float atol, float rtol, float* out2,
                         double* scratch, hipStream_t st);
 // the same per row and up to each row's sign; scratch: k * 64 * 4 doubles

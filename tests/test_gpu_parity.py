@@ -420,6 +420,7 @@ def test_solver_vs_reference_golden(prec, engines, golden):
 
 
 def test_solver_algebra_kernels(engines):
+    # graded / rank-deficient spectra, odd row lengths and the other solver entry points: tests/test_gpu_solver_algebra.py
     eng = engines(TINY_DDPM)
     n = TINY_DDPM.n
     for k in (1, 5, 16, 64):
