@@ -1,6 +1,6 @@
 /* Diagnostics of libloco_hip -- NOT part of the drop-in boundary (include/loco_hip.h).
  *
- * These two entry points exist only in a library built with -DLOCO_DIAG (`make -C loco-edit_amd/csrc diag` ->
+ * These entry points exist only in a library built with -DLOCO_DIAG (`make -C loco-edit_amd/csrc diag` ->
  * loco-edit_amd/libloco_hip_diag.so); the by-hand tuning scripts under tests/ load that build through LOCO_HIP_LIB.  The
  * shipped libloco_hip.so does not export them. */
 #ifndef LOCO_HIP_DIAG_H
@@ -14,6 +14,64 @@ extern "C" {
  * mode: 0 raw, 1 GN+SiLU, 2 GN, 3 tangent, 4 cotangent; tile: -1 auto or a variant id. */
 int  loco_bench_conv(loco_ctx* ctx, int32_t cin, int32_t cout, int32_t H, int32_t W, int32_t B, int32_t mode,
                      int32_t taps, int32_t tile, int32_t iters, float* ms_avg, void* stream);
+
+/* Test hook: ONE convolution on caller-supplied operands, through the same run_conv -> plan_conv path the engine's passes use
+ * (tests/test_gpu_conv_oracle.py compares it with a float64 reference, tests/conv_oracle.py).
+ *
+ * Geometry is that of the LAUNCH (ConvArgs): Cin channels of Hin x Win go in, Cout channels of Hout x Wout come out with
+ *   Hout = Hin / 2 (stride 2), 2 Hin (upsample or zins), Hin (otherwise); Wout likewise.
+ * The output map must be one the kernels' tiles cover exactly: Hout and Wout powers of two from 8 (what loco_create admits), or
+ * Wout a multiple of 32 with Hout a multiple of 8 and Hout Wout a multiple of 256; other maps are refused.
+ * pad < 0 picks what the engine sets: 1 for 3x3 stride 1, 0 for 3x3 stride 2 (the zero row / column sits at the bottom / right)
+ * and for 1x1, 2 for zins.
+ *
+ * Weights are HOST pointers in the torch layout of the module the operator belongs to:
+ *   transposed = 0: weight [Cout][Cin][k][k] -- the launch is conv2d(a, weight)
+ *   transposed = 1: weight [Cin][Cout][k][k] -- the launch is the data gradient of that module, conv_transpose2d(a, weight),
+ *                   on the dgrad layouts with flipped taps (what setw(..., dgrad = true) picks).  bias stays per launch Cout.
+ * They are packed by make_conv into all six layouts (fp32, split-bf16 records, f16 records; forward and dgrad) and released
+ * when the call returns.
+ *
+ * Every other operand is a DEVICE pointer to contiguous fp32; null = absent.  Samples are dense ([B][...]).
+ *   in [B][Cin][Hin][Win]; bias2 [B][Cout]; res [B][Cout][Hout][Wout]; out [B][Cout][Hout][Wout]
+ *   prologue (mode != CM_NONE): sc, sh [Cin] (y = sc x + sh), and for the tangent / cotangent modes (3, 4) the primal
+ *   prim [Cin][Hin][Win] (B = 1), mr [Cin / cpg][2] = {mean, rstd} per group, gamma [Cin], tst [B][Cin / cpg][2] = {m1, m2} per
+ *   group and tc [B][Cin][2] = the same {m1, m2} per channel -- both in their MATHEMATICAL meaning, unscaled.
+ *   second operator (Cin2 > 0; the ResBlock shortcut, a 1x1 conv onto the same output): in2 [B][Cin2][Hout][Wout],
+ *   w2 [Cout][Cin2] (host), bias2nd [Cout] (host) or null.
+ *   norm-cotangent term (cot_d != null): out += S d - (rstd m1 + xhat rstd m2) for the GroupNorm + SiLU whose input is the
+ *   output tensor: d = cot_d [B][Cout][Hout][Wout], primal cot_prim [Cout][Hout][Wout], cot_sc, cot_sh [Cout],
+ *   cot_mr [Cout / cot_cpg][2], cot_tc [B][Cout][2] = {m1, m2} per channel, unscaled.
+ *
+ * The one convention the engine's statistics kernels add (launch_gn_tstats, launch_gn_lin_fused_finalize) and this entry point
+ * reproduces: the per-channel array a low-precision kernel reads (ConvArgs::tc, ::cot_tc) holds {m1, m2} for the tangent mode
+ * and {rstd m1, rstd m2} for the cotangent mode and the norm-cotangent term; the per-group array the exact-fp32 kernel reads
+ * (ConvArgs::tst) is never scaled.  The {S = sc act'(sc x + sh), xhat} records of prim / cot_prim are built by launch_gn_cache.
+ *
+ * in_arena = 1: `in` (and in2, prim, cot_d) are copied into the engine's padded arenas, as every inner conv sees them;
+ * in_arena = 0: the kernel reads the caller's `in` (ConvArgs::in_padded = 0: the network's first conv on the user's tensor).
+ *
+ * plan (cap bytes, may be null) receives one line per launch and part, as planned by plan_conv:
+ *   "launch=L part=P kernel=<conv_variant_name> tile=T nsplit=S B=b s0=first sample gemm=0|1 gemm_tm=M pair=0|1 Cin2=C
+ *    sc_first=0|1 cot=0|1\n"      (a shortcut that runs first is a launch of its own, listed first)
+ * Returns 0, or 1 when a norm-cotangent term was asked for and the planner declined it (out then holds the plain result and
+ * loco_last_error says "declined"); < 0 on errors (shapes that exceed the arenas or the workspace among them). */
+typedef struct loco_conv_desc {
+    int32_t struct_size;
+    int32_t Cin, Cout, Hin, Win, B, taps;
+    int32_t stride, upsample, zins, mode, cpg;
+    int32_t transposed, accumulate, in_arena, pad;
+    int32_t Cin2, cot_cpg;
+    float   res_scale;
+    int32_t reserved;
+    const float *weight, *bias;                                  /* host */
+    const float *in, *bias2, *res;
+    const float *prim, *sc, *sh, *mr, *gamma, *tst, *tc;
+    const float *in2, *w2, *bias2nd;                             /* in2: device; w2, bias2nd: host */
+    const float *cot_d, *cot_prim, *cot_sc, *cot_sh, *cot_mr, *cot_tc;
+    float* out;
+} loco_conv_desc;
+int  loco_debug_conv(loco_ctx* ctx, const loco_conv_desc* desc, char* plan, int64_t cap, void* stream);
 
 /* Debug / test hook: copy an internal primal activation ("down.0.block.0" ...)
  * of the last forward/primal call into dst (device), returns element count or <0. */

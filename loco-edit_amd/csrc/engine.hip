@@ -31,6 +31,9 @@
 #endif
 #include "kernels.h"
 #include "program.h"
+#ifdef LOCO_DIAG
+#include "conv_plan_text.h"
+#endif
 
 using namespace loco;
 
@@ -127,6 +130,9 @@ struct loco_ctx {
     float* partial = nullptr;      // split-K workspace
     size_t partial_floats = 0;
     const float* bench_out = nullptr; int64_t bench_out_count = 0;      // diag: output tensor of the last loco_bench_conv
+#ifdef LOCO_DIAG
+    std::string* plan_log = nullptr;                                    // diag: run_conv appends the text of every plan it executes (loco_debug_conv)
+#endif
     float *tact = nullptr, *tproj = nullptr;
     float* eps_buf = nullptr;      // [max_batch][n]
     float* gx0 = nullptr;          // [max_batch][n] direct cotangent term
@@ -649,6 +655,9 @@ bool run_conv(loco_ctx* c, const ConvArgs& a0, int taps, hipStream_t st, const S
     }
     const ConvPlan p = plan_conv(e, a, taps, rq ? &q : nullptr, second ? &sc : nullptr);
     if (p.sc_first) run_conv(c, *second, 1, st);
+#ifdef LOCO_DIAG
+    if (c->plan_log) conv_plan_text(p, taps, c->prec, *c->plan_log);
+#endif
     if (rq && rq->kind != ST_NONE && rq->n) rq->n->ready = true;
     if (rq && rq->keep_ntile) *rq->keep_ntile = p.keep_ntile;
     const int HWo = a.Hout * a.Wout, Gn = c->cfg.gn_groups;
@@ -2626,6 +2635,156 @@ int loco_bench_conv(loco_ctx* c, int32_t cin, int32_t cout, int32_t H, int32_t W
     HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
     *ms_avg = ms / iters;
     HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+// loco_debug_conv: the per-channel {m1, m2} a low-precision kernel reads, as the engine's statistics kernels leave them
+// (launch_gn_tstats): unscaled for the tangent mode, times the group's rstd for the cotangent forms
+}  // extern "C"
+__global__ void diag_scale_tc(const float* tc, const float* mr, int C, int cpg, long n, int by_rstd, float* out) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;      // one {m1, m2} pair of [B][C]
+    if (i >= n) return;
+    const float f = by_rstd ? mr[2 * (int)((i % C) / cpg) + 1] : 1.0f;
+    out[2 * i] = f * tc[2 * i];
+    out[2 * i + 1] = f * tc[2 * i + 1];
+}
+extern "C" {
+int loco_debug_conv(loco_ctx* c, const loco_conv_desc* d, char* plan, int64_t cap, void* stream) {
+    if (!c) return -2;
+    if (!d || d->struct_size != (int32_t)sizeof(loco_conv_desc)) { c->err = "debug_conv: descriptor size mismatch"; return -2; }
+    if (finalize_params(c)) return -3;
+    hipStream_t st = (hipStream_t)stream;
+    const int taps = d->taps, k = taps == 9 ? 3 : 1, B = d->B;
+    if ((taps != 9 && taps != 1) || d->Cin < 1 || d->Cout < 1 || d->Hin < 1 || d->Win < 1 || B < 1 || (d->stride != 1 && d->stride != 2) ||
+        d->mode < CM_NONE || d->mode > CM_GN_GELU || (d->upsample && d->zins) || (d->stride == 2 && (d->upsample || d->zins)) ||
+        !d->weight || !d->in || !d->out) { c->err = "debug_conv: bad descriptor"; return -2; }
+    if (d->stride == 2 && ((d->Hin | d->Win) & 1)) { c->err = "debug_conv: stride 2 needs an even map"; return -2; }
+    const bool lin = d->mode == CM_TAN_SILU || d->mode == CM_COT_SILU;
+    if (d->mode != CM_NONE && (!d->sc || !d->sh)) { c->err = "debug_conv: the prologue modes need sc / sh"; return -2; }
+    if (lin && (!d->prim || !d->mr || !d->gamma || !d->tst || !d->tc || d->cpg < 1 || d->Cin % d->cpg)) {
+        c->err = "debug_conv: modes 3 / 4 need prim, mr, gamma, tst, tc and cpg"; return -2;
+    }
+    if (d->Cin2 > 0 && (!d->in2 || !d->w2)) { c->err = "debug_conv: the second operator needs in2 and w2"; return -2; }
+    if (d->Cin2 > 0 && (d->res || d->accumulate || taps != 9)) {      // its output IS the residual of the 3x3 operator
+        c->err = "debug_conv: the second operator goes with a 3x3 conv without res / accumulate"; return -2;
+    }
+    if (d->cot_d && (!d->cot_prim || !d->cot_sc || !d->cot_sh || !d->cot_mr || !d->cot_tc || d->cot_cpg < 1 || d->Cout % d->cot_cpg)) {
+        c->err = "debug_conv: the norm-cotangent term needs cot_prim, cot_sc, cot_sh, cot_mr, cot_tc and cot_cpg"; return -2;
+    }
+    const int Hout = d->stride == 2 ? d->Hin / 2 : (d->upsample || d->zins) ? 2 * d->Hin : d->Hin;
+    const int Wout = d->stride == 2 ? d->Win / 2 : (d->upsample || d->zins) ? 2 * d->Win : d->Win;
+    {   // Every conv kernel walks the output map in tiles of min(Wout, 32) columns (a power of two) x 64 / 128 / 256 pixels and
+        // writes whole tiles: maps as loco_create admits them (powers of two from 8 x 8), or whole 32-column, 8-row tiles.  Any
+        // other map (48 x 48, 128 x 144) would be walked past its last row: refused here, never launched.
+        auto pow2 = [](int v) { return v >= 8 && (v & (v - 1)) == 0; };
+        if (!((pow2(Hout) && pow2(Wout)) || (Wout % 32 == 0 && Hout % 8 == 0 && ((long)Hout * Wout) % 256 == 0))) {
+            c->err = "debug_conv: output map outside the tile geometry of the conv kernels"; return -2;
+        }
+    }
+    const long in_e = (long)d->Cin * d->Hin * d->Win, out_e = (long)d->Cout * Hout * Wout, in2_e = (long)d->Cin2 * Hout * Wout;
+    if ((in_e | out_e | in2_e) & 3) { c->err = "debug_conv: planes must be whole 16-byte units"; return -2; }
+    auto up64 = [](long v) { return (v + 63) & ~63L; };
+    // arena T: in | in2 | cot_d (dense samples); arena P: prim; {S, xhat} records: prim | cot_prim
+    const long offT_in2 = d->in_arena ? up64(in_e * B) : 0, offT_cot = offT_in2 + up64(in2_e * B);
+    const long needT = offT_cot + (d->cot_d ? out_e * B : 0);
+    const long sx_cot = lin ? up64(in_e) : 0, need_sx = sx_cot + (d->cot_d ? out_e : 0);
+    if (needT > (long)c->cfg.max_batch * c->prog->per_sample || (lin && in_e > (long)c->cfg.max_batch * c->prog->per_sample) ||
+        need_sx > c->prog->sx_total) { c->err = "debug_conv: shape exceeds the arenas"; return -2; }
+    // the launch's small arrays: one allocation of this call (sc sh mr gamma | tst tc per sample | cot_tc per sample)
+    const int G = lin ? d->Cin / d->cpg : 0;
+    const long tbs = up64(2L * G) + up64(2L * d->Cin);
+    const long small_n = (lin ? (long)B * tbs : 0) + (d->cot_d ? (long)B * up64(2L * d->Cout) : 0) + 64;
+    const size_t owned0 = c->owned.size();
+    const size_t bytes0 = c->bytes;
+    auto release = [&]() {      // what this call allocated (weight layouts, small arrays)
+        (void)hipStreamSynchronize(st);
+        while (c->owned.size() > owned0) { (void)hipFree(c->owned.back()); c->owned.pop_back(); }
+        c->bytes = bytes0;
+    };
+    auto host_param = [&](const float* p, std::vector<int64_t> shape) {
+        HostParam h; h.shape = shape; h.loaded = true;
+        size_t n = 1; for (int64_t s : shape) n *= (size_t)s;
+        if (p) h.data.assign(p, p + n); else h.data.assign(n, 0.f);
+        return h;
+    };
+    // the module's weight: [Cout][Cin][k][k] forward, [Cin][Cout][k][k] behind the transposed (dgrad) operator
+    const int m_out = d->transposed ? d->Cin : d->Cout, m_in = d->transposed ? d->Cout : d->Cin;
+    HostParam w = host_param(d->weight, {m_out, m_in, k, k}), wb0 = host_param(nullptr, {m_out});
+    HostParam w2 = host_param(d->Cin2 > 0 ? d->w2 : nullptr, {d->Cout, d->Cin2 > 0 ? d->Cin2 : 1, 1, 1}), wb2 = host_param(nullptr, {d->Cout});
+    ConvP cp, cp2;
+    float *bias_d = nullptr, *bias2nd_d = nullptr, *small = nullptr;
+    int rc = make_conv(c, {&w}, {&wb0}, &cp);
+    if (!rc && d->Cin2 > 0) rc = make_conv(c, {&w2}, {&wb2}, &cp2);
+    if (!rc && d->bias) rc = upload(c, &bias_d, std::vector<float>(d->bias, d->bias + d->Cout));
+    if (!rc && d->Cin2 > 0 && d->bias2nd) rc = upload(c, &bias2nd_d, std::vector<float>(d->bias2nd, d->bias2nd + d->Cout));
+    if (!rc) rc = dalloc(c, &small, (size_t)small_n);
+    if (rc) { release(); return -1; }
+    auto copy = [&](float* dst, const float* src, long n) {
+        return hipMemcpyAsync(dst, src, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st);
+    };
+    hipError_t he = hipSuccess;
+    ConvArgs a; conv_defaults(a);
+    if (d->in_arena) { he = copy(c->arenaT, d->in, in_e * B); a.in = c->arenaT; } else a.in = d->in;
+    a.in_bs = in_e; a.Cin = d->Cin; a.Hin = d->Hin; a.Win = d->Win;
+    setw(a, cp, d->transposed != 0);
+    a.bias = bias_d;
+    a.out = d->out; a.out_bs = out_e; a.Cout = d->Cout; a.Hout = Hout; a.Wout = Wout; a.B = B;
+    a.bias2 = d->bias2; a.bias2_bs = d->Cout;
+    a.res = d->res; a.res_bs = out_e; a.res_scale = d->res_scale;
+    a.mode = d->mode; a.stride = d->stride; a.upsample = d->upsample; a.zins = d->zins; a.accumulate = d->accumulate;
+    a.pad = d->pad >= 0 ? d->pad : taps == 1 ? 0 : d->zins ? 2 : d->stride == 2 ? 0 : 1;
+    a.sc = d->sc; a.sh = d->sh; a.scsh_bs = 0; a.cpg = d->cpg;
+    if (lin) {
+        if (he == hipSuccess) he = copy(c->arenaP, d->prim, in_e);
+        a.prim = c->arenaP; a.prim_bs = 0;
+        a.mr = d->mr; a.mr_bs = 0; a.gamma_ = d->gamma;
+        // per sample: the group means as given (exact-fp32 kernel), then their per-channel expansion as the statistics kernels scale it
+        for (int b = 0; b < B && he == hipSuccess; ++b) he = copy(small + b * tbs, d->tst + (long)b * 2 * G, 2L * G);
+        a.tst = small; a.tst_bs = tbs;
+        for (int b = 0; b < B; ++b)
+            hipLaunchKernelGGL(diag_scale_tc, dim3((unsigned)((d->Cin + 255) / 256)), dim3(256), 0, st, d->tc + (long)b * 2 * d->Cin, d->mr,
+                               d->Cin, d->cpg, (long)d->Cin, d->mode == CM_COT_SILU ? 1 : 0, small + b * tbs + up64(2L * G));
+        a.tc = small + up64(2L * G); a.tc_bs = tbs;
+        launch_gn_cache(c->arenaP, d->Cin, d->Hin * d->Win, d->cpg, d->sc, d->sh, d->mr, c->sxcache, st, ACT_SILU);
+        a.sx = c->sxcache;
+    }
+    ConvArgs n2; conv_defaults(n2);
+    if (d->Cin2 > 0) {
+        float* in2 = c->arenaT + offT_in2;
+        if (he == hipSuccess) he = copy(in2, d->in2, in2_e * B);
+        n2.in = in2; n2.in_bs = in2_e; n2.Cin = d->Cin2; n2.Hin = Hout; n2.Win = Wout;
+        setw(n2, cp2, false); n2.bias = bias2nd_d; n2.pad = 0;
+        n2.out = d->out; n2.out_bs = out_e; n2.Cout = d->Cout; n2.Hout = Hout; n2.Wout = Wout; n2.B = B;
+        a.res = d->out; a.res_bs = out_e;      // (as the ResBlock: the block output is the shortcut's output + conv2)
+    }
+    if (d->cot_d) {
+        float* cd = c->arenaT + offT_cot;
+        float* ctc = small + (lin ? (long)B * tbs : 0);
+        const long cbs = up64(2L * d->Cout);
+        if (he == hipSuccess) he = copy(cd, d->cot_d, out_e * B);
+        for (int b = 0; b < B; ++b)
+            hipLaunchKernelGGL(diag_scale_tc, dim3((unsigned)((d->Cout + 255) / 256)), dim3(256), 0, st, d->cot_tc + (long)b * 2 * d->Cout,
+                               d->cot_mr, d->Cout, d->cot_cpg, (long)d->Cout, 1, ctc + b * cbs);
+        launch_gn_cache(d->cot_prim, d->Cout, Hout * Wout, d->cot_cpg, d->cot_sc, d->cot_sh, d->cot_mr, c->sxcache + sx_cot, st, ACT_SILU);
+        a.cot_d = cd; a.cot_d_bs = out_e; a.cot_sx = c->sxcache + sx_cot; a.cot_tc = ctc; a.cot_tc_bs = cbs;
+    }
+    if (he != hipSuccess) { c->err = std::string("debug_conv: ") + hipGetErrorString(he); release(); return -1; }
+    std::string text;
+    const int act0 = c->cfg.act;
+    if (d->mode == CM_GN_GELU) c->cfg.act = ACT_GELU;      // a GELU network's forward prologue (run_conv hands cfg.act to the kernels)
+    c->plan_log = &text;
+    const bool rode = run_conv(c, a, taps, st, nullptr, d->Cin2 > 0 ? &n2 : nullptr);
+    c->plan_log = nullptr;
+    c->cfg.act = act0;
+    he = hipGetLastError();
+    release();
+    if (he == hipSuccess) he = hipGetLastError();
+    if (he != hipSuccess) { c->err = std::string("debug_conv: ") + hipGetErrorString(he); return -1; }
+    if (plan && cap > 0) {
+        if ((int64_t)text.size() + 1 > cap) { c->err = "debug_conv: plan buffer too small"; return -4; }
+        std::memcpy(plan, text.c_str(), text.size() + 1);
+    }
+    if (d->cot_d && !rode) { c->err = "debug_conv: norm-cotangent term declined"; return 1; }
     return 0;
 }
 

@@ -20,7 +20,7 @@ _LIB_PATH = os.environ.get("LOCO_HIP_LIB") or os.path.join(os.path.dirname(os.pa
 _lib = None
 
 # diagnostics of include/loco_hip_diag.h: only in a -DLOCO_DIAG build (make -C loco-edit_amd/csrc diag)
-DIAG_SYMBOLS = ["loco_bench_conv", "loco_debug_tensor"]
+DIAG_SYMBOLS = ["loco_bench_conv", "loco_debug_conv", "loco_debug_tensor"]
 
 # every symbol include/loco_hip.h declares
 SYMBOLS = [
@@ -55,6 +55,17 @@ class LocoCfg(C.Structure):
         ("act", C.c_int32), ("res_scale", C.c_float), ("added_kv", C.c_int32),
         ("time_cond_proj_dim", C.c_int32),
     ]
+
+
+class LocoConvDesc(C.Structure):
+    """loco_conv_desc of include/loco_hip_diag.h (loco_debug_conv): one conv launch on caller-supplied operands."""
+    _PTRS = ("weight", "bias", "in", "bias2", "res", "prim", "sc", "sh", "mr", "gamma", "tst", "tc", "in2", "w2", "bias2nd",
+             "cot_d", "cot_prim", "cot_sc", "cot_sh", "cot_mr", "cot_tc", "out")
+    _HOST = ("weight", "bias", "w2", "bias2nd")
+    _fields_ = ([("struct_size", C.c_int32)] +
+                [(k, C.c_int32) for k in ("Cin", "Cout", "Hin", "Win", "B", "taps", "stride", "upsample", "zins", "mode", "cpg",
+                                          "transposed", "accumulate", "in_arena", "pad", "Cin2", "cot_cpg")] +
+                [("res_scale", C.c_float), ("reserved", C.c_int32)] + [(k, C.c_void_p) for k in _PTRS])
 
 
 class LocoTextCfg(C.Structure):
@@ -169,6 +180,8 @@ def load_library():
         lib.loco_bench_conv.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(f32), vp]
         lib.loco_debug_tensor.argtypes = [vp, C.c_char_p, vp, i64, vp]
         lib.loco_debug_tensor.restype = i64
+    if hasattr(lib, "loco_debug_conv"):
+        lib.loco_debug_conv.argtypes = [vp, C.POINTER(LocoConvDesc), C.c_char_p, i64, vp]
     _lib = lib
     return lib
 
@@ -662,6 +675,40 @@ class LocoEngine:
         self._check(self.lib.loco_bench_conv(self._ctx, cin, cout, H, W, B, mode, taps, tile, iters, C.byref(ms),
                                              _stream()), "loco_bench_conv")
         return float(ms.value)
+
+    def debug_conv(self, out: torch.Tensor, **desc):
+        """One conv launch on caller-supplied operands through run_conv -> plan_conv (loco_debug_conv, include/loco_hip_diag.h).
+        `desc`: the fields of loco_conv_desc; weight / bias / w2 / bias2nd are CPU float32 tensors, every other operand a
+        contiguous float32 device tensor.  Writes `out` and returns (plan, cot_rode): the plan as a list of dicts, one per
+        launch and part, and whether a requested norm-cotangent term rode in the epilogue."""
+        self._need_diag("loco_debug_conv")
+        d = LocoConvDesc()
+        d.struct_size = C.sizeof(LocoConvDesc)
+        d.stride, d.in_arena, d.pad, d.res_scale = 1, 1, -1, 1.0
+        keep = []
+        _chk_dev(out)
+        d.out = out.data_ptr()
+        for k, v in desc.items():
+            if k not in LocoConvDesc._PTRS:
+                if not hasattr(d, k) or k in ("struct_size", "reserved"):
+                    raise TypeError(f"debug_conv: no descriptor field {k!r}")
+                setattr(d, k, v)
+            elif v is not None:
+                if k in LocoConvDesc._HOST:
+                    v = v.detach().to("cpu", torch.float32).contiguous()
+                else:
+                    _chk_dev(v)
+                keep.append(v)
+                setattr(d, k, v.data_ptr())
+        buf = C.create_string_buffer(1 << 12)
+        rc = self.lib.loco_debug_conv(self._ctx, C.byref(d), buf, len(buf), _stream())
+        if rc not in (0, 1):
+            self._check(rc, "loco_debug_conv")
+        plan = []
+        for line in buf.value.decode().splitlines():
+            rec = dict(f.split("=", 1) for f in line.split(" "))
+            plan.append({k: (v if k == "kernel" else int(v)) for k, v in rec.items()})
+        return plan, rc == 0
 
     def profile_enable(self, on):
         """True/1: per kernel variant; 2: per layer shape; False: off."""
