@@ -1,5 +1,5 @@
 // Split-bf16 ("bf16x3") and f16 convolution: dispatch of the launches conv_plan.hip planned to the kernel templates of
-// conv_bf16_kernel.h, conv_pair_kernel.h, conv_dual_kernel.h and conv_gemm_kernel.h (instantiated in conv_bf16_inst_*.hip).
+// conv_bf16_kernel.h, conv_pair_kernel.h and conv_gemm_kernel.h (instantiated in conv_bf16_inst_*.hip).
 #include "kernels.h"
 #include <cstdio>
 #include <cstdlib>
@@ -10,7 +10,6 @@ enum : int { PR_BF16X3 = 0, PR_F16 = 1 };
 template <int PR, int TAPS, int MODE> void launch_tile_b(const ConvArgs& a, hipStream_t st);   // conv_bf16_inst_*.hip
 template <int PR, int MODE> void launch_kcat_b(const ConvArgs& a, hipStream_t st);            // conv_bf16_inst_*.hip
 template <int PR, int MODE> void launch_pair_b(const ConvArgs& a, hipStream_t st);            // conv_bf16_inst_k.hip (conv_pair_kernel.h)
-template <int PR, int MODE> void launch_dual_b(const ConvArgs& a, hipStream_t st);            // conv_bf16_inst_h / _i.hip (conv_dual_kernel.h)
 void launch_conv_gemm(const ConvArgs& a, hipStream_t st);      // conv_bf16_inst_j.hip (conv_gemm_kernel.h)
 
 template <int PR>
@@ -33,19 +32,6 @@ static void launch_lowp(const ConvArgs& a, int taps, hipStream_t st) {
         else launch_kcat_b<PR, CM_TAN_SILU>(a, st);
         return;
     }
-#ifdef LOCO_DIAG
-    if constexpr (PR == PR_BF16X3) {
-        if (taps == 9 && a.dual) {           // conv_plan_parts checked conv_dual_ok
-            switch (a.mode) {
-                case CM_NONE: launch_dual_b<PR, CM_NONE>(a, st); break;
-                case CM_GN_SILU: launch_dual_b<PR, CM_GN_SILU>(a, st); break;
-                case CM_TAN_SILU: launch_dual_b<PR, CM_TAN_SILU>(a, st); break;
-                default: launch_dual_b<PR, CM_COT_SILU>(a, st); break;
-            }
-            return;
-        }
-    }
-#endif
     if constexpr (PR == PR_BF16X3) {
         if (taps == 9 && a.pair) {           // the 16x16x32 tap-pair kernel (conv_plan.hip conv_pair_ok)
             switch (a.mode) {

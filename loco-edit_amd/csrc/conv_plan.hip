@@ -15,24 +15,14 @@ namespace loco {
 constexpr int BKC = 16;   // channels per K chunk of the low-precision kernels
 constexpr int BKF = 8;    // ... of the exact-fp32 kernel
 
-// tile variants: 0: 128 x 128, 1: 128 x 64, 2: 32 x 128, 3: 64 x 64, 4: 128 x 256 (four waves, mapped to 5), 5: 128 x 256,
-// 6: 128 x 128 in the compact two-workgroups-per-CU layout (diagnostics build); couts x pixels
-static const int kMT[7] = {128, 128, 32, 64, 128, 128, 128}, kNT[7] = {128, 64, 128, 64, 256, 256, 128};
+// tile variants: 0: 128 x 128, 1: 128 x 64, 2: 32 x 128, 3: 64 x 64, 4: 128 x 256 (four waves, mapped to 5), 5: 128 x 256;
+// couts x pixels
+static const int kMT[6] = {128, 128, 32, 64, 128, 128}, kNT[6] = {128, 64, 128, 64, 256, 256};
 
 static int env_int(const char* name, int dflt) {
     const char* e = getenv(name);
     return e ? atoi(e) : dflt;
 }
-// A/B switches of the opt-in kernel families that are compiled into the diagnostics build only (`make diag`): off elsewhere
-static int diag_switch(const char* name) {
-#ifdef LOCO_DIAG
-    return env_int(name, 0);
-#else
-    (void)name;
-    return 0;
-#endif
-}
-
 // the exact-fp32 kernel's tiles (variants 0 - 3)
 static int pick_tile(int Cout, int HW) {
     if (HW >= 128) return Cout > 32 ? 0 : 2;
@@ -70,14 +60,9 @@ static int conv_bf16_pick_tile(int Cout, int HW, int B, int tile_override) {
 constexpr int kTile0MaxHW = 65536;
 
 static int bf16_tile_of(const ConvArgs& a, int tile_override = -1) {
-    // LOCO_CONV_2WG=1: the big-image 3x3 convs on 128 x 128 tiles of four waves in the compact LDS layout (STG 3 of
-    // conv_bf16_kernel.h, 81 920 B), two workgroups per CU, instead of one 128 x 256 workgroup of eight waves
-    static const bool two_per_cu = diag_switch("LOCO_CONV_2WG") != 0;
     int tile = conv_bf16_pick_tile(a.Cout, a.Hout * a.Wout, a.B, tile_override);
     if (tile == 4) tile = 5;
     if (tile == 5 && a.taps == 1 && !a.gemm && a.B >= 2 && a.Hout * a.Wout <= kTile0MaxHW) return 0;
-    if (tile == 5 && two_per_cu && a.taps == 9 && a.stride == 1 && !a.upsample && !a.zins && (a.Cin % BKC) == 0 &&
-        a.in_padded && a.pad == 1 && a.Wout >= 32) return 6;
     if (a.stride == 2 && tile == 5) tile = 0;   // the double-buffered stride-2 halo of a 256-pixel tile exceeds LDS
     return tile;
 }
@@ -138,26 +123,10 @@ static bool conv_lowp_can_fuse_stats(const ConvArgs& a) {
 static bool conv_pair_ok(const ConvArgs& a) {
     static const bool on = env_int("LOCO_CONV_PAIR", 1) != 0;
     if (!on || a.Hout * a.Wout < 16384 || a.taps != 9 || a.Cin2 > 0 || a.nsplit != 1 || a.stride != 1 || a.upsample || a.zins ||
-        a.pad != 1 || !a.in_padded || (a.Cin % (2 * BKC)) != 0 || (a.Cout % 128) != 0 || (a.Wout % 32) != 0 || (a.Hout % 8) != 0 ||
-        a.pers_groups || a.dual)
+        a.pad != 1 || !a.in_padded || (a.Cin % (2 * BKC)) != 0 || (a.Cout % 128) != 0 || (a.Wout % 32) != 0 || (a.Hout % 8) != 0)
         return false;
     if (!(a.mode == CM_NONE || a.mode == CM_GN_SILU || a.mode == CM_TAN_SILU || a.mode == CM_COT_SILU)) return false;
     return a.tile == 5;
-}
-
-// Dual-probe tile policy.  Opt-in (LOCO_CONV_DUAL=1, diagnostics build): measured neutral on the headline (+1.2 %) and on
-// config 3 (-0.2 %) in round 5 (profiles/r05_experiments.md: the tile halves the weight bytes per FLOP, but weight traffic is
-// not what a launch waits for).  A launch needs at least 192 dual units (pixel tiles x cout tiles x probe pairs): below ~3/4 of
-// the CUs the wider tile leaves too much of the chip idle (the 128 x 128 level of the headline: 64 tiles x 2 pairs).
-static bool conv_dual_ok(const ConvArgs& a) {
-    static const bool on = diag_switch("LOCO_CONV_DUAL") != 0;
-    if (!on || a.taps != 9 || a.Cin2 > 0 || a.nsplit != 1 || a.stride != 1 || a.upsample || a.zins || a.pad != 1 || (a.Cin % BKC) != 0 ||
-        !a.in_padded || a.Wout < 32 || (a.Wout % 32) != 0 || (a.Hout % 8) != 0 || (a.Cout % 128) != 0 || a.B < 2 || a.cot_d)
-        return false;
-    if (!(a.mode == CM_NONE || a.mode == CM_GN_SILU || a.mode == CM_TAN_SILU || a.mode == CM_COT_SILU)) return false;
-    if (a.tile != 5) return false;
-    const long units = (long)((a.Hout * a.Wout) / 256) * (a.Cout / 128) * (a.B / 2);
-    return units >= 192;
 }
 
 // `a` restricted to its samples nb .. B - 1
@@ -176,32 +145,6 @@ static ConvArgs conv_shift_batch(const ConvArgs& a, int nb) {
     if (t.cot_d) { t.cot_d += (long)nb * a.cot_d_bs; t.cot_tc += (long)nb * a.cot_tc_bs; }
     if (t.st_part) t.st_part += (long)nb * a.Cout * ((a.Hout * a.Wout) / conv_bf16_tile_pixels(a)) * 2;
     return t;
-}
-
-static void conv_pers_plan(ConvArgs& a) {
-    // Opt-in (LOCO_CONV_PERS=1: raw / forward forms, 2: every form; diagnostics build): measured neutral to slightly negative in
-    // the flow (r05: headline 299.4 vs 300.2 ms, 25-frame decode step 44.1 -> 45.0 ms) although the isolated raw / forward
-    // launches gain 5 %
-    a.pers_groups = 0;
-    static const int on = diag_switch("LOCO_CONV_PERS");
-    if (!on || a.taps != 9 || a.Cin2 > 0 || a.nsplit != 1 || a.stride != 1 || a.upsample || a.zins || a.pad != 1 || !a.in_padded ||
-        (a.Cin % (2 * BKC)) != 0 || (a.Cout % 128) != 0 || a.B < 2 || a.cot_d || bf16_tile_of(a) != 5)
-        return;
-    // The raw-input and forward forms only (r05, 128 -> 128 @256^2, 5 probes: 246 -> 232 us raw, 261 -> 248 us GroupNorm + SiLU).  The
-    // tangent / cotangent forms LOSE under a walk over probes (274 -> 276, 128 -> 256: 523 -> 552 us): with one workgroup per
-    // (tile, probe) the five probes of a pixel tile run at the same time on one XCD and share one fetch of the tile's primal
-    // {S, xhat} cache (8 of their 12 bytes per element); walked one after the other by one CU, the cache is fetched five times.
-    // LOCO_CONV_PERS=2 walks them too (A/B).
-    if (!(a.mode == CM_NONE || a.mode == CM_GN_SILU || a.mode == CM_GN_GELU ||
-          (on == 2 && (a.mode == CM_TAN_SILU || a.mode == CM_COT_SILU)))) return;
-    // G workgroups share a tile, each walks ceil(B / G) probes: as many groups as keep the grid within one round of the chip
-    const long wg0 = (long)((a.Hout * a.Wout) / 256) * (a.Cout / 128);
-    int G = wg0 >= 256 ? 1 : (int)(256 / wg0);
-    if (G > a.B) G = a.B;
-    const int per = (a.B + G - 1) / G;
-    // worth it when a workgroup gets at least two probes, the walks are balanced and the grid fills most of the chip
-    if (per < 2 || a.B * 10 < G * per * 8 || wg0 * G < 192) return;
-    a.pers_groups = G;
 }
 
 // Compute-shaped 1x1 operators on the DMA-fed GEMM kernel: eligibility, the cout tile and the split-K factor (overwrites
@@ -245,30 +188,11 @@ static void conv_gemm_plan(ConvArgs& a) {
 
 void conv_plan_family(ConvArgs& a, int prec) {
     if (prec == 1 && a.taps == 1) conv_gemm_plan(a);     // compute-shaped 1x1 operators (the transformer's linear layers)
-    if (prec == 1 && a.taps == 9) conv_pers_plan(a);     // 3x3 launches with several probes per (pixel tile, cout tile) slot
 }
 
-int conv_plan_parts(ConvArgs& a, int prec, int tile_override, ConvArgs parts[2]) {
-    a.dual = 0;
+void conv_plan_tile_pair(ConvArgs& a, int prec, int tile_override) {
     a.tile = tile_for(a, prec, tile_override);
-    a.pair = 0;
-    parts[0] = a;
-    int n = 1;
-    if (prec == 1 && a.taps == 9 && conv_dual_ok(a)) {      // the even part on the dual-probe tile, an odd last probe on its own
-        parts[0].B = a.B & ~1;
-        parts[0].dual = 1;
-        if (a.B & 1) {
-            parts[1] = conv_shift_batch(a, a.B - 1);
-            parts[1].pers_groups = 0;
-            n = 2;
-        }
-    }
-    for (int i = 0; i < n; ++i) {
-        ConvArgs& p = parts[i];
-        p.tile = tile_for(p, prec, tile_override);
-        p.pair = prec == 1 && conv_pair_ok(p);
-    }
-    return n;
+    a.pair = prec == 1 && conv_pair_ok(a);
 }
 
 // the grid of B probes x `per_probe` workgroups (128-cout tiles) ends in a short round of r <= 160 workgroups (tail_split)
@@ -310,14 +234,12 @@ static int stats_route(const ConvEnv& e, const StatAsk* q, bool want, ConvArgs& 
         if (kept) *keep_ntile = ntile;
         return epi;
     }
-    // Tangent / cotangent group means in the conv epilogue (round 6, LOCO_FUSE_LIN=0: off): whole cout tiles, no split-K, not the
-    // opt-in persistent / dual-probe kernels (their epilogues take the forward statistics only), not next to a norm-cotangent
-    // term (the epilogue holds one of the two in its record registers).  A tangent launch that finishes one part of a
-    // concatenation keeps its (norm-independent) raw sums in the part's buffer, at this lane's samples: lane rows are
+    // Tangent / cotangent group means in the conv epilogue (round 6, LOCO_FUSE_LIN=0: off): whole cout tiles, no split-K, not next
+    // to a norm-cotangent term (the epilogue holds one of the two in its record registers).  A tangent launch that finishes one
+    // part of a concatenation keeps its (norm-independent) raw sums in the part's buffer, at this lane's samples: lane rows are
     // keep_floats / max_batch floats apart whatever tile either lane runs.
     const bool cot_cache = q->kind == ST_COT && q->norm && q->sx;
-    if ((q->kind == ST_TAN || cot_cache) && e.fuse_lin && !x.cot_d && conv_lowp_can_fuse_stats(x) && !x.pers_groups &&
-        !conv_dual_ok(x)) {
+    if ((q->kind == ST_TAN || cot_cache) && e.fuse_lin && !x.cot_d && conv_lowp_can_fuse_stats(x)) {
         const size_t lane_off = (size_t)e.lane_s0 * (q->keep_floats / e.max_batch);
         const bool keptl = q->kind == ST_TAN && q->keep && s0 == 0 && x.B == B && lane_off + need <= q->keep_floats;
         if (keptl || (q->norm && need <= e.stpart_floats)) {
@@ -337,7 +259,7 @@ static ConvLaunch plan_launch(const ConvEnv& e, const StatAsk* q, bool want, con
     l.args.tile = tile_for(x, e.prec, -1);
     l.stats = stats_route(e, q, want, l.args, s0, B, keep_ntile);
     if (l.stats == SR_EPI || l.stats == SR_KEEP) l.ntile = (x.Hout * x.Wout) / conv_bf16_tile_pixels(l.args);
-    l.nparts = conv_plan_parts(l.args, e.prec, -1, l.parts);
+    conv_plan_tile_pair(l.args, e.prec, -1);
     return l;
 }
 
@@ -345,7 +267,7 @@ ConvPlan plan_conv(const ConvEnv& e, const ConvArgs& a0, int taps, const StatAsk
     ConvPlan p;
     ConvArgs a = a0;
     a.taps = taps;
-    a.dual = 0; a.pers_groups = 0; a.gemm = 0;
+    a.gemm = 0;
     if (sc) {
         // the shortcut K-concatenated into this 3x3 launch (conv_lowp_kcat: one write-out, no read-modify-write of the block
         // output, one launch less) where the launch allows it -- one round of whole probes (no tail-probe split) -- else run first
@@ -383,7 +305,7 @@ ConvPlan plan_conv(const ConvEnv& e, const ConvArgs& a0, int taps, const StatAsk
     conv_plan_family(a, e.prec);
     a.tile = tile_for(a, e.prec, -1);
     int split = 1;
-    const int tail = e.prec >= 1 && a.nsplit == 1 && a.B >= 2 && !a.gemm && !a.pers_groups ? tail_split(a, e.partial_floats, &split) : 0;
+    const int tail = e.prec >= 1 && a.nsplit == 1 && a.B >= 2 && !a.gemm ? tail_split(a, e.partial_floats, &split) : 0;
     const bool want = q && q->kind != ST_NONE && e.prec >= 1 && e.fuse_stats;
     if (!tail) {
         p.l[0] = plan_launch(e, q, want, a, 0, a.B, &p.keep_ntile);
@@ -409,21 +331,19 @@ ConvPlan plan_conv(const ConvEnv& e, const ConvArgs& a0, int taps, const StatAsk
 const char* conv_variant_name(const ConvArgs& a, int taps, int prec) {
     static const char* tiles[6] = {"2,2,2,2", "4,1,1,2", "1,4,1,1", "2,2,1,1", "2,2,2,4", "2,4,2,2"};
     static char names[3][2][6][6][56];      // lock-step tiles: [prec][3x3 / 1x1][tile][mode]
-    static char others[5][3][6][40];        // the other kernels: [kernel][prec][mode or gemm_tm]
+    static char others[3][3][6][40];        // the other kernels: [kernel][prec][mode or gemm_tm]
     const int mode = (a.mode < 0 || a.mode > 5) ? 2 : a.mode;
     const char* other = nullptr;
     int k = 0, v = mode;
     if (prec && taps == 9 && a.Cin2 > 0) other = prec == 1 ? "conv_kcat_bf16x3<2,4,2,2,%d>" : "conv_kcat_f16<2,4,2,2,%d>";
     else if (prec == 1 && taps == 1 && a.gemm) { k = 1; other = "conv_gemm_bf16x3<%d>"; v = a.gemm_tm; }
-    else if (prec == 1 && taps == 9 && a.pers_groups > 0 && !a.dual) { k = 2; other = "conv_pers_bf16x3<9,2,4,2,2,%d>"; }
-    else if (prec == 1 && taps == 9 && a.pair) { k = 3; other = "conv_pair_bf16x3<%d>"; }      // the 16x16x32 tap-pair kernel
-    else if (prec == 1 && taps == 9 && a.dual) { k = 4; other = "conv_dual_bf16x3<%d>"; }
+    else if (prec == 1 && taps == 9 && a.pair) { k = 2; other = "conv_pair_bf16x3<%d>"; }      // the 16x16x32 tap-pair kernel
     if (other) {
         char* n = others[k][prec][v];
         if (!n[0]) snprintf(n, 40, other, v);
         return n;
     }
-    int t = a.tile == 6 ? 0 : a.tile;      // the two-per-CU variant is a 128 x 128 tile too
+    int t = a.tile;
     if (t < 0 || t > 5) t = 0;
     int m = mode;
     if (taps != 9 && m != CM_NONE) m = CM_GN;

@@ -677,16 +677,13 @@ bool run_conv(loco_ctx* c, const ConvArgs& a0, int taps, hipStream_t st, const S
     for (int li = 0; li < p.nl; ++li) {
         const ConvLaunch& l = p.l[li];
         const ConvArgs& x = l.args;
-        for (int pi = 0; pi < l.nparts; ++pi) {
-            const ConvArgs& y = l.parts[pi];
-            double flops = 2.0 * (y.Cin * taps + y.Cin2) * y.Cout * (double)y.Hout * y.Wout * y.B;
-            if (y.zins) flops *= 0.25;     // algorithmic work of the stride-2 data gradient
-            timed(c->prof_on ? conv_variant_name(y, taps, c->prec) : nullptr, flops, y, [&] {
-                if (c->prec == 1) launch_conv_bf16x3(y, taps, st);
-                else if (c->prec == 2) launch_conv_f16(y, taps, st);
-                else launch_conv(y, taps, st);
-            });
-        }
+        double flops = 2.0 * (x.Cin * taps + x.Cin2) * x.Cout * (double)x.Hout * x.Wout * x.B;
+        if (x.zins) flops *= 0.25;     // algorithmic work of the stride-2 data gradient
+        timed(c->prof_on ? conv_variant_name(x, taps, c->prec) : nullptr, flops, x, [&] {
+            if (c->prec == 1) launch_conv_bf16x3(x, taps, st);
+            else if (c->prec == 2) launch_conv_f16(x, taps, st);
+            else launch_conv(x, taps, st);
+        });
         if (x.nsplit > 1) {
             timed("conv_splitk_reduce", 0.0, x, [&] {
                 if (l.stats != SR_SPLITK) { launch_conv_splitk_reduce(x, st); return; }
@@ -2614,15 +2611,14 @@ int loco_bench_conv(loco_ctx* c, int32_t cin, int32_t cout, int32_t H, int32_t W
     }
     if (getenv("LOCO_BENCH_ACC") && atoi(getenv("LOCO_BENCH_ACC"))) a.accumulate = 1;
     conv_plan_family(a, c->prec);
-    if (const char* e = getenv("LOCO_DUAL_WHATIF")) a.no_deep = atoi(e);      // stamp build of the dual tile only (bits 2 / 4)
-    ConvArgs parts[2];
-    const int nparts = conv_plan_parts(a, c->prec, tile, parts);
+    // what-if bits of the lock-step kernel's stamp build (-DLOCO_DUAL_STAMP, tests/diag/lowp_stamps.py): 2 halo loads collapsed,
+    // 4 weight DMAs collapsed, 8 no conversions
+    if (const char* e = getenv("LOCO_DUAL_WHATIF")) a.no_deep = atoi(e);
+    conv_plan_tile_pair(a, c->prec, tile);
     auto run = [&]() {
-        for (int pi = 0; pi < nparts; ++pi) {
-            if (c->prec == 1) launch_conv_bf16x3(parts[pi], taps, st);
-            else if (c->prec == 2) launch_conv_f16(parts[pi], taps, st);
-            else launch_conv(parts[pi], taps, st);
-        }
+        if (c->prec == 1) launch_conv_bf16x3(a, taps, st);
+        else if (c->prec == 2) launch_conv_f16(a, taps, st);
+        else launch_conv(a, taps, st);
         launch_conv_splitk_reduce(a, st);
     };
     run();

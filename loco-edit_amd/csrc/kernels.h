@@ -112,14 +112,10 @@ struct ConvArgs {
     const float* cot_d; long cot_d_bs; const float2* cot_sx; const float* cot_tc; long cot_tc_bs;
     int act;           // ActKind of the prologue modes (exact-fp32 kernel, split-K statistics epilogue)
     float res_scale;   // out = conv + bias + res_scale * res  (DeepFloyd-IF: (x + h) / sqrt 2 with the conv's weights pre-scaled); conv_defaults: 1
-    int dual;          // 1: run on the dual-probe tile of conv_dual_kernel.h (B even; set by conv_plan_parts, never by the engine)
     // 1x1 operator as a DMA-fed GEMM (conv_gemm_kernel.h; set by conv_gemm_plan): gemm_tm = 2 / 4 (128 / 256 couts per
     // workgroup); the activations' split records are written to the END of the workspace `partial` (partial_floats floats)
     int gemm, gemm_tm;
     size_t partial_floats;
-    // 3x3 kernel persistent over the probes of a tile (conv_bf16_kernel.h PHASE 3; set by conv_pers_plan): number of workgroups
-    // that share one (pixel tile, cout tile), each walking the probes b, b + pers_groups, ...; 0: one workgroup per (tile, probe)
-    int pers_groups;
     // kernel of the launch as planned (conv_plan.hip, read by the dispatchers and conv_variant_name): the tile variant and
     // whether a 3x3 launch runs the tap-pair kernel of conv_pair_kernel.h
     int tile, pair;
@@ -133,7 +129,7 @@ void launch_conv_splitk_reduce(const ConvArgs& a, hipStream_t st);
 
 // ---- launch policy of the convolutions (conv_plan.hip, host code only) ----
 // run_conv asks plan_conv for every decision about a conv and executes the plan; the dispatchers and the profile names read
-// what the plan recorded in ConvArgs (tile, pair, dual, gemm, pers_groups, Cin2).  ConvEnv: what the context contributes.
+// what the plan recorded in ConvArgs (tile, pair, gemm, Cin2).  ConvEnv: what the context contributes.
 struct ConvEnv {
     int prec = 1;                                          // 0: exact fp32, 1: split-bf16, 2: f16
     int chip_share = 1;                                    // passes enqueued side by side (loco_set_chip_share)
@@ -162,11 +158,9 @@ enum StatRoute : int {
     SR_KEEP = 4,      // conv epilogue partials kept for the norm over a concatenation, nothing else
 };
 
-// one conv launch and its split-K reduce: samples [s0, s0 + args.B) of the conv.  The kernels it runs are `parts`: the launch
-// itself, or its even part on the dual-probe tile + the odd last probe.
+// one conv launch and its split-K reduce: samples [s0, s0 + args.B) of the conv
 struct ConvLaunch {
     ConvArgs args;
-    ConvArgs parts[2]; int nparts = 1;
     int s0 = 0;
     int stats = SR_NONE;
     int ntile = 0;      // pixel tiles per row of args.st_part (SR_EPI / SR_KEEP)
@@ -184,11 +178,11 @@ struct ConvPlan {
 // every decision about conv `a` (`taps` 9 or 1; `ask`: statistics asked for; `shortcut`: the ResBlock's 1x1 operator on the
 // same output tensor).  Pure: reads its arguments (and the process-wide A/B switches of conv_plan.hip) only.
 ConvPlan plan_conv(const ConvEnv& env, const ConvArgs& a, int taps, const StatAsk* ask, const ConvArgs* shortcut);
-// the two steps run_conv and loco_bench_conv share: the kernel family of a conv (DMA-fed GEMM or persistent 3x3; may set
-// a.nsplit), then -- with batch and split-K factor final -- the launch's tile and kernels (returns the number of parts).
+// the two steps run_conv and loco_bench_conv share: the kernel family of a conv (the DMA-fed GEMM; may set a.nsplit), then
+// -- with batch and split-K factor final -- the launch's tile variant and whether it runs the tap-pair kernel (a.tile, a.pair).
 // tile_override >= 0: the tile variant of the big-image case (loco_bench_conv).
 void conv_plan_family(ConvArgs& a, int prec);
-int conv_plan_parts(ConvArgs& a, int prec, int tile_override, ConvArgs parts[2]);
+void conv_plan_tile_pair(ConvArgs& a, int prec, int tile_override);
 
 int conv_bf16_tile_couts(const ConvArgs& a);    // couts per workgroup of the planned launch
 // name of the kernel the planned launch runs (the per-kernel profile)

@@ -20,8 +20,8 @@ static std::map<std::string, long> g_cov;
         }                                                                                      \
     } while (0)
 
-static const int kMT[7] = {128, 128, 32, 64, 128, 128, 128}, kNT[7] = {128, 64, 128, 64, 256, 256, 128};
-static const char* kTileName[7] = {"2,2,2,2", "4,1,1,2", "1,4,1,1", "2,2,1,1", "2,2,2,4", "2,4,2,2", "2,2,2,2"};
+static const int kMT[6] = {128, 128, 32, 64, 128, 128}, kNT[6] = {128, 64, 128, 64, 256, 256};
+static const char* kTileName[6] = {"2,2,2,2", "4,1,1,2", "1,4,1,1", "2,2,1,1", "2,2,2,4", "2,4,2,2"};
 
 // never dereferenced: distinct addresses so pointer shifts can be checked
 template <class T> static T* fake(uintptr_t base) { return reinterpret_cast<T*>(base << 32); }
@@ -93,12 +93,9 @@ static std::string sig(const ConvPlan& p) {
         snprintf(buf, sizeof buf, "B%d s0%d ns%d st%d nt%d cin2 %d stp%lx|", l.args.B, l.s0, l.args.nsplit, l.stats, l.ntile, l.args.Cin2,
                  (unsigned long)(uintptr_t)l.args.st_part);
         s += buf;
-        for (int j = 0; j < l.nparts; ++j) {
-            const ConvArgs& y = l.parts[j];
-            snprintf(buf, sizeof buf, "[B%d t%d pr%d d%d g%d/%d pg%d ns%d]", y.B, y.tile, y.pair, y.dual, y.gemm, y.gemm_tm, y.pers_groups,
-                     y.nsplit);
-            s += buf;
-        }
+        const ConvArgs& y = l.args;
+        snprintf(buf, sizeof buf, "[B%d t%d pr%d g%d/%d ns%d]", y.B, y.tile, y.pair, y.gemm, y.gemm_tm, y.nsplit);
+        s += buf;
     }
     return s;
 }
@@ -132,7 +129,6 @@ static void check_case(const Case& k) {
             g_cov["split-K"]++;
             CHECK((size_t)x.nsplit * x.B * x.Cout * HW <= k.partial_floats, "split-K workspace");
         }
-        if (x.pers_groups) g_cov["persistent"]++;
         // statistics route
         g_cov["route " + std::to_string(l.stats)]++;
         if (x.st_part) {
@@ -149,7 +145,6 @@ static void check_case(const Case& k) {
                 CHECK(p.keep_ntile == l.ntile, "kept partials without keep_ntile");
                 g_cov[k.lane_s0 ? "kept, lane 1" : "kept, lane 0"]++;
             }
-            if (x.st_kind == ST_TAN || x.st_kind == ST_COT) CHECK(!x.pers_groups && !x.dual, "linear statistics on pers / dual");
         } else {
             CHECK(l.stats != SR_EPI && l.stats != SR_KEEP, "epilogue route without a sink");
         }
@@ -162,30 +157,24 @@ static void check_case(const Case& k) {
             CHECK(x.res == nullptr && x.in2 == b.sc.in && x.bias2 == b.sc.bias, "kcat operands");
         }
         if (p.sc_first) CHECK(x.res == b.sc.out + (x.out - b.a.out), "residual of a shortcut run first");
-        // kernels of the launch
-        int pb = 0;
-        for (int j = 0; j < l.nparts; ++j) {
-            const ConvArgs& y = l.parts[j];
-            pb += y.B;
-            g_cov["tile " + std::to_string(y.tile)]++;
-            if (y.pair) {
-                g_cov["tap-pair"]++;
-                CHECK(k.prec == 1 && k.taps == 9 && y.tile == 5 && y.nsplit == 1 && !y.dual && !y.pers_groups && !y.Cin2, "pair");
-            }
-            if (y.dual) g_cov["dual"]++;
-            if (y.cot_d) CHECK(p.cot, "cot_d on a launch although declined");
-            // the profile name is the kernel that runs
-            const std::string name = conv_variant_name(y, k.taps, k.prec);
-            if (!y.gemm && !y.Cin2 && !y.pers_groups && !y.pair && !y.dual) {
-                const std::string want = std::string(k.prec == 0 ? "conv_mfma_f32" : k.prec == 1 ? "conv_mfma_bf16x3" : "conv_mfma_f16") +
-                                         "<" + std::to_string(k.taps) + "," + kTileName[y.tile] + ",";
-                CHECK(name.compare(0, want.size(), want) == 0, "name %s, tile %d", name.c_str(), y.tile);
-                if (k.taps == 1 && y.tile == 0 && k.prec) g_cov["1x1 named on the 128 x 128 tile"]++;
-            }
-            if (y.gemm) CHECK(name.find("conv_gemm_bf16x3") == 0, "gemm name %s", name.c_str());
-            if (y.pair) CHECK(name.find("conv_pair_bf16x3") == 0, "pair name %s", name.c_str());
+        // kernel of the launch
+        const ConvArgs& y = x;
+        g_cov["tile " + std::to_string(y.tile)]++;
+        if (y.pair) {
+            g_cov["tap-pair"]++;
+            CHECK(k.prec == 1 && k.taps == 9 && y.tile == 5 && y.nsplit == 1 && !y.Cin2, "pair");
         }
-        CHECK(pb == x.B, "parts cover %d of %d samples", pb, x.B);
+        if (y.cot_d) CHECK(p.cot, "cot_d on a launch although declined");
+        // the profile name is the kernel that runs
+        const std::string name = conv_variant_name(y, k.taps, k.prec);
+        if (!y.gemm && !y.Cin2 && !y.pair) {
+            const std::string want = std::string(k.prec == 0 ? "conv_mfma_f32" : k.prec == 1 ? "conv_mfma_bf16x3" : "conv_mfma_f16") +
+                                     "<" + std::to_string(k.taps) + "," + kTileName[y.tile] + ",";
+            CHECK(name.compare(0, want.size(), want) == 0, "name %s, tile %d", name.c_str(), y.tile);
+            if (k.taps == 1 && y.tile == 0 && k.prec) g_cov["1x1 named on the 128 x 128 tile"]++;
+        }
+        if (y.gemm) CHECK(name.find("conv_gemm_bf16x3") == 0, "gemm name %s", name.c_str());
+        if (y.pair) CHECK(name.find("conv_pair_bf16x3") == 0, "pair name %s", name.c_str());
     }
     // tail-probe split
     if (p.nl == 2) {
@@ -194,7 +183,7 @@ static void check_case(const Case& k) {
         const long nb = m.B;
         CHECK(m.B + t.B == k.B && m.nsplit == 1 && t.nsplit >= 2 && t.nsplit <= 4 && p.l[1].s0 == nb, "tail split %d + %d, ns %d / %d", m.B,
               t.B, m.nsplit, t.nsplit);
-        CHECK(!m.Cin2 && !m.gemm && !m.pers_groups && k.prec >= 1, "tail split of a kcat / gemm / pers launch");
+        CHECK(!m.Cin2 && !m.gemm && k.prec >= 1, "tail split of a kcat / gemm launch");
         const ConvArgs& a = m;
         CHECK(t.in == a.in + nb * a.in_bs && t.out == a.out + nb * a.out_bs && t.prim == a.prim + nb * a.prim_bs &&
                   t.sc == a.sc + nb * a.scsh_bs && t.sh == a.sh + nb * a.scsh_bs && t.mr == a.mr + nb * a.mr_bs &&
@@ -316,13 +305,11 @@ int main() {
               "tail split: nl %d, B %d + %d, ns %d", p.nl, p.l[0].args.B, p.l[1].args.B, p.l[1].args.nsplit);
     }
     // every kind of decision is reached
-    const bool diag = getenv("LOCO_CONV_DUAL") && getenv("LOCO_CONV_PERS");
     std::string need[] = {"prec0", "prec1", "prec2", "gemm", "split-K", "tail split", "kcat", "shortcut first", "tap-pair",
                           "route 0", "route 1", "route 2", "route 3", "route 4", "stats over the whole batch", "kept, lane 0",
                           "kept, lane 1", "two lanes kept", "cot taken", "cot declined", "tile 0", "tile 1", "tile 2", "tile 3",
                           "tile 5", "1x1 named on the 128 x 128 tile"};
     for (const std::string& s : need) CHECK(g_cov[s] > 0, "never reached: %s", s.c_str());
-    if (diag) for (const char* s : {"dual", "persistent"}) CHECK(g_cov[s] > 0, "never reached: %s", s);
     for (const auto& kv : g_cov) printf("%-36s %ld\n", kv.first.c_str(), kv.second);
     printf("%s: %d failure(s)\n", g_fail ? "FAILED" : "ok", g_fail);
     return g_fail ? 1 : 0;

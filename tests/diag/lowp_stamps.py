@@ -1,4 +1,4 @@
-"""Diagnostic (by hand; needs tests/diag/lib/libloco_hip_stamp.so = the diag build with conv_bf16_inst_c.hip / _i.hip compiled
+"""Diagnostic (by hand; needs tests/diag/lib/libloco_hip_stamp.so = the diag build with conv_bf16_inst_c.hip compiled
 -DLOCO_DUAL_STAMP): where a 128 x 256 tile of the lock-step kernel spends its cycles.  Phase stamps (s_memtime, wave 0) of every
 workgroup of one launch of the Cin -> 128 tangent conv at 256^2, 5 probes: 0 start | 1 index setup done | 2 prologue done |
 3 stage loop done | 4 epilogue done.  LOCO_DUAL_WHATIF bits: 2 halo loads collapsed, 4 weight DMAs collapsed, 8 no conversions."""
@@ -9,7 +9,6 @@ import torch
 import loco_edit_amd  # noqa
 import loco_edit_amd.hip as H
 from loco_edit_amd.config import CELEBA_DDPM, synth_params
-os.environ["LOCO_CONV_DUAL"] = "0"
 eng = H.LocoEngine(CELEBA_DDPM, max_batch=8)
 eng.load_state_dict(synth_params(CELEBA_DDPM, 0))
 eng.set_precision("bf16x3")

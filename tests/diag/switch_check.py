@@ -1,7 +1,9 @@
-"""Diagnostic (by hand): the dual-probe conv tile against the 128 x 256 tile, bit for bit.  Runs one forward batch, one J V and
-one U^T J of B samples / probes at 256 x 256 in a child process per setting of a 0 / 1 environment switch (default
-LOCO_CONV_DUAL; also LOCO_TSTATS_PB) and compares the outputs (same products in the same order: expected difference exactly 0).
-      python3 tests/diag/dual_check.py [B] [cfg] [ENV_NAME]"""
+"""Diagnostic (by hand, and the child script of tests/test_gpu_parity.py): the two settings of a 0 / 1 environment switch against
+each other.  Runs one forward batch, one J V and one U^T J of B samples / probes at 256 x 256 in a child process per setting
+(the switches are read once per process; default LOCO_CONV_PAIR: the tap-pair kernel against the 32x32x16 kernel) and compares
+the outputs: bit for bit (same products in the same order: expected difference exactly 0), or SWITCH_CHECK_RTOL > 0 for a kernel
+with another summation order (rel-L2 per output).
+      python3 tests/diag/switch_check.py [B] [cfg] [ENV_NAME]"""
 import os, shutil, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 if len(sys.argv) > 1 and sys.argv[1] == "--child":
@@ -32,20 +34,20 @@ if len(sys.argv) > 1 and sys.argv[1] == "--child":
 import torch
 B = sys.argv[1] if len(sys.argv) > 1 else "5"
 cfg = sys.argv[2] if len(sys.argv) > 2 else "CELEBA_DDPM"
-ENVN = sys.argv[3] if len(sys.argv) > 3 else "LOCO_CONV_DUAL"      # the 0 / 1 switch under test
+ENVN = sys.argv[3] if len(sys.argv) > 3 else "LOCO_CONV_PAIR"      # the 0 / 1 switch under test
 res = {}
-SETTINGS = ("0", "1") if os.environ.get("DUAL_CHECK_SKIP_REPEAT") else ("0", "0b", "1")      # "0b": the default twice (run-to-run)
-TMP = tempfile.mkdtemp(prefix="dual_check_")      # private to this run: concurrent runs must not read each other's files
+SETTINGS = ("0", "1") if os.environ.get("SWITCH_CHECK_SKIP_REPEAT") else ("0", "0b", "1")      # "0b": the default twice (run-to-run)
+TMP = tempfile.mkdtemp(prefix="switch_check_")      # private to this run: concurrent runs must not read each other's files
 for v in SETTINGS:
     out = os.path.join(TMP, f"{v}.pt")
-    env = dict(os.environ, **{ENVN: (os.environ.get("DUAL_CHECK_ON", "1") if v[0] == "1" else "0")})      # DUAL_CHECK_ON: the value that means `on`
+    env = dict(os.environ, **{ENVN: (os.environ.get("SWITCH_CHECK_ON", "1") if v[0] == "1" else "0")})      # SWITCH_CHECK_ON: the value that means `on`
     subprocess.run([sys.executable, os.path.abspath(__file__), "--child", B, cfg, out], check=True, env=env)
     res[v] = torch.load(out)
 shutil.rmtree(TMP, ignore_errors=True)
 for k in (res["0"] if "0b" in res else ()):
-    print(f"{k}: run-to-run difference of the 128 x 256 tile itself: {(res['0'][k] - res['0b'][k]).abs().max().item():.3e}")
+    print(f"{k}: run-to-run difference of setting 0 itself: {(res['0'][k] - res['0b'][k]).abs().max().item():.3e}")
 ok = True
-RTOL = float(os.environ.get("DUAL_CHECK_RTOL", "0"))      # > 0: a kernel with another summation order (rel-L2 per output <= RTOL)
+RTOL = float(os.environ.get("SWITCH_CHECK_RTOL", "0"))      # > 0: a kernel with another summation order (rel-L2 per output <= RTOL)
 for k in res["0"]:
     a, b = res["0"][k], res["1"][k]
     d = (a - b).abs().max().item()
