@@ -436,6 +436,52 @@ int  loco_sam_profile_read(loco_sam* t, float* ms4);
 const char* loco_sam_last_error(loco_sam* t);
 void loco_sam_destroy(loco_sam* t);
 
+/* --- CLIP image encoder (scores of the text-guided edits) ---
+ * The CLIPVisionModelWithProjection of transformers: patch embedding (no bias) + class token + learned position embedding,
+ * pre_layrnorm, `layers` pre-LN blocks (LayerNorm -> full multi-head self-attention, scale head_dim^-0.5 -> residual;
+ * LayerNorm -> fc1 -> act -> fc2 -> residual), post_layernorm of the class token, visual_projection.  Exact fp32 throughout
+ * (independent of loco_set_precision / LOCO_PRECISION), sums in a fixed order, no host synchronisation inside an encode.  Its
+ * own handle; the workspace for max_images images is allocated at create. */
+typedef struct loco_clipvis loco_clipvis;
+typedef struct loco_clipvis_cfg {
+    int32_t image_size;      /* S: side of pixel_values (224) */
+    int32_t patch_size;      /* 14 / 16 / 32; the token grid is G = S / patch_size, T = 1 + G^2 tokens per image */
+    int32_t width;           /* hidden_size D: 768 (ViT-B), 1024 (ViT-L) */
+    int32_t layers;          /* num_hidden_layers: 12 / 24 */
+    int32_t heads;           /* num_attention_heads: 12 / 16; head width hd = D / heads <= 106 (the attention kernel's LDS,
+                              * 4 (144 hd + 1088) bytes, must fit 64 KiB); loco_clipvis_create refuses the rest */
+    int32_t mlp_dim;         /* intermediate_size: 4 D */
+    int32_t projection_dim;  /* P: rows of visual_projection (512 / 768) */
+    int32_t act;             /* hidden_act: 0 quick_gelu x sigmoid(1.702 x) (the OpenAI checkpoints), 1 exact erf gelu */
+    float   ln_eps;          /* layer_norm_eps (1e-5) */
+    float   image_mean[3];   /* loco_clipvis_preprocess: the normalisation of CLIPImageProcessor */
+    float   image_std[3];    /* (0.48145466, 0.4578275, 0.40821073) / (0.26862954, 0.26130258, 0.27577711) */
+} loco_clipvis_cfg;
+/* max_images: the largest n one loco_clipvis_encode call may carry (the device workspace is sized for it). */
+int  loco_clipvis_create(const loco_clipvis_cfg* cfg, int32_t device, int32_t max_images, loco_clipvis** out);
+/* One call per state_dict entry in CLIPVisionModelWithProjection naming without the `vision_model.` prefix
+ * (embeddings.class_embedding, embeddings.patch_embedding.weight, embeddings.position_embedding.weight, pre_layrnorm.* (sic),
+ * encoder.layers.{i}.{layer_norm1,self_attn.{q,k,v,out}_proj,layer_norm2,mlp.fc1,mlp.fc2}.*, post_layernorm.*,
+ * visual_projection.weight).  `host`: fp32 values, a host or a device pointer. */
+int  loco_clipvis_load_param(loco_clipvis* t, const char* name, const float* host, const int64_t* shape, int32_t ndim);
+int  loco_clipvis_params_missing(loco_clipvis* t);
+/* out_dev[n][3][S][S] (fp32) from frames_dev[n][H][W][3] (uint8, device), the steps of CLIPImageProcessor in float arithmetic:
+ * shortest edge -> S (the other edge int(long S / short)) by bicubic interpolation with antialiasing (a = -0.5, support
+ * 2 max(scale, 1), weights normalised per output pixel: torch's interpolate(mode="bicubic", antialias=True)), centre crop
+ * S x S at offset (size - S) / 2, / 255, (v - image_mean) / image_std.  One pass per axis, only the cropped columns and rows
+ * are computed; the row buffer between the passes belongs to the handle and grows on demand (a growing call waits for the
+ * device).  PIL, through which transformers resizes, rounds to uint8 after each pass: its result differs by up to a few grey
+ * levels where a resize happens.  n is not bound by max_images. */
+int  loco_clipvis_preprocess(loco_clipvis* t, const uint8_t* frames_dev, int32_t n, int32_t H, int32_t W, float* out_dev, void* stream);
+/* embeds_dev[n][P] = the un-normalised image_embeds of pixel_values[n][3][S][S] (device), 1 <= n <= max_images.  Optional
+ * (NULL to skip): hidden_dev[n][T][D] = last_hidden_state (the last block's output, before post_layernorm), pooled_dev[n][D] =
+ * pooler_output (post_layernorm of the class token).  Each image's rows are bit-identical whatever n and its position. */
+int  loco_clipvis_encode(loco_clipvis* t, const float* pixel_values, int32_t n, float* embeds_dev, float* hidden_dev, float* pooled_dev,
+                         void* stream);
+/* Message of the last failed call on t; t == NULL: of the last failed loco_clipvis_create. */
+const char* loco_clipvis_last_error(loco_clipvis* t);
+void loco_clipvis_destroy(loco_clipvis* t);
+
 #ifdef __cplusplus
 }
 #endif

@@ -121,6 +121,15 @@ def build_parser():
                    help='Segment Anything model that produces mask/mask.pt on the GPU when it is missing: a local SamModel '
                         'folder (config.json + model.safetensors or pytorch_model.bin) or a checkpoint file in SamModel naming. '
                         'Nothing is downloaded (--mask_model_name stays a name only). Empty: mask/mask.pt must exist')
+    p.add_argument('--clip_model_path', type=str, default='',
+                   help='T-LOCO semantic edits: CLIP model that scores the returned frames on the GPU (image-text cosine with '
+                        '--for_prompt / --edit_prompt, cosine with the unedited frame, directional similarity) into '
+                        '<result_folder>/<EXP_NAME>_clip.json: a local transformers CLIPModel folder (config.json + '
+                        'model.safetensors or pytorch_model.bin, its tokenizer files or --tokenizer_path) or a state_dict file. '
+                        'Empty: no scores, nothing else changes')
+    p.add_argument('--clip_preprocess', type=str, default='device', choices=['pil', 'device'],
+                   help="--clip_model_path: 'device' resizes the frames on the GPU in float arithmetic, 'pil' on the host with PIL "
+                        "(CLIPImageProcessor's input exactly)")
     p.add_argument('--lcm_timesteps', type=str, default=None, choices=['linspace', 'stride'],
                    help='latent-consistency models (required for them): which published LCMScheduler.set_timesteps rule picks the '
                         "N sampling timesteps out of the 50 training ones -- 'linspace' (current diffusers: N = 4 gives "

@@ -15,7 +15,12 @@ undefined names).  This module is a working restatement of that intent:
   from a file (``LOCO_LPIPS_WEIGHTS`` / ``--lpips_weights``) and without one it raises instead of returning a
   made-up number.
 
-Plain torch on the host: evaluation is not on the hot path and there is no ``torchmetrics`` here to pin the
+* ``clip`` / ``clip_dir``: did a text-guided edit do what the edit prompt asked -- the image-text cosine of the edited image
+  with ``--edit_prompt``, and the directional similarity cos(E(edited) - E(original), E(edit prompt) - E(source prompt)) --
+  from a CLIP model on the HIP engine (``clip_score.py``, ``csrc/clipvis.hip``).  No CLIP checkpoint is available offline:
+  the model comes from ``--clip_model_path`` and without one it raises.
+
+SSIM, masked MSE and LPIPS are plain torch on the host: evaluation is not on the hot path and there is no ``torchmetrics`` here to pin the
 SSIM against (parity unpinned; the unit tests check the defining properties).
 """
 from __future__ import annotations
@@ -128,12 +133,48 @@ def lpips(preds: torch.Tensor, target: torch.Tensor, weights=None, normalize: bo
 
 
 METRICS = {"ssim": ssim, "mmse": masked_mse, "lpips": lpips}
+CLIP_METRICS = ("clip", "clip_dir")
 
 
 def _load_png(path: str) -> torch.Tensor:
     from PIL import Image
     a = np.asarray(Image.open(path).convert("RGB"), dtype=np.float32)
     return torch.from_numpy(a).permute(2, 0, 1).unsqueeze(0)
+
+
+def _load_png_uint8(path: str) -> torch.Tensor:
+    from PIL import Image
+    return torch.from_numpy(np.asarray(Image.open(path).convert("RGB"), dtype=np.uint8).copy())
+
+
+def evaluate_clip_folders(folder_preds: str, folder_original: str, metric: str = "clip", clip_model_path: str = "", for_prompt: str = "",
+                          edit_prompt: str = "", clip_preprocess: str = "pil", tokenizer_path: str = "", scorer=None) -> dict:
+    """Pair ``*.png`` by file name and average a CLIP score of the edited images: ``clip`` = cosine of the edited image with
+    ``edit_prompt``, ``clip_dir`` = cos(E(edited) - E(original), E(edit_prompt) - E(for_prompt)).  ``values`` holds per pair
+    all four numbers of ``clip_score.ClipScorer.score``."""
+    from .clip_score import load_clip, score_embeddings
+    if metric not in CLIP_METRICS:
+        raise ValueError("eval_metric choice: " + ", ".join(CLIP_METRICS))
+    if scorer is None:
+        scorer = load_clip(clip_model_path, tokenizer_path=tokenizer_path or None, preprocess=clip_preprocess)     # raises without a path
+    if not edit_prompt or (metric == "clip_dir" and not for_prompt):
+        raise ValueError("clip needs --edit_prompt, clip_dir --for_prompt and --edit_prompt")
+    pp = sorted(glob.glob(os.path.join(folder_preds, "*.png")))
+    tp = sorted(glob.glob(os.path.join(folder_original, "*.png")))
+    if len(pp) != len(tp) or not pp:
+        raise ValueError(f"{len(pp)} predictions vs {len(tp)} originals")
+    emb = scorer.text_embeds([p for p in (for_prompt, edit_prompt) if p])
+    e_for, e_edit = (emb[0], emb[1]) if for_prompt else (None, emb[0])
+    key = "clip_edit" if metric == "clip" else "directional"
+    recs = []
+    for a, b in zip(pp, tp):
+        if os.path.basename(a) != os.path.basename(b):
+            raise ValueError("pairs not match")
+        img = torch.cat([scorer.image_embeds(_load_png_uint8(b)[None]), scorer.image_embeds(_load_png_uint8(a)[None])])
+        recs.append(dict(score_embeddings(img, 0, e_for, e_edit)[1], file=os.path.basename(a)))
+    vals = [r[key] for r in recs]
+    return {"metric": metric, "n": len(vals), "mean": float(np.mean(vals)), "values": vals, "records": recs,
+            "clip_model_path": clip_model_path, "clip_preprocess": scorer.preprocess_mode}
 
 
 def evaluate_folders(folder_preds: str, folder_original: str, metric: str = "ssim", mask_folder: str = "",
@@ -170,7 +211,18 @@ def main(argv=None):
     ap.add_argument("--mask_folder", type=str, default="")
     ap.add_argument("--outside_mask", action="store_true", help="mmse over ~mask (the protected region)")
     ap.add_argument("--lpips_weights", type=str, default="", help="state dict: AlexNet features + lpips heads")
+    ap.add_argument("--clip_model_path", type=str, default="", help="clip / clip_dir: a transformers CLIPModel folder or file")
+    ap.add_argument("--tokenizer_path", type=str, default="", help="clip / clip_dir: tokenizer folder when the model folder has none")
+    ap.add_argument("--for_prompt", type=str, default="", help="clip_dir: the source prompt")
+    ap.add_argument("--edit_prompt", type=str, default="", help="clip / clip_dir: the edit prompt")
+    ap.add_argument("--clip_preprocess", type=str, default="pil", choices=("pil", "device"),
+                    help="pil: resize on the host with PIL (CLIPImageProcessor's input exactly); device: on the GPU in float arithmetic")
     a = ap.parse_args(argv)
+    if a.eval_metric in CLIP_METRICS:
+        r = evaluate_clip_folders(a.folder_preds, a.folder_original, a.eval_metric, a.clip_model_path, a.for_prompt, a.edit_prompt,
+                                  a.clip_preprocess, a.tokenizer_path)
+        print(f"{r['metric']}: {r['mean']:.6f} over {r['n']} pairs")
+        return r
     r = evaluate_folders(a.folder_preds, a.folder_original, a.eval_metric, a.mask_folder, a.outside_mask,
                          a.lpips_weights or None)
     print(f"{r['metric']}: {r['mean']:.6f} over {r['n']} pairs")

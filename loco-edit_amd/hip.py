@@ -36,6 +36,8 @@ SYMBOLS = [
     "loco_diffedit_mask", "loco_cfg_masked_step", "loco_set_time_cond", "loco_lcm_step",
     "loco_sam_create", "loco_sam_load_param", "loco_sam_params_missing", "loco_sam_encode", "loco_sam_profile",
     "loco_sam_profile_read", "loco_sam_last_error", "loco_sam_destroy",
+    "loco_clipvis_create", "loco_clipvis_load_param", "loco_clipvis_params_missing", "loco_clipvis_preprocess",
+    "loco_clipvis_encode", "loco_clipvis_last_error", "loco_clipvis_destroy",
 ]
 
 # threshold rules of loco_diffedit_mask (include/loco_hip.h)
@@ -86,6 +88,12 @@ class LocoSamCfg(C.Structure):
     _fields_ = [("image_size", C.c_int32), ("patch_size", C.c_int32), ("width", C.c_int32), ("depth", C.c_int32),
                 ("heads", C.c_int32), ("mlp_dim", C.c_int32), ("window_size", C.c_int32), ("num_global", C.c_int32),
                 ("global_attn", C.c_int32 * SAM_MAX_GLOBAL), ("out_channels", C.c_int32), ("ln_eps", C.c_float)]
+
+
+class LocoClipVisCfg(C.Structure):
+    _fields_ = [("image_size", C.c_int32), ("patch_size", C.c_int32), ("width", C.c_int32), ("layers", C.c_int32),
+                ("heads", C.c_int32), ("mlp_dim", C.c_int32), ("projection_dim", C.c_int32), ("act", C.c_int32),
+                ("ln_eps", C.c_float), ("image_mean", C.c_float * 3), ("image_std", C.c_float * 3)]
 
 
 def library_path() -> str:
@@ -176,6 +184,16 @@ def load_library():
         lib.loco_sam_last_error.restype = C.c_char_p
         lib.loco_sam_destroy.argtypes = [vp]
         lib.loco_sam_destroy.restype = None
+    if hasattr(lib, "loco_clipvis_create"):
+        lib.loco_clipvis_create.argtypes = [C.POINTER(LocoClipVisCfg), i32, i32, C.POINTER(vp)]
+        lib.loco_clipvis_load_param.argtypes = [vp, C.c_char_p, vp, C.POINTER(i64), i32]
+        lib.loco_clipvis_params_missing.argtypes = [vp]
+        lib.loco_clipvis_preprocess.argtypes = [vp, vp, i32, i32, i32, vp, vp]
+        lib.loco_clipvis_encode.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+        lib.loco_clipvis_last_error.argtypes = [vp]
+        lib.loco_clipvis_last_error.restype = C.c_char_p
+        lib.loco_clipvis_destroy.argtypes = [vp]
+        lib.loco_clipvis_destroy.restype = None
     if hasattr(lib, "loco_bench_conv"):          # diag build only
         lib.loco_bench_conv.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(f32), vp]
         lib.loco_debug_tensor.argtypes = [vp, C.c_char_p, vp, i64, vp]
@@ -894,3 +912,61 @@ class LocoSamEngine(_EncoderEngine):
         ms = (C.c_float * 4)()
         self._check(self.lib.loco_sam_profile_read(self._t, ms), "loco_sam_profile_read")
         return dict(zip(("gemm", "window_attn", "global_attn", "other"), [float(v) for v in ms]))
+
+
+class LocoClipVisionEngine(_EncoderEngine):
+    """The CLIP image encoder (= loco_clipvis, include/loco_hip.h): parameters and the workspace of `max_images` images on
+    the device.  `cfg` is a ``clip_score.ClipVisionConfig``; ``preprocess`` turns uint8 frames [n, H, W, 3] into the
+    pixel_values [n, 3, S, S] of CLIPImageProcessor in float arithmetic, ``encode`` turns pixel_values into the
+    un-normalised image_embeds [n, P], exact fp32.  ``load_state_dict`` takes the names of CLIPVisionModelWithProjection
+    without the ``vision_model.`` prefix (clip_score.split_clip_state_dict produces them)."""
+    _prefix, _label = "loco_clipvis", "CLIP image encoder"
+
+    def __init__(self, cfg, max_images: int = 8, device: Optional[torch.device] = None):
+        self._open(device)
+        self.cfg, self.max_images = cfg, int(max_images)
+        c = LocoClipVisCfg(image_size=cfg.image_size, patch_size=cfg.patch_size, width=cfg.width, layers=cfg.layers, heads=cfg.heads,
+                           mlp_dim=cfg.mlp_dim, projection_dim=cfg.projection_dim, act={"quick_gelu": 0, "gelu": 1}[cfg.act],
+                           ln_eps=cfg.ln_eps)
+        for i in range(3):
+            c.image_mean[i], c.image_std[i] = cfg.image_mean[i], cfg.image_std[i]
+        self._create("loco_clipvis_create", c, self.max_images)
+
+    @property
+    def tokens(self) -> int:
+        return 1 + (self.cfg.image_size // self.cfg.patch_size) ** 2
+
+    def preprocess(self, frames_uint8: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """frames [n, H, W, 3] or [H, W, 3] (uint8, host or device) -> pixel_values [n, 3, S, S] fp32 on the device."""
+        fr = torch.as_tensor(frames_uint8)
+        if fr.dim() == 3:
+            fr = fr[None]
+        if fr.dim() != 4 or fr.shape[-1] != 3 or fr.dtype != torch.uint8 or 0 in fr.shape:
+            raise ValueError(f"frames must be uint8 [n, H, W, 3], got {fr.dtype} {tuple(fr.shape)}")
+        fr = fr.to(self.device).contiguous()
+        n, H, W, S = fr.shape[0], fr.shape[1], fr.shape[2], self.cfg.image_size
+        if out is None:
+            out = torch.empty(n, 3, S, S, device=self.device, dtype=torch.float32)
+        _chk_dev(out)
+        if tuple(out.shape) != (n, 3, S, S):
+            raise ValueError(f"out must be [{n}, 3, {S}, {S}], got {tuple(out.shape)}")
+        with torch.cuda.device(self.device):
+            self._check(self.lib.loco_clipvis_preprocess(self._t, _ptr(fr), n, H, W, _ptr(out), _stream()), "loco_clipvis_preprocess")
+        return out
+
+    def encode(self, pixel_values: torch.Tensor, want_hidden: bool = False):
+        """pixel_values [n, 3, S, S] (fp32, host or device), n <= max_images -> image_embeds [n, P] on the device;
+        ``want_hidden``: (image_embeds, last_hidden_state [n, T, D], pooler_output [n, D])."""
+        S, D, P = self.cfg.image_size, self.cfg.width, self.cfg.projection_dim
+        pv = torch.as_tensor(pixel_values)
+        if pv.dim() != 4 or tuple(pv.shape[1:]) != (3, S, S) or pv.shape[0] < 1:
+            raise ValueError(f"pixel_values must be [n, 3, {S}, {S}], got {tuple(pv.shape)}")
+        n = pv.shape[0]
+        pv = pv.to(device=self.device, dtype=torch.float32).contiguous()
+        emb = torch.empty(n, P, device=self.device, dtype=torch.float32)
+        hid = torch.empty(n, self.tokens, D, device=self.device, dtype=torch.float32) if want_hidden else None
+        pool = torch.empty(n, D, device=self.device, dtype=torch.float32) if want_hidden else None
+        with torch.cuda.device(self.device):
+            self._check(self.lib.loco_clipvis_encode(self._t, _ptr(pv), n, _ptr(emb), _ptr(hid), _ptr(pool), _stream()),
+                        "loco_clipvis_encode")
+        return (emb, hid, pool) if want_hidden else emb

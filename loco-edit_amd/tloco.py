@@ -32,6 +32,7 @@ encode of for / edit / null / neg / inv; a driver's ``edit_prompt`` re-encodes),
 """
 from __future__ import annotations
 
+import json
 import os
 import zlib
 from typing import Dict, List, Optional, Tuple
@@ -285,6 +286,7 @@ class CFGJacobianOperator:
 
 class EditDeepFloydIF(object):
     text_encoder = None
+    _clip = None                                # the CLIP scorer of --clip_model_path, created on first use, once per object
     BRANCH_NAMES = ("for", "edit", "null")      # one engine context per prompt of the guidance (a subclass may run fewer)
 
     def __init__(self, args):
@@ -722,13 +724,62 @@ class EditDeepFloydIF(object):
                                    edit_prompt_emb=self.edit_prompt_emb, null_prompt_emb=self.null_prompt_emb, mode="null+(for-null)")
         return x0[0].detach().cpu().numpy()
 
-    def _walk(self, original_xt, v_row, vis_num):
-        """+/- walk of edit.py:1840-1860 in one kernel (frames x + j*scale*step*v)."""
+    def _walk_alphas(self, vis_num) -> List[float]:
         S = self.x_space_guidance_num_step
         idxs = [0, S] if vis_num == 1 else list(range(0, S + 1, (S + 1) // vis_num))
         step = self.x_space_guidance_scale * self.x_space_guidance_edit_step
-        alphas = [-j * step for j in reversed(idxs)][:-1] + [j * step for j in idxs]
-        return self.engine.edit_axpy(original_xt.contiguous(), v_row.contiguous().view(-1), alphas)
+        return [-j * step for j in reversed(idxs)][:-1] + [j * step for j in idxs]
+
+    def _walk(self, original_xt, v_row, vis_num):
+        """+/- walk of edit.py:1840-1860 in one kernel (frames x + j*scale*step*v)."""
+        return self.engine.edit_axpy(original_xt.contiguous(), v_row.contiguous().view(-1), self._walk_alphas(vis_num))
+
+    # ------------------------------------------------------------------ CLIP scores of the returned frames (--clip_model_path)
+    @property
+    def clip_scoring(self) -> bool:
+        return bool(getattr(self.args, "clip_model_path", ""))
+
+    def _decoded_as(self, suffix, decode):
+        """`decode()` under EXP_NAME + suffix, so that the image it saves does not take the edit's file name."""
+        name = self.EXP_NAME
+        self.EXP_NAME = name + suffix
+        try:
+            return decode()
+        finally:
+            self.EXP_NAME = name
+
+    def _score_clip(self, frames, alphas=None, original_frame=None):
+        """Scores uint8 frames [n, H, W, 3] with the CLIP model of --clip_model_path (clip_score.ClipScorer.score) and writes
+        <result_folder>/<EXP_NAME>_clip.json from the main rank: the model path, the preprocessing mode, both prompts and per
+        returned frame the walk's alpha with clip_for / clip_edit / image_sim / directional.  The original is the walk's
+        alpha = 0 frame, or `original_frame` [1, H, W, 3] (the unedited latent decoded once more) where the ablation returns none:
+        its record is kept apart under "original_frame", the frames' alphas are null.  Returns the JSON's dict (None off the main
+        rank and without the flag)."""
+        if not self.clip_scoring or frames is None or not self.sharder.is_main:
+            return None
+        if self._clip is None:
+            from .clip_score import load_clip
+            self._clip = load_clip(self.args.clip_model_path, tokenizer_path=getattr(self.args, "tokenizer_path", "") or None,
+                                   device=self.device, preprocess=getattr(self.args, "clip_preprocess", "device"))
+        frames = torch.as_tensor(frames)
+        n = frames.shape[0]
+        if original_frame is not None:
+            alphas, oi = [None] * n, 0
+            frames = torch.cat([torch.as_tensor(original_frame).to(frames.device), frames])
+        else:
+            alphas = [float(a) for a in alphas]
+            if len(alphas) != n or 0.0 not in alphas:
+                raise ValueError(f"{n} frames, walk alphas {alphas}: no unedited frame to score against")
+            oi = alphas.index(0.0)
+        recs = self._clip.score(frames, oi, self.for_prompt, self.edit_prompt)
+        out = {"clip_model_path": self.args.clip_model_path, "clip_preprocess": self._clip.preprocess_mode,
+               "for_prompt": self.for_prompt, "edit_prompt": self.edit_prompt, "exp_name": self.EXP_NAME,
+               "original": "alpha=0 frame" if original_frame is None else "the unedited latent, decoded once more",
+               "original_frame": None if original_frame is None else recs[0],
+               "frames": [dict(alpha=a, **r) for a, r in zip(alphas, recs[0 if original_frame is None else 1:])]}
+        with open(os.path.join(self.result_folder, f"{self.EXP_NAME}_clip.json"), "w") as f:
+            json.dump(out, f, indent=1)
+        return out
 
     def _xT(self):
         if self.dataset_name != 'Random':
@@ -849,6 +900,7 @@ class EditDeepFloydIF(object):
                 xb = self._walk(original_xt, vT[pc_idx, :], vis_num)
             x0 = self.DDPMforwardsteps(xb, t_start_idx=self.edit_t_idx, t_end_idx=-1, for_prompt_emb=F, edit_prompt_emb=E,
                                        null_prompt_emb=N, mode="null+(for-null)")
+            self._score_clip(x0, alphas=self._walk_alphas(vis_num))
         elif self.ablation_method == "sega":
             self.EXP_NAME = f'sega-edit_prompt-{self.edit_prompt}-mask_type-{self.mask_type}-select_mask{mask_index}'
             x0 = self.DDPMforwardsteps(xt, t_start_idx=self.edit_t_idx, t_end_idx=-1, for_prompt_emb=F, edit_prompt_emb=E,
@@ -859,4 +911,10 @@ class EditDeepFloydIF(object):
                                              null_prompt_emb=N, mask=mask)
         else:
             raise NotImplementedError(f"ablation_method {self.ablation_method!r}")
+        if self.clip_scoring and self.ablation_method in ("sega", "diffedit"):
+            # these return no unedited frame: xt decoded once more under the `for` prompt (on every rank: the sampler is shared)
+            x_orig = self._decoded_as("_clip_original", lambda: self.DDPMforwardsteps(
+                xt, t_start_idx=self.edit_t_idx, t_end_idx=-1, for_prompt_emb=F, edit_prompt_emb=E, null_prompt_emb=N,
+                mode="null+(for-null)"))
+            self._score_clip(x0, original_frame=x_orig)
         return x0

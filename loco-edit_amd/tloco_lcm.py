@@ -305,7 +305,14 @@ class EditLatentConsistency(EditStableDiffusion):
         assert t_idx == self.edit_t_idx
         if self.use_sega:
             self.EXP_NAME = f'sega_{self.edit_t_idx}T-{op}-block_{block_idx}_pos-edit_prompt-{self.edit_prompt}'
-            return self.LCMforwardsteps(zt, t_start_idx=self.edit_t_idx, t_end_idx=-1, prompt=self.edit_prompt)
+            out = self.LCMforwardsteps(zt, t_start_idx=self.edit_t_idx, t_end_idx=-1, prompt=self.edit_prompt)
+            if self.clip_scoring and not non_semantic:
+                # no unedited frame comes back: zt decoded once more under the `for` prompt, after the edit (the sampler draws
+                # its re-injected noise from the global generator: the edit's frames are those of a run without scores)
+                _, x_orig = self._decoded_as("_clip_original", lambda: self.LCMforwardsteps(
+                    zt, t_start_idx=self.edit_t_idx, t_end_idx=-1, prompt=self.for_prompt))
+                self._score_clip(out[1], original_frame=x_orig)
+            return out
         print('!!!RUN LOCAL PULLBACK!!!')
         if non_semantic:
             _, _, vT_modify = self.local_encoder_decoder_pullback_zt(
@@ -336,7 +343,11 @@ class EditLatentConsistency(EditStableDiffusion):
             zc = torch.cat(zt_list, dim=0)
             zts[direction] = zc[[0, -1], :] if vis_num == 1 else zc[::(zc.size(0) // vis_num)]
         zb = torch.cat([(zts[-1].flip(dims=[0]))[:-1], zts[1]], dim=0).contiguous()
-        return self.LCMforwardsteps(zb, t_start_idx=self.edit_t_idx, t_end_idx=-1, prompt=self.for_prompt)
+        out = self.LCMforwardsteps(zb, t_start_idx=self.edit_t_idx, t_end_idx=-1, prompt=self.for_prompt)
+        if self.clip_scoring and not non_semantic:
+            # one text-supervised direction: frame j of the walk sits at alpha = j scale step
+            self._score_clip(out[1], alphas=self._walk_alphas(vis_num))
+        return out
 
     # names of the Stable Diffusion class that do not exist on this one (edit.py:42-481)
     _classifer_free_guidance = None

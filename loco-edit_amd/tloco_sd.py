@@ -447,8 +447,15 @@ class EditStableDiffusion(EditDeepFloydIF):
         F, E, N = self.for_prompt_emb, self.edit_prompt_emb, self.null_prompt_emb
         if self.use_sega:
             self.EXP_NAME = f'sega-edit_prompt-{self.edit_prompt}'
-            return self.DDIMforwardsteps(zt, t_start_idx=self.edit_t_idx, t_end_idx=-1, for_prompt_emb=F, edit_prompt_emb=E,
-                                         null_prompt_emb=N, mode="null+(for-null)+(edit-null)")
+            out = self.DDIMforwardsteps(zt, t_start_idx=self.edit_t_idx, t_end_idx=-1, for_prompt_emb=F, edit_prompt_emb=E,
+                                        null_prompt_emb=N, mode="null+(for-null)+(edit-null)")
+            if self.clip_scoring:
+                # no unedited frame comes back: zt decoded once more under the `for` prompt (on every rank: the sampler is shared)
+                _, x_orig = self._decoded_as("_clip_original", lambda: self.DDIMforwardsteps(
+                    zt, t_start_idx=self.edit_t_idx, t_end_idx=-1, for_prompt_emb=F, edit_prompt_emb=E, null_prompt_emb=N,
+                    mode="null+(for-null)"))
+                self._score_clip(out[1], original_frame=x_orig)
+            return out
         save_dir = os.path.join(self.result_folder, "basis",
                                 f'local_basis-{self.edit_t}T-"{self.edit_prompt}"-pca-rank-{pca_rank}-select-mask{mask_index}')
 
@@ -461,8 +468,10 @@ class EditStableDiffusion(EditDeepFloydIF):
                              f'_select_mask{mask_index}_null_space_projection_{null_space_projection}_null_space_rank_'
                              f'{pca_rank_null}_{self.tilda_v_score_type}')
             zb = self._walk(original_zt, vT[pc_idx, :], vis_num)
-        return self.DDIMforwardsteps(zb, t_start_idx=self.edit_t_idx, t_end_idx=-1, for_prompt_emb=F, edit_prompt_emb=E,
-                                     null_prompt_emb=N, mode="null+(for-null)")
+        out = self.DDIMforwardsteps(zb, t_start_idx=self.edit_t_idx, t_end_idx=-1, for_prompt_emb=F, edit_prompt_emb=E,
+                                    null_prompt_emb=N, mode="null+(for-null)")
+        self._score_clip(out[1], alphas=self._walk_alphas(vis_num))
+        return out
 
     run_edit_null_space_projection_xt = None
     run_edit_null_space_projection_xt_semantic = None
