@@ -833,219 +833,168 @@ bool xa_fused(const XA& x, int kind, const float* X, long x_bs, const float* K1,
     launch_xattn_fused(a, x.st);
     return true;
 }
-void xa_conv1x1(loco_ctx* c, const ConvP& w, bool dgrad, const float* in, long in_bs, float* out, long out_bs, int C, int H,
-                int W, int B, const float* res, long res_bs, bool with_bias, hipStream_t st, const StatReq* rq = nullptr) {
-    ConvArgs a; conv_defaults(a);
-    a.in = in; a.in_bs = in_bs; a.Cin = C; a.Hin = H; a.Win = W;
-    setw(a, w, dgrad); a.pad = 0;
-    if (with_bias) a.bias = w.bias;
-    a.res = res; a.res_bs = res_bs;
-    a.out = out; a.out_bs = out_bs; a.Cout = C; a.Hout = H; a.Wout = W; a.B = B;
-    run_conv(c, a, 1, st, rq);
+// the row step of one pass, fused where the shape allows: P = softmax(scale Xq^T K_ctx) per sample, O = V_ctx P^T
+void xa_forward(const XA& x, const float* Xq, float* P, float* O, long bs) {
+    const Op& op = *x.op;
+    if (xa_fused(x, 0, Xq, bs, op.xK, op.xV, P, bs, O, bs)) return;
+    xa_scores(x, Xq, bs, op.xK, P, bs, x.scale, true);
+    launch_softmax_rows(P, (long)x.NH * x.T, x.Lp, x.st, x.B, bs);
+    xa_values(x, op.xV, P, bs, O, bs);
+}
+// ... and of the two linear passes, per probe through the softmax Jacobian at the primal P (B = 1), S = this pass's scores:
+// tangent X = dq, K1 = K_ctx, K2 = V_ctx -> O = do;  cotangent X = g_o, K1 = V_ctx, K2 = K_ctx -> O = g_q
+void xa_linear(const XA& x, const float* X, const float* K1, const float* K2, float* P, float* S, float* O) {
+    const long PS = x.c->prog->per_sample;
+    if (xa_fused(x, 1, X, PS, K1, K2, P, 0, O, PS)) return;
+    xa_scores(x, X, PS, K1, S, PS, 1.f, false);
+    launch_softmax_jac(S, P, (long)x.NH * x.T, x.Lp, (long)x.NH * x.T, x.scale, x.st, x.B, PS);
+    xa_values(x, K2, S, PS, O, PS);
 }
 
-// ------------------------------ self-attention core of a SpatialTransformer block ------------------------------
-// Between the fused q/k/v map (per-head rows [q_h | k_h | v_h] of `op.qkv`) and the attended values `op.o`; the same
-// strided products and row kernels as the AttentionBlock (and its flash tangent / cotangent where the head width allows).
-struct SA { loco_ctx* c; const Op* op; int B, T, NH, CH; hipStream_t st; };
-void sa_forward(const SA& s, float* ar) {
-    loco_ctx* c = s.c;
-    const long PS = c->prog->per_sample, HS = 3L * s.CH * s.T, SS = (long)s.T * s.T;
-    float* q = ar + c->tens[s.op->qkv].off; float* k = q + (long)s.CH * s.T; float* v = k + (long)s.CH * s.T;
-    float* S = ar + c->tens[s.op->S].off; float* o = ar + c->tens[s.op->o].off;
-    GemmArgs g; std::memset(&g, 0, sizeof(g));
-    g.A = q; g.sam = 1; g.sak = s.T; g.sab = PS; g.sah = HS;
-    g.Bm = k; g.sbk = s.T; g.sbn = 1; g.sbb = PS; g.sbh = HS;
-    g.C = S; g.scm = s.T; g.scn = 1; g.scb = PS; g.sch = SS;
-    g.M = s.T; g.N = s.T; g.K = s.CH; g.batch = s.B; g.batch2 = s.NH; g.alpha = 1.0f / std::sqrt((float)s.CH); g.beta = 0.f;
-    attn_gemm(c, g, s.st);
-    launch_softmax_rows(S, (long)s.NH * s.T, s.T, s.st, s.B, PS);
-    GemmArgs h; std::memset(&h, 0, sizeof(h));
-    h.A = v; h.sam = s.T; h.sak = 1; h.sab = PS; h.sah = HS;
-    h.Bm = S; h.sbk = 1; h.sbn = s.T; h.sbb = PS; h.sbh = SS;
-    h.C = o; h.scm = s.T; h.scn = 1; h.scb = PS; h.sch = (long)s.CH * s.T;
-    h.M = s.CH; h.N = s.T; h.K = s.T; h.batch = s.B; h.batch2 = s.NH; h.alpha = 1.f; h.beta = 0.f;
-    attn_gemm(c, h, s.st);
-}
-void sa_tangent(const SA& s) {       // dq, dk, dv in arenaT(qkv) -> do in arenaT(o); primal in arenaP (B = 1)
-    loco_ctx* c = s.c;
-    const int T = s.T, CH = s.CH, NH = s.NH, B = s.B;
-    const long PS = c->prog->per_sample, HS = 3L * CH * T, SS = (long)T * T;
-    float* q = c->arenaP + c->tens[s.op->qkv].off; float* k = q + (long)CH * T; float* v = k + (long)CH * T;
-    float* dq = c->arenaT + c->tens[s.op->qkv].off; float* dk = dq + (long)CH * T; float* dv = dk + (long)CH * T;
-    float* SP = c->arenaP + c->tens[s.op->S].off; float* ST = c->arenaT + c->tens[s.op->S].off;
-    float* oP = c->arenaP + c->tens[s.op->o].off; float* oT = c->arenaT + c->tens[s.op->o].off;
-    const float scale = 1.0f / std::sqrt((float)CH);
-    if (c->flash_attn && c->prec >= 1 && attn_flash_supported(T, CH)) {
-        AttnFlashArgs fa; std::memset(&fa, 0, sizeof(fa));
-        fa.ws = reinterpret_cast<unsigned char*>(c->partial); fa.ws_bytes = c->partial_floats * sizeof(float);      // (records of the operands: attn_flash.hip)
-        fa.T = T; fa.NH = NH; fa.B = B; fa.CH = CH; fa.scale = scale; fa.q = q; fa.k = k; fa.v = v; fa.hs = HS; fa.P = SP; fa.o = oP;
-        fa.dq = dq; fa.dk = dk; fa.dv = dv; fa.bs_d = PS; fa.out = oT; fa.bs_out = PS;
-        launch_attn_flash_tangent(fa, s.st);
-        return;
+// ------------------------------ multi-head self-attention core ------------------------------
+// Between the fused q/k/v map (per-head rows [q_h | k_h | v_h] of `op.qkv`) and the attended values `op.o`, for the
+// AttentionBlock (OP_ATTN) and the SpatialTransformer's attn1 (OP_XFMR):  P = softmax_j(scale q^T k), o = v P^T.
+// With cfg.added_kv (the DeepFloyd-IF AttentionBlock, diffusers AttnAddedKVProcessor) the keys / values are [text ; image]:
+// P = softmax_j(scale q^T [K_text | k]) over Lt + T columns (the Lt - L padding columns carry -1e30), o = [V_text | v] P^T.
+// K_text / V_text [C][Lt] are constants of the prompt (loco_set_context), so tangents / cotangents reach them through q only.
+// Strided products on column ranges of one score matrix S [NH][T][Tk] per sample, the text columns first.
+struct Attn {
+    loco_ctx* c; const Op* op; hipStream_t st;
+    int B, T, NH, CH, Lt, Tk;       // Lt text key columns (0: none) ahead of the T image ones, Tk = Lt + T
+    long HS, SS, OS, KS;            // head strides: q / k / v inside op.qkv, S, o, K_text / V_text
+    float scale;
+    bool pair;                      // the tangent may K-concatenate its two product pairs (attn_tangent)
+    float* at(float* arena, int id) const { return arena + c->tens[id].off; }
+    // the tangent / cotangent kernels of attn_flash.hip take this shape (no [T x Tk] matrix per probe)
+    bool flash() const {
+        return c->flash_attn && c->prec >= 1 && (Lt ? attn_flash_text_supported(T, CH, Lt) : attn_flash_supported(T, CH));
     }
-    GemmArgs g; std::memset(&g, 0, sizeof(g));
-    g.A = dq; g.sam = 1; g.sak = T; g.sab = PS; g.sah = HS;
-    g.Bm = k; g.sbk = T; g.sbn = 1; g.sbb = 0; g.sbh = HS;
-    g.C = ST; g.scm = T; g.scn = 1; g.scb = PS; g.sch = SS;
-    g.M = T; g.N = T; g.K = CH; g.batch = B; g.batch2 = NH; g.alpha = 1.f; g.beta = 0.f;
-    attn_gemm(c, g, s.st);
-    g.A = q; g.sab = 0; g.Bm = dk; g.sbb = PS; g.beta = 1.f;
-    attn_gemm(c, g, s.st);
-    launch_softmax_jac(ST, SP, (long)NH * T, T, (long)NH * T, scale, s.st, B, PS);
-    GemmArgs h; std::memset(&h, 0, sizeof(h));
-    h.A = dv; h.sam = T; h.sak = 1; h.sab = PS; h.sah = HS;
-    h.Bm = SP; h.sbk = 1; h.sbn = T; h.sbb = 0; h.sbh = SS;
-    h.C = oT; h.scm = T; h.scn = 1; h.scb = PS; h.sch = (long)CH * T;
-    h.M = CH; h.N = T; h.K = T; h.batch = B; h.batch2 = NH; h.alpha = 1.f; h.beta = 0.f;
-    attn_gemm(c, h, s.st);
-    h.A = v; h.sab = 0; h.Bm = ST; h.sbb = PS; h.beta = 1.f;
-    attn_gemm(c, h, s.st);
-}
-void sa_cotangent(const SA& s) {     // g_o in arenaT(o) -> g_q, g_k, g_v in arenaT(qkv)
-    loco_ctx* c = s.c;
-    const int T = s.T, CH = s.CH, NH = s.NH, B = s.B;
-    const long PS = c->prog->per_sample, HS = 3L * CH * T, SS = (long)T * T, OS = (long)CH * T;
-    float* q = c->arenaP + c->tens[s.op->qkv].off; float* k = q + (long)CH * T; float* v = k + (long)CH * T;
-    float* gq = c->arenaT + c->tens[s.op->qkv].off; float* gk = gq + (long)CH * T; float* gv = gk + (long)CH * T;
-    float* SP = c->arenaP + c->tens[s.op->S].off; float* SG = c->arenaT + c->tens[s.op->S].off;
-    float* oP = c->arenaP + c->tens[s.op->o].off; float* oG = c->arenaT + c->tens[s.op->o].off;
-    const float scale = 1.0f / std::sqrt((float)CH);
-    if (c->flash_attn && c->prec >= 1 && attn_flash_supported(T, CH)) {
-        AttnFlashArgs fa; std::memset(&fa, 0, sizeof(fa));
-        fa.ws = reinterpret_cast<unsigned char*>(c->partial); fa.ws_bytes = c->partial_floats * sizeof(float);      // (records of the operands: attn_flash.hip)
-        fa.T = T; fa.NH = NH; fa.B = B; fa.CH = CH; fa.scale = scale; fa.q = q; fa.k = k; fa.v = v; fa.hs = HS; fa.P = SP; fa.o = oP;
-        fa.go = oG; fa.bs_go = PS; fa.gq = gq; fa.gk = gk; fa.gv = gv; fa.bs_g = PS; fa.delta = c->attn_delta;
-        launch_attn_flash_cotangent(fa, s.st);
-        return;
-    }
-    GemmArgs g; std::memset(&g, 0, sizeof(g));                      // g_v[c][j] = sum_i g_o[c][i] P[i][j]
-    g.A = oG; g.sam = T; g.sak = 1; g.sab = PS; g.sah = OS;
-    g.Bm = SP; g.sbk = T; g.sbn = 1; g.sbb = 0; g.sbh = SS;
-    g.C = gv; g.scm = T; g.scn = 1; g.scb = PS; g.sch = HS;
-    g.M = CH; g.N = T; g.K = T; g.batch = B; g.batch2 = NH; g.alpha = 1.f; g.beta = 0.f;
-    attn_gemm(c, g, s.st);
-    GemmArgs h; std::memset(&h, 0, sizeof(h));                      // g_P[i][j] = sum_c g_o[c][i] v[c][j]
-    h.A = oG; h.sam = 1; h.sak = T; h.sab = PS; h.sah = OS;
-    h.Bm = v; h.sbk = T; h.sbn = 1; h.sbb = 0; h.sbh = HS;
-    h.C = SG; h.scm = T; h.scn = 1; h.scb = PS; h.sch = SS;
-    h.M = T; h.N = T; h.K = CH; h.batch = B; h.batch2 = NH; h.alpha = 1.f; h.beta = 0.f;
-    attn_gemm(c, h, s.st);
-    launch_softmax_jac(SG, SP, (long)NH * T, T, (long)NH * T, scale, s.st, B, PS);
-    GemmArgs a; std::memset(&a, 0, sizeof(a));                      // g_q[c][i] = sum_j k[c][j] g_S[i][j]
-    a.A = k; a.sam = T; a.sak = 1; a.sab = 0; a.sah = HS;
-    a.Bm = SG; a.sbk = 1; a.sbn = T; a.sbb = PS; a.sbh = SS;
-    a.C = gq; a.scm = T; a.scn = 1; a.scb = PS; a.sch = HS;
-    a.M = CH; a.N = T; a.K = T; a.batch = B; a.batch2 = NH; a.alpha = 1.f; a.beta = 0.f;
-    attn_gemm(c, a, s.st);
-    GemmArgs b = a;                                                 // g_k[c][j] = sum_i q[c][i] g_S[i][j]
-    b.A = q; b.Bm = SG; b.sbk = T; b.sbn = 1; b.C = gk;
-    attn_gemm(c, b, s.st);
-}
-
-// ------------------------------ attention over [text ; image] keys (cfg.added_kv) ------------------------------
-// The DeepFloyd-IF AttentionBlock (diffusers AttnAddedKVProcessor): P = softmax_j(scale q^T [K_text | k]) over Lp + T
-// columns (the Lp - L padding columns carry -1e30), o = [V_text | v] P^T.  K_text / V_text [C][Lp] are constants of the
-// prompt (loco_set_context), so tangents / cotangents reach them through q only.  Strided products on column ranges of
-// one score matrix S [NH][T][Lp + T] per sample; q / k / v of head h start HS floats apart inside `op.qkv`.
-struct AKV {
-    loco_ctx* c; const Op* op; int B, T, NH, CH, Lp, Tk; long HS, SS, KS; float scale; hipStream_t st;
 };
-AKV akv_of(loco_ctx* c, const Op& op, int B, hipStream_t st) {
-    AKV s; s.c = c; s.op = &op; s.B = B; s.st = st;
+Attn attn_of(loco_ctx* c, const Op& op, int B, hipStream_t st) {
+    Attn s; s.c = c; s.op = &op; s.st = st; s.B = B;
     const Tens& t = c->tens[op.in];
-    s.T = t.H * t.W; s.NH = op.heads; s.CH = t.C / op.heads; s.Lp = c->prog->ctx_Lp; s.Tk = s.Lp + s.T;
-    s.HS = 3L * s.CH * s.T; s.SS = (long)s.T * s.Tk; s.KS = (long)s.CH * s.Lp;
+    s.T = t.H * t.W; s.NH = op.heads; s.CH = t.C / op.heads; s.Lt = op.added_kv ? c->prog->ctx_Lp : 0; s.Tk = s.Lt + s.T;
+    s.HS = 3L * s.CH * s.T; s.SS = (long)s.T * s.Tk; s.OS = (long)s.CH * s.T; s.KS = (long)s.CH * s.Lt;
     s.scale = 1.0f / std::sqrt((float)s.CH);
+    s.pair = op.kind == OP_ATTN && !op.added_kv;
     return s;
 }
-// S[b][h][i][col0 + j] (+)= alpha * sum_c X[b][h][c][i] K[.][h][c][j]     X: q-like [CH][T] per head (head stride xh)
-void akv_scores(const AKV& s, const float* X, long xb, long xh, const float* K, long kb, long kh, int kcols, float* S, long sb,
-                int col0, int N, float alpha, float beta, bool mask, bool exact) {
+// The three products.  `text`: over the Lt text columns of S, against K_text / V_text ([CH][Lt] per head, KS apart) -- these go
+// to launch_gemm (exact fp32) in every precision; else over the T image columns, against k / v-like operands ([CH][T] per
+// head, HS apart) through attn_gemm.  Operands of the primal pass have batch stride 0, per-probe ones per_sample.
+constexpr bool TEXT = true, IMAGE = false;
+// S[b][h][i][col0 + j] (+)= alpha * sum_c X[b][h][c][i] K[.][h][c][j]  (+ X2^T K2, K-concatenated);  X: [CH][T] per head, xh apart
+GemmArgs attn_scores(const Attn& s, bool text, const float* X, long xb, long xh, const float* K, long kb, float* S, long sb,
+                     float alpha, float beta, bool mask = false, const float* X2 = nullptr, long xb2 = 0,
+                     const float* K2 = nullptr, long kb2 = 0) {
+    const int n = text ? s.Lt : s.T;
     GemmArgs g; std::memset(&g, 0, sizeof(g));
     g.A = X; g.sam = 1; g.sak = s.T; g.sab = xb; g.sah = xh;
-    g.Bm = K; g.sbk = kcols; g.sbn = 1; g.sbb = kb; g.sbh = kh;
-    g.C = S + col0; g.scm = s.Tk; g.scn = 1; g.scb = sb; g.sch = s.SS;
-    g.M = s.T; g.N = N; g.K = s.CH; g.batch = s.B; g.batch2 = s.NH; g.alpha = alpha; g.beta = beta;
-    g.colbias = mask ? s.c->ctx_colbias : nullptr;
-    if (exact) launch_gemm(g, s.st); else attn_gemm(s.c, g, s.st);
+    g.Bm = K; g.sbk = n; g.sbn = 1; g.sbb = kb; g.sbh = text ? s.KS : s.HS;
+    g.C = S + (text ? 0 : s.Lt); g.scm = s.Tk; g.scn = 1; g.scb = sb; g.sch = s.SS;
+    g.M = s.T; g.N = n; g.K = s.CH; g.batch = s.B; g.batch2 = s.NH; g.alpha = alpha; g.beta = beta;
+    g.colbias = mask ? s.c->ctx_colbias : nullptr;            // key padding of the prompt: forward text scores only
+    g.A2 = X2; g.sab2 = xb2; g.Bm2 = K2; g.sbb2 = kb2;
+    return g;
 }
-// O[b][h][c][i] (+)= sum_j V[.][h][c][j] S[b][h][i][col0 + j]
-void akv_values(const AKV& s, const float* V, long vb, long vh, int vcols, const float* S, long sb, int col0, int K, float* O,
-                long ob, long oh, float beta, bool exact) {
+// O[b][h][c][i] (+)= sum_j V[.][h][c][j] S[b][h][i][col0 + j]  (+ V2 S2^T, K-concatenated);  O: [CH][T] per head, oh apart
+GemmArgs attn_values(const Attn& s, bool text, const float* V, long vb, const float* S, long sb, float* O, long ob, long oh,
+                     float beta, const float* V2 = nullptr, long vb2 = 0, const float* S2 = nullptr, long sb2 = 0) {
+    const int n = text ? s.Lt : s.T, col0 = text ? 0 : s.Lt;
     GemmArgs g; std::memset(&g, 0, sizeof(g));
-    g.A = V; g.sam = vcols; g.sak = 1; g.sab = vb; g.sah = vh;
+    g.A = V; g.sam = n; g.sak = 1; g.sab = vb; g.sah = text ? s.KS : s.HS;
     g.Bm = S + col0; g.sbk = 1; g.sbn = s.Tk; g.sbb = sb; g.sbh = s.SS;
     g.C = O; g.scm = s.T; g.scn = 1; g.scb = ob; g.sch = oh;
-    g.M = s.CH; g.N = s.T; g.K = K; g.batch = s.B; g.batch2 = s.NH; g.alpha = 1.f; g.beta = beta;
-    if (exact) launch_gemm(g, s.st); else attn_gemm(s.c, g, s.st);
+    g.M = s.CH; g.N = s.T; g.K = n; g.batch = s.B; g.batch2 = s.NH; g.alpha = 1.f; g.beta = beta;
+    g.A2 = V2; g.sab2 = vb2; g.Bm2 = S2 ? S2 + col0 : nullptr; g.sbb2 = sb2;
+    return g;
 }
-// G[b][h][c][j] = sum_i X[.][h][c][i] S[b][h][i][col0 + j]            (g_v = g_o P, g_k = q g_S)
-void akv_keys(const AKV& s, const float* X, long xb, long xh, const float* S, long sb, int col0, float* G, long gb, long gh) {
+// G[b][h][c][j] = sum_i X[.][h][c][i] S[b][h][i][Lt + j]  over the image columns  (g_v = g_o P, g_k = q g_S);  G inside op.qkv
+GemmArgs attn_keys(const Attn& s, const float* X, long xb, long xh, const float* S, long sb, float* G, long gb) {
     GemmArgs g; std::memset(&g, 0, sizeof(g));
     g.A = X; g.sam = s.T; g.sak = 1; g.sab = xb; g.sah = xh;
-    g.Bm = S + col0; g.sbk = s.Tk; g.sbn = 1; g.sbb = sb; g.sbh = s.SS;
-    g.C = G; g.scm = s.T; g.scn = 1; g.scb = gb; g.sch = gh;
+    g.Bm = S + s.Lt; g.sbk = s.Tk; g.sbn = 1; g.sbb = sb; g.sbh = s.SS;
+    g.C = G; g.scm = s.T; g.scn = 1; g.scb = gb; g.sch = s.HS;
     g.M = s.CH; g.N = s.T; g.K = s.T; g.batch = s.B; g.batch2 = s.NH; g.alpha = 1.f; g.beta = 0.f;
-    attn_gemm(s.c, g, s.st);
+    return g;
 }
-void akv_forward(const AKV& s, float* ar, long bs) {           // q, k, v in ar(qkv) -> P in ar(S), o in ar(o)
+// what the flash tangent and cotangent share: the shape, the primal q / k / v / P / o and the text keys / values; the caller
+// adds its per-probe tensors
+AttnFlashArgs attn_flash_args(const Attn& s) {
     loco_ctx* c = s.c; const Op& op = *s.op;
-    float* q = ar + c->tens[op.qkv].off; float* k = q + (long)s.CH * s.T; float* v = k + (long)s.CH * s.T;
-    float* S = ar + c->tens[op.S].off; float* o = ar + c->tens[op.o].off;
-    akv_scores(s, q, bs, s.HS, op.xK, 0, s.KS, s.Lp, S, bs, 0, s.Lp, s.scale, 0.f, true, true);
-    akv_scores(s, q, bs, s.HS, k, bs, s.HS, s.T, S, bs, s.Lp, s.T, s.scale, 0.f, false, false);
+    AttnFlashArgs fa; std::memset(&fa, 0, sizeof(fa));
+    fa.ws = reinterpret_cast<unsigned char*>(c->partial); fa.ws_bytes = c->partial_floats * sizeof(float);      // (records of the operands: attn_flash.hip)
+    fa.T = s.T; fa.NH = s.NH; fa.B = s.B; fa.CH = s.CH; fa.scale = s.scale;
+    fa.q = s.at(c->arenaP, op.qkv); fa.k = fa.q + s.OS; fa.v = fa.k + s.OS; fa.hs = s.HS;
+    fa.P = s.at(c->arenaP, op.S); fa.o = s.at(c->arenaP, op.o);
+    if (s.Lt) { fa.Lt = s.Lt; fa.kt = op.xK; fa.vt = op.xV; }
+    return fa;
+}
+void attn_forward(const Attn& s, float* arena, long bs) {      // q, k, v in arena(qkv) -> P in arena(S), o in arena(o)
+    loco_ctx* c = s.c; const Op& op = *s.op;
+    float* q = s.at(arena, op.qkv); float* k = q + s.OS; float* v = k + s.OS;
+    float* S = s.at(arena, op.S); float* o = s.at(arena, op.o);
+    if (s.Lt) launch_gemm(attn_scores(s, TEXT, q, bs, s.HS, op.xK, 0, S, bs, s.scale, 0.f, true), s.st);
+    attn_gemm(c, attn_scores(s, IMAGE, q, bs, s.HS, k, bs, S, bs, s.scale, 0.f), s.st);
     launch_softmax_rows(S, (long)s.NH * s.T, s.Tk, s.st, s.B, bs);
-    akv_values(s, v, bs, s.HS, s.T, S, bs, s.Lp, s.T, o, bs, (long)s.CH * s.T, 0.f, false);
-    akv_values(s, op.xV, 0, s.KS, s.Lp, S, bs, 0, s.Lp, o, bs, (long)s.CH * s.T, 1.f, true);
+    attn_gemm(c, attn_values(s, IMAGE, v, bs, S, bs, o, bs, s.OS, 0.f), s.st);
+    if (s.Lt) launch_gemm(attn_values(s, TEXT, op.xV, 0, S, bs, o, bs, s.OS, 1.f), s.st);
 }
-void akv_tangent(const AKV& s) {        // dq, dk, dv in arenaT(qkv) -> do in arenaT(o); primal in arenaP (B = 1)
+void attn_tangent(const Attn& s) {      // dq, dk, dv in arenaT(qkv) -> do in arenaT(o); primal in arenaP (B = 1)
     loco_ctx* c = s.c; const Op& op = *s.op;
-    const long PS = c->prog->per_sample, OS = (long)s.CH * s.T;
-    float* q = c->arenaP + c->tens[op.qkv].off; float* k = q + OS; float* v = k + OS;
-    float* dq = c->arenaT + c->tens[op.qkv].off; float* dk = dq + OS; float* dv = dk + OS;
-    float* SP = c->arenaP + c->tens[op.S].off; float* ST = c->arenaT + c->tens[op.S].off;
-    float* oT = c->arenaT + c->tens[op.o].off;
-    if (c->flash_attn && c->prec >= 1 && attn_flash_text_supported(s.T, s.CH, s.Lp)) {      // no [T x (Lp + T)] tangent (attn_flash.hip TXT)
-        AttnFlashArgs fa; std::memset(&fa, 0, sizeof(fa));
-        fa.ws = reinterpret_cast<unsigned char*>(c->partial); fa.ws_bytes = c->partial_floats * sizeof(float);      // (records of the operands: attn_flash.hip)
-        fa.T = s.T; fa.NH = s.NH; fa.B = s.B; fa.CH = s.CH; fa.scale = s.scale; fa.q = q; fa.k = k; fa.v = v; fa.hs = s.HS;
-        fa.P = SP; fa.o = c->arenaP + c->tens[op.o].off; fa.Lt = s.Lp; fa.kt = op.xK; fa.vt = op.xV;
+    const long PS = c->prog->per_sample;
+    float* q = s.at(c->arenaP, op.qkv); float* k = q + s.OS; float* v = k + s.OS;
+    float* dq = s.at(c->arenaT, op.qkv); float* dk = dq + s.OS; float* dv = dk + s.OS;
+    float* SP = s.at(c->arenaP, op.S); float* ST = s.at(c->arenaT, op.S);
+    float* oT = s.at(c->arenaT, op.o);
+    if (s.flash()) {        // do from dq, dk, dv and the primal P / o in one kernel
+        AttnFlashArgs fa = attn_flash_args(s);
         fa.dq = dq; fa.dk = dk; fa.dv = dv; fa.bs_d = PS; fa.out = oT; fa.bs_out = PS;
         launch_attn_flash_tangent(fa, s.st);
         return;
     }
-    akv_scores(s, dq, PS, s.HS, op.xK, 0, s.KS, s.Lp, ST, PS, 0, s.Lp, 1.f, 0.f, false, true);       // dS_text = dq^T K_text
-    akv_scores(s, dq, PS, s.HS, k, 0, s.HS, s.T, ST, PS, s.Lp, s.T, 1.f, 0.f, false, false);         // dS_img = dq^T k
-    akv_scores(s, q, 0, s.HS, dk, PS, s.HS, s.T, ST, PS, s.Lp, s.T, 1.f, 1.f, false, false);         //        + q^T dk
+    // dS = dq^T k + q^T dk and do = dv P^T + v dP^T: one launch per pair (K-concatenation) where the launches
+    // are latency-shaped (T <= 256: 327.7 vs 330.0 ms per headline step); at 1024 tokens two launches with
+    // beta = 1 measured faster (616 vs 639 ms per tloco_if64 step)
+    // -- and where the record GEMM takes the product (the decoder's 4096-token head): one write of dS instead of a write
+    // and a read-modify-write (500 vs 276 + 586 us, tests/diag/gemm_rec_bench.hip)
+    // The AttentionBlock without text keys only (s.pair): the others always issue two launches.
+    const GemmArgs dS2 = attn_scores(s, IMAGE, dq, PS, s.HS, k, 0, ST, PS, 1.f, 0.f, false, q, 0, dk, PS);
+    const bool kcat = s.pair && (s.T <= 256 || attn_gemm_rec(c, dS2));
+    if (s.Lt) launch_gemm(attn_scores(s, TEXT, dq, PS, s.HS, op.xK, 0, ST, PS, 1.f, 0.f), s.st);        // dS_text = dq^T K_text
+    if (kcat) attn_gemm(c, dS2, s.st);                                                                  // dS = dq^T k + q^T dk
+    else {
+        attn_gemm(c, attn_scores(s, IMAGE, dq, PS, s.HS, k, 0, ST, PS, 1.f, 0.f), s.st);                // dS_img = dq^T k
+        attn_gemm(c, attn_scores(s, IMAGE, q, 0, s.HS, dk, PS, ST, PS, 1.f, 1.f), s.st);                //        + q^T dk
+    }
     launch_softmax_jac(ST, SP, (long)s.NH * s.T, s.Tk, (long)s.NH * s.T, s.scale, s.st, s.B, PS);
-    akv_values(s, dv, PS, s.HS, s.T, SP, 0, s.Lp, s.T, oT, PS, OS, 0.f, false);                      // do = dv P_img^T
-    akv_values(s, v, 0, s.HS, s.T, ST, PS, s.Lp, s.T, oT, PS, OS, 1.f, false);                       //    + v dP_img^T
-    akv_values(s, op.xV, 0, s.KS, s.Lp, ST, PS, 0, s.Lp, oT, PS, OS, 1.f, true);                     //    + V_text dP_text^T
+    if (kcat) attn_gemm(c, attn_values(s, IMAGE, dv, PS, SP, 0, oT, PS, s.OS, 0.f, v, 0, ST, PS), s.st);   // do = dv P^T + v dP^T
+    else {
+        attn_gemm(c, attn_values(s, IMAGE, dv, PS, SP, 0, oT, PS, s.OS, 0.f), s.st);                    // do = dv P_img^T
+        attn_gemm(c, attn_values(s, IMAGE, v, 0, ST, PS, oT, PS, s.OS, 1.f), s.st);                     //    + v dP_img^T
+    }
+    if (s.Lt) launch_gemm(attn_values(s, TEXT, op.xV, 0, ST, PS, oT, PS, s.OS, 1.f), s.st);             //    + V_text dP_text^T
 }
-void akv_cotangent(const AKV& s) {      // g_o in arenaT(o) -> g_q, g_k, g_v in arenaT(qkv)
+void attn_cotangent(const Attn& s) {    // g_o in arenaT(o) -> g_q, g_k, g_v in arenaT(qkv)
     loco_ctx* c = s.c; const Op& op = *s.op;
-    const long PS = c->prog->per_sample, OS = (long)s.CH * s.T;
-    float* q = c->arenaP + c->tens[op.qkv].off; float* k = q + OS; float* v = k + OS;
-    float* gq = c->arenaT + c->tens[op.qkv].off; float* gk = gq + OS; float* gv = gk + OS;
-    float* SP = c->arenaP + c->tens[op.S].off; float* SG = c->arenaT + c->tens[op.S].off;
-    float* oG = c->arenaT + c->tens[op.o].off;
-    if (c->flash_attn && c->prec >= 1 && attn_flash_text_supported(s.T, s.CH, s.Lp)) {
-        AttnFlashArgs fa; std::memset(&fa, 0, sizeof(fa));
-        fa.ws = reinterpret_cast<unsigned char*>(c->partial); fa.ws_bytes = c->partial_floats * sizeof(float);      // (records of the operands: attn_flash.hip)
-        fa.T = s.T; fa.NH = s.NH; fa.B = s.B; fa.CH = s.CH; fa.scale = s.scale; fa.q = q; fa.k = k; fa.v = v; fa.hs = s.HS;
-        fa.P = SP; fa.o = c->arenaP + c->tens[op.o].off; fa.Lt = s.Lp; fa.kt = op.xK; fa.vt = op.xV;
+    const long PS = c->prog->per_sample;
+    float* q = s.at(c->arenaP, op.qkv); float* k = q + s.OS; float* v = k + s.OS;
+    float* gq = s.at(c->arenaT, op.qkv); float* gk = gq + s.OS; float* gv = gk + s.OS;
+    float* SP = s.at(c->arenaP, op.S); float* SG = s.at(c->arenaT, op.S);
+    float* oG = s.at(c->arenaT, op.o);
+    if (s.flash()) {        // g_q, g_k, g_v from g_o and the primal q / k / v / P / o
+        AttnFlashArgs fa = attn_flash_args(s);
         fa.go = oG; fa.bs_go = PS; fa.gq = gq; fa.gk = gk; fa.gv = gv; fa.bs_g = PS; fa.delta = c->attn_delta;
         launch_attn_flash_cotangent(fa, s.st);
         return;
     }
-    akv_keys(s, oG, PS, OS, SP, 0, s.Lp, gv, PS, s.HS);                                              // g_v = g_o P_img
-    akv_scores(s, oG, PS, OS, op.xV, 0, s.KS, s.Lp, SG, PS, 0, s.Lp, 1.f, 0.f, false, true);         // g_P_text = g_o^T V_text
-    akv_scores(s, oG, PS, OS, v, 0, s.HS, s.T, SG, PS, s.Lp, s.T, 1.f, 0.f, false, false);           // g_P_img = g_o^T v
+    attn_gemm(c, attn_keys(s, oG, PS, s.OS, SP, 0, gv, PS), s.st);                                      // g_v = g_o P_img
+    if (s.Lt) launch_gemm(attn_scores(s, TEXT, oG, PS, s.OS, op.xV, 0, SG, PS, 1.f, 0.f), s.st);        // g_P_text = g_o^T V_text
+    attn_gemm(c, attn_scores(s, IMAGE, oG, PS, s.OS, v, 0, SG, PS, 1.f, 0.f), s.st);                    // g_P_img = g_o^T v
     launch_softmax_jac(SG, SP, (long)s.NH * s.T, s.Tk, (long)s.NH * s.T, s.scale, s.st, s.B, PS);
-    akv_values(s, k, 0, s.HS, s.T, SG, PS, s.Lp, s.T, gq, PS, s.HS, 0.f, false);                     // g_q = k g_S_img^T
-    akv_values(s, op.xK, 0, s.KS, s.Lp, SG, PS, 0, s.Lp, gq, PS, s.HS, 1.f, true);                   //     + K_text g_S_text^T
-    akv_keys(s, q, 0, s.HS, SG, PS, s.Lp, gk, PS, s.HS);                                             // g_k = q g_S_img
+    attn_gemm(c, attn_values(s, IMAGE, k, 0, SG, PS, gq, PS, s.HS, 0.f), s.st);                         // g_q = k g_S_img^T
+    if (s.Lt) launch_gemm(attn_values(s, TEXT, op.xK, 0, SG, PS, gq, PS, s.HS, 1.f), s.st);             //     + K_text g_S_text^T
+    attn_gemm(c, attn_keys(s, q, 0, s.HS, SG, PS, gk, PS), s.st);                                       // g_k = q g_S_img
 }
 
 // y[Cout][T] (+ bias, + residual) = W x[Cin][T] as a 1x1 conv; dgrad: the transposed map
@@ -1149,7 +1098,7 @@ int forward_pass(loco_ctx* c, const float* x, float t, int B, float* arena, floa
                 break;
             }
             case OP_ATTN: {
-                const int C = to.C, T = HW, NH = op.heads, CH = C / NH;
+                const int C = to.C;
                 if (!op.n1.ready) gn_forward_stats(p, op.n1, p.T(op.in), p.bs(), HW);
                 op.n1.ready = false;
                 NS s = nstats(c, stats, op.n1);
@@ -1161,25 +1110,8 @@ int forward_pass(loco_ctx* c, const float* x, float t, int B, float* arena, floa
                 run_conv(c, a, 1, st);
                 // per head h: q = qkv[h*3*CH ...], k = +CH, v = +2CH channels (QKVAttentionLegacy, unet.py:346;
                 // with one head this is the [q|k|v] stacking of the fused DDPM projection)
-                float* q = p.T(op.qkv); float* k = q + (long)CH * T; float* v = k + (long)CH * T;
-                if (op.added_kv) {
-                    if (!c->has_ctx) { c->err = "this architecture attends over the prompt's states: call loco_set_context first"; return -1; }
-                    akv_forward(akv_of(c, op, B, st), arena, p.bs());
-                } else {
-                GemmArgs g; std::memset(&g, 0, sizeof(g));
-                g.A = q; g.sam = 1; g.sak = T; g.sab = p.bs(); g.sah = 3L * CH * T;
-                g.Bm = k; g.sbk = T; g.sbn = 1; g.sbb = p.bs(); g.sbh = 3L * CH * T;
-                g.C = p.T(op.S); g.scm = T; g.scn = 1; g.scb = p.bs(); g.sch = (long)T * T;
-                g.M = T; g.N = T; g.K = CH; g.batch = B; g.batch2 = NH; g.alpha = 1.0f / std::sqrt((float)CH); g.beta = 0.f;
-                attn_gemm(c, g, st);
-                launch_softmax_rows(p.T(op.S), (long)NH * T, T, st, B, p.bs());
-                GemmArgs h; std::memset(&h, 0, sizeof(h));
-                h.A = v; h.sam = T; h.sak = 1; h.sab = p.bs(); h.sah = 3L * CH * T;
-                h.Bm = p.T(op.S); h.sbk = 1; h.sbn = T; h.sbb = p.bs(); h.sbh = (long)T * T;
-                h.C = p.T(op.o); h.scm = T; h.scn = 1; h.scb = p.bs(); h.sch = (long)CH * T;
-                h.M = CH; h.N = T; h.K = T; h.batch = B; h.batch2 = NH; h.alpha = 1.f; h.beta = 0.f;
-                attn_gemm(c, h, st);
-                }
+                if (op.added_kv && !c->has_ctx) { c->err = "this architecture attends over the prompt's states: call loco_set_context first"; return -1; }
+                attn_forward(attn_of(c, op, B, st), arena, p.bs());
                 ConvArgs pr; conv_defaults(pr);
                 pr.in = p.T(op.o); pr.in_bs = p.bs(); pr.Cin = C; pr.Hin = to.H; pr.Win = to.W;
                 setw(pr, op.proj, false); pr.bias = op.proj.bias; pr.pad = 0;
@@ -1201,20 +1133,16 @@ int forward_pass(loco_ctx* c, const float* x, float t, int B, float* arena, floa
                     qa.mode = CM_GN; qa.sc = sx.sc; qa.sh = sx.sh; qa.scsh_bs = SB;
                     qa.out = p.T(op.xq); qa.out_bs = p.bs(); qa.Cout = C; qa.Hout = to.H; qa.Wout = to.W; qa.B = B;
                     run_conv(c, qa, 1, st);
-                    if (!xa_fused(x, 0, p.T(op.xq), p.bs(), op.xK, op.xV, p.T(op.xS), p.bs(), p.T(op.xo), p.bs())) {
-                        xa_scores(x, p.T(op.xq), p.bs(), op.xK, p.T(op.xS), p.bs(), x.scale, true);
-                        launch_softmax_rows(p.T(op.xS), (long)NH * T, x.Lp, st, B, p.bs());
-                        xa_values(x, op.xV, p.T(op.xS), p.bs(), p.T(op.xo), p.bs());
-                    }
+                    xa_forward(x, p.T(op.xq), p.T(op.xS), p.T(op.xo), p.bs());
                     const StatReq rqx = next_fwd(op.out);
-                    xa_conv1x1(c, op.xproj, false, p.T(op.xo), p.bs(), p.T(op.out), p.bs(), C, to.H, to.W, B,
-                               p.T(op.xmid), p.bs(), true, st, &rqx);
+                    lin1x1(c, op.xproj, false, p.T(op.xo), p.bs(), C, p.T(op.out), p.bs(), C, to.H, to.W, B,
+                           p.T(op.xmid), p.bs(), true, st, &rqx);
                 }
                 break;
             }
             case OP_XFMR: {      // latent-diffusion SpatialTransformer (oracle/loco_oracle.py _ldm_spatial_transformer)
                 if (!c->has_ctx) { c->err = "this architecture has cross-attention stages: call loco_set_context first"; return -1; }
-                const int C = to.C, T = HW, NH = op.heads, H = to.H, W = to.W;
+                const int C = to.C, T = HW, H = to.H, W = to.W;
                 const long PSb = p.bs();
                 auto X = [&](int i) { return p.T(op.xt[i]); };
                 if (!op.n1.ready) gn_forward_stats(p, op.n1, p.T(op.in), PSb, HW);
@@ -1228,21 +1156,16 @@ int forward_pass(loco_ctx* c, const float* x, float t, int B, float* arena, floa
                     a.out = X(X_H0); a.out_bs = PSb; a.Cout = C; a.Hout = H; a.Wout = W; a.B = B;
                     run_conv(c, a, 1, st);
                 }
-                const SA sa{c, &op, B, T, NH, C / NH, st};
                 const XA xa = xa_of(c, op, B, st);
                 // x = x + attn1(LN1(x))
                 launch_ln_fwd(X(X_H0), PSb, B, C, T, op.lng[0], op.lnb[0], 1e-5f, X(X_A1), PSb, X(X_LN1), PSb, st);
                 lin1x1(c, op.qkvc, false, X(X_A1), PSb, C, X(X_QKV), PSb, 3 * C, H, W, B, nullptr, 0, false, st);
-                sa_forward(sa, arena);
+                attn_forward(attn_of(c, op, B, st), arena, PSb);
                 lin1x1(c, op.to_out1, false, X(X_O), PSb, C, X(X_H1), PSb, C, H, W, B, X(X_H0), PSb, true, st);
                 // x = x + attn2(LN2(x), context)
                 launch_ln_fwd(X(X_H1), PSb, B, C, T, op.lng[1], op.lnb[1], 1e-5f, X(X_A2), PSb, X(X_LN2), PSb, st);
                 lin1x1(c, op.xqc, false, X(X_A2), PSb, C, X(X_XQ), PSb, C, H, W, B, nullptr, 0, false, st);
-                if (!xa_fused(xa, 0, X(X_XQ), PSb, op.xK, op.xV, X(X_XS), PSb, X(X_XO), PSb)) {
-                    xa_scores(xa, X(X_XQ), PSb, op.xK, X(X_XS), PSb, xa.scale, true);
-                    launch_softmax_rows(X(X_XS), (long)NH * T, xa.Lp, st, B, PSb);
-                    xa_values(xa, op.xV, X(X_XS), PSb, X(X_XO), PSb);
-                }
+                xa_forward(xa, X(X_XQ), X(X_XS), X(X_XO), PSb);
                 lin1x1(c, op.to_out2, false, X(X_XO), PSb, C, X(X_H2), PSb, C, H, W, B, X(X_H1), PSb, true, st);
                 // x = x + Linear(GEGLU(LN3(x)))
                 launch_ln_fwd(X(X_H2), PSb, B, C, T, op.lng[2], op.lnb[2], 1e-5f, X(X_A3), PSb, X(X_LN3), PSb, st);
@@ -1394,7 +1317,7 @@ int tangent_pass(loco_ctx* c, const float* V, int B, hipStream_t st) {
                 break;
             }
             case OP_ATTN: {
-                const int C = to.C, T = HW, NH = op.heads, CH = C / NH;
+                const int C = to.C;
                 if (!op.n1.ready) tangent_stats(c, op.n1, TT(op.in), PS, TP(op.in), HW, B, st);
                 op.n1.ready = false;
                 NS sp = nstats(c, c->statsP, op.n1);
@@ -1406,47 +1329,7 @@ int tangent_pass(loco_ctx* c, const float* V, int B, hipStream_t st) {
                 setw(a, op.qkvc, false); a.pad = 0;
                 a.out = TT(op.qkv); a.out_bs = PS; a.Cout = 3 * C; a.Hout = to.H; a.Wout = to.W; a.B = B;
                 run_conv(c, a, 1, st);
-                const long HS = 3L * CH * T, SS = (long)T * T;
-                float* q = TP(op.qkv); float* k = q + (long)CH * T; float* v = k + (long)CH * T;
-                float* dq = TT(op.qkv); float* dk = dq + (long)CH * T; float* dv = dk + (long)CH * T;
-                const bool flash = (c->flash_attn && c->prec >= 1 && attn_flash_supported(T, CH)) || op.added_kv;   // added_kv: its own products
-                if (op.added_kv) akv_tangent(akv_of(c, op, B, st));
-                else if (flash) {   // do from dq, dk, dv and the primal P / o in one kernel, no [T x T] tangent (attn_flash.hip)
-                    AttnFlashArgs fa; std::memset(&fa, 0, sizeof(fa));
-                    fa.ws = reinterpret_cast<unsigned char*>(c->partial); fa.ws_bytes = c->partial_floats * sizeof(float);      // (records of the operands: attn_flash.hip)
-                    fa.T = T; fa.NH = NH; fa.B = B; fa.CH = CH; fa.scale = 1.0f / std::sqrt((float)CH);
-                    fa.q = q; fa.k = k; fa.v = v; fa.hs = HS; fa.P = TP(op.S); fa.o = TP(op.o);
-                    fa.dq = dq; fa.dk = dk; fa.dv = dv; fa.bs_d = PS; fa.out = TT(op.o); fa.bs_out = PS;
-                    launch_attn_flash_tangent(fa, st);
-                }
-                GemmArgs g; std::memset(&g, 0, sizeof(g));
-                g.A = dq; g.sam = 1; g.sak = T; g.sab = PS; g.sah = HS;
-                g.Bm = k; g.sbk = T; g.sbn = 1; g.sbb = 0; g.sbh = HS;
-                g.C = TT(op.S); g.scm = T; g.scn = 1; g.scb = PS; g.sch = SS;
-                g.M = T; g.N = T; g.K = CH; g.batch = B; g.batch2 = NH; g.alpha = 1.f; g.beta = 0.f;
-                // dS = dq^T k + q^T dk and do = dv P^T + v dP^T: one launch per pair (K-concatenation) where the launches
-                // are latency-shaped (T <= 256: 327.7 vs 330.0 ms per headline step); at 1024 tokens two launches with
-                // beta = 1 measured faster (616 vs 639 ms per tloco_if64 step)
-                // -- and where the record GEMM takes the product (the decoder's 4096-token head): one write of dS instead of a write
-                // and a read-modify-write (500 vs 276 + 586 us, tests/diag/gemm_rec_bench.hip)
-                bool kcat = T <= 256;
-                if (!kcat && !flash) { GemmArgs g2 = g; g2.A2 = q; g2.Bm2 = dk; g2.sbb2 = PS; kcat = attn_gemm_rec(c, g2); }
-                if (kcat) { g.A2 = q; g.sab2 = 0; g.Bm2 = dk; g.sbb2 = PS; }
-                if (!flash) {
-                attn_gemm(c, g, st);
-                if (!kcat) { g.A = q; g.sab = 0; g.Bm = dk; g.sbb = PS; g.beta = 1.f; attn_gemm(c, g, st); }
-                launch_softmax_jac(TT(op.S), TP(op.S), (long)NH * T, T, (long)NH * T, 1.0f / std::sqrt((float)CH), st, B, PS);
-                }
-                GemmArgs h; std::memset(&h, 0, sizeof(h));
-                h.A = dv; h.sam = T; h.sak = 1; h.sab = PS; h.sah = HS;
-                h.Bm = TP(op.S); h.sbk = 1; h.sbn = T; h.sbb = 0; h.sbh = SS;
-                h.C = TT(op.o); h.scm = T; h.scn = 1; h.scb = PS; h.sch = (long)CH * T;
-                h.M = CH; h.N = T; h.K = T; h.batch = B; h.batch2 = NH; h.alpha = 1.f; h.beta = 0.f;
-                if (kcat) { h.A2 = v; h.sab2 = 0; h.Bm2 = TT(op.S); h.sbb2 = PS; }
-                if (!flash) {
-                attn_gemm(c, h, st);
-                if (!kcat) { h.A = v; h.sab = 0; h.Bm = TT(op.S); h.sbb = PS; h.beta = 1.f; attn_gemm(c, h, st); }
-                }
+                attn_tangent(attn_of(c, op, B, st));
                 ConvArgs pr; conv_defaults(pr);
                 pr.in = TT(op.o); pr.in_bs = PS; pr.Cin = C; pr.Hin = to.H; pr.Win = to.W;
                 setw(pr, op.proj, false); pr.pad = 0; pr.res = TT(op.in); pr.res_bs = PS;
@@ -1463,19 +1346,15 @@ int tangent_pass(loco_ctx* c, const float* V, int B, hipStream_t st) {
                     NS stx = nstats(c, c->statsT, op.nx);
                     launch_gn_apply(1, TT(op.xmid), PS, TP(op.xmid), 0, nullptr, 0, TT(op.xhn), PS, 0, B, C, HW,
                                     cfg.gn_groups, spx.sc, spx.sh, spx.mr, 0, 0, stx.tst, c->prog->stats_per_sample, st);
-                    xa_conv1x1(c, op.xqc, false, TT(op.xhn), PS, TT(op.xq), PS, C, to.H, to.W, B, nullptr, 0, false, st);
-                    if (!xa_fused(x, 1, TT(op.xq), PS, op.xK, op.xV, TP(op.xS), 0, TT(op.xo), PS)) {
-                        xa_scores(x, TT(op.xq), PS, op.xK, TT(op.xS), PS, 1.f, false);                  // dS = dq^T K
-                        launch_softmax_jac(TT(op.xS), TP(op.xS), (long)NH * T, x.Lp, (long)NH * T, x.scale, st, B, PS);
-                        xa_values(x, op.xV, TT(op.xS), PS, TT(op.xo), PS);                              // do = V dP^T
-                    }
+                    lin1x1(c, op.xqc, false, TT(op.xhn), PS, C, TT(op.xq), PS, C, to.H, to.W, B, nullptr, 0, false, st);
+                    xa_linear(x, TT(op.xq), op.xK, op.xV, TP(op.xS), TT(op.xS), TT(op.xo));           // dq -> do
                     const StatReq rqx = next_tan(op.out);
-                    xa_conv1x1(c, op.xproj, false, TT(op.xo), PS, TT(op.out), PS, C, to.H, to.W, B, TT(op.xmid), PS, false, st, &rqx);
+                    lin1x1(c, op.xproj, false, TT(op.xo), PS, C, TT(op.out), PS, C, to.H, to.W, B, TT(op.xmid), PS, false, st, &rqx);
                 }
                 break;
             }
             case OP_XFMR: {
-                const int C = to.C, T = HW, NH = op.heads, H = to.H, W = to.W;
+                const int C = to.C, T = HW, H = to.H, W = to.W;
                 auto XP = [&](int i) { return TP(op.xt[i]); };
                 auto XT_ = [&](int i) { return TT(op.xt[i]); };
                 if (!op.n1.ready) tangent_stats(c, op.n1, TT(op.in), PS, TP(op.in), HW, B, st);
@@ -1485,19 +1364,14 @@ int tangent_pass(loco_ctx* c, const float* V, int B, hipStream_t st) {
                 launch_gn_apply(1, TT(op.in), PS, TP(op.in), 0, nullptr, 0, XT_(X_G0), PS, 0, B, C, HW,
                                 cfg.gn_groups, sp.sc, sp.sh, sp.mr, 0, 0, stt.tst, c->prog->stats_per_sample, st);
                 lin1x1(c, op.pj_in, false, XT_(X_G0), PS, C, XT_(X_H0), PS, C, H, W, B, nullptr, 0, false, st);
-                const SA sa{c, &op, B, T, NH, C / NH, st};
                 const XA xa = xa_of(c, op, B, st);
                 launch_ln_tan(XT_(X_H0), PS, XP(X_H0), XP(X_LN1), B, C, T, op.lng[0], XT_(X_A1), PS, st);
                 lin1x1(c, op.qkvc, false, XT_(X_A1), PS, C, XT_(X_QKV), PS, 3 * C, H, W, B, nullptr, 0, false, st);
-                sa_tangent(sa);
+                attn_tangent(attn_of(c, op, B, st));
                 lin1x1(c, op.to_out1, false, XT_(X_O), PS, C, XT_(X_H1), PS, C, H, W, B, XT_(X_H0), PS, false, st);
                 launch_ln_tan(XT_(X_H1), PS, XP(X_H1), XP(X_LN2), B, C, T, op.lng[1], XT_(X_A2), PS, st);
                 lin1x1(c, op.xqc, false, XT_(X_A2), PS, C, XT_(X_XQ), PS, C, H, W, B, nullptr, 0, false, st);
-                if (!xa_fused(xa, 1, XT_(X_XQ), PS, op.xK, op.xV, XP(X_XS), 0, XT_(X_XO), PS)) {
-                    xa_scores(xa, XT_(X_XQ), PS, op.xK, XT_(X_XS), PS, 1.f, false);                   // dS = dq^T K
-                    launch_softmax_jac(XT_(X_XS), XP(X_XS), (long)NH * T, xa.Lp, (long)NH * T, xa.scale, st, B, PS);
-                    xa_values(xa, op.xV, XT_(X_XS), PS, XT_(X_XO), PS);                              // do = V dP^T
-                }
+                xa_linear(xa, XT_(X_XQ), op.xK, op.xV, XP(X_XS), XT_(X_XS), XT_(X_XO));             // dq -> do
                 lin1x1(c, op.to_out2, false, XT_(X_XO), PS, C, XT_(X_H2), PS, C, H, W, B, XT_(X_H1), PS, false, st);
                 launch_ln_tan(XT_(X_H2), PS, XP(X_H2), XP(X_LN3), B, C, T, op.lng[2], XT_(X_A3), PS, st);
                 lin1x1(c, op.ff1, false, XT_(X_A3), PS, C, XT_(X_F), PS, 8 * C, H, W, B, nullptr, 0, false, st);
@@ -1670,21 +1544,14 @@ int cotangent_pass(loco_ctx* c, const float* ge, const float* gx0, float* Aout, 
                 break;
             }
             case OP_ATTN: {
-                const int C = to.C, T = HW, NH = op.heads, CH = C / NH;
-                const long HS = 3L * CH * T, SS = (long)T * T, OS = (long)CH * T;
-                float* q = TP(op.qkv); float* k = q + (long)CH * T; float* v = k + (long)CH * T;
-                float* gq = TG(op.qkv); float* gk = gq + (long)CH * T; float* gv = gk + (long)CH * T;
+                const int C = to.C;
                 const int so = op.has_x ? op.xmid : op.out;       // output tensor of the self-attention stage
                 if (op.has_x) {
                     // cotangent of the cross-attention stage: g_out -> g_xmid (residual + the q path through GN)
                     const XA x = xa_of(c, op, B, st);
-                    xa_conv1x1(c, op.xproj, true, TG(op.out), PS, TG(op.xo), PS, C, to.H, to.W, B, nullptr, 0, false, st);
-                    if (!xa_fused(x, 1, TG(op.xo), PS, op.xV, op.xK, TP(op.xS), 0, TG(op.xq), PS)) {
-                        xa_scores(x, TG(op.xo), PS, op.xV, TG(op.xS), PS, 1.f, false);                  // g_P = g_o^T V
-                        launch_softmax_jac(TG(op.xS), TP(op.xS), (long)NH * T, x.Lp, (long)NH * T, x.scale, st, B, PS);
-                        xa_values(x, op.xK, TG(op.xS), PS, TG(op.xq), PS);                              // g_q = K g_S^T
-                    }
-                    xa_conv1x1(c, op.xqc, true, TG(op.xq), PS, TG(op.xhn), PS, C, to.H, to.W, B, nullptr, 0, false, st);
+                    lin1x1(c, op.xproj, true, TG(op.out), PS, C, TG(op.xo), PS, C, to.H, to.W, B, nullptr, 0, false, st);
+                    xa_linear(x, TG(op.xo), op.xV, op.xK, TP(op.xS), TG(op.xS), TG(op.xq));           // g_o -> g_q
+                    lin1x1(c, op.xqc, true, TG(op.xq), PS, C, TG(op.xhn), PS, C, to.H, to.W, B, nullptr, 0, false, st);
                     cot_stats(c, op.nx, TG(op.xhn), PS, TP(op.xmid), HW, B, 2, st);
                     NS spx = nstats(c, c->statsP, op.nx);
                     NS stx = nstats(c, c->statsT, op.nx);
@@ -1697,44 +1564,7 @@ int cotangent_pass(loco_ctx* c, const float* ge, const float* gx0, float* Aout, 
                 setw(pr, op.proj, true); pr.pad = 0;
                 pr.out = TG(op.o); pr.out_bs = PS; pr.Cout = C; pr.Hout = to.H; pr.Wout = to.W; pr.B = B;
                 run_conv(c, pr, 1, st);
-                const bool flash = (c->flash_attn && c->prec >= 1 && attn_flash_supported(T, CH)) || op.added_kv;   // added_kv: its own products
-                if (op.added_kv) akv_cotangent(akv_of(c, op, B, st));
-                else if (flash) {   // g_q, g_k, g_v from g_o and the primal q / k / v / P / o, no [T x T] cotangent (attn_flash.hip)
-                    AttnFlashArgs fa; std::memset(&fa, 0, sizeof(fa));
-                    fa.ws = reinterpret_cast<unsigned char*>(c->partial); fa.ws_bytes = c->partial_floats * sizeof(float);      // (records of the operands: attn_flash.hip)
-                    fa.T = T; fa.NH = NH; fa.B = B; fa.CH = CH; fa.scale = 1.0f / std::sqrt((float)CH);
-                    fa.q = q; fa.k = k; fa.v = v; fa.hs = HS; fa.P = TP(op.S); fa.o = TP(op.o);
-                    fa.go = TG(op.o); fa.bs_go = PS; fa.gq = gq; fa.gk = gk; fa.gv = gv; fa.bs_g = PS; fa.delta = c->attn_delta;
-                    launch_attn_flash_cotangent(fa, st);
-                }
-                // g_v[c][j] = sum_i g_o[c][i] P[i][j]
-                GemmArgs g; std::memset(&g, 0, sizeof(g));
-                g.A = TG(op.o); g.sam = T; g.sak = 1; g.sab = PS; g.sah = OS;
-                g.Bm = TP(op.S); g.sbk = T; g.sbn = 1; g.sbb = 0; g.sbh = SS;
-                g.C = gv; g.scm = T; g.scn = 1; g.scb = PS; g.sch = HS;
-                g.M = CH; g.N = T; g.K = T; g.batch = B; g.batch2 = NH; g.alpha = 1.f; g.beta = 0.f;
-                if (!flash) attn_gemm(c, g, st);
-                // g_P[i][j] = sum_c g_o[c][i] v[c][j]
-                GemmArgs h; std::memset(&h, 0, sizeof(h));
-                h.A = TG(op.o); h.sam = 1; h.sak = T; h.sab = PS; h.sah = OS;
-                h.Bm = v; h.sbk = T; h.sbn = 1; h.sbb = 0; h.sbh = HS;
-                h.C = TG(op.S); h.scm = T; h.scn = 1; h.scb = PS; h.sch = SS;
-                h.M = T; h.N = T; h.K = CH; h.batch = B; h.batch2 = NH; h.alpha = 1.f; h.beta = 0.f;
-                if (!flash) {
-                attn_gemm(c, h, st);
-                launch_softmax_jac(TG(op.S), TP(op.S), (long)NH * T, T, (long)NH * T, 1.0f / std::sqrt((float)CH), st, B, PS);
-                }
-                // g_q[c][i] = sum_j k[c][j] g_S[i][j]
-                GemmArgs gq_; std::memset(&gq_, 0, sizeof(gq_));
-                gq_.A = k; gq_.sam = T; gq_.sak = 1; gq_.sab = 0; gq_.sah = HS;
-                gq_.Bm = TG(op.S); gq_.sbk = 1; gq_.sbn = T; gq_.sbb = PS; gq_.sbh = SS;
-                gq_.C = gq; gq_.scm = T; gq_.scn = 1; gq_.scb = PS; gq_.sch = HS;
-                gq_.M = CH; gq_.N = T; gq_.K = T; gq_.batch = B; gq_.batch2 = NH; gq_.alpha = 1.f; gq_.beta = 0.f;
-                if (!flash) attn_gemm(c, gq_, st);
-                // g_k[c][j] = sum_i q[c][i] g_S[i][j]
-                GemmArgs gk_ = gq_;
-                gk_.A = q; gk_.Bm = TG(op.S); gk_.sbk = T; gk_.sbn = 1; gk_.C = gk;
-                if (!flash) attn_gemm(c, gk_, st);
+                attn_cotangent(attn_of(c, op, B, st));      // g_q, g_k, g_v = the transposes of q^T k -> P -> v P^T
                 // g_hn = Wqkv^T g_qkv
                 ConvArgs a; conv_defaults(a);
                 a.in = TG(op.qkv); a.in_bs = PS; a.Cin = 3 * C; a.Hin = to.H; a.Win = to.W;
@@ -1749,10 +1579,9 @@ int cotangent_pass(loco_ctx* c, const float* ge, const float* gx0, float* Aout, 
                 break;
             }
             case OP_XFMR: {      // transposes of the forward chain, last map first
-                const int C = to.C, T = HW, NH = op.heads, H = to.H, W = to.W;
+                const int C = to.C, T = HW, H = to.H, W = to.W;
                 auto XP = [&](int i) { return TP(op.xt[i]); };
                 auto XG = [&](int i) { return TG(op.xt[i]); };
-                const SA sa{c, &op, B, T, NH, C / NH, st};
                 const XA xa = xa_of(c, op, B, st);
                 lin1x1(c, op.pj_out, true, TG(op.out), PS, C, XG(X_H3), PS, C, H, W, B, nullptr, 0, false, st);          // g_h3
                 // feed-forward: h3 = h2 + ff2(geglu(ff1(LN3(h2))))
@@ -1762,16 +1591,12 @@ int cotangent_pass(loco_ctx* c, const float* ge, const float* gx0, float* Aout, 
                 launch_ln_cot(XG(X_A3), PS, XP(X_H2), XP(X_LN3), B, C, T, op.lng[2], XG(X_H3), PS, XG(X_H2), PS, st);  // g_h2
                 // cross-attention: h2 = h1 + to_out2(V P^T), q = to_q(LN2(h1))
                 lin1x1(c, op.to_out2, true, XG(X_H2), PS, C, XG(X_XO), PS, C, H, W, B, nullptr, 0, false, st);
-                if (!xa_fused(xa, 1, XG(X_XO), PS, op.xV, op.xK, XP(X_XS), 0, XG(X_XQ), PS)) {
-                    xa_scores(xa, XG(X_XO), PS, op.xV, XG(X_XS), PS, 1.f, false);                     // g_P = g_o^T V
-                    launch_softmax_jac(XG(X_XS), XP(X_XS), (long)NH * T, xa.Lp, (long)NH * T, xa.scale, st, B, PS);
-                    xa_values(xa, op.xK, XG(X_XS), PS, XG(X_XQ), PS);                                // g_q = K g_S^T
-                }
+                xa_linear(xa, XG(X_XO), op.xV, op.xK, XP(X_XS), XG(X_XS), XG(X_XQ));                // g_o -> g_q
                 lin1x1(c, op.xqc, true, XG(X_XQ), PS, C, XG(X_A2), PS, C, H, W, B, nullptr, 0, false, st);
                 launch_ln_cot(XG(X_A2), PS, XP(X_H1), XP(X_LN2), B, C, T, op.lng[1], XG(X_H2), PS, XG(X_H1), PS, st);  // g_h1
                 // self-attention: h1 = h0 + to_out1(attn(qkv(LN1(h0))))
                 lin1x1(c, op.to_out1, true, XG(X_H1), PS, C, XG(X_O), PS, C, H, W, B, nullptr, 0, false, st);
-                sa_cotangent(sa);
+                attn_cotangent(attn_of(c, op, B, st));
                 lin1x1(c, op.qkvc, true, XG(X_QKV), PS, 3 * C, XG(X_A1), PS, C, H, W, B, nullptr, 0, false, st);
                 launch_ln_cot(XG(X_A1), PS, XP(X_H0), XP(X_LN1), B, C, T, op.lng[0], XG(X_H1), PS, XG(X_H0), PS, st);  // g_h0
                 // proj_in of GN(x), and the residual  out = x + ...

@@ -65,7 +65,7 @@ int main(int argc, char** argv) {
     float *SP = dalloc(TT, 7, 1.0f / T), *ST = dalloc(TT * B, 8, 1.0f / T), *S2 = dalloc(TT * B, 9, 0.f), *oT = dalloc(CT * B, 10, 0.f);
     CK(hipDeviceSynchronize());
     loco::GemmArgs g;
-    // dS = dq^T k   (engine.hip sa_tangent): A = dq (m = token: unit stride, k = channel), B = k shared
+    // dS = dq^T k   (engine.hip attn_tangent): A = dq (m = token: unit stride, k = channel), B = k shared
     std::memset(&g, 0, sizeof(g));
     g.A = dq; g.sam = 1; g.sak = T; g.sab = CT; g.Bm = k; g.sbk = T; g.sbn = 1; g.sbb = 0;
     g.C = S2; g.scm = T; g.scn = 1; g.scb = TT; g.M = T; g.N = T; g.K = C; g.batch = B; g.alpha = 1.f; g.beta = 0.f;
