@@ -482,6 +482,47 @@ int  loco_clipvis_encode(loco_clipvis* t, const float* pixel_values, int32_t n, 
 const char* loco_clipvis_last_error(loco_clipvis* t);
 void loco_clipvis_destroy(loco_clipvis* t);
 
+/* --- Edit-quality scores of decoded frames (the unconditional drivers' --quality_metrics, eval.py --backend hip) ---
+ * LPIPS with the AlexNet backbone, SSIM and mask-restricted MSE between the images of a[n] and b[n], pair by pair, as
+ * eval.py defines them.  Independent of loco_set_precision / LOCO_PRECISION, sums in a fixed order, no atomics, no host
+ * synchronisation inside a call; a pair's results are bit-identical whatever n and wherever the pair sits in the batch.  Its
+ * own handle; the workspace for max_pairs pairs of max_h x max_w images is allocated at create.  SSIM and masked MSE work on
+ * a handle without parameters, LPIPS needs all of them. */
+typedef struct loco_quality loco_quality;
+typedef struct loco_quality_cfg {
+    int32_t max_h, max_w;        /* the largest image a call may carry */
+    double  ssim_window[11];     /* the 1-D Gaussian window of SSIM (sigma 1.5, normalised to sum 1), computed by the host in
+                                  * float64; the 2-D window is its outer product */
+} loco_quality_cfg;
+int  loco_quality_create(const loco_quality_cfg* cfg, int32_t device, int32_t max_pairs, loco_quality** out);
+/* One call per entry of the LPIPS weights under the names of eval.lpips_weight_names(): features.{0,3,6,8,10}.{weight,bias}
+ * (torchvision AlexNet: [64,3,11,11], [192,64,5,5], [384,192,3,3], [256,384,3,3], [256,256,3,3]) and lin{0..4}.model.1.weight
+ * ([1,C,1,1], the non-negative heads of the lpips package).  `host`: fp32 values, a host or a device pointer. */
+int  loco_quality_load_param(loco_quality* q, const char* name, const float* host, const int64_t* shape, int32_t ndim);
+int  loco_quality_params_missing(loco_quality* q);
+/* out_dev[n] = LPIPS of a_dev[n][3][H][W] and b_dev[n][3][H][W] (device, fp32, in [-1, 1]; normalize != 0: in [0, 1]).  Input
+ * scaling (x - shift) / scale; five convolutions with bias and ReLU (11x11 stride 4 pad 2, 5x5 pad 2, three 3x3 pad 1; 3x3
+ * stride-2 max-pool before the second and the third) as implicit GEMMs on the exact-fp32 matrix instruction; after each,
+ * x / (sqrt(sum_c x^2) + 1e-10), squared difference of the pair, the 1x1 head, spatial mean; the sum of the five taps.  Optional
+ * (NULL to skip): taps_dev[n][5], the five terms.  Refused: H or W below 31 (the last taps would be empty) or above the
+ * configured maximum, n outside [1, max_pairs], parameters missing. */
+int  loco_quality_lpips(loco_quality* q, const float* a_dev, const float* b_dev, int32_t n, int32_t H, int32_t W, int32_t normalize,
+                        float* out_dev, float* taps_dev, void* stream);
+/* out_dev[n] = mean SSIM of a_dev[n][C][H][W] and b_dev (fp32): 11x11 Gaussian window, reflect padding of 5, k1 = 0.01,
+ * k2 = 0.03, the 5-pixel border of the map cropped when H > 10 and W > 10, mean over channels and pixels.  The window moments
+ * are summed in double from the fp32 inputs (E[x^2] - mu^2 cancels to the order of c2 in fp32).  Refused: a side below 6
+ * (reflect padding undefined) or above the configured maximum, n outside [1, max_pairs], n C above 3 max_pairs planes of the
+ * configured size. */
+int  loco_quality_ssim(loco_quality* q, const float* a_dev, const float* b_dev, int32_t n, int32_t C, int32_t H, int32_t W,
+                       double data_range, double* out_dev, void* stream);
+/* sum_dev[i] = sum over mask_dev[i][e] != 0 of (a_dev[i][e] - b_dev[i][e])^2 in double, count_dev[i] = the masked elements of
+ * image i (e < elems).  The mean is the caller's: a count may be zero. */
+int  loco_quality_masked_mse(loco_quality* q, const float* a_dev, const float* b_dev, const uint8_t* mask_dev, int32_t n, int64_t elems,
+                             double* sum_dev, int64_t* count_dev, void* stream);
+/* Message of the last failed call on q; q == NULL: of the last failed loco_quality_create. */
+const char* loco_quality_last_error(loco_quality* q);
+void loco_quality_destroy(loco_quality* q);
+
 #ifdef __cplusplus
 }
 #endif

@@ -130,6 +130,14 @@ def build_parser():
     p.add_argument('--clip_preprocess', type=str, default='device', choices=['pil', 'device'],
                    help="--clip_model_path: 'device' resizes the frames on the GPU in float arithmetic, 'pil' on the host with PIL "
                         "(CLIPImageProcessor's input exactly)")
+    p.add_argument('--quality_metrics', type=str, default='',
+                   help='score the decoded frames of an edit on the GPU against the unedited frame into '
+                        '<result_folder>/<name>_quality.json: a comma list drawn from ssim,mmse,lpips (mmse: MSE inside the '
+                        "run's mask and outside it). Empty: no scores, nothing else changes")
+    p.add_argument('--lpips_weights', type=str, default='',
+                   help="--quality_metrics lpips: a state dict with torchvision AlexNet's features.* and the lpips package's "
+                        "lin*.model.1.weight heads, or 'features_file,heads_file'; no pretrained weights are available offline "
+                        'and without them lpips raises')
     p.add_argument('--lcm_timesteps', type=str, default=None, choices=['linspace', 'stride'],
                    help='latent-consistency models (required for them): which published LCMScheduler.set_timesteps rule picks the '
                         "N sampling timesteps out of the 50 training ones -- 'linspace' (current diffusers: N = 4 gives "

@@ -31,6 +31,9 @@ class EditUncondDiffusion(object):
         if self.dtype != torch.float32:
             raise ValueError("the unconditional hot path keeps fp32 tensors (scripts/main_celeba_hf_null_space_projection.sh:7); "
                              "the conv arithmetic is chosen with --precision")
+        # --quality_metrics: the scorer of the decoded frames (None when off); lpips without weights raises here, before any solve
+        from .quality import scorer_from_args
+        self.quality = scorer_from_args(args, self.device)
 
         # get model (edit.py:2046-2052)
         self.unet = get_custom_diffusion_model(args)
@@ -234,7 +237,9 @@ class EditUncondDiffusion(object):
             xt_vis_list.append(xt_edit)
         self.EXP_NAME = f'{idx}-Edit_xt-noise-{BASIS_NAME}'
         xt_vis = torch.cat(xt_vis_list, dim=0)
-        self.DDIMforwardsteps(xt_vis, t_start_idx=self.edit_t_idx, t_end_idx=-1, performance_boosting=True)
+        dec = self.DDIMforwardsteps(xt_vis, t_start_idx=self.edit_t_idx, t_end_idx=-1, performance_boosting=True)
+        # frame 0 is the decoded unedited xt, the last one the composed edit; no mask on this path
+        self._score_quality((dec / 2 + 0.5).clamp(0, 1), self.EXP_NAME, None, None, original_index=0)
         return xt
 
     def _segment(self, x0_fn):
@@ -374,12 +379,27 @@ class EditUncondDiffusion(object):
                 self.EXP_NAME = name
                 image = (dec[pc_idx * per:(pc_idx + 1) * per] / 2 + 0.5).clamp(0, 1)
                 self._save_image(image, os.path.join(self.result_folder, f'{name}.png'), nrow=image.size(0))
+                self._score_quality(image, name, self._walk_alphas(vis_num), mask)
             return frames[-1]
         for pc_idx in range(n_pc):
             self.EXP_NAME = names[pc_idx]
             xt = self.edit_batch(original_xt, vT[pc_idx, :], vis_num)
-            self.DDIMforwardsteps(xt, t_start_idx=self.edit_t_idx, t_end_idx=-1, performance_boosting=True)
+            dec = self.DDIMforwardsteps(xt, t_start_idx=self.edit_t_idx, t_end_idx=-1, performance_boosting=True)
+            self._score_quality((dec / 2 + 0.5).clamp(0, 1), names[pc_idx], self._walk_alphas(vis_num), mask)
         return xt
+
+    def _score_quality(self, image, name, alphas, mask, original_index=None):
+        """--quality_metrics: scores the decoded frames `image` [n,3,H,W] in [0, 1] (before they are quantised for the PNG) against
+        the walk's alpha = 0 frame (or frame `original_index`) with quality.QualityScorer and writes
+        <result_folder>/<name>_quality.json from the main rank.  Returns the JSON's dict (None off the main rank and without the flag)."""
+        if getattr(self, "quality", None) is None or not self.sharder.is_main:
+            return None
+        if original_index is None:
+            if 0.0 not in alphas:
+                raise ValueError(f"walk alphas {alphas}: no unedited frame to score against")
+            original_index = alphas.index(0.0)
+        return self.quality.write(os.path.join(self.result_folder, f'{name}_quality.json'), image, original_index, mask=mask,
+                                  alphas=alphas, exp_name=name)
 
     def _decode_frames(self, batch, n_pc, per):
         """Decode the frames of all directions (``n_pc`` walks of ``per`` frames) from the edit step to x0.
@@ -416,12 +436,15 @@ class EditUncondDiffusion(object):
         repeated ``xt + scale*step*vk`` equals ``xt + j*scale*step*vk`` up to fp32
         rounding of the repeated adds; the reference's order of additions is kept by
         accumulating the scalar the same way."""
+        return self.engine.edit_axpy(original_xt.contiguous(), vk_row.contiguous().view(-1), self._walk_alphas(vis_num))
+
+    def _walk_alphas(self, vis_num):
+        """The step sizes of the frames of one walk, the unedited frame (0) in the middle."""
         S = self.x_space_guidance_num_step
         stride = None if vis_num == 1 else (S + 1) // vis_num
         idxs = [0, S] if vis_num == 1 else list(range(0, S + 1, stride))
         step = self.x_space_guidance_scale * self.x_space_guidance_edit_step
-        alphas = [-j * step for j in reversed(idxs)][:-1] + [j * step for j in idxs]
-        return self.engine.edit_axpy(original_xt.contiguous(), vk_row.contiguous().view(-1), alphas)
+        return [-j * step for j in reversed(idxs)][:-1] + [j * step for j in idxs]
 
     @torch.no_grad()
     def x_space_guidance_direct(self, xt, t_idx, vk, single_edit_step):

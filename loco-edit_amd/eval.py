@@ -20,8 +20,9 @@ undefined names).  This module is a working restatement of that intent:
   from a CLIP model on the HIP engine (``clip_score.py``, ``csrc/clipvis.hip``).  No CLIP checkpoint is available offline:
   the model comes from ``--clip_model_path`` and without one it raises.
 
-SSIM, masked MSE and LPIPS are plain torch on the host: evaluation is not on the hot path and there is no ``torchmetrics`` here to pin the
-SSIM against (parity unpinned; the unit tests check the defining properties).
+SSIM, masked MSE and LPIPS below are plain torch on the host (there is no ``torchmetrics`` here to pin the SSIM against: parity
+unpinned; the unit tests check the defining properties).  ``--backend hip`` runs the same three metrics on the device
+(``quality.QualityScorer``, ``csrc/quality.hip``), which is also what the drivers' ``--quality_metrics`` uses on the decoded frames.
 """
 from __future__ import annotations
 
@@ -178,11 +179,21 @@ def evaluate_clip_folders(folder_preds: str, folder_original: str, metric: str =
 
 
 def evaluate_folders(folder_preds: str, folder_original: str, metric: str = "ssim", mask_folder: str = "",
-                     outside_mask: bool = False, lpips_weights=None) -> dict:
+                     outside_mask: bool = False, lpips_weights=None, backend: str = "torch", device=None) -> dict:
     """Pair ``*.png`` by file name (``eval.py:56-72``) and average the metric; for ``mmse`` the mask of image
-    ``<stem>.png`` is ``<mask_folder>/<stem>.pt`` (a bool tensor ``[3,H,W]`` or ``[H,W]``)."""
+    ``<stem>.png`` is ``<mask_folder>/<stem>.pt`` (a bool tensor ``[3,H,W]`` or ``[H,W]``).  ``backend``: ``torch`` = the host
+    functions of this module, ``hip`` = the same metrics on the device (``quality.QualityScorer``)."""
     if metric not in METRICS:
         raise ValueError("eval_metric choice: " + ", ".join(METRICS))
+    if backend not in ("torch", "hip"):
+        raise ValueError("backend choice: torch, hip")
+    fns = METRICS
+    if backend == "hip":
+        from .quality import QualityScorer
+        if metric == "lpips" and lpips_weights is None:
+            lpips_weights = os.environ.get("LOCO_LPIPS_WEIGHTS", "")
+        scorer = QualityScorer(device if device is not None else "cuda:0", [metric], lpips_weights if metric == "lpips" else None)
+        fns = {"ssim": lambda x, y: scorer.ssim(x, y)[0], "mmse": lambda x, y, m: scorer.masked_mse(x, y, m)[0]}
     pp = sorted(glob.glob(os.path.join(folder_preds, "*.png")))
     tp = sorted(glob.glob(os.path.join(folder_original, "*.png")))
     if len(pp) != len(tp) or not pp:
@@ -196,10 +207,12 @@ def evaluate_folders(folder_preds: str, folder_original: str, metric: str = "ssi
             m = torch.load(os.path.join(mask_folder or os.path.join(folder_preds, "mask"),
                                         os.path.splitext(os.path.basename(a))[0] + ".pt"))
             m = m if m.dim() == 3 else m[None].repeat(3, 1, 1)
-            vals.append(float(masked_mse(x, y, (~m if outside_mask else m)[None])))
+            vals.append(float(fns["mmse"](x, y, (~m if outside_mask else m)[None])))
+        elif metric == "lpips" and backend == "hip":
+            vals.append(float(scorer.lpips(x / 127.5 - 1, y / 127.5 - 1)[0]))
         else:
             vals.append(float(lpips(x / 127.5 - 1, y / 127.5 - 1, weights=lpips_weights) if metric == "lpips"
-                              else METRICS[metric](x, y)))
+                              else fns[metric](x, y)))
     return {"metric": metric, "n": len(vals), "mean": float(np.mean(vals)), "values": vals}
 
 
@@ -217,6 +230,8 @@ def main(argv=None):
     ap.add_argument("--edit_prompt", type=str, default="", help="clip / clip_dir: the edit prompt")
     ap.add_argument("--clip_preprocess", type=str, default="pil", choices=("pil", "device"),
                     help="pil: resize on the host with PIL (CLIPImageProcessor's input exactly); device: on the GPU in float arithmetic")
+    ap.add_argument("--backend", type=str, default="torch", choices=("torch", "hip"),
+                    help="ssim / mmse / lpips: torch = on the host, hip = on the device (csrc/quality.hip)")
     a = ap.parse_args(argv)
     if a.eval_metric in CLIP_METRICS:
         r = evaluate_clip_folders(a.folder_preds, a.folder_original, a.eval_metric, a.clip_model_path, a.for_prompt, a.edit_prompt,
@@ -224,7 +239,7 @@ def main(argv=None):
         print(f"{r['metric']}: {r['mean']:.6f} over {r['n']} pairs")
         return r
     r = evaluate_folders(a.folder_preds, a.folder_original, a.eval_metric, a.mask_folder, a.outside_mask,
-                         a.lpips_weights or None)
+                         a.lpips_weights or None, backend=a.backend)
     print(f"{r['metric']}: {r['mean']:.6f} over {r['n']} pairs")
     return r
 

@@ -38,6 +38,8 @@ SYMBOLS = [
     "loco_sam_profile_read", "loco_sam_last_error", "loco_sam_destroy",
     "loco_clipvis_create", "loco_clipvis_load_param", "loco_clipvis_params_missing", "loco_clipvis_preprocess",
     "loco_clipvis_encode", "loco_clipvis_last_error", "loco_clipvis_destroy",
+    "loco_quality_create", "loco_quality_load_param", "loco_quality_params_missing", "loco_quality_lpips", "loco_quality_ssim",
+    "loco_quality_masked_mse", "loco_quality_last_error", "loco_quality_destroy",
 ]
 
 # threshold rules of loco_diffedit_mask (include/loco_hip.h)
@@ -94,6 +96,10 @@ class LocoClipVisCfg(C.Structure):
     _fields_ = [("image_size", C.c_int32), ("patch_size", C.c_int32), ("width", C.c_int32), ("layers", C.c_int32),
                 ("heads", C.c_int32), ("mlp_dim", C.c_int32), ("projection_dim", C.c_int32), ("act", C.c_int32),
                 ("ln_eps", C.c_float), ("image_mean", C.c_float * 3), ("image_std", C.c_float * 3)]
+
+
+class LocoQualityCfg(C.Structure):
+    _fields_ = [("max_h", C.c_int32), ("max_w", C.c_int32), ("ssim_window", C.c_double * 11)]
 
 
 def library_path() -> str:
@@ -194,6 +200,17 @@ def load_library():
         lib.loco_clipvis_last_error.restype = C.c_char_p
         lib.loco_clipvis_destroy.argtypes = [vp]
         lib.loco_clipvis_destroy.restype = None
+    if hasattr(lib, "loco_quality_create"):
+        lib.loco_quality_create.argtypes = [C.POINTER(LocoQualityCfg), i32, i32, C.POINTER(vp)]
+        lib.loco_quality_load_param.argtypes = [vp, C.c_char_p, vp, C.POINTER(i64), i32]
+        lib.loco_quality_params_missing.argtypes = [vp]
+        lib.loco_quality_lpips.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
+        lib.loco_quality_ssim.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.c_double, vp, vp]
+        lib.loco_quality_masked_mse.argtypes = [vp, vp, vp, vp, i32, i64, vp, vp, vp]
+        lib.loco_quality_last_error.argtypes = [vp]
+        lib.loco_quality_last_error.restype = C.c_char_p
+        lib.loco_quality_destroy.argtypes = [vp]
+        lib.loco_quality_destroy.restype = None
     if hasattr(lib, "loco_bench_conv"):          # diag build only
         lib.loco_bench_conv.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(f32), vp]
         lib.loco_debug_tensor.argtypes = [vp, C.c_char_p, vp, i64, vp]
@@ -970,3 +987,71 @@ class LocoClipVisionEngine(_EncoderEngine):
             self._check(self.lib.loco_clipvis_encode(self._t, _ptr(pv), n, _ptr(emb), _ptr(hid), _ptr(pool), _stream()),
                         "loco_clipvis_encode")
         return (emb, hid, pool) if want_hidden else emb
+
+
+class LocoQualityEngine(_EncoderEngine):
+    """The edit-quality scorer (= loco_quality, include/loco_hip.h): LPIPS (AlexNet), SSIM and mask-restricted MSE between
+    the images of two batches, pair by pair, as ``eval.lpips`` / ``eval.ssim`` / ``eval.masked_mse`` define them.  The
+    workspace holds `max_pairs` pairs of `max_hw` = (H, W) images.  ``load_state_dict`` takes the names of
+    ``eval.lpips_weight_names()``; ``ssim`` and ``masked_mse`` need no parameters.  Every method returns one value per pair
+    on the device."""
+    _prefix, _label = "loco_quality", "quality scorer"
+
+    def __init__(self, max_hw=(256, 256), max_pairs: int = 32, device: Optional[torch.device] = None):
+        self._open(device)
+        self.max_hw, self.max_pairs = (int(max_hw[0]), int(max_hw[1])), int(max_pairs)
+        c = LocoQualityCfg(max_h=self.max_hw[0], max_w=self.max_hw[1])
+        x = torch.arange(11, dtype=torch.float64) - 5.0                # the 1-D factor of eval._gaussian_window, in float64
+        g = torch.exp(-(x / 1.5) ** 2 / 2)
+        g = g / g.sum()
+        for i in range(11):
+            c.ssim_window[i] = float(g[i])
+        self._create("loco_quality_create", c, self.max_pairs)
+
+    def _pair(self, a, b, channels=None):
+        a, b = torch.as_tensor(a), torch.as_tensor(b)
+        if a.shape != b.shape or a.dim() != 4 or a.shape[0] < 1 or (channels is not None and a.shape[1] != channels):
+            raise ValueError(f"expected a and b of the same shape [n,{channels or 'C'},H,W], got {tuple(a.shape)} and {tuple(b.shape)}")
+        return (a.to(device=self.device, dtype=torch.float32).contiguous(), b.to(device=self.device, dtype=torch.float32).contiguous())
+
+    def lpips(self, a: torch.Tensor, b: torch.Tensor, normalize: bool = False, want_taps: bool = False):
+        """a, b [n,3,H,W] in [-1, 1] (``normalize``: in [0, 1]), n <= max_pairs -> LPIPS [n] fp32; ``want_taps``: (LPIPS, the five
+        terms [n,5])."""
+        a, b = self._pair(a, b, 3)
+        n, _, H, W = a.shape
+        out = torch.empty(n, device=self.device, dtype=torch.float32)
+        taps = torch.empty(n, 5, device=self.device, dtype=torch.float32) if want_taps else None
+        with torch.cuda.device(self.device):
+            self._check(self.lib.loco_quality_lpips(self._t, _ptr(a), _ptr(b), n, H, W, int(bool(normalize)), _ptr(out), _ptr(taps),
+                                                    _stream()), "loco_quality_lpips")
+        return (out, taps) if want_taps else out
+
+    def ssim(self, a: torch.Tensor, b: torch.Tensor, data_range=None) -> torch.Tensor:
+        """a, b [n,C,H,W] -> mean SSIM of every pair [n] float64.  ``data_range=None``: the larger of the two dynamic ranges over
+        the batch, as in ``eval.ssim`` (read back from the device before the call)."""
+        a, b = self._pair(a, b)
+        n, ch, H, W = a.shape
+        if data_range is None:
+            lo_a, hi_a = torch.aminmax(a)
+            lo_b, hi_b = torch.aminmax(b)
+            data_range = max(float(hi_a.double() - lo_a.double()), float(hi_b.double() - lo_b.double()))
+        out = torch.empty(n, device=self.device, dtype=torch.float64)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.loco_quality_ssim(self._t, _ptr(a), _ptr(b), n, ch, H, W, float(data_range), _ptr(out), _stream()),
+                        "loco_quality_ssim")
+        return out
+
+    def masked_mse(self, a: torch.Tensor, b: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+        """MSE of every pair over ``mask`` only (boolean, broadcastable to the images) [n] float64; ``ValueError("empty mask")``
+        when a pair has no masked element, as ``eval.masked_mse``."""
+        a, b = self._pair(a, b)
+        n = a.shape[0]
+        m = torch.as_tensor(mask).to(self.device).to(torch.bool).expand_as(a).to(torch.uint8).contiguous()
+        s = torch.empty(n, device=self.device, dtype=torch.float64)
+        cnt = torch.empty(n, device=self.device, dtype=torch.int64)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.loco_quality_masked_mse(self._t, _ptr(a), _ptr(b), _ptr(m), n, a[0].numel(), _ptr(s), _ptr(cnt),
+                                                         _stream()), "loco_quality_masked_mse")
+        if bool((cnt == 0).any()):
+            raise ValueError("empty mask")
+        return s / cnt.double()

@@ -287,10 +287,14 @@ class CFGJacobianOperator:
 class EditDeepFloydIF(object):
     text_encoder = None
     _clip = None                                # the CLIP scorer of --clip_model_path, created on first use, once per object
+    _quality = None                             # the quality.QualityScorer of --quality_metrics
     BRANCH_NAMES = ("for", "edit", "null")      # one engine context per prompt of the guidance (a subclass may run fewer)
 
     def __init__(self, args):
         self.device, self.dtype = args.device, args.dtype
+        # --quality_metrics: the scorer of the returned frames (None when off); lpips without weights raises here, before any solve
+        from .quality import scorer_from_args
+        self._quality = scorer_from_args(args, self.device)
         if self.dtype == torch.float16:
             # `--dtype fp16` (the reference loads its IF / SD pipelines with torch_dtype=float16, utils.py:260-283, and casts to
             # fp32 before the SVD, edit.py:1653): tensors stay fp32 on this engine, the request selects the f16 conv arithmetic
@@ -781,6 +785,22 @@ class EditDeepFloydIF(object):
             json.dump(out, f, indent=1)
         return out
 
+    def _score_quality(self, frames, alphas, mask=None):
+        """--quality_metrics: scores the returned uint8 frames [n, H, W, 3] of a walk against its alpha = 0 frame with
+        quality.QualityScorer (ssim, mmse inside / outside `mask`, lpips) and writes <result_folder>/<EXP_NAME>_quality.json from
+        the main rank.  `mask` [3, h, w] is used when it has the frames' size (the latent drivers' masks do not: their MSEs are
+        null).  Returns the JSON's dict (None off the main rank and without the flag)."""
+        if self._quality is None or frames is None or not self.sharder.is_main:
+            return None
+        image = torch.as_tensor(frames).to(self.device).permute(0, 3, 1, 2).to(torch.float32) / 255.0
+        alphas = [float(a) for a in alphas]
+        if len(alphas) != image.shape[0] or 0.0 not in alphas:
+            raise ValueError(f"{image.shape[0]} frames, walk alphas {alphas}: no unedited frame to score against")
+        if mask is not None and tuple(mask.shape[-2:]) != tuple(image.shape[-2:]):
+            mask = None
+        return self._quality.write(os.path.join(self.result_folder, f"{self.EXP_NAME}_quality.json"), image, alphas.index(0.0),
+                                   mask=mask, alphas=alphas, exp_name=self.EXP_NAME)
+
     def _xT(self):
         if self.dataset_name != 'Random':
             raise ValueError("T-LOCO runs from x_T ~ N(0, I) (dataset_name 'Random', edit.py:1763)")
@@ -901,6 +921,7 @@ class EditDeepFloydIF(object):
             x0 = self.DDPMforwardsteps(xb, t_start_idx=self.edit_t_idx, t_end_idx=-1, for_prompt_emb=F, edit_prompt_emb=E,
                                        null_prompt_emb=N, mode="null+(for-null)")
             self._score_clip(x0, alphas=self._walk_alphas(vis_num))
+            self._score_quality(x0, self._walk_alphas(vis_num), mask)
         elif self.ablation_method == "sega":
             self.EXP_NAME = f'sega-edit_prompt-{self.edit_prompt}-mask_type-{self.mask_type}-select_mask{mask_index}'
             x0 = self.DDPMforwardsteps(xt, t_start_idx=self.edit_t_idx, t_end_idx=-1, for_prompt_emb=F, edit_prompt_emb=E,

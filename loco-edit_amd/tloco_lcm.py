@@ -347,6 +347,8 @@ class EditLatentConsistency(EditStableDiffusion):
         if self.clip_scoring and not non_semantic:
             # one text-supervised direction: frame j of the walk sits at alpha = j scale step
             self._score_clip(out[1], alphas=self._walk_alphas(vis_num))
+        if not non_semantic:
+            self._score_quality(out[1], self._walk_alphas(vis_num), mask)       # (gates itself on --quality_metrics)
         return out
 
     # names of the Stable Diffusion class that do not exist on this one (edit.py:42-481)

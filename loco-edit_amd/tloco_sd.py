@@ -471,6 +471,7 @@ class EditStableDiffusion(EditDeepFloydIF):
         out = self.DDIMforwardsteps(zb, t_start_idx=self.edit_t_idx, t_end_idx=-1, for_prompt_emb=F, edit_prompt_emb=E,
                                     null_prompt_emb=N, mode="null+(for-null)")
         self._score_clip(out[1], alphas=self._walk_alphas(vis_num))
+        self._score_quality(out[1], self._walk_alphas(vis_num), mask)
         return out
 
     run_edit_null_space_projection_xt = None
