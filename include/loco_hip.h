@@ -436,6 +436,61 @@ int  loco_sam_profile_read(loco_sam* t, float* ms4);
 const char* loco_sam_last_error(loco_sam* t);
 void loco_sam_destroy(loco_sam* t);
 
+/* --- Segment Anything prompt encoder + mask decoder + mask scoring (edit masks) ---
+ * The head of transformers' SamModel for point prompts with multimask_output = true, as mask_segmentation.SamHead states it:
+ * one foreground point and the padding point per prompt (random-Fourier features of the shared positional matrix, accurate
+ * sinf / cosf), the two-way transformer (`layers` blocks: token self-attention, token -> image attention, MLP, image -> token
+ * attention, each with its LayerNorm; the final token -> image attention), two stride-2 transposed convolutions with a channel
+ * LayerNorm and erf-GELUs, the hypernetwork product and the IoU head.  NQ = num_multimask_outputs + 4 tokens per prompt.
+ * Exact fp32 throughout (independent of loco_set_precision / LOCO_PRECISION), sums in a fixed order, no atomics on floats, no
+ * host synchronisation inside a call; a prompt's rows are bit-identical whatever P and its position.  Its own handle; the
+ * workspace for max_prompts prompts is allocated at create: the per-prompt image tokens [P][C][G^2] and one more tensor of
+ * that size for the projections of them the algorithm needs, never a [P][G^2] x NQ score tensor nor the maps after the second
+ * transposed convolution. */
+typedef struct loco_samdec loco_samdec;
+typedef struct loco_samdec_cfg {
+    int32_t grid;                      /* G: side of the image embedding (64) */
+    int32_t image_size;                /* S = G * patch (1024): recorded, the coordinates arrive normalised */
+    int32_t hidden;                    /* C: 256; 32, 64, 128 or 256 (the upscaling kernel is built for C / 4 = 8 ... 64) */
+    int32_t layers;                    /* num_hidden_layers of the two-way transformer (2) */
+    int32_t heads;                     /* num_attention_heads (8): C and C / attention_downsample_rate are multiples of it; the
+                                        * cross-attention head width C / rate / heads must be a power of two <= 64 */
+    int32_t mlp_dim;                   /* 2048, a multiple of 4 */
+    int32_t attention_downsample_rate; /* 2 */
+    int32_t num_multimask_outputs;     /* 3 (<= 4: 8 tokens per prompt at most) */
+    int32_t iou_head_depth;            /* 3 (>= 2) */
+    int32_t iou_head_hidden_dim;       /* 256, a multiple of 4 */
+    float   layer_norm_eps;            /* 1e-6 (the LayerNorm after the final attention uses 1e-5, as transformers' default) */
+    int32_t hidden_act;                /* activation of the transformer's MLP: 0 relu, 1 erf gelu */
+    int32_t max_prompts;               /* the largest P of a predict call (64) */
+} loco_samdec_cfg;
+int  loco_samdec_create(const loco_samdec_cfg* cfg, int32_t device, loco_samdec** out);
+/* One call per entry in SamModel naming: shared_image_embedding.positional_embedding, prompt_encoder.{no_mask_embed,
+ * not_a_point_embed,point_embed.1}.weight, mask_decoder.* (mask_segmentation.head_param_shapes lists them). */
+int  loco_samdec_load_param(loco_samdec* t, const char* name, const float* host, const int64_t* shape, int32_t ndim);
+int  loco_samdec_params_missing(loco_samdec* t);
+/* Once per image, emb_dev[C][G][G]: src = emb + no_mask_embed, the grid's positional encoding pos, layer 0's k / v projections
+ * of src + pos / src and its image -> token query projection, and pos W for the later projections of keys + pos (the image
+ * tokens of layer 0 are the same for every prompt; (keys + pos) W is evaluated as keys W + pos W from layer 1 on). */
+int  loco_samdec_set_image(loco_samdec* t, const float* emb_dev, void* stream);
+/* coords_dev[P][2]: (x, y) of the foreground points as 2 (p + 0.5) / S - 1 in fp32, 1 <= P <= max_prompts.
+ * masks_out[P][num_multimask_outputs][4G][4G], iou_out[P][num_multimask_outputs]: mask token 0 is dropped. */
+int  loco_samdec_predict(loco_samdec* t, const float* coords_dev, int32_t P, float* masks_out, float* iou_out, void* stream);
+/* The automatic mask generator's view of low_res_dev[N][h][w] at the original size: each logit is the bilinear resampling
+ * (align_corners = false) to image_size x image_size, cropped to reshaped h x w, resampled to orig h x w; neither map is
+ * stored.  counts_out[N][2] = pixels above thr + offset and above thr - offset, boxes_out[N][4] = inclusive XYXY box of
+ * logit > thr, 0 0 0 0 for an empty mask.  Works on a handle without parameters. */
+int  loco_samdec_score(loco_samdec* t, const float* low_res_dev, int32_t N, int32_t h, int32_t w, int32_t orig_h, int32_t orig_w,
+                       int32_t reshaped_h, int32_t reshaped_w, int32_t image_size, float thr, float offset, int32_t* counts_out,
+                       int32_t* boxes_out, void* stream);
+/* masks_out[K][orig_h][orig_w] (uint8 0 / 1) = logit > thr of the rows rows_dev[K] (int32, each in [0, N)) of low_res_dev. */
+int  loco_samdec_binarize(loco_samdec* t, const float* low_res_dev, int32_t N, const int32_t* rows_dev, int32_t K, int32_t h, int32_t w,
+                          int32_t orig_h, int32_t orig_w, int32_t reshaped_h, int32_t reshaped_w, int32_t image_size, float thr,
+                          uint8_t* masks_out, void* stream);
+/* Message of the last failed call on t; t == NULL: of the last failed loco_samdec_create. */
+const char* loco_samdec_last_error(loco_samdec* t);
+void loco_samdec_destroy(loco_samdec* t);
+
 /* --- CLIP image encoder (scores of the text-guided edits) ---
  * The CLIPVisionModelWithProjection of transformers: patch embedding (no bias) + class token + learned position embedding,
  * pre_layrnorm, `layers` pre-LN blocks (LayerNorm -> full multi-head self-attention, scale head_dim^-0.5 -> residual;

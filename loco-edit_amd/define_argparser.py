@@ -121,6 +121,9 @@ def build_parser():
                    help='Segment Anything model that produces mask/mask.pt on the GPU when it is missing: a local SamModel '
                         'folder (config.json + model.safetensors or pytorch_model.bin) or a checkpoint file in SamModel naming. '
                         'Nothing is downloaded (--mask_model_name stays a name only). Empty: mask/mask.pt must exist')
+    p.add_argument('--mask_head', type=str, default='torch', choices=['torch', 'hip'],
+                   help='prompt encoder / mask decoder / mask filters behind --mask_model_path: torch (functions on the device) or '
+                        'hip (the kernels of csrc/samdec.hip)')
     p.add_argument('--clip_model_path', type=str, default='',
                    help='T-LOCO semantic edits: CLIP model that scores the returned frames on the GPU (image-text cosine with '
                         '--for_prompt / --edit_prompt, cosine with the unedited frame, directional similarity) into '

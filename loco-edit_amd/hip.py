@@ -36,6 +36,8 @@ SYMBOLS = [
     "loco_diffedit_mask", "loco_cfg_masked_step", "loco_set_time_cond", "loco_lcm_step",
     "loco_sam_create", "loco_sam_load_param", "loco_sam_params_missing", "loco_sam_encode", "loco_sam_profile",
     "loco_sam_profile_read", "loco_sam_last_error", "loco_sam_destroy",
+    "loco_samdec_create", "loco_samdec_load_param", "loco_samdec_params_missing", "loco_samdec_set_image", "loco_samdec_predict",
+    "loco_samdec_score", "loco_samdec_binarize", "loco_samdec_last_error", "loco_samdec_destroy",
     "loco_clipvis_create", "loco_clipvis_load_param", "loco_clipvis_params_missing", "loco_clipvis_preprocess",
     "loco_clipvis_encode", "loco_clipvis_last_error", "loco_clipvis_destroy",
     "loco_quality_create", "loco_quality_load_param", "loco_quality_params_missing", "loco_quality_lpips", "loco_quality_ssim",
@@ -90,6 +92,13 @@ class LocoSamCfg(C.Structure):
     _fields_ = [("image_size", C.c_int32), ("patch_size", C.c_int32), ("width", C.c_int32), ("depth", C.c_int32),
                 ("heads", C.c_int32), ("mlp_dim", C.c_int32), ("window_size", C.c_int32), ("num_global", C.c_int32),
                 ("global_attn", C.c_int32 * SAM_MAX_GLOBAL), ("out_channels", C.c_int32), ("ln_eps", C.c_float)]
+
+
+class LocoSamDecCfg(C.Structure):
+    _fields_ = [("grid", C.c_int32), ("image_size", C.c_int32), ("hidden", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32),
+                ("mlp_dim", C.c_int32), ("attention_downsample_rate", C.c_int32), ("num_multimask_outputs", C.c_int32),
+                ("iou_head_depth", C.c_int32), ("iou_head_hidden_dim", C.c_int32), ("layer_norm_eps", C.c_float),
+                ("hidden_act", C.c_int32), ("max_prompts", C.c_int32)]
 
 
 class LocoClipVisCfg(C.Structure):
@@ -190,6 +199,18 @@ def load_library():
         lib.loco_sam_last_error.restype = C.c_char_p
         lib.loco_sam_destroy.argtypes = [vp]
         lib.loco_sam_destroy.restype = None
+    if hasattr(lib, "loco_samdec_create"):
+        lib.loco_samdec_create.argtypes = [C.POINTER(LocoSamDecCfg), i32, C.POINTER(vp)]
+        lib.loco_samdec_load_param.argtypes = [vp, C.c_char_p, vp, C.POINTER(i64), i32]
+        lib.loco_samdec_params_missing.argtypes = [vp]
+        lib.loco_samdec_set_image.argtypes = [vp, vp, vp]
+        lib.loco_samdec_predict.argtypes = [vp, vp, i32, vp, vp, vp]
+        lib.loco_samdec_score.argtypes = [vp, vp] + [i32] * 8 + [f32, f32, vp, vp, vp]
+        lib.loco_samdec_binarize.argtypes = [vp, vp, i32, vp] + [i32] * 8 + [f32, vp, vp]
+        lib.loco_samdec_last_error.argtypes = [vp]
+        lib.loco_samdec_last_error.restype = C.c_char_p
+        lib.loco_samdec_destroy.argtypes = [vp]
+        lib.loco_samdec_destroy.restype = None
     if hasattr(lib, "loco_clipvis_create"):
         lib.loco_clipvis_create.argtypes = [C.POINTER(LocoClipVisCfg), i32, i32, C.POINTER(vp)]
         lib.loco_clipvis_load_param.argtypes = [vp, C.c_char_p, vp, C.POINTER(i64), i32]
@@ -929,6 +950,90 @@ class LocoSamEngine(_EncoderEngine):
         ms = (C.c_float * 4)()
         self._check(self.lib.loco_sam_profile_read(self._t, ms), "loco_sam_profile_read")
         return dict(zip(("gemm", "window_attn", "global_attn", "other"), [float(v) for v in ms]))
+
+
+class LocoSamHeadEngine(_EncoderEngine):
+    """The prompt encoder, mask decoder and mask scoring of Segment Anything (= loco_samdec, include/loco_hip.h): parameters
+    and the workspace of `max_prompts` point prompts on the device.  `cfg` is a ``mask_segmentation.SamConfig``;
+    ``load_state_dict`` takes the names of SamModel (mask_segmentation.head_state_dict produces them).  ``set_image`` once per
+    image embedding, then ``predict`` per batch of prompts; ``score`` / ``binarize`` are the automatic mask generator's view of
+    low-resolution logits at the original size.  Exact fp32."""
+    _prefix, _label = "loco_samdec", "SAM prompt encoder / mask decoder"
+
+    def __init__(self, cfg, max_prompts: int = 64, device: Optional[torch.device] = None):
+        self._open(device)
+        self.cfg, self.max_prompts = cfg, int(max_prompts)
+        d, v = cfg.decoder, cfg.vision
+        if d.hidden_act not in ("relu", "gelu"):
+            raise ValueError(f"mask_decoder hidden_act {d.hidden_act!r}: the head builds relu and the erf gelu")
+        self.grid, self.hidden, self.num_masks = v.grid, d.hidden_size, d.num_multimask_outputs
+        c = LocoSamDecCfg(grid=v.grid, image_size=v.image_size, hidden=d.hidden_size, layers=d.num_hidden_layers,
+                          heads=d.num_attention_heads, mlp_dim=d.mlp_dim, attention_downsample_rate=d.attention_downsample_rate,
+                          num_multimask_outputs=d.num_multimask_outputs, iou_head_depth=d.iou_head_depth,
+                          iou_head_hidden_dim=d.iou_head_hidden_dim, layer_norm_eps=d.layer_norm_eps,
+                          hidden_act={"relu": 0, "gelu": 1}[d.hidden_act], max_prompts=self.max_prompts)
+        self._create("loco_samdec_create", c)
+
+    def set_image(self, image_embeddings: torch.Tensor):
+        """image_embeddings [1, C, G, G] or [C, G, G] (fp32): everything that does not depend on the prompts."""
+        C_, G = self.hidden, self.grid
+        emb = torch.as_tensor(image_embeddings)
+        if tuple(emb.shape) == (1, C_, G, G):
+            emb = emb[0]
+        if tuple(emb.shape) != (C_, G, G):
+            raise ValueError(f"image_embeddings must be [1, {C_}, {G}, {G}] (the grid of this head), got {tuple(image_embeddings.shape)}")
+        emb = emb.to(device=self.device, dtype=torch.float32).contiguous()
+        with torch.cuda.device(self.device):
+            self._check(self.lib.loco_samdec_set_image(self._t, _ptr(emb), _stream()), "loco_samdec_set_image")
+
+    def predict(self, coords: torch.Tensor):
+        """coords [P, 2] fp32: (x, y) as 2 (p + 0.5) / S - 1 -> (low-resolution logits [P, n, 4G, 4G], predicted IoU [P, n])."""
+        coords = torch.as_tensor(coords)
+        if coords.dim() != 2 or coords.shape[1] != 2:
+            raise ValueError(f"coords must be [P, 2], got {tuple(coords.shape)}")
+        P, n, side = coords.shape[0], self.num_masks, 4 * self.grid
+        if not 1 <= P <= self.max_prompts:
+            raise ValueError(f"{P} prompts: one predict call carries 1 ... max_prompts = {self.max_prompts}")
+        coords = coords.to(device=self.device, dtype=torch.float32).contiguous()
+        masks = torch.empty(P, n, side, side, device=self.device, dtype=torch.float32)
+        iou = torch.empty(P, n, device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.loco_samdec_predict(self._t, _ptr(coords), P, _ptr(masks), _ptr(iou), _stream()), "loco_samdec_predict")
+        return masks, iou
+
+    def _low(self, low_res):
+        low = torch.as_tensor(low_res)
+        if low.dim() != 3:
+            raise ValueError(f"low_res must be [N, h, w], got {tuple(low.shape)}")
+        return low.to(device=self.device, dtype=torch.float32).contiguous()
+
+    def score(self, low_res, original_size, reshaped_size, image_size: int, mask_threshold: float, offset: float):
+        """low_res [N, h, w] -> (counts [N, 2] int32: pixels above threshold + offset / - offset; boxes [N, 4] int32: inclusive
+        XYXY of logit > threshold), all at `original_size` through the two bilinear stages of MaskGenerator.upsample."""
+        low = self._low(low_res)
+        N, h, w = low.shape
+        counts = torch.empty(N, 2, device=self.device, dtype=torch.int32)
+        boxes = torch.empty(N, 4, device=self.device, dtype=torch.int32)
+        (oh, ow), (rh, rw) = original_size, reshaped_size
+        with torch.cuda.device(self.device):
+            self._check(self.lib.loco_samdec_score(self._t, _ptr(low), N, h, w, int(oh), int(ow), int(rh), int(rw), int(image_size),
+                                                   float(mask_threshold), float(offset), _ptr(counts), _ptr(boxes), _stream()),
+                        "loco_samdec_score")
+        return counts, boxes
+
+    def binarize(self, low_res, rows, original_size, reshaped_size, image_size: int, mask_threshold: float) -> torch.Tensor:
+        """bool [K, H, W]: logit > threshold at `original_size` for the rows `rows` [K] of low_res [N, h, w]."""
+        low = self._low(low_res)
+        N, h, w = low.shape
+        rows = torch.as_tensor(rows).to(device=self.device, dtype=torch.int32).contiguous()
+        (oh, ow), (rh, rw) = original_size, reshaped_size
+        K = int(rows.numel())
+        out = torch.empty(K, int(oh), int(ow), device=self.device, dtype=torch.uint8)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.loco_samdec_binarize(self._t, _ptr(low), N, _ptr(rows), K, h, w, int(oh), int(ow), int(rh), int(rw),
+                                                      int(image_size), float(mask_threshold), _ptr(out), _stream()),
+                        "loco_samdec_binarize")
+        return out.bool()
 
 
 class LocoClipVisionEngine(_EncoderEngine):

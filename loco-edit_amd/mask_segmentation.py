@@ -2,7 +2,9 @@
 pipeline does on a ``SamModel``, without ``transformers`` and without any hub access.
 
 * the image encoder (a ViT, nearly all of the arithmetic) is the HIP engine ``hip.LocoSamEngine`` (csrc/samenc.hip);
-* the prompt encoder and the mask decoder (about 4 M parameters) are the plain torch functions below, run on the device;
+* the prompt encoder and the mask decoder (about 4 M parameters) are the plain torch functions below, run on the device,
+  or, with ``head="hip"`` / ``--mask_head hip``, the HIP engine ``hip.LocoSamHeadEngine`` (csrc/samdec.hip), which also
+  scores and binarises the candidates for the generator's filters;
 * ``MaskGenerator`` is the automatic mask generator of the pipeline with its defaults: one crop layer, a 32 x 32 point
   grid in batches of 64, the predicted-IoU and stability filters, boxes with the near-crop-edge filter, greedy box NMS.
 
@@ -239,6 +241,63 @@ def head_param_names(cfg: SamConfig) -> List[str]:
     return n
 
 
+def head_param_shapes(cfg: SamConfig) -> Dict[str, Tuple[int, ...]]:
+    """Names (in SamModel naming) and shapes the HIP head's parameter table holds (hip.LocoSamHeadEngine): what
+    ``head_param_names`` lists, less ``point_embed.0`` (the background point, which no prompt here uses)."""
+    d, C = cfg.decoder, cfg.decoder.hidden_size
+    Ci, nm, hid = C // d.attention_downsample_rate, d.num_multimask_outputs + 1, d.iou_head_hidden_dim
+    s: Dict[str, Tuple[int, ...]] = {
+        "shared_image_embedding.positional_embedding": (2, C // 2), "prompt_encoder.no_mask_embed.weight": (1, C),
+        "prompt_encoder.not_a_point_embed.weight": (1, C), "prompt_encoder.point_embed.1.weight": (1, C),
+        "mask_decoder.iou_token.weight": (1, C), "mask_decoder.mask_tokens.weight": (nm, C)}
+    M = "mask_decoder."
+
+    def lin(p, o, i):
+        s[p + ".weight"], s[p + ".bias"] = (o, i), (o,)
+
+    def attn(p, inner):
+        for q in ("q_proj", "k_proj", "v_proj"):
+            lin(p + "." + q, inner, C)
+        lin(p + ".out_proj", C, inner)
+    for i in range(d.num_hidden_layers):
+        p = M + f"transformer.layers.{i}."
+        attn(p + "self_attn", C)
+        attn(p + "cross_attn_token_to_image", Ci)
+        attn(p + "cross_attn_image_to_token", Ci)
+        for j in range(1, 5):
+            s[p + f"layer_norm{j}.weight"], s[p + f"layer_norm{j}.bias"] = (C,), (C,)
+        lin(p + "mlp.lin1", d.mlp_dim, C)
+        lin(p + "mlp.lin2", C, d.mlp_dim)
+    attn(M + "transformer.final_attn_token_to_image", Ci)
+    s[M + "transformer.layer_norm_final_attn.weight"], s[M + "transformer.layer_norm_final_attn.bias"] = (C,), (C,)
+    s[M + "upscale_conv1.weight"], s[M + "upscale_conv1.bias"] = (C, C // 4, 2, 2), (C // 4,)
+    s[M + "upscale_conv2.weight"], s[M + "upscale_conv2.bias"] = (C // 4, C // 8, 2, 2), (C // 8,)
+    s[M + "upscale_layer_norm.weight"], s[M + "upscale_layer_norm.bias"] = (C // 4,), (C // 4,)
+    for i in range(nm):
+        p = M + f"output_hypernetworks_mlps.{i}."
+        lin(p + "proj_in", C, C)
+        lin(p + "layers.0", C, C)
+        lin(p + "proj_out", C // 8, C)
+    p = M + "iou_prediction_head."
+    lin(p + "proj_in", hid, C)
+    for j in range(d.iou_head_depth - 2):
+        lin(p + f"layers.{j}", hid, hid)
+    lin(p + "proj_out", nm, hid)
+    return s
+
+
+def head_state_dict(sd: Dict[str, torch.Tensor], cfg: SamConfig) -> Dict[str, torch.Tensor]:
+    """The HIP head's part of a normalised state dict, checked against the geometry."""
+    want = head_param_shapes(cfg)
+    missing = sorted(k for k in want if k not in sd)
+    if missing:
+        raise ValueError(f"missing keys of the SAM prompt encoder / mask decoder: {missing[:8]}" + (" ..." if len(missing) > 8 else ""))
+    for k, shp in want.items():
+        if tuple(sd[k].shape) != shp:
+            raise ValueError(f"{k}: shape {tuple(sd[k].shape)}, expected {shp}")
+    return {k: sd[k] for k in want}
+
+
 def load_sam(path_or_sd) -> Tuple[SamConfig, Dict[str, torch.Tensor]]:
     """-> (geometry, normalised state dict) from a local ``SamModel`` folder (``config.json`` + ``model.safetensors`` or
     ``pytorch_model.bin``), a checkpoint file, or a bare state dict.  Local files only."""
@@ -421,6 +480,48 @@ class SamHead:
         return self.decode(image_embeddings, self.embed_points(points), image_pe)
 
 
+def prompt_coords(points, image_size: int) -> torch.Tensor:
+    """points [P, 2] (x, y) in the resized image's pixel frame -> what ``SamHead.embed_points`` feeds the random-Fourier
+    features for the foreground point: 2 (p + 0.5) / S - 1 in the points' own precision, then fp32."""
+    pts = torch.as_tensor(points) + 0.5
+    pts = torch.stack([pts[..., 0] / image_size, pts[..., 1] / image_size], dim=-1)
+    return (2 * pts - 1).to(torch.float32)
+
+
+class SamHeadHip:
+    """``SamHead`` on the HIP engine ``hip.LocoSamHeadEngine`` (csrc/samdec.hip): the same ``cfg`` / ``image_pe`` / ``predict``
+    that ``MaskGenerator.generate`` uses, plus ``score`` / ``binarize`` for its filters.  Exact fp32, no torch fallback."""
+
+    def __init__(self, cfg: SamConfig, sd: Dict[str, torch.Tensor], device="cuda:0", max_prompts: int = 64):
+        from .hip import LocoSamHeadEngine
+        self.cfg = cfg
+        self.engine = LocoSamHeadEngine(cfg, max_prompts=max_prompts, device=torch.device(device))
+        self.engine.load_state_dict(head_state_dict(sd, cfg))
+        self.device = self.engine.device
+        self._seen = None
+
+    def image_pe(self):
+        """None: the engine computes the grid's positional encoding itself in ``set_image``."""
+        return None
+
+    def set_image(self, image_embeddings):
+        self.engine.set_image(image_embeddings)
+        self._seen = (image_embeddings, getattr(image_embeddings, "_version", None))
+
+    def predict(self, image_embeddings, points, image_pe=None):
+        """image_embeddings [1, C, G, G], points [P, 2] -> (pred_masks [P, 3, 4G, 4G], iou_scores [P, 3]).  The image side is
+        set up again only when the embedding tensor is not the one last seen (or was written to since)."""
+        if self._seen is None or self._seen[0] is not image_embeddings or self._seen[1] != getattr(image_embeddings, "_version", None):
+            self.set_image(image_embeddings)
+        return self.engine.predict(prompt_coords(points, self.cfg.vision.image_size))
+
+    def score(self, low_res, original_size, reshaped_size, image_size, mask_threshold, offset):
+        return self.engine.score(low_res, original_size, reshaped_size, image_size, mask_threshold, offset)
+
+    def binarize(self, low_res, rows, original_size, reshaped_size, image_size, mask_threshold):
+        return self.engine.binarize(low_res, rows, original_size, reshaped_size, image_size, mask_threshold)
+
+
 # ---------------------------------------------------------------------------------------- automatic mask generator
 def build_point_grid(n_per_side: int) -> np.ndarray:
     offset = 1 / (2 * n_per_side)
@@ -516,13 +617,32 @@ class MaskGenerator:
         m = m[..., : reshaped_size[0], : reshaped_size[1]]
         return F.interpolate(m, tuple(original_size), mode="bilinear", align_corners=False)
 
-    def filter_batch(self, low_res, iou_scores, original_size, reshaped_size, image_size: int, crop_box=None):
+    def filter_batch(self, low_res, iou_scores, original_size, reshaped_size, image_size: int, crop_box=None, scorer=None):
         """One decoder batch -> (masks bool [k, H, W], scores [k], boxes [k, 4]) after the score, stability and edge filters.
         crop_box [left, top, right, bottom]: the part of the image the batch saw (None: all of it, the one crop layer of the
-        defaults); the masks come back padded to the image, the boxes stay in the crop's frame as in the pipeline."""
+        defaults); the masks come back padded to the image, the boxes stay in the crop's frame as in the pipeline.
+        scorer (``SamHeadHip`` or anything with its ``score`` / ``binarize``): the filters run on its counts and boxes, taken
+        at the original size without storing the upsampled logits, and only the survivors are binarised."""
         oh, ow = original_size
         crop = [0, 0, ow, oh] if crop_box is None else [int(v) for v in crop_box]
         left, top, right, bottom = crop
+        if scorer is not None:
+            size = (bottom - top, right - left)
+            low = low_res.flatten(0, 1)
+            counts, boxes = scorer.score(low, size, reshaped_size, image_size, self.mask_threshold, self.stability_score_offset)
+            scores = iou_scores.flatten(0, 1).to(counts.device)
+            keep = torch.ones(low.shape[0], dtype=torch.bool, device=counts.device)
+            if self.pred_iou_thresh > 0.0:
+                keep = keep & (scores > self.pred_iou_thresh)
+            if self.stability_score_thresh > 0.0:
+                keep = keep & ((counts[:, 0] / counts[:, 1]) > self.stability_score_thresh)
+            boxes = boxes.to(torch.int64)
+            keep = keep & ~box_near_crop_edge(boxes, crop, [0, 0, ow, oh])
+            rows = torch.nonzero(keep).flatten()
+            masks = scorer.binarize(low, rows, size, reshaped_size, image_size, self.mask_threshold)
+            if crop != [0, 0, ow, oh]:
+                masks = F.pad(masks, (left, ow - right, top, oh - bottom), value=False)
+            return masks, scores[rows], boxes[rows]
         masks = self.upsample(low_res, (bottom - top, right - left), reshaped_size, image_size).flatten(0, 1)
         scores = iou_scores.flatten(0, 1).to(masks.device)
         keep = torch.ones(masks.shape[0], dtype=torch.bool, device=masks.device)
@@ -546,14 +666,17 @@ class MaskGenerator:
         keep = greedy_nms(boxes, scores, self.crops_nms_thresh).to(masks.device)
         return masks[keep], scores[keep], boxes[keep]
 
-    def generate(self, head: SamHead, image_embeddings, original_size, reshaped_size):
+    def generate(self, head, image_embeddings, original_size, reshaped_size, scorer=None):
         S = head.cfg.vision.image_size
         pts = self.grid_points(original_size, S)
         pe = head.image_pe()
         batches = []
         for i in range(0, pts.shape[0], self.points_per_batch):
             low, iou = head.predict(image_embeddings, pts[i: i + self.points_per_batch], pe)
-            batches.append(self.filter_batch(low, iou, original_size, reshaped_size, S))
+            if scorer is None:
+                batches.append(self.filter_batch(low, iou, original_size, reshaped_size, S))
+            else:
+                batches.append(self.filter_batch(low, iou, original_size, reshaped_size, S, scorer=scorer))
         return self.finish(batches)
 
 
@@ -562,8 +685,15 @@ class SAM(object):
     """``SAM(args, log_dir).mask_segmentation(image, resolution)`` of the reference: bool masks [N, res, res], written to
     ``<log_dir>/mask/mask.pt`` with the overlay PNGs.  The model comes from ``args.mask_model_path`` (a local folder or file)."""
 
-    def __init__(self, args, log_dir, **generator_kwargs):
+    HEADS = ("torch", "hip")
+
+    def __init__(self, args, log_dir, head=None, **generator_kwargs):
+        """head: "torch" (``SamHead`` and the torch filters, the default) or "hip" (``SamHeadHip``: decoder, scoring and
+        binarisation on csrc/samdec.hip); None: ``args.mask_head`` (--mask_head), "torch" without it."""
         from .hip import LocoSamEngine
+        head = head if head is not None else (getattr(args, "mask_head", "") or "torch")
+        if head not in self.HEADS:
+            raise ValueError(f"mask head {head!r}: one of {self.HEADS}")
         path = getattr(args, "mask_model_path", "")
         if not path:
             raise ValueError("--mask_model_path is empty: SAM needs a local SamModel folder or checkpoint")
@@ -572,8 +702,14 @@ class SAM(object):
         self.cfg, sd = load_sam(path)
         self.engine = LocoSamEngine(self.cfg.vision, device=self.device)
         self.engine.load_state_dict(vision_state_dict(sd, self.cfg.vision))
-        self.head = SamHead(self.cfg, sd, device=self.engine.device)
+        self.head_kind = head
         self.generator = MaskGenerator(**generator_kwargs)
+        if head == "hip":
+            self.head = SamHeadHip(self.cfg, sd, device=self.engine.device, max_prompts=self.generator.points_per_batch)
+            self.scorer = self.head
+        else:
+            self.head = SamHead(self.cfg, sd, device=self.engine.device)
+            self.scorer = None
         self.log_dir = os.path.join(log_dir, "mask")
         self.transparency = 0.4
         os.makedirs(self.log_dir, exist_ok=True)
@@ -591,7 +727,10 @@ class SAM(object):
         emb = self.engine.encode(pv)
         torch.cuda.synchronize(self.engine.device)
         t1 = time.perf_counter()
-        out = self.generator.generate(self.head, emb, orig, resh)
+        if self.scorer is None:
+            out = self.generator.generate(self.head, emb, orig, resh)
+        else:
+            out = self.generator.generate(self.head, emb, orig, resh, scorer=self.scorer)
         torch.cuda.synchronize(self.engine.device)
         t2 = time.perf_counter()
         self.last_timing = {"encoder_ms": (t1 - t0) * 1e3, "decoder_generator_ms": (t2 - t1) * 1e3}
