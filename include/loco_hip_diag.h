@@ -19,7 +19,7 @@ int  loco_bench_conv(loco_ctx* ctx, int32_t cin, int32_t cout, int32_t H, int32_
  * (tests/test_gpu_conv_oracle.py compares it with a float64 reference, tests/conv_oracle.py).
  *
  * Geometry is that of the LAUNCH (ConvArgs): Cin channels of Hin x Win go in, Cout channels of Hout x Wout come out with
- *   Hout = Hin / 2 (stride 2), 2 Hin (upsample or zins), Hin (otherwise); Wout likewise.
+ *   Hout = Hin / 2 (stride 2, or pool2), 2 Hin (upsample or zins), Hin (otherwise); Wout likewise.
  * The output map must be one the kernels' tiles cover exactly: Hout and Wout powers of two from 8 (what loco_create admits), or
  * Wout a multiple of 32 with Hout a multiple of 8 and Hout Wout a multiple of 256; other maps are refused.
  * pad < 0 picks what the engine sets: 1 for 3x3 stride 1, 0 for 3x3 stride 2 (the zero row / column sits at the bottom / right)
@@ -48,6 +48,14 @@ int  loco_bench_conv(loco_ctx* ctx, int32_t cin, int32_t cout, int32_t H, int32_
  * and {rstd m1, rstd m2} for the cotangent mode and the norm-cotangent term; the per-group array the exact-fp32 kernel reads
  * (ConvArgs::tst) is never scaled.  The {S = sc act'(sc x + sh), xhat} records of prim / cot_prim are built by launch_gn_cache.
  *
+ *   pool2 = 1 (raw 3x3 stride-1 launches, even maps): the launch is conv + 2x2 sum-pool, the cotangent of the nearest-x2 up conv
+ *   (ConvArgs::pool2); out [B][Cout][Hin / 2][Win / 2] (accumulate applies to it), the full-resolution intermediate is this call's.
+ *   tangent statistics request (st_prim != null; mode CM_NONE launches): the launch carries the request the tangent pass attaches
+ *   for the next norm over one part of a concatenation (raw {sum d, sum x d} row partials kept from the conv epilogue where
+ *   the planner routes them there), x = st_prim [Cout][Hout][Wout] the primal of the output tensor, st_mr [Cout / st_cpg][2] =
+ *   {mean, rstd} of that norm's groups.  st_out [2][B][Cout / st_cpg][2] receives {m1, m2} per (sample, group): [0] merged from
+ *   the kept partials (all-ones bit patterns, i.e. NaN, where the launch kept none), [1] by the standalone pass over the finished tensor.
+ *
  * in_arena = 1: `in` (and in2, prim, cot_d) are copied into the engine's padded arenas, as every inner conv sees them;
  * in_arena = 0: the kernel reads the caller's `in` (ConvArgs::in_padded = 0: the network's first conv on the user's tensor).
  *
@@ -63,13 +71,16 @@ typedef struct loco_conv_desc {
     int32_t transposed, accumulate, in_arena, pad;
     int32_t Cin2, cot_cpg;
     float   res_scale;
-    int32_t reserved;
+    int32_t st_cpg;
     const float *weight, *bias;                                  /* host */
     const float *in, *bias2, *res;
     const float *prim, *sc, *sh, *mr, *gamma, *tst, *tc;
     const float *in2, *w2, *bias2nd;                             /* in2: device; w2, bias2nd: host */
     const float *cot_d, *cot_prim, *cot_sc, *cot_sh, *cot_mr, *cot_tc;
     float* out;
+    const float *st_prim, *st_mr;                                /* tangent statistics request, see above */
+    float* st_out;
+    int32_t pool2;                                               /* 1: a 2x2 sum-pool follows the conv, see above */
 } loco_conv_desc;
 int  loco_debug_conv(loco_ctx* ctx, const loco_conv_desc* desc, char* plan, int64_t cap, void* stream);
 

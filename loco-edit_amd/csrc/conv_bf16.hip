@@ -11,6 +11,8 @@ template <int PR, int TAPS, int MODE> void launch_tile_b(const ConvArgs& a, hipS
 template <int PR, int MODE> void launch_kcat_b(const ConvArgs& a, hipStream_t st);            // conv_bf16_inst_*.hip
 template <int PR, int MODE> void launch_pair_b(const ConvArgs& a, hipStream_t st);            // conv_bf16_inst_k.hip (conv_pair_kernel.h)
 void launch_conv_gemm(const ConvArgs& a, hipStream_t st);      // conv_bf16_inst_j.hip (conv_gemm_kernel.h)
+template <int PR> void launch_poly_b(const ConvArgs& a, hipStream_t st);                      // conv_bf16_inst_p*.hip
+template <int PR> void launch_poly_in_b(const ConvArgs& a, hipStream_t st);                   // conv_bf16_inst_p*.hip
 
 template <int PR>
 static void launch_lowp(const ConvArgs& a, int taps, hipStream_t st) {
@@ -26,6 +28,8 @@ static void launch_lowp(const ConvArgs& a, int taps, hipStream_t st) {
     if constexpr (PR == PR_BF16X3) {
         if (taps == 1 && a.gemm) { launch_conv_gemm(a, st); return; }
     }
+    if (taps == 9 && a.poly == 2) { launch_poly_in_b<PR>(a, st); return; }      // transposed up conv + 2x2 pool (conv_plan.hip conv_poly_in_ok)
+    if (taps == 9 && a.poly) { launch_poly_b<PR>(a, st); return; }      // polyphase up / zero-insert conv (conv_plan.hip conv_poly_ok)
     if (taps == 9 && a.Cin2 > 0) {       // K-concatenated shortcut (plan_conv checked conv_lowp_can_kcat)
         if (a.mode == CM_GN_SILU) launch_kcat_b<PR, CM_GN_SILU>(a, st);
         else if (a.mode == CM_GN_GELU) launch_kcat_b<PR, CM_GN_GELU>(a, st);      // forward pass of a GELU network (DeepFloyd IF)

@@ -453,6 +453,115 @@ __device__ __forceinline__ void conv_lowp_epilogue_direct(const ConvArgs& a, f32
     }
 }
 
+// Epilogue of the polyphase form (conv_lowp_body, TAPS == 4; 128 virtual couts x 256 low-resolution pixels): the tile is row
+// phase pa of 64 channels, staging rows r and r + 32 of a round are column phases 0 and 1 of ONE channel (polyphase_vcout), and
+// both are read back by the same lane at the same 4 pixels -- interleaved they are 8 consecutive pixels of output row 2 y + pa:
+// two 16-byte stores.  `a` is the virtual conv (launch_poly_b): a.Cout = 4 C, a.Hout x a.Wout the low-resolution map.  Bias and
+// accumulate at the real channel / address; tangent statistics (ST_TAN) as raw {sum d, sum x d} per (channel, row phase, pixel
+// tile): 2 x (low-resolution tiles) partials per channel row, each over 512 output pixels.
+template <int WM, int WN, int TM, int TN>
+__device__ __forceinline__ void conv_lowp_epilogue_poly(const ConvArgs& a, f32x16 (&acc)[TM][TN], unsigned char* smem_b, const int cot_id,
+                                                        const int pa, const int oy0, const int ox0, const int TW, const int tile_id,
+                                                        const int b) {
+    constexpr int NTHR = WM * WN * 64, NT = WN * TN * 32, NQ = NT / 4, RSTEP = NTHR / NQ, NP = 32 / RSTEP;
+    static_assert(WM == 2 && NTHR % NQ == 0 && 32 % RSTEP == 0 && NQ == 64, "polyphase epilogue: a task row is one wave");
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int l31 = lane & 31, khalf = lane >> 5, wm = wave / WN, wn = wave % WN;
+    const int C = a.Cout >> 2, ncb = C >> 6;
+    const int ch0 = (cot_id - pa * ncb) * 64;                    // first real channel of the tile
+    const int Wo = 2 * a.Wout;
+    const unsigned out_plane = 4u * (unsigned)(a.Hout * a.Wout);
+    float* const S = reinterpret_cast<float*>(smem_b);
+    float* const ob = a.out + (long)b * a.out_bs;
+    const float* const b2 = a.bias2 ? a.bias2 + (long)b * a.bias2_bs : nullptr;
+    const bool accu = a.accumulate != 0;
+    const bool tan_st = a.st_kind == ST_TAN;
+    const int twsh = 31 - __builtin_clz((unsigned)TW);
+    const int row0 = tid / NQ, quad0 = tid & (NQ - 1);
+    const unsigned pix0 = (unsigned)((2 * (oy0 + ((quad0 * 4) >> twsh)) + pa) * Wo + 2 * (ox0 + ((quad0 * 4) & (TW - 1))));
+    constexpr int NV = 2 * TM * NP;
+    float av[NV];
+#pragma unroll
+    for (int h = 0; h < TM; ++h) {
+        if (h > 0) {
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+        }
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                S[(wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf) * NT + (wn * TN + j) * 32 + l31] = acc[h][j][r];
+        f32x4 xs[NP][2];
+        if (tan_st) {
+#pragma unroll
+            for (int q = 0; q < NP; ++q) {
+                const unsigned o = (unsigned)(ch0 + h * 32 + q * RSTEP + row0) * out_plane + pix0;
+                xs[q][0] = *reinterpret_cast<const f32x4*>(a.st_x + o);
+                xs[q][1] = *reinterpret_cast<const f32x4*>(a.st_x + o + 4);
+            }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        f32x4 o0[NP], o1[NP];
+#pragma unroll
+        for (int q = 0; q < NP; ++q) {
+            const f32x4 v0 = *reinterpret_cast<const f32x4*>(&S[(q * RSTEP + row0) * NT + quad0 * 4]);
+            const f32x4 v1 = *reinterpret_cast<const f32x4*>(&S[(32 + q * RSTEP + row0) * NT + quad0 * 4]);
+            o0[q] = f32x4{v0[0], v1[0], v0[1], v1[1]};
+            o1[q] = f32x4{v0[2], v1[2], v0[3], v1[3]};
+        }
+        if (accu) {
+            f32x4 r0[NP], r1[NP];
+#pragma unroll
+            for (int q = 0; q < NP; ++q) {
+                const unsigned o = (unsigned)(ch0 + h * 32 + q * RSTEP + row0) * out_plane + pix0;
+                r0[q] = *reinterpret_cast<const f32x4*>(ob + o);
+                r1[q] = *reinterpret_cast<const f32x4*>(ob + o + 4);
+            }
+#pragma unroll
+            for (int q = 0; q < NP; ++q) { o0[q] += r0[q]; o1[q] += r1[q]; }
+        }
+#pragma unroll
+        for (int q = 0; q < NP; ++q) {
+            const int co = ch0 + h * 32 + q * RSTEP + row0;
+            const unsigned o = (unsigned)co * out_plane + pix0;
+            float add = 0.f;
+            if (a.bias) add += a.bias[co];
+            if (b2) add += b2[co];
+            o0[q] += add; o1[q] += add;
+            __builtin_nontemporal_store(o0[q], reinterpret_cast<f32x4*>(ob + o));
+            __builtin_nontemporal_store(o1[q], reinterpret_cast<f32x4*>(ob + o + 4));
+            if (tan_st) {
+                const f32x4 va = o0[q], vb = o1[q], xa = xs[q][0], xb = xs[q][1];
+                av[(h * NP + q) * 2] = ((va[0] + va[1]) + (va[2] + va[3])) + ((vb[0] + vb[1]) + (vb[2] + vb[3]));
+                av[(h * NP + q) * 2 + 1] = (fmaf(xa[0], va[0], xa[1] * va[1]) + fmaf(xa[2], va[2], xa[3] * va[3])) +
+                                           (fmaf(xb[0], vb[0], xb[1] * vb[1]) + fmaf(xb[2], vb[2], xb[3] * vb[3]));
+            }
+        }
+    }
+    if (tan_st) {
+        // one recursive-halving reduction over the wave (= the 64 lanes of every task row), as conv_lowp_epilogue_staged
+        constexpr int STEPS = rs_steps(NV, 64), LEFT = NV >> STEPS;
+        static_assert((NV & (NV - 1)) == 0, "row sums per lane");
+        rs_reduce<NV, 1, 64>(av, lane);
+        if (lane < (1 << STEPS)) {
+            int base = 0;
+#pragma unroll
+            for (int sb = 0; sb < STEPS; ++sb) base += ((lane >> sb) & 1) * (NV >> (sb + 1));
+            const int ntl = (a.Hout * a.Wout) / NT, ntile = 2 * ntl;
+            float* const sp = a.st_part + (long)b * C * ntile * 2;
+#pragma unroll
+            for (int i = 0; i < LEFT; ++i) {
+                const int idx = base + i, hq = idx >> 1;
+                const int h = hq / NP, q = hq - h * NP;
+                const int co = ch0 + h * 32 + q * RSTEP + row0;
+                sp[((long)co * ntile + pa * ntl + tile_id) * 2 + (idx & 1)] = av[i];
+            }
+        }
+    }
+}
+
 // PHASE 0: the whole kernel.  K-concatenated pair (ResBlock conv2 + its 1x1 shortcut on the block input, one accumulator
 // tile, one write-out): PHASE 1 = the first operator's stage loop only (accumulators zeroed, no epilogue), PHASE 2 = the
 // second operator's stage loop on top of the same accumulators, then the epilogue.
@@ -464,9 +573,20 @@ __device__ __forceinline__ void conv_lowp_body(const ConvArgs& a, f32x16 (&acc)[
     constexpr int NPC = RB / 16;                      // 16-byte pieces per record
     constexpr int MT = WM * TM * 32;
     constexpr int NT = WN * TN * 32;
-    constexpr int KS = (TAPS == 9) ? 3 : 1;
+    // TAPS == 4: the polyphase form of a 3x3 conv over a nearest-x2 or zero-inserted input (ConvArgs::poly): a 2x2 conv of the
+    // low-resolution tensor per output phase, on the 3x3 halo geometry (HK) with the tap origin shifted by the phase
+    // STG 0 (POLY): output phases -- 4 C virtual couts over the low-resolution input, epilogue interleaves the phases;
+    // STG 1 (PIN): INPUT phases -- the transposed 3x3 conv followed by the 2x2 sum-pool (the up conv's cotangent) is a 4x4
+    // stride-2 conv = four K-concatenated 2x2 convs, one per phase-subsampled input g[2u+p][2v+q] (virtual Cin = 4 Cin, phase-major
+    // chunks, per-pixel staging of the stride-2 samples), tap origin (1 - p, 1 - q) per chunk, ordinary epilogue at low resolution
+    constexpr bool POLY = (TAPS == 4 && STG == 0), PIN = (TAPS == 4 && STG == 1);
+    static_assert(TAPS != 4 || POLY || PIN, "4-tap kernels: the two polyphase forms");
+    static_assert(!PIN || (MODE == CM_NONE && PHASE == 0), "polyphase input form: raw");
+    constexpr int KS = (TAPS == 9) ? 3 : (TAPS == 4 ? 2 : 1);
+    constexpr int HK = (TAPS == 1) ? 1 : 3;          // kernel extent the halo is staged for
     constexpr int NTS = KS;                          // taps per weight stage (one kernel row)
-    constexpr int NROW = (TAPS == 9) ? 3 : 1;        // weight stages per channel chunk
+    constexpr int NROW = KS;                         // weight stages per channel chunk
+    static_assert(!POLY || (WM == 2 && TM == 2 && MODE == CM_NONE && PHASE == 0), "polyphase output form: 128 x 256 tile, raw vector staging");
     constexpr bool NEEDP = (MODE == CM_TAN_SILU || MODE == CM_COT_SILU);
     // GEN: general per-pixel staging (stride 2, upsample, zero insertion, partial channel chunks, caller-owned
     // tensors); !GEN: 16-byte loads of 4 consecutive pixels from padded arena tensors (stride-1 convs)
@@ -583,16 +703,25 @@ __device__ __forceinline__ void conv_lowp_body(const ConvArgs& a, f32x16 (&acc)[
                 }
         }
     }
-    const int halo_w = (TW - 1) * S + KS;
-    const int halo_h = (TH - 1) * S + KS;
+    const int halo_w = (TW - 1) * S + HK;
+    const int halo_h = (TH - 1) * S + HK;
     const int halo_sz = halo_h * halo_w;
+    // polyphase: the cout tile is one row phase pa and 64 channels; its first 64 rows (waves wm = 0) are column phase 0, the
+    // others column phase 1 (polyphase_vcout).  Phase (pa, pb) reads rows y + pa - 1 + {0, 1}, columns x + pb - 1 + {0, 1}: in
+    // halo coordinates (origin y - 1, x - 1) the tap origin is (pa, pb), a workgroup- / wave-uniform addend
+    int pa_ = 0, pb_ = 0;
+    if constexpr (POLY) {
+        pa_ = __builtin_amdgcn_readfirstlane(idiv_small(cot_id, a.Cout >> 8));      // (Cout = 4 C virtual couts, C / 64 tiles per row phase)
+        pb_ = __builtin_amdgcn_readfirstlane(wm);
+    }
+    int tap0 = pa_ * halo_w + pb_;      // halo record the 2x2 footprint starts at (PIN: set per chunk in the stage loop)
     // + dump records for the lanes without a halo item
     const int HBYTES = (halo_sz + NDUMMY) * HP;
     Hsb = smem_b + NWB * WBYTES;
 
     const int LH = (a.upsample || a.zins) ? a.Hin * 2 : a.Hin;
     const int LW = (a.upsample || a.zins) ? a.Win * 2 : a.Win;
-    const long in_plane = (long)a.Hin * a.Win;
+    const long in_plane = PIN ? 4L * a.Hin * a.Win : (long)a.Hin * a.Win;      // (PIN: a.Hin x a.Win is one phase image of the 2x map)
 
     // staging items of this thread: (octet of 8 channels, halo position).  Loads are issued
     // UNCONDITIONALLY from clamped addresses (uniform base + 32-bit per-lane offset) and masked
@@ -613,7 +742,7 @@ __device__ __forceinline__ void conv_lowp_body(const ConvArgs& a, f32x16 (&acc)[
             if (Y >= 0 && Y < LH && X >= 0 && X < LW) {
                 if (a.upsample) off = (Y >> 1) * a.Win + (X >> 1);
                 else if (a.zins) off = ((Y | X) & 1) ? -1 : (Y >> 1) * a.Win + (X >> 1);
-                else off = Y * a.Win + X;
+                else off = PIN ? 4 * Y * a.Win + 2 * X : Y * a.Win + X;      // (PIN: sample (2Y, 2X) of the map; the phase shift is per chunk)
             }
         } else {
             pos = -1; oct = 0;
@@ -723,7 +852,7 @@ __device__ __forceinline__ void conv_lowp_body(const ConvArgs& a, f32x16 (&acc)[
     // !GEN: the item (4 channels x 4 pixels) is staged in NPART parts of KP channels, one part per weight stage, so
     // only KP channels are live in registers at a time (3x3: 2 parts of 2 channels; 1x1: the whole item).  Parts
     // split the CHANNELS, not the pixels: every load stays a full 16-byte run of 4 pixels.
-    constexpr int NPART = (!GEN && NROW == 3) ? 2 : 1;
+    constexpr int NPART = (!GEN && NROW >= 2) ? 2 : 1;
     constexpr int KP = 4 / NPART;
     // The staged values stay whole 16-byte vectors from the load to their last use (components are sub-register
     // reads): split into scalars, the register allocator parks the load results in freed fragment registers and copies
@@ -844,8 +973,14 @@ __device__ __forceinline__ void conv_lowp_body(const ConvArgs& a, f32x16 (&acc)[
         }
     };
     auto load_regs = [&](float (&hvd)[NITEM][8], int chunk) {
-        const int c0 = chunk * BKC;
-        if (c0 + BKC <= a.Cin) {
+        int c0 = chunk * BKC;
+        long poff = 0;
+        if constexpr (PIN) {      // chunk = (phase, 16 real channels): the channels' planes, shifted to the phase's first sample
+            const int cpp = a.Cin >> 6, ph = __builtin_amdgcn_readfirstlane(idiv_small(chunk, cpp));
+            c0 = (chunk - ph * cpp) * BKC;
+            poff = (long)(ph >> 1) * 2 * a.Win + (ph & 1);
+        }
+        if (PIN || c0 + BKC <= a.Cin) {
             // fast path: all 16 channels exist -> wave-uniform plane base + per-lane 32-bit offset
             if constexpr (TAPS == 9 && !NEEDP) {
                 // 3x3 operators on the per-pixel path that read one value per element (stride 2, folded upsampling, caller-owned
@@ -864,7 +999,7 @@ __device__ __forceinline__ void conv_lowp_body(const ConvArgs& a, f32x16 (&acc)[
             } else {
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
-                const float* pk = inb + (long)(c0 + k) * in_plane;
+                const float* pk = inb + (long)(c0 + k) * in_plane + poff;
                 const float2* sk = NEEDP ? sxb + (long)(c0 + k) * in_plane : nullptr;
 #pragma unroll
                 for (int i = 0; i < NITEM; ++i) {
@@ -978,7 +1113,7 @@ __device__ __forceinline__ void conv_lowp_body(const ConvArgs& a, f32x16 (&acc)[
     constexpr int NLO = PR == PR_BF16X3 ? 1 : 0;     // lo halves exist only in the split arithmetic
     struct Frag { s16x8 ah[TM], al[NLO ? TM : 1], bh[TN], bl[NLO ? TN : 1]; };
     auto load_frag = [&](Frag& f, int row, int tp) {
-        const int tapoff = (TAPS == 9) ? row * halo_w + tp : 0;
+        const int tapoff = (TAPS == 9) ? row * halo_w + tp : (TAPS == 4 ? tap0 + row * halo_w + tp : 0);
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
             f.ah[i] = *reinterpret_cast<const s16x8*>(Ws + tp * MT * RB + aoff_hi[i]);
@@ -1323,6 +1458,10 @@ __device__ __forceinline__ void conv_lowp_body(const ConvArgs& a, f32x16 (&acc)[
     }
     for (int ci = 0; ci < nch; ++ci) {
         const int chunk = cbeg + ci;
+        if constexpr (PIN) {      // input phase (p, q) of this chunk reads rows y - p + {0, 1}: halo origin (1 - p, 1 - q)
+            const int ph = __builtin_amdgcn_readfirstlane(idiv_small(chunk, a.Cin >> 6));
+            tap0 = (1 - (ph >> 1)) * halo_w + 1 - (ph & 1);
+        }
 #pragma unroll
         for (int row = 0; row < NROW; ++row) {
             const int s_ = ci * NROW + row;
@@ -1332,7 +1471,7 @@ __device__ __forceinline__ void conv_lowp_body(const ConvArgs& a, f32x16 (&acc)[
             unsigned char* const Hnxt = Hsb + ((ci + 1) & 1) * HBYTES;
             // which halo part of the next chunk this row converts (-1: none) and which it loads at its end
             constexpr bool one = (NROW == 1);
-            const int st_part = one ? 0 : (NPART == 2 ? (row == 0 ? 0 : row == 1 ? 1 : -1) : (row == 2 ? 0 : -1));
+            const int st_part = one ? 0 : (NPART == 2 ? (row == 0 ? 0 : row == 1 ? 1 : -1) : (row == NROW - 1 ? 0 : -1));
             // vector path: a part's registers are re-loaded right after they are converted (mid-stage), so the
             // loads have one to two whole stages to land; per-pixel path: loads at the end of row 0
             const int ld_part = one ? 0 : (NPART == 2 ? (row == 0 ? 1 : row == 1 ? 0 : -1) : (row == 0 ? 0 : -1));
@@ -1386,7 +1525,8 @@ __device__ __forceinline__ void conv_lowp_body(const ConvArgs& a, f32x16 (&acc)[
         return;
     }
     LP_STAMP(3);
-    conv_lowp_epilogue<WM, WN, TM, TN, (TAPS == 1 && PHASE == 0) ? (EPI_COT1 | EPI_STATS) : EPI_STATS>(a, acc, smem_b, co0, oy0, ox0, TW, tile_id, b, split);
+    if constexpr (POLY) conv_lowp_epilogue_poly<WM, WN, TM, TN>(a, acc, smem_b, cot_id, pa_, oy0, ox0, TW, tile_id, b);
+    else conv_lowp_epilogue<WM, WN, TM, TN, (TAPS == 1 && PHASE == 0) ? (EPI_COT1 | EPI_STATS) : EPI_STATS>(a, acc, smem_b, co0, oy0, ox0, TW, tile_id, b, split);
     LP_STAMP(4);
 #undef LP_STAMP
 }
@@ -1430,10 +1570,10 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_kcat_f16(ConvArgs a) { conv
 template <int PR, int TAPS, int WM, int WN, int TM, int TN, int MODE, int STG>
 static void launch_one_b2(const ConvArgs& a, hipStream_t st) {
     constexpr int MT = WM * TM * 32, NT = WN * TN * 32;
-    constexpr int KS = (TAPS == 9) ? 3 : 1;
+    constexpr int KS = (TAPS == 9) ? 3 : (TAPS == 4 ? 2 : 1), HK = (TAPS == 1) ? 1 : 3;
     int TW = a.Wout < 32 ? a.Wout : 32;
     int TH = NT / TW;
-    int halo_w = (TW - 1) * a.stride + KS, halo_h = (TH - 1) * a.stride + KS;
+    int halo_w = (TW - 1) * a.stride + HK, halo_h = (TH - 1) * a.stride + HK;
     const int nwb = (TAPS == 9 && STG != 2) ? 3 : 2;
     size_t lds = (size_t)nwb * KS * MT * rec_bytes<PR>() + 2 * ((size_t)halo_w * halo_h + NDUMMY) * halo_pitch<PR>();
     const size_t stage_bytes = (size_t)WM * 32 * NT * 4;      // epilogue staging tile S[WM*32 couts][NT pixels]
@@ -1485,6 +1625,26 @@ void launch_kcat_b(const ConvArgs& a, hipStream_t st) {
     if (first_on_device(once))
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipLaunchKernelGGL(kern, grid, dim3(WM * WN * 64), lds, st, a);
+}
+
+// Polyphase launch (ConvArgs::poly, planned by conv_plan.hip conv_poly_ok): the kernel sees the VIRTUAL stride-1 conv -- 4 C couts
+// over the low-resolution map, 4 taps -- and its epilogue writes phase (pa, pb) of channel co to (co, 2 y + pa, 2 x + pb)
+template <int PR>
+void launch_poly_b(const ConvArgs& a, hipStream_t st) {
+    ConvArgs v = a;
+    v.Cout = 4 * a.Cout; v.Hout = a.Hin; v.Wout = a.Win;
+    v.upsample = 0; v.zins = 0; v.stride = 1; v.pad = 1; v.nsplit = 1;
+    launch_one_b2<PR, 4, 2, 4, 2, 2, CM_NONE, 0>(v, st);
+}
+
+// Polyphase input form (ConvArgs::poly == 2: transposed 3x3 conv + 2x2 sum-pool in one launch): the kernel sees a stride-1 conv of
+// 4 Cin virtual channels -- the four phase images of the 2x map -- onto the low-resolution output
+template <int PR>
+void launch_poly_in_b(const ConvArgs& a, hipStream_t st) {
+    ConvArgs v = a;
+    v.Cin = 4 * a.Cin; v.Hin = a.Hin / 2; v.Win = a.Win / 2;
+    v.upsample = 0; v.zins = 0; v.stride = 1; v.pad = 1; v.nsplit = 1;
+    launch_one_b2<PR, 4, 2, 4, 2, 2, CM_NONE, 1>(v, st);
 }
 
 template <int PR, int TAPS, int MODE>

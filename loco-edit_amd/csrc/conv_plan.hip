@@ -69,8 +69,36 @@ static int bf16_tile_of(const ConvArgs& a, int tile_override = -1) {
 static int tile_for(const ConvArgs& a, int prec, int tile_override) {
     return prec ? bf16_tile_of(a, tile_override) : pick_tile(a.Cout, a.Hout * a.Wout);
 }
-static int conv_bf16_tile_pixels(const ConvArgs& a) { return a.gemm ? 256 : kNT[a.tile]; }
+// (polyphase: a workgroup finishes 256 low-resolution pixels in both column phases = 512 output pixels of 64 channels; its
+//  epilogue statistics are per channel row, so whole 128-cout tiles of the lock-step kernel are whole tiles of it too)
+static int conv_bf16_tile_pixels(const ConvArgs& a) { return a.poly == 1 ? 512 : a.gemm ? 256 : kNT[a.tile]; }
 int conv_bf16_tile_couts(const ConvArgs& a) { return a.gemm ? 64 * a.gemm_tm : kMT[a.tile]; }
+
+// Polyphase form of the 3x3 convs over a nearest-x2 or zero-inserted input (conv_bf16_kernel.h, TAPS = 4): per output phase a
+// 2x2 conv of the low-resolution tensor on folded weights (polyphase_fold) -- 16 tap products per low-resolution pixel where the
+// 3x3 route issues 36, on the vector staging of an arena tensor instead of the per-pixel staging that fabricates the duplicates /
+// zeros.  Raw launches of whole 128-cout tiles on maps of whole 32 x 8 low-resolution tiles, probe batches, never split-K; the
+// epilogue takes bias, bias2 and accumulate, no residual.  LOCO_POLYPHASE=0: the 3x3 route.
+static bool conv_poly_ok(const ConvEnv& e, const ConvArgs& a, int taps) {
+    static const bool on = env_int("LOCO_POLYPHASE", 1) != 0;
+    if (!on || e.prec < 1 || taps != 9 || a.mode != CM_NONE || !(a.upsample || a.zins) || a.stride != 1) return false;
+    if (!(e.prec == 2 ? a.wph : a.wpb) || !a.in_padded || a.res || a.Cin2 > 0 || a.cot_d) return false;
+    if (a.upsample ? a.pad != 1 : (a.pad != 1 && a.pad != 2)) return false;
+    if ((a.Cin % BKC) != 0 || (a.Cout % 128) != 0 || a.B < 2) return false;
+    if (a.Hin * a.Win < 4096 || a.Win < 32 || (a.Win % 32) != 0 || (a.Hin % 8) != 0) return false;
+    return a.Hout == 2 * a.Hin && a.Wout == 2 * a.Win;
+}
+// The up conv's cotangent, pool2x2_sum(conv3x3_pad1(g)) (ConvArgs::pool2), as ONE launch of the polyphase input form: a 4x4
+// stride-2 conv, 16 tap products per low-resolution pixel for the 36 of the 3x3 conv at full resolution, no full-resolution
+// intermediate and no pooling pass.  Same shape rules as conv_poly_ok on the low-resolution (output) map.
+static bool conv_poly_in_ok(const ConvEnv& e, const ConvArgs& a, int taps) {
+    static const bool on = env_int("LOCO_POLYPHASE", 1) != 0;
+    if (!on || e.prec < 1 || taps != 9 || a.mode != CM_NONE || !a.pool2 || a.upsample || a.zins || a.stride != 1 || a.pad != 1) return false;
+    if (!(e.prec == 2 ? a.wqh : a.wqb) || a.res || a.bias2 || a.Cin2 > 0 || a.cot_d) return false;
+    if ((a.Cin % BKC) != 0 || (a.Cout % 128) != 0 || a.B < 2 || ((a.Hin | a.Win) & 1)) return false;
+    if (a.Hout * a.Wout < 4096 || a.Wout < 32 || (a.Wout % 32) != 0 || (a.Hout % 8) != 0) return false;
+    return a.Hin == 2 * a.Hout && a.Win == 2 * a.Wout;
+}
 
 // split-K factor for the split-bf16 kernels: splitting costs a partial round trip + a reduce launch, so only
 // split when the un-split grid would leave more than half of the CUs idle
@@ -122,7 +150,7 @@ static bool conv_lowp_can_fuse_stats(const ConvArgs& a) {
 // and 128^2; +-1 % at 64^2, where its two-latency prologue shows).  LOCO_CONV_PAIR=0: the 32x32x16 kernel.
 static bool conv_pair_ok(const ConvArgs& a) {
     static const bool on = env_int("LOCO_CONV_PAIR", 1) != 0;
-    if (!on || a.Hout * a.Wout < 16384 || a.taps != 9 || a.Cin2 > 0 || a.nsplit != 1 || a.stride != 1 || a.upsample || a.zins ||
+    if (!on || a.poly || a.Hout * a.Wout < 16384 || a.taps != 9 || a.Cin2 > 0 || a.nsplit != 1 || a.stride != 1 || a.upsample || a.zins ||
         a.pad != 1 || !a.in_padded || (a.Cin % (2 * BKC)) != 0 || (a.Cout % 128) != 0 || (a.Wout % 32) != 0 || (a.Hout % 8) != 0)
         return false;
     if (!(a.mode == CM_NONE || a.mode == CM_GN_SILU || a.mode == CM_TAN_SILU || a.mode == CM_COT_SILU)) return false;
@@ -229,7 +257,7 @@ static int stats_route(const ConvEnv& e, const StatAsk* q, bool want, ConvArgs& 
     const size_t need = (size_t)x.B * x.Cout * ntile * 2;
     const int epi = q->norm ? SR_EPI : SR_KEEP;
     const bool kept = q->keep && s0 == 0 && x.B == B && need <= q->keep_floats;      // the whole batch in one launch
-    if (q->kind == ST_FWD && conv_lowp_can_fuse_stats(x) && (kept || (q->norm && need <= e.stpart_floats))) {
+    if (q->kind == ST_FWD && x.poly != 1 && conv_lowp_can_fuse_stats(x) && (kept || (q->norm && need <= e.stpart_floats))) {
         x.st_part = kept ? q->keep : e.stpart; x.st_kind = ST_FWD;
         if (kept) *keep_ntile = ntile;
         return epi;
@@ -238,7 +266,7 @@ static int stats_route(const ConvEnv& e, const StatAsk* q, bool want, ConvArgs& 
     // to a norm-cotangent term (the epilogue holds one of the two in its record registers).  A tangent launch that finishes one
     // part of a concatenation keeps its (norm-independent) raw sums in the part's buffer, at this lane's samples: lane rows are
     // keep_floats / max_batch floats apart whatever tile either lane runs.
-    const bool cot_cache = q->kind == ST_COT && q->norm && q->sx;
+    const bool cot_cache = q->kind == ST_COT && q->norm && q->sx && x.poly != 1;      // (the polyphase output form's epilogue takes the tangent kind only)
     if ((q->kind == ST_TAN || cot_cache) && e.fuse_lin && !x.cot_d && conv_lowp_can_fuse_stats(x)) {
         const size_t lane_off = (size_t)e.lane_s0 * (q->keep_floats / e.max_batch);
         const bool keptl = q->kind == ST_TAN && q->keep && s0 == 0 && x.B == B && lane_off + need <= q->keep_floats;
@@ -268,6 +296,14 @@ ConvPlan plan_conv(const ConvEnv& e, const ConvArgs& a0, int taps, const StatAsk
     ConvArgs a = a0;
     a.taps = taps;
     a.gemm = 0;
+    a.poly = 0;
+    if (a.pool2) {
+        if (conv_poly_in_ok(e, a, taps)) a.poly = 2;
+        else {      // the 3x3 conv at full resolution into pool_tmp, then the pooling pass (run_conv)
+            p.pool_after = true; p.pool_out = a.out; p.pool_out_bs = a.out_bs; p.pool_acc = a.accumulate;
+            a.out = a.pool_tmp; a.out_bs = a.pool_tmp_bs; a.Hout = a.Hin; a.Wout = a.Win; a.accumulate = 0; a.pool2 = 0;
+        }
+    }
     if (sc) {
         // the shortcut K-concatenated into this 3x3 launch (conv_lowp_kcat: one write-out, no read-modify-write of the block
         // output, one launch less) where the launch allows it -- one round of whole probes (no tail-probe split) -- else run first
@@ -302,10 +338,13 @@ ConvPlan plan_conv(const ConvEnv& e, const ConvArgs& a0, int taps, const StatAsk
     if (a.nsplit < 1) a.nsplit = 1;
     a.partial = e.partial;
     a.partial_floats = e.partial_floats;
+    if (!a.poly && conv_poly_ok(e, a, taps)) a.poly = 1;
+    if (a.poly == 1) { a.nsplit = 1; a.wb = e.prec == 2 ? a.wph : a.wpb; }
+    if (a.poly == 2) { a.nsplit = 1; a.wb = e.prec == 2 ? a.wqh : a.wqb; }
     conv_plan_family(a, e.prec);
     a.tile = tile_for(a, e.prec, -1);
     int split = 1;
-    const int tail = e.prec >= 1 && a.nsplit == 1 && a.B >= 2 && !a.gemm ? tail_split(a, e.partial_floats, &split) : 0;
+    const int tail = e.prec >= 1 && a.nsplit == 1 && a.B >= 2 && !a.gemm && !a.poly ? tail_split(a, e.partial_floats, &split) : 0;
     const bool want = q && q->kind != ST_NONE && e.prec >= 1 && e.fuse_stats;
     if (!tail) {
         p.l[0] = plan_launch(e, q, want, a, 0, a.B, &p.keep_ntile);
@@ -328,6 +367,52 @@ ConvPlan plan_conv(const ConvEnv& e, const ConvArgs& a0, int taps, const StatAsk
     return p;
 }
 
+// Folded operators of the polyphase form (kernels.h).  Per dimension, output phase p reads the two low-resolution rows
+// y + p - 1 + {0, 1} with the row-tap sets below (the column rule is the same):
+//   nearest x2, pad 1 (out row 2y+p reads up-sampled rows 2y+p-1+k = low rows y + floor((p-1+k)/2)):
+//       p = 0: {w0}, {w1 + w2}     p = 1: {w0 + w1}, {w2}
+//   zero insertion, pad P (tap k reads inserted row 2y+p-P+k: data only where that is even, low row y + (p-P+k)/2):
+//       P = 2:  p = 0: {w0}, {w2}   p = 1: {w1}, {}        P = 1:  p = 0: {}, {w1}   p = 1: {w0}, {w2}
+void polyphase_fold(int kind, int nin, int nout, const float* w, long so, long si, long st, float* out) {
+    // sel[p][t][k]: tap k of the 3-tap row operator contributes to footprint row t of phase p
+    static const int sel[3][2][2][3] = {
+        {{{1, 0, 0}, {0, 1, 1}}, {{1, 1, 0}, {0, 0, 1}}},
+        {{{1, 0, 0}, {0, 0, 1}}, {{0, 1, 0}, {0, 0, 0}}},
+        {{{0, 0, 0}, {0, 1, 0}}, {{1, 0, 0}, {0, 0, 1}}}};
+    const long V = 4L * nout;
+    for (int i = 0; i < nin; ++i)
+        for (int pa = 0; pa < 2; ++pa)
+            for (int pb = 0; pb < 2; ++pb)
+                for (int ty = 0; ty < 2; ++ty)
+                    for (int tx = 0; tx < 2; ++tx)
+                        for (int o = 0; o < nout; ++o) {
+                            double acc = 0.0;
+                            for (int ky = 0; ky < 3; ++ky)
+                                for (int kx = 0; kx < 3; ++kx)
+                                    if (sel[kind][pa][ty][ky] && sel[kind][pb][tx][kx]) acc += (double)w[o * so + i * si + (3 * ky + kx) * st];
+                            out[((long)i * 4 + 2 * ty + tx) * V + polyphase_vcout(nout, pa, pb, o)] = (float)acc;
+                        }
+}
+
+void polyphase_fold_in(int nin, int nout, const float* w, long so, long si, long st, float* out, int noutP) {
+    for (int p = 0; p < 2; ++p)
+        for (int q = 0; q < 2; ++q)
+            for (int i = 0; i < nin; ++i)
+                for (int ty = 0; ty < 2; ++ty)
+                    for (int tx = 0; tx < 2; ++tx) {
+                        const int m = 2 * ty + 1 - p, n = 2 * tx + 1 - q;      // tap of the 4x4 operator
+                        for (int o = 0; o < nout; ++o) {
+                            double acc = 0.0;
+                            for (int a = 0; a < 2; ++a)
+                                for (int b = 0; b < 2; ++b) {
+                                    const int ky = m - a, kx = n - b;
+                                    if (ky >= 0 && ky < 3 && kx >= 0 && kx < 3) acc += (double)w[o * so + i * si + (3 * ky + kx) * st];
+                                }
+                            out[((((long)(2 * p + q) * nin + i) * 4) + 2 * ty + tx) * noutP + o] = (float)acc;
+                        }
+                    }
+}
+
 const char* conv_variant_name(const ConvArgs& a, int taps, int prec) {
     static const char* tiles[6] = {"2,2,2,2", "4,1,1,2", "1,4,1,1", "2,2,1,1", "2,2,2,4", "2,4,2,2"};
     static char names[3][2][6][6][56];      // lock-step tiles: [prec][3x3 / 1x1][tile][mode]
@@ -335,6 +420,11 @@ const char* conv_variant_name(const ConvArgs& a, int taps, int prec) {
     const int mode = (a.mode < 0 || a.mode > 5) ? 2 : a.mode;
     const char* other = nullptr;
     int k = 0, v = mode;
+    if (prec && taps == 9 && a.poly) {      // the polyphase launch: the lock-step kernel's 4-tap instance (raw, vector staging)
+        static const char* pn[2][3] = {{"", "conv_mfma_bf16x3<4,2,4,2,2,0>", "conv_mfma_f16<4,2,4,2,2,0>"},
+                                       {"", "conv_mfma_bf16x3<4,2,4,2,2,0>+pool", "conv_mfma_f16<4,2,4,2,2,0>+pool"}};
+        return pn[a.poly == 2][prec];
+    }
     if (prec && taps == 9 && a.Cin2 > 0) other = prec == 1 ? "conv_kcat_bf16x3<2,4,2,2,%d>" : "conv_kcat_f16<2,4,2,2,%d>";
     else if (prec == 1 && taps == 1 && a.gemm) { k = 1; other = "conv_gemm_bf16x3<%d>"; v = a.gemm_tm; }
     else if (prec == 1 && taps == 9 && a.pair) { k = 2; other = "conv_pair_bf16x3<%d>"; }      // the 16x16x32 tap-pair kernel

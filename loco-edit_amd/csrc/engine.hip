@@ -56,6 +56,16 @@ struct ConvP {       // one convolution's parameters in kernel layouts
     float* wbd = nullptr;   // split-bf16 dgrad records   [Cout/16][taps][CinP][32 x u16]
     float* whf = nullptr;   // f16 forward records        [Cin/16][taps][CoutP][16 x f16]
     float* whd = nullptr;   // f16 dgrad records          [Cout/16][taps][CinP][16 x f16]
+    // polyphase form of an up / down-sampling conv (kernels.h polyphase_fold): records of the folded operator, 4 taps x 4 couts
+    // virtual couts -- of the forward operator for the nearest-x2 conv, of the dgrad operator (poly_dgrad) for the stride-2
+    // conv's zero-insert data gradient; nullptr: none (the 3x3 route)
+    float* wpb = nullptr;   // split-bf16
+    float* wph = nullptr;   // f16
+    bool poly_dgrad = false;
+    // the up conv's cotangent as one launch (kernels.h ConvArgs::pool2, polyphase_fold_in): records of the dgrad operator folded
+    // with the 2x2 sum-pool, [4 Cout/16][4][CinP]
+    float* wqb = nullptr;   // split-bf16
+    float* wqh = nullptr;   // f16
     float* bias = nullptr;
     int cin = 0, cout = 0, taps = 0;
 };
@@ -306,8 +316,9 @@ static std::vector<float> build_records_f16(int nin, int nout, int taps, F get) 
 }
 
 // weights [cout][cin][k][k] -> forward [cin][taps][coutP], dgrad [cout][taps][cinP] with flipped taps
+// poly_kind >= 0 (PolyKind): also the folded polyphase operator of the forward (poly_dgrad false) or dgrad form
 int make_conv(loco_ctx* c, const std::vector<const HostParam*>& ws, const std::vector<const HostParam*>& bs,
-              ConvP* out, int row_limit = -1) {
+              ConvP* out, int row_limit = -1, int poly_kind = -1, bool poly_dgrad = false) {
     int cin = (int)ws[0]->shape[1], k = ws[0]->shape.size() > 2 ? (int)ws[0]->shape[2] : 1;
     int taps = ws[0]->shape.size() == 4 ? k * k : k;      // Conv2d, Conv1d (k=1) or Linear
     int cout = 0;
@@ -344,10 +355,27 @@ int make_conv(loco_ctx* c, const std::vector<const HostParam*>& ws, const std::v
     std::vector<float> hf = build_records_f16(cin, cout, taps, fwd);
     std::vector<float> hd = build_records_f16(cout, cin, taps, dgr);
     if (upload(c, &out->whf, hf) || upload(c, &out->whd, hd)) return -1;
+    const int pin = poly_dgrad ? cout : cin, pout = poly_dgrad ? cin : cout;      // channels the folded operator reads / writes
+    if (poly_kind >= 0 && taps == 9 && pin % 16 == 0 && pout % 128 == 0) {
+        const int poutP = poly_dgrad ? cinP : coutP;
+        std::vector<float> pf((size_t)pin * 16 * pout);
+        polyphase_fold(poly_kind, pin, pout, (poly_dgrad ? wd : wf).data(), 1, 9L * poutP, poutP, pf.data());
+        auto fold = [&](int o, int i, int t) { return pf[((size_t)i * 4 + t) * 4 * pout + o]; };
+        std::vector<float> rp = build_records(pin, 4 * pout, 4, fold), hp = build_records_f16(pin, 4 * pout, 4, fold);
+        if (upload(c, &out->wpb, rp) || upload(c, &out->wph, hp)) return -1;
+        out->poly_dgrad = poly_dgrad;
+    }
+    if (poly_kind == POLY_UP && !poly_dgrad && taps == 9 && cout % 16 == 0 && cin % 128 == 0) {
+        std::vector<float> qf((size_t)4 * cout * 4 * cinP, 0.f);      // [4 phases x cout][4][cinP]: the forward layout of a 4-tap operator
+        polyphase_fold_in(cout, cin, wd.data(), 1, 9L * cinP, cinP, qf.data(), cinP);
+        auto fold = [&](int o, int i, int t) { return qf[((size_t)i * 4 + t) * cinP + o]; };
+        std::vector<float> rq = build_records(4 * cout, cin, 4, fold), hq = build_records_f16(4 * cout, cin, 4, fold);
+        if (upload(c, &out->wqb, rq) || upload(c, &out->wqh, hq)) return -1;
+    }
     return 0;
 }
-int make_conv1(loco_ctx* c, const std::string& name, ConvP* out, int row_limit = -1) {
-    return make_conv(c, {&c->params[name + ".weight"]}, {&c->params[name + ".bias"]}, out, row_limit);
+int make_conv1(loco_ctx* c, const std::string& name, ConvP* out, int row_limit = -1, int poly_kind = -1, bool poly_dgrad = false) {
+    return make_conv(c, {&c->params[name + ".weight"]}, {&c->params[name + ".bias"]}, out, row_limit, poly_kind, poly_dgrad);
 }
 // the same operator with weight and bias multiplied by `s` (the ResBlock output scale of cfg.res_scale lives in conv2 / the shortcut)
 int make_conv1_scaled(loco_ctx* c, const std::string& name, ConvP* out, float s) {
@@ -462,7 +490,12 @@ int finalize_params(loco_ctx* c) {
                 }
                 break;
             }
-            case OP_DOWN: case OP_UP: if (make_conv1(c, op.pn_conv, &ow.conv)) return -1; break;
+            case OP_DOWN: case OP_UP: {
+                // (the folded polyphase operators: the up conv's forward form, the down conv's zero-insert data gradient)
+                const int pk = op.kind == OP_UP ? POLY_UP : (op.sym_down ? POLY_ZINS_PAD1 : POLY_ZINS_PAD2);
+                if (make_conv1(c, op.pn_conv, &ow.conv, -1, pk, op.kind == OP_DOWN)) return -1;
+                break;
+            }
             case OP_XFMR: {
                 const int C = c->tens[op.in].C, NH = op.heads, CH = C / NH;
                 const std::string b = op.name + ".transformer_blocks.0";
@@ -679,6 +712,7 @@ bool run_conv(loco_ctx* c, const ConvArgs& a0, int taps, hipStream_t st, const S
         const ConvArgs& x = l.args;
         double flops = 2.0 * (x.Cin * taps + x.Cin2) * x.Cout * (double)x.Hout * x.Wout * x.B;
         if (x.zins) flops *= 0.25;     // algorithmic work of the stride-2 data gradient
+        if (x.poly == 2) flops *= 4.0;    // (Hout x Wout is the pooled map: the 3x3 conv runs at full resolution)
         timed(c->prof_on ? conv_variant_name(x, taps, c->prec) : nullptr, flops, x, [&] {
             if (c->prec == 1) launch_conv_bf16x3(x, taps, st);
             else if (c->prec == 2) launch_conv_f16(x, taps, st);
@@ -709,6 +743,8 @@ bool run_conv(loco_ctx* c, const ConvArgs& a0, int taps, hipStream_t st, const S
         }
     }
     if (p.stats_all) stats_standalone(c, *rq, a.out, a.out_bs, a.B, HWo, 0, st);
+    if (p.pool_after)      // ConvArgs::pool2 on the 3x3 route: the launches wrote pool_tmp
+        launch_pool2x2_sum(a.pool_tmp, a.pool_tmp_bs, p.pool_out, p.pool_out_bs, p.pool_acc, a.B, a.Cout, a.Hout, a.Wout, st);
     return p.cot;
 }
 
@@ -716,6 +752,11 @@ inline void setw(ConvArgs& a, const ConvP& p, bool dgrad) {
     a.w = dgrad ? p.wd : p.wf;
     a.wb = dgrad ? (const void*)p.wbd : (const void*)p.wbf;
     a.wh = dgrad ? (const void*)p.whd : (const void*)p.whf;
+    const bool folded = p.wpb && p.poly_dgrad == dgrad;      // (plan_conv takes them on the up / zero-insert launches it routes polyphase)
+    a.wpb = folded ? p.wpb : nullptr;
+    a.wph = folded ? p.wph : nullptr;
+    a.wqb = dgrad ? p.wqb : nullptr;
+    a.wqh = dgrad ? p.wqh : nullptr;
 }
 
 // the norm (if any) that takes its statistics over exactly tensor `tid`
@@ -1456,9 +1497,10 @@ int cotangent_pass(loco_ctx* c, const float* ge, const float* gx0, float* Aout, 
                 ConvArgs a; conv_defaults(a);
                 a.in = TG(op.out); a.in_bs = PS; a.Cin = to.C; a.Hin = to.H; a.Win = to.W;
                 setw(a, op.conv, true);
-                a.out = TG(op.up); a.out_bs = PS; a.Cout = ti.C; a.Hout = to.H; a.Wout = to.W; a.B = B;
+                // nearest^T (conv^T g): one polyphase launch where plan_conv takes it, else the conv into op.up and the pooling pass
+                a.pool2 = 1; a.pool_tmp = TG(op.up); a.pool_tmp_bs = PS;
+                a.out = TG(op.in); a.out_bs = PS; a.Cout = ti.C; a.Hout = ti.H; a.Wout = ti.W; a.B = B;
                 run_conv(c, a, 9, st);
-                launch_pool2x2_sum(TG(op.up), PS, TG(op.in), PS, 0, B, ti.C, ti.H, ti.W, st);
                 break;
             }
             case OP_DOWN: {
@@ -2390,8 +2432,14 @@ int loco_bench_conv(loco_ctx* c, int32_t cin, int32_t cout, int32_t H, int32_t W
     if (finalize_params(c)) return -3;
     hipStream_t st = (hipStream_t)stream;
     const long HW = (long)H * W;
-    const long in_e = (long)cin * HW, out_e = (long)cout * HW;
-    if ((in_e + out_e) * B > (long)c->cfg.max_batch * c->prog->per_sample || 2 * in_e > (long)c->prog->per_sample ||
+    // LOCO_BENCH_GEOM (3x3 only; H x W stays the OUTPUT map): 1 = over a nearest-x2 input, 2 / 3 = over a zero-inserted input with
+    // pad 2 / 1 (the stride-2 conv's data gradient) -- the polyphase route where plan_conv takes it (LOCO_POLYPHASE=0: the 3x3 route);
+    // 4 = conv + 2x2 sum-pool as ONE polyphase launch (ConvArgs::pool2; H x W is the INPUT map; the 3x3 route of this form is the
+    // plain launch + launch_pool2x2_sum)
+    const int geom = (taps == 9 && getenv("LOCO_BENCH_GEOM")) ? atoi(getenv("LOCO_BENCH_GEOM")) : 0;
+    if (geom < 0 || geom > 4 || (geom && ((H | W) & 1))) { c->err = "bench_conv: bad LOCO_BENCH_GEOM"; return -2; }
+    const long in_e = (long)cin * ((geom && geom != 4) ? HW / 4 : HW), out_e = (long)cout * HW;
+    if ((in_e + out_e + (geom == 4 ? out_e / 4 : 0)) * B > (long)c->cfg.max_batch * c->prog->per_sample || 2 * in_e > (long)c->prog->per_sample ||
         in_e > c->prog->sx_total) { c->err = "bench_conv: shape exceeds the arenas"; return -2; }
     float* in = c->arenaT;
     float* out = c->arenaT + in_e * B;
@@ -2405,12 +2453,12 @@ int loco_bench_conv(loco_ctx* c, int32_t cin, int32_t cout, int32_t H, int32_t W
     launch_fill_random(c->statsP, c->prog->stats_per_sample, 4u, 1.0f, st);
     launch_fill_random(c->statsT, c->prog->stats_per_sample * B, 5u, 0.01f, st);
     // weights: any conv of matching size is fine for timing; synthesise records in the split-K workspace
-    size_t wfl = (size_t)((cin + 15) / 16) * 16 * taps * ((cout + 31) & ~31);
+    size_t wfl = (size_t)((cin + 15) / 16) * 16 * (geom ? 16 : taps) * ((cout + 31) & ~31);      // (geom: room for the folded records, 4 taps x 4 couts)
     if (wfl * 2 > c->partial_floats) { c->err = "bench_conv: weights exceed workspace"; return -2; }
     float* wf = c->partial + c->partial_floats - wfl * 2;
     launch_fill_random(wf, (long)wfl * 2, 6u, 0.05f * zw, st);
     if (c->prec == 1) {      // split-bf16 records: well-formed ones
-        const long nrec = (long)((cin + 15) / 16) * taps * ((cout + 31) & ~31);
+        const long nrec = (long)((cin + 15) / 16) * (geom ? 16 : taps) * ((cout + 31) & ~31);
         hipLaunchKernelGGL(diag_fill_records, dim3((unsigned)((nrec + 255) / 256)), dim3(256), 0, st,
                            reinterpret_cast<unsigned char*>(wf), nrec, (cout + 31) & ~31, 7u, 0.05f * zw);
     }
@@ -2420,6 +2468,15 @@ int loco_bench_conv(loco_ctx* c, int32_t cin, int32_t cout, int32_t H, int32_t W
     a.w = wf; a.wb = wf; a.wh = wf;
     a.out = out; a.out_bs = out_e; a.Cout = cout; a.Hout = H; a.Wout = W; a.B = B;
     a.mode = mode; a.pad = taps == 9 ? 1 : 0; a.in_padded = 1; a.taps = taps;
+    if (geom == 4) {
+        a.pool2 = 1; a.pool_tmp = out; a.pool_tmp_bs = out_e;
+        a.out = out + out_e * B; a.out_bs = out_e / 4; a.Hout = H / 2; a.Wout = W / 2;
+        a.wqb = wf; a.wqh = wf;
+    } else if (geom) {
+        a.Hin = H / 2; a.Win = W / 2;
+        if (geom == 1) a.upsample = 1; else { a.zins = 1; a.pad = geom == 2 ? 2 : 1; }
+        a.wpb = wf; a.wph = wf;
+    }
     a.sc = c->statsP; a.sh = c->statsP + cin; a.scsh_bs = 0; a.mr = c->statsP + 2 * cin; a.mr_bs = 0;
     a.gamma_ = c->statsP; a.tst = c->statsT; a.tst_bs = c->prog->stats_per_sample; a.cpg = cin / c->cfg.gn_groups;
     a.tc = c->statsT + 64; a.tc_bs = c->prog->stats_per_sample;
@@ -2440,6 +2497,13 @@ int loco_bench_conv(loco_ctx* c, int32_t cin, int32_t cout, int32_t H, int32_t W
     // 4 weight DMAs collapsed, 8 no conversions
     if (const char* e = getenv("LOCO_DUAL_WHATIF")) a.no_deep = atoi(e);
     conv_plan_tile_pair(a, c->prec, tile);
+    if (geom) {      // the polyphase decision is plan_conv's alone
+        ConvEnv e;
+        e.prec = c->prec; e.partial = a.partial; e.partial_floats = a.partial_floats; e.max_batch = c->cfg.max_batch;
+        a.poly = plan_conv(e, a, taps, nullptr, nullptr).l[0].args.poly;
+        if (a.poly) a.nsplit = 1;
+        if (geom == 4 && a.poly != 2) { c->err = "bench_conv: the shape does not take the pooled polyphase launch"; return -2; }
+    }
     auto run = [&]() {
         if (c->prec == 1) launch_conv_bf16x3(a, taps, st);
         else if (c->prec == 2) launch_conv_f16(a, taps, st);
@@ -2492,13 +2556,16 @@ int loco_debug_conv(loco_ctx* c, const loco_conv_desc* d, char* plan, int64_t ca
     if (d->cot_d && (!d->cot_prim || !d->cot_sc || !d->cot_sh || !d->cot_mr || !d->cot_tc || d->cot_cpg < 1 || d->Cout % d->cot_cpg)) {
         c->err = "debug_conv: the norm-cotangent term needs cot_prim, cot_sc, cot_sh, cot_mr, cot_tc and cot_cpg"; return -2;
     }
-    const int Hout = d->stride == 2 ? d->Hin / 2 : (d->upsample || d->zins) ? 2 * d->Hin : d->Hin;
-    const int Wout = d->stride == 2 ? d->Win / 2 : (d->upsample || d->zins) ? 2 * d->Win : d->Win;
+    if (d->pool2 && (taps != 9 || d->stride != 1 || d->upsample || d->zins || d->mode != CM_NONE || d->Cin2 > 0 || d->res || d->cot_d ||
+                     ((d->Hin | d->Win) & 1))) { c->err = "debug_conv: pool2 goes with a raw 3x3 stride-1 conv of an even map"; return -2; }
+    const int Hout = (d->stride == 2 || d->pool2) ? d->Hin / 2 : (d->upsample || d->zins) ? 2 * d->Hin : d->Hin;
+    const int Wout = (d->stride == 2 || d->pool2) ? d->Win / 2 : (d->upsample || d->zins) ? 2 * d->Win : d->Win;
     {   // Every conv kernel walks the output map in tiles of min(Wout, 32) columns (a power of two) x 64 / 128 / 256 pixels and
         // writes whole tiles: maps as loco_create admits them (powers of two from 8 x 8), or whole 32-column, 8-row tiles.  Any
         // other map (48 x 48, 128 x 144) would be walked past its last row: refused here, never launched.
         auto pow2 = [](int v) { return v >= 8 && (v & (v - 1)) == 0; };
-        if (!((pow2(Hout) && pow2(Wout)) || (Wout % 32 == 0 && Hout % 8 == 0 && ((long)Hout * Wout) % 256 == 0))) {
+        auto walks = [&](int h, int w) { return (pow2(h) && pow2(w)) || (w % 32 == 0 && h % 8 == 0 && ((long)h * w) % 256 == 0); };
+        if (!walks(Hout, Wout) || (d->pool2 && !walks(d->Hin, d->Win))) {
             c->err = "debug_conv: output map outside the tile geometry of the conv kernels"; return -2;
         }
     }
@@ -2514,7 +2581,13 @@ int loco_debug_conv(loco_ctx* c, const loco_conv_desc* d, char* plan, int64_t ca
     // the launch's small arrays: one allocation of this call (sc sh mr gamma | tst tc per sample | cot_tc per sample)
     const int G = lin ? d->Cin / d->cpg : 0;
     const long tbs = up64(2L * G) + up64(2L * d->Cin);
-    const long small_n = (lin ? (long)B * tbs : 0) + (d->cot_d ? (long)B * up64(2L * d->Cout) : 0) + 64;
+    // tangent statistics request (st_prim): kept row partials, a zeroed sc / sh pair for the standalone pass
+    const bool st_req = d->st_prim != nullptr;
+    if (st_req && (!d->st_mr || !d->st_out || d->st_cpg < 1 || d->Cout % d->st_cpg || d->cot_d || d->Cin2 > 0)) {
+        c->err = "debug_conv: the statistics request needs st_prim, st_mr, st_out and st_cpg (no second operator, no cot_d)"; return -2;
+    }
+    const long keep_n = st_req ? up64((long)B * d->Cout * ((long)Hout * Wout / 64 + 1) * 2) : 0;
+    const long small_n = (lin ? (long)B * tbs : 0) + (d->cot_d ? (long)B * up64(2L * d->Cout) : 0) + 64 + keep_n + (st_req ? up64(2L * d->Cout) : 0);
     const size_t owned0 = c->owned.size();
     const size_t bytes0 = c->bytes;
     auto release = [&]() {      // what this call allocated (weight layouts, small arrays)
@@ -2534,7 +2607,10 @@ int loco_debug_conv(loco_ctx* c, const loco_conv_desc* d, char* plan, int64_t ca
     HostParam w2 = host_param(d->Cin2 > 0 ? d->w2 : nullptr, {d->Cout, d->Cin2 > 0 ? d->Cin2 : 1, 1, 1}), wb2 = host_param(nullptr, {d->Cout});
     ConvP cp, cp2;
     float *bias_d = nullptr, *bias2nd_d = nullptr, *small = nullptr;
-    int rc = make_conv(c, {&w}, {&wb0}, &cp);
+    const int poly_kind = taps != 9 ? -1 : (d->upsample || d->pool2) ? POLY_UP : d->zins ? ((d->pad >= 0 ? d->pad : 2) == 1 ? POLY_ZINS_PAD1 : POLY_ZINS_PAD2) : -1;
+    int rc = make_conv(c, {&w}, {&wb0}, &cp, -1, poly_kind, d->transposed != 0 && !d->pool2);
+    float* pool_tmp = nullptr;
+    if (!rc && d->pool2) rc = dalloc(c, &pool_tmp, (size_t)B * d->Cout * d->Hin * d->Win);
     if (!rc && d->Cin2 > 0) rc = make_conv(c, {&w2}, {&wb2}, &cp2);
     if (!rc && d->bias) rc = upload(c, &bias_d, std::vector<float>(d->bias, d->bias + d->Cout));
     if (!rc && d->Cin2 > 0 && d->bias2nd) rc = upload(c, &bias2nd_d, std::vector<float>(d->bias2nd, d->bias2nd + d->Cout));
@@ -2554,6 +2630,7 @@ int loco_debug_conv(loco_ctx* c, const loco_conv_desc* d, char* plan, int64_t ca
     a.res = d->res; a.res_bs = out_e; a.res_scale = d->res_scale;
     a.mode = d->mode; a.stride = d->stride; a.upsample = d->upsample; a.zins = d->zins; a.accumulate = d->accumulate;
     a.pad = d->pad >= 0 ? d->pad : taps == 1 ? 0 : d->zins ? 2 : d->stride == 2 ? 0 : 1;
+    if (d->pool2) { a.pool2 = 1; a.pool_tmp = pool_tmp; a.pool_tmp_bs = (long)d->Cout * d->Hin * d->Win; }
     a.sc = d->sc; a.sh = d->sh; a.scsh_bs = 0; a.cpg = d->cpg;
     if (lin) {
         if (he == hipSuccess) he = copy(c->arenaP, d->prim, in_e);
@@ -2594,9 +2671,28 @@ int loco_debug_conv(loco_ctx* c, const loco_conv_desc* d, char* plan, int64_t ca
     const int act0 = c->cfg.act;
     if (d->mode == CM_GN_GELU) c->cfg.act = ACT_GELU;      // a GELU network's forward prologue (run_conv hands cfg.act to the kernels)
     c->plan_log = &text;
-    const bool rode = run_conv(c, a, taps, st, nullptr, d->Cin2 > 0 ? &n2 : nullptr);
+    StatReq srq;
+    int kept_ntile = 0;
+    float* const keep_buf = small + (small_n - keep_n - (st_req ? up64(2L * d->Cout) : 0));
+    if (st_req) {      // as next_tan asks for one part of a concatenation: the raw row partials stay in `keep`
+        srq.kind = ST_TAN; srq.prim = d->st_prim; srq.keep = keep_buf; srq.keep_floats = (size_t)keep_n; srq.keep_ntile = &kept_ntile;
+    }
+    const bool rode = run_conv(c, a, taps, st, st_req ? &srq : nullptr, d->Cin2 > 0 ? &n2 : nullptr);
     c->plan_log = nullptr;
     c->cfg.act = act0;
+    if (st_req) {
+        // st_out[0]: {m1, m2} per (sample, group) from the partials the launch kept (NaN where it kept none); st_out[1]: the
+        // standalone pass over the finished tensor
+        const int G2 = d->Cout / d->st_cpg;
+        float* const zero = keep_buf + keep_n;
+        (void)hipMemsetAsync(zero, 0, (size_t)up64(2L * d->Cout) * sizeof(float), st);
+        (void)hipMemsetAsync(d->st_out, 0xff, (size_t)B * G2 * 2 * sizeof(float), st);
+        if (kept_ntile > 0)
+            launch_gn_lin_fused_finalize(ST_TAN, keep_buf, d->Cout, kept_ntile, nullptr, 0, B, d->Cout, Hout * Wout, G2, d->st_mr, d->st_out,
+                                         nullptr, 2L * G2, st);
+        launch_gn_tstats(d->out, out_e, d->st_prim, 0, B, d->Cout, Hout * Wout, G2, zero, zero + d->Cout, d->st_mr, 0, 0, 0,
+                         d->st_out + (long)B * G2 * 2, nullptr, 2L * G2, c->red, st, ACT_SILU);
+    }
     he = hipGetLastError();
     release();
     if (he == hipSuccess) he = hipGetLastError();

@@ -119,7 +119,34 @@ struct ConvArgs {
     // kernel of the launch as planned (conv_plan.hip, read by the dispatchers and conv_variant_name): the tile variant and
     // whether a 3x3 launch runs the tap-pair kernel of conv_pair_kernel.h
     int tile, pair;
+    // Polyphase form of a 3x3 conv over a nearest-x2 or zero-inserted input (conv_plan.hip conv_poly_ok; conv_bf16_kernel.h,
+    // TAPS = 4): per output phase (a, b) a 2x2 conv of the low-resolution input, 16 tap products per low-resolution pixel instead
+    // of 36.  wpb / wph: the folded operator's bf16x3 / f16 records, [Cin/16][4][4 Cout] with the virtual couts in the order
+    // of polyphase_vcout (nullptr: the conv has none and keeps the 3x3 route); poly: the plan took it (wb points at the records).
+    const void* wpb; const void* wph;
+    int poly;      // 0: none, 1: the output-phase form above, 2: the input-phase form below
+    // pool2: the launch is a 3x3 conv (pad 1) of the Hin x Win map FOLLOWED by a 2x2 sum-pool -- the cotangent of the nearest-x2 up
+    // conv; out / Hout x Wout describe the POOLED tensor (Hout = Hin / 2).  Where plan_conv takes the polyphase input form (poly ==
+    // 2: one 4x4 stride-2 conv = four K-concatenated 2x2 convs over the phase-subsampled input, records wqb / wqh,
+    // [4 Cin/16][4][Cout]) one launch writes `out`; else the 3x3 conv writes pool_tmp ([B][Cout][Hin][Win], batch stride
+    // pool_tmp_bs) and run_conv pools it into `out` (ConvPlan::pool_after).
+    int pool2; float* pool_tmp; long pool_tmp_bs;
+    const void* wqb; const void* wqh;
 };
+
+// ---- polyphase folding of a 3x3 operator (conv_plan.hip, host code only) ----
+// kind of the folded conv: the nearest-x2 conv (pad 1) or the zero-insert data gradient with pad 2 / pad 1
+enum PolyKind : int { POLY_UP = 0, POLY_ZINS_PAD2 = 1, POLY_ZINS_PAD1 = 2 };
+// virtual cout of (output phase a = Y & 1, b = X & 1, channel co) among the 4 C: a 128-cout tile is one row phase and 64
+// channels in both column phases (the two halves of the tile), so that a workgroup writes whole runs of an output row
+inline int polyphase_vcout(int C, int a, int b, int co) { return ((a * (C / 64) + co / 64) * 2 + b) * 64 + (co % 64); }
+// w3(o, i, t) = w[o * so + i * si + t * st], t = 3 ky + kx (a correlation), o < nout, i < nin  ->  out[(i * 4 + 2 ty + tx) * 4 nout + vcout]:
+// phase (a, b) of the output reads the low-resolution pixels (y + a - 1 + ty, x + b - 1 + tx).  Sums in double, rounded once.
+void polyphase_fold(int kind, int nin, int nout, const float* w, long so, long si, long st, float* out);
+// the input-phase form of pool2x2_sum(conv3x3_pad1(g)) = conv4x4_stride2_pad1(g), W4[m][n] = sum_{a+ky=m, b+kx=n} w3[ky][kx] (a, b in
+// {0, 1}): out[(((2p+q) * nin + i) * 4 + 2 ty + tx) * noutP + o] = W4[2 ty + 1 - p][2 tx + 1 - q](o, i) -- phase image g[2u+p][2v+q]
+// is read at (y - p + ty, x - q + tx).  noutP: the row pitch of `out` (>= nout).
+void polyphase_fold_in(int nin, int nout, const float* w, long so, long si, long st, float* out, int noutP);
 
 // the conv kernel of a launch planned by conv_plan.hip; when a.nsplit > 1 the caller follows with launch_conv_splitk_reduce (run_conv does)
 void launch_conv(const ConvArgs& a, int taps, hipStream_t st);
@@ -172,6 +199,8 @@ struct ConvPlan {
     ConvLaunch l[2];
     bool stats_all = false;    // a standalone statistics pass over the whole batch follows the launches
     int keep_ntile = 0;        // tile count of the kept partials (0: none kept)
+    // ConvArgs::pool2 on the 3x3 route: l[].args write ConvArgs::pool_tmp at full resolution, and a 2x2 sum-pool into pool_out follows
+    bool pool_after = false; float* pool_out = nullptr; long pool_out_bs = 0; int pool_acc = 0;
     bool cot = false;          // the requested norm-cotangent term (ConvArgs::cot_d) rides in the epilogue
 };
 

@@ -66,12 +66,12 @@ class LocoCfg(C.Structure):
 class LocoConvDesc(C.Structure):
     """loco_conv_desc of include/loco_hip_diag.h (loco_debug_conv): one conv launch on caller-supplied operands."""
     _PTRS = ("weight", "bias", "in", "bias2", "res", "prim", "sc", "sh", "mr", "gamma", "tst", "tc", "in2", "w2", "bias2nd",
-             "cot_d", "cot_prim", "cot_sc", "cot_sh", "cot_mr", "cot_tc", "out")
+             "cot_d", "cot_prim", "cot_sc", "cot_sh", "cot_mr", "cot_tc", "out", "st_prim", "st_mr", "st_out")
     _HOST = ("weight", "bias", "w2", "bias2nd")
     _fields_ = ([("struct_size", C.c_int32)] +
                 [(k, C.c_int32) for k in ("Cin", "Cout", "Hin", "Win", "B", "taps", "stride", "upsample", "zins", "mode", "cpg",
                                           "transposed", "accumulate", "in_arena", "pad", "Cin2", "cot_cpg")] +
-                [("res_scale", C.c_float), ("reserved", C.c_int32)] + [(k, C.c_void_p) for k in _PTRS])
+                [("res_scale", C.c_float), ("st_cpg", C.c_int32)] + [(k, C.c_void_p) for k in _PTRS] + [("pool2", C.c_int32)])
 
 
 class LocoTextCfg(C.Structure):
@@ -746,7 +746,7 @@ class LocoEngine:
         d.out = out.data_ptr()
         for k, v in desc.items():
             if k not in LocoConvDesc._PTRS:
-                if not hasattr(d, k) or k in ("struct_size", "reserved"):
+                if not hasattr(d, k) or k == "struct_size":
                     raise TypeError(f"debug_conv: no descriptor field {k!r}")
                 setattr(d, k, v)
             elif v is not None:
