@@ -194,6 +194,35 @@ int  loco_convergence(loco_ctx* ctx, const float* Vprev, const float* V, int64_t
 int  loco_convergence_rows(loco_ctx* ctx, const float* Vprev, const float* V, int32_t k, int64_t n,
                            float atol, float* out2, void* stream);
 
+/* Block Krylov solver for the same basis (opt-in; DESIGN.md "Block Krylov solver"): Rayleigh-Ritz on J^T J over every
+ * block of iterates instead of the last one.  The caller keeps Q [m, n] (orthonormal fp32 rows in blocks of k, block 0
+ * = the QR'd start) and Ustore [m, n_out] (the rows J Q); the context keeps, per `slot` (0 or 1: two solves may be in
+ * flight, e.g. the modify-space and null-space solves of one edit), T = Q J^T J Q^T, its Ritz pairs, the Gram of the
+ * residual block and the signs of the returned rows, all in double.  1 <= k <= 32, m a multiple of k, m <= 64,
+ * n <= C*H*W of the context; every pointer is device memory of the caller; nothing is allocated and the only values
+ * meant to be read back per step are the four floats of `stat`:
+ *   stat[0], stat[1]  distance and allclose flag of loco_convergence_rows between Y and Yprev (-1, 0 without Yprev)
+ *   stat[2]           the largest residual estimate of this step
+ *   stat[3]           1 when the next block is entirely zero (the Krylov space is invariant), else 0
+ *
+ * loco_krylov_extend: A [k, n] = J^T J (newest k rows of Q), overwritten.  Fills T's newest block column and row from
+ * A Q^T, orthogonalises A against the m rows of Q (block Gram-Schmidt, two passes) into the residual block R, keeps
+ * G = R R^T and the Ritz pairs of T[:m, :m], and -- when `next` is not NULL -- writes the next block to next [k, n]
+ * (rows m .. m+k of Q, or A itself): R orthonormalised within itself, a direction whose singular value is below
+ * 1e-6 of the largest Ritz value left as a ZERO row in place, then projected once more against Q.  Sets stat[3]. */
+int  loco_krylov_extend(loco_ctx* ctx, float* A, int32_t k, const float* Q, int32_t m, int64_t n, float* next,
+                        float* stat, int32_t slot, void* stream);
+/* After loco_krylov_extend with the same Q, m, slot: Y [k, n] = the top-k Ritz vectors W[:k] Q (sign: largest-|.| entry
+ * of each row positive), resid[k] = sqrt(w_i^T G w_i) / theta_0 with w_i the last k entries of Ritz vector i -- the
+ * norm of J^T J y_i - theta_i y_i relative to the largest Ritz value, at no further pass -- and, with Yprev [k, n]
+ * (NULL: none), the row-wise convergence test against it.  Sets stat[0..2]. */
+int  loco_krylov_ritz(loco_ctx* ctx, const float* Q, int32_t m, int64_t n, int32_t k, float* Y, const float* Yprev,
+                      float atol, float* resid, float* stat, int32_t slot, void* stream);
+/* After loco_krylov_ritz: UY [k, n_out] = the same combination and signs of the rows of Ustore [m, n_out] (= J Y), and
+ * s[k] = ||UY_i||^2, the Rayleigh quotient of J^T J on the rows themselves.  n_out may exceed the context's width. */
+int  loco_krylov_left(loco_ctx* ctx, const float* Ustore, int32_t m, int64_t n_out, int32_t k, float* UY, float* s,
+                      int32_t slot, void* stream);
+
 /* Null-space projection + row normalisation (edit.py:2317-2323):
  * out = normalize_rows(Vm - (Vn^T (Vn Vm^T))^T); Vn==nullptr: normalise only. */
 int  loco_null_project(loco_ctx* ctx, const float* Vm, int32_t k, const float* Vn, int32_t k0,

@@ -149,6 +149,8 @@ struct loco_ctx {
     float* ge = nullptr;           // [max_batch][n] cotangent seed of eps
     float* tmpA = nullptr;         // [64][n] temp for solver rotations
     double *G = nullptr, *Q = nullptr, *W = nullptr, *gscratch = nullptr;
+    double* kry[2] = {nullptr, nullptr};   // block Krylov solver: state of up to two solves in flight (kernels.h KRY_*)
+    int kry_m[2] = {0, 0}, kry_k[2] = {0, 0};   // rows and block size the Ritz vectors of each slot were computed for (0: none yet)
     float* alphas = nullptr;
     float* ctx_colbias = nullptr;  // [Lp]: 0 for real tokens, -1e30 for the padding
     bool has_ctx = false;
@@ -1792,6 +1794,7 @@ int create_ctx(loco_ctx* c, const loco_unet_cfg* cfg, std::shared_ptr<const Prog
         size_t nblk = ((size_t)c->prog->n_in + 255) / 256;
         if (dalloc(c, &c->gscratch, nblk * 64 * 64 + 4096)) return -1;
     }
+    if (dalloc(c, &c->kry[0], KRY_STATE) || dalloc(c, &c->kry[1], KRY_STATE)) return -1;
     if (dalloc(c, &c->alphas, 256) || dalloc(c, &c->cond_add, (size_t)cfg->ch * 4)) return -1;
     if (dalloc(c, &c->cond_in, (size_t)cfg->ch)) return -1;
     {
@@ -2159,6 +2162,82 @@ int loco_convergence_rows(loco_ctx* c, const float* Vprev, const float* V, int32
         if ((size_t)k * nseg * 4 > cap) { c->err = "convergence_rows: k rows of this length exceed the reduction workspace"; return -2; }
     }
     launch_convergence_rows(Vprev, V, k, n, atol, 1e-5f, out2, c->gscratch, (hipStream_t)stream);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+// ---- block Krylov solver (DESIGN.md "Block Krylov solver"): one step = loco_krylov_extend + loco_krylov_ritz ----
+static const char* krylov_sizes(loco_ctx* c, int32_t k, int32_t m, int64_t n, int32_t slot, bool n_is_input) {
+    if (slot < 0 || slot > 1) return "krylov: slot must be 0 or 1";
+    if (k < 1 || k > KRYLOV_MAX_BLOCK) return "krylov: need 1 <= k <= 32 (two blocks must fit in 64 rows)";
+    if (m < k || m > 64 || m % k != 0) return "krylov: m must be a multiple of k with k <= m <= 64";
+    if (n < 1) return "krylov: empty rows";
+    if (n_is_input && n > c->prog->n_in) return "krylov: rows longer than the context's input";
+    return nullptr;
+}
+
+int loco_krylov_extend(loco_ctx* c, float* A, int32_t k, const float* Q, int32_t m, int64_t n, float* next, float* stat,
+                       int32_t slot, void* stream) {
+    if (!c) return -2;
+    if (const char* e = krylov_sizes(c, k, m, n, slot, true)) { c->err = e; return -2; }
+    if (!A || !Q || !stat) { c->err = "krylov_extend: null pointer"; return -2; }
+    hipStream_t st = (hipStream_t)stream;
+    double* S = c->kry[slot];
+    // projection coefficients Ct [m][k] = Q A^T: T's newest block column / row, and the first Gram-Schmidt pass
+    launch_cross_gram(Q, m, A, k, n, c->G, c->gscratch, st);
+    launch_krylov_fill_t(c->G, m, k, S + KRY_T, c->Q, st);
+    launch_project_rows(A, k, Q, m, n, c->G, A, st);
+    launch_cross_gram(Q, m, A, k, n, c->G, c->gscratch, st);          // second pass ("twice is enough")
+    launch_project_rows(A, k, Q, m, n, c->G, A, st);
+    launch_gram(A, k, n, S + KRY_G, c->gscratch, st);                 // G = R R^T: the residual estimate and the next block's Gram
+    launch_jacobi_eig(c->Q, m, S + KRY_THETA, S + KRY_W, st);         // Ritz pairs of T[:m][:m]
+    c->kry_m[slot] = m;
+    c->kry_k[slot] = k;
+    if (next) {
+        // next block = R orthonormalised within itself (loco_orthonormalize's sequence on the Gram already at hand),
+        // directions below KRYLOV_DROP * theta_0 zeroed in place, then one more projection against Q
+        launch_jacobi_eig(S + KRY_G, k, c->W, c->Q, st);
+        launch_krylov_floor(c->W, k, S + KRY_THETA, stat, st);
+        launch_rotate_rows(A, c->tmpA, k, n, c->Q, c->W, 0, st);
+        const double* gate = c->W + SOLVER_W_GATE;
+        launch_gram(c->tmpA, k, n, c->G, c->gscratch, st, gate);
+        launch_cholesky(c->G, k, st, 0.25, c->W, gate);
+        launch_trsm_rows(c->tmpA, next, k, n, c->G, st, gate);
+        launch_cross_gram(Q, m, next, k, n, c->G, c->gscratch, st);
+        launch_project_rows(next, k, Q, m, n, c->G, next, st);
+    } else {
+        HIPCHK(c, hipMemsetAsync(stat + 3, 0, sizeof(float), st));
+    }
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+int loco_krylov_ritz(loco_ctx* c, const float* Q, int32_t m, int64_t n, int32_t k, float* Y, const float* Yprev, float atol,
+                     float* resid, float* stat, int32_t slot, void* stream) {
+    if (!c) return -2;
+    if (const char* e = krylov_sizes(c, k, m, n, slot, true)) { c->err = e; return -2; }
+    if (!Q || !Y || !resid || !stat) { c->err = "krylov_ritz: null pointer"; return -2; }
+    if (c->kry_m[slot] != m || c->kry_k[slot] != k) { c->err = "krylov_ritz: loco_krylov_extend has not been called for these m rows in blocks of k"; return -2; }
+    hipStream_t st = (hipStream_t)stream;
+    double* S = c->kry[slot];
+    launch_rotate_rect(Q, Y, k, m, n, S + KRY_W, m, nullptr, st);
+    launch_sign_fix(Y, k, n, nullptr, nullptr, reinterpret_cast<float*>(c->red), st, S + KRY_SIGN);
+    launch_krylov_resid(S + KRY_W, m, k, S + KRY_G, S + KRY_THETA, resid, stat, Yprev != nullptr, st);
+    if (Yprev) launch_convergence_rows(Yprev, Y, k, n, atol, 1e-5f, stat, c->gscratch, st);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+int loco_krylov_left(loco_ctx* c, const float* Ustore, int32_t m, int64_t n_out, int32_t k, float* UY, float* s, int32_t slot,
+                     void* stream) {
+    if (!c) return -2;
+    if (const char* e = krylov_sizes(c, k, m, n_out, slot, false)) { c->err = e; return -2; }
+    if (!Ustore || !UY || !s) { c->err = "krylov_left: null pointer"; return -2; }
+    if (c->kry_m[slot] != m || c->kry_k[slot] != k) { c->err = "krylov_left: loco_krylov_extend and loco_krylov_ritz have not been called for these m rows in blocks of k"; return -2; }
+    hipStream_t st = (hipStream_t)stream;
+    double* S = c->kry[slot];
+    launch_rotate_rect(Ustore, UY, k, m, n_out, S + KRY_W, m, S + KRY_SIGN, st);
+    launch_row_sqnorm(UY, k, n_out, s, c->gscratch, st);
     HIPCHK(c, hipGetLastError());
     return 0;
 }

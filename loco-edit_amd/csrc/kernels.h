@@ -440,7 +440,9 @@ void launch_jacobi_eig(double* G, int k, double* w, double* Q, hipStream_t st);
 void launch_rotate_rows(const float* Ain, float* Aout, int k, long n, const double* Q, const double* w,
                         int mode, hipStream_t st);
 // s_out[i] = sqrt(w_i), 0 for w_i <= SOLVER_W_FLOOR * w[0]
-void launch_sign_fix(float* A, int k, long n, float* s_out, const double* w, float* scratch, hipStream_t st);   // scratch: k * ceil(n/4096) floats
+// sign_out[i] (optional) = -1 when row i was flipped, else +1; s_out may be nullptr (w is then not read)
+void launch_sign_fix(float* A, int k, long n, float* s_out, const double* w, float* scratch, hipStream_t st,
+                     double* sign_out = nullptr);   // scratch: k * ceil(n/4096) floats
 // Cholesky factor of G (k x k double, lower) in one workgroup, then A <- L^{-1} A.
 // drop_below = 0: pivots are clamped to 1e-300 (CholeskyQR of independent rows).  drop_below > 0 (the Gram of rows that
 // are unit vectors up to rounding, or zero): a row whose pivot -- what is left of its squared norm after the rows
@@ -459,6 +461,27 @@ void launch_convergence_rows(const float* a, const float* b, int k, long n, floa
 void launch_project_rows(const float* Vm, int k, const float* Vn, int k0, long n, const double* C,
                          float* out, hipStream_t st);
 void launch_normalize_rows(float* A, int k, long n, double* scratch, hipStream_t st);
+// ---- block Krylov solver: per-solve state, one buffer of KRY_STATE doubles (engine.hip keeps two slots) ----------
+constexpr int KRYLOV_MAX_BLOCK = 32;            // two blocks must fit in the eigensolver's 64 rows
+constexpr double KRYLOV_DROP = 1e-6;            // singular value of a residual direction, relative to theta_0, below which it is noise
+constexpr int KRY_T = 0;                        // T [64][64] = Q J^T J Q^T
+constexpr int KRY_W = KRY_T + 64 * 64;          // Ritz vectors as rows, packed [m][m]
+constexpr int KRY_THETA = KRY_W + 64 * 64;      // Ritz values, descending (SOLVER_W_GATE + 1 doubles)
+constexpr int KRY_G = KRY_THETA + 72;           // (65 rounded up to a multiple of 8)  Gram of the residual block [k][k]
+constexpr int KRY_SIGN = KRY_G + KRYLOV_MAX_BLOCK * KRYLOV_MAX_BLOCK;   // sign of each returned row
+constexpr int KRY_STATE = KRY_SIGN + KRYLOV_MAX_BLOCK;
+// T's block column / row of the newest k rows from Ct [m][k] = Q A^T; Tp = T[:m][:m] packed
+void launch_krylov_fill_t(const double* Ct, int m, int k, double* T, double* Tp, hipStream_t st);
+// out [k][n] = diag(sign) W[:k][:m] Q [m][n]; W has leading dimension ldw; sign may be nullptr
+void launch_rotate_rect(const float* Q, float* out, int k, int m, long n, const double* W, int ldw, const double* sign,
+                        hipStream_t st);
+// resid[k] and stat[2] (their maximum); has_prev == 0 also sets stat[0] = -1, stat[1] = 0
+void launch_krylov_resid(const double* W, int m, int k, const double* G, const double* theta, float* resid, float* stat,
+                         int has_prev, hipStream_t st);
+// zero the eigenvalues w[k] whose root is below KRYLOV_DROP * theta[0]; stat[3] = 1 when none is left
+void launch_krylov_floor(double* w, int k, const double* theta, float* stat, hipStream_t st);
+// s[i] = ||A_i||^2; scratch: k * 64 doubles
+void launch_row_sqnorm(const float* A, int k, long n, float* s, double* scratch, hipStream_t st);
 void launch_edit_axpy(const float* x, const float* v, const float* alphas_dev, int B, long n, float* out,
                       hipStream_t st);
 void launch_mask_gather(const float* U, const int* idx, long L, long n, int k, float* out, hipStream_t st);

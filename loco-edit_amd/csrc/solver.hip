@@ -254,7 +254,7 @@ __global__ __launch_bounds__(256) void sign_cand_kernel(const float* A, long n, 
     if (threadIdx.x == 0) cand[(long)blockIdx.y * nseg + blockIdx.x] = bestv[0];
 }
 __global__ __launch_bounds__(256) void sign_apply_kernel(float* A, long n, int nseg, const float* cand, float* s_out,
-                                                         const double* w) {
+                                                         const double* w, double* sign_out) {
     __shared__ float bestv[256];
     float bv = 0.f;
     for (int i = threadIdx.x; i < nseg; i += 256) {
@@ -277,11 +277,14 @@ __global__ __launch_bounds__(256) void sign_apply_kernel(float* A, long n, int n
         double ev = w[blockIdx.y];
         s_out[blockIdx.y] = (float)(ev > SOLVER_W_FLOOR * w[0] ? sqrt(ev) : 0.0);
     }
+    if (blockIdx.x == 0 && threadIdx.x == 0 && sign_out) sign_out[blockIdx.y] = bestv[0] < 0.f ? -1.0 : 1.0;
 }
-void launch_sign_fix(float* A, int k, long n, float* s_out, const double* w, float* scratch, hipStream_t st) {
+void launch_sign_fix(float* A, int k, long n, float* s_out, const double* w, float* scratch, hipStream_t st,
+                     double* sign_out) {
     const int nseg = (int)((n + SIGN_SEG - 1) / SIGN_SEG);
     hipLaunchKernelGGL(sign_cand_kernel, dim3(nseg, k), dim3(256), 0, st, A, n, nseg, scratch);
-    hipLaunchKernelGGL(sign_apply_kernel, dim3(nseg, k), dim3(256), 0, st, A, n, nseg, scratch, s_out, w);
+    hipLaunchKernelGGL(sign_apply_kernel, dim3(nseg, k), dim3(256), 0, st, A, n, nseg, scratch, s_out, w,
+                       sign_out);
 }
 
 // in-place lower Cholesky of a k x k double matrix (row-major), one workgroup; drop_below / w / gate: kernels.h
@@ -494,6 +497,134 @@ __global__ __launch_bounds__(256) void normalize_rows_kernel(float* A, long n) {
 void launch_normalize_rows(float* A, int k, long n, double* scratch, hipStream_t st) {
     (void)scratch;
     hipLaunchKernelGGL(normalize_rows_kernel, dim3(k), dim3(256), 0, st, A, n);
+}
+
+// ---------------------------------------------------------------------------
+// Block Krylov solver (Rayleigh-Ritz on J^T J over every stored block; DESIGN.md "Block Krylov solver").
+// Q [m][n]: the stored orthonormal rows, m <= 64 in blocks of k <= 32; T [64][64] (double) = Q J^T J Q^T.
+
+// Block column (and, by symmetry, block row) j of T from Ct [m][k] = Q A_j^T, the diagonal block symmetrised; then
+// T[:m][:m] packed (leading dimension m) for the eigensolver.  One workgroup.
+__global__ __launch_bounds__(256) void krylov_fill_t_kernel(const double* Ct, int m, int k, double* T, double* Tp) {
+    const int m0 = m - k;
+    for (int e = threadIdx.x; e < m * k; e += 256) {
+        const int i = e / k, b = e % k, col = m0 + b;
+        double v = Ct[e];
+        if (i >= m0) v = 0.5 * (v + Ct[col * k + (i - m0)]);     // both writers of a diagonal-block entry store this value
+        T[i * 64 + col] = v;
+        T[col * 64 + i] = v;
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < m * m; e += 256) Tp[e] = T[(e / m) * 64 + e % m];
+}
+void launch_krylov_fill_t(const double* Ct, int m, int k, double* T, double* Tp, hipStream_t st) {
+    hipLaunchKernelGGL(krylov_fill_t_kernel, dim3(1), dim3(256), 0, st, Ct, m, k, T, Tp);
+}
+
+// out[i][c] = sign_i * sum_{j < m} W[i][j] * Q[j][c]   (i < k <= 32, m <= 64; sign == nullptr: +1)
+__global__ __launch_bounds__(256) void rotate_rect_kernel(const float* Q, float* out, int k, int m, long n,
+                                                          const double* W, int ldw, const double* sign) {
+    extern __shared__ double ws[];      // [k][m]
+    for (int e = threadIdx.x; e < k * m; e += 256) {
+        const int i = e / m, j = e % m;
+        ws[e] = W[i * ldw + j] * (sign ? sign[i] : 1.0);
+    }
+    __syncthreads();
+    for (long c = (long)blockIdx.x * 256 + threadIdx.x; c < n; c += (long)gridDim.x * 256) {
+        float col[64];
+#pragma unroll
+        for (int j = 0; j < 64; ++j) col[j] = (j < m) ? Q[(long)j * n + c] : 0.f;
+        for (int i = 0; i < k; ++i) {
+            double acc = 0.0;
+#pragma unroll
+            for (int j = 0; j < 64; ++j)
+                if (j < m) acc += ws[i * m + j] * (double)col[j];
+            out[(long)i * n + c] = (float)acc;
+        }
+    }
+}
+void launch_rotate_rect(const float* Q, float* out, int k, int m, long n, const double* W, int ldw, const double* sign,
+                        hipStream_t st) {
+    int blocks = (int)((n + 255) / 256);
+    if (blocks > 1024) blocks = 1024;
+    hipLaunchKernelGGL(rotate_rect_kernel, dim3(blocks), dim3(256), (size_t)k * m * sizeof(double), st, Q, out, k, m,
+                       n, W, ldw, sign);
+}
+
+// resid[i] = sqrt(w_i^T G w_i) / theta_0 with w_i the last k entries of Ritz vector i (W [m][m], rows), G [k][k] the Gram
+// of the residual block: ||J^T J y_i - theta_i y_i|| relative to the largest Ritz value.  stat[2] = the largest of
+// them; without a previous iterate to compare with, stat[0] = -1 and stat[1] = 0 stand for the convergence test.
+__global__ __launch_bounds__(64) void krylov_resid_kernel(const double* W, int m, int k, const double* G,
+                                                          const double* theta, float* resid, float* stat, int has_prev) {
+    __shared__ double r[64];
+    const int i = threadIdx.x;
+    double v = 0.0;
+    if (i < k) {
+        const double* w = W + i * m + (m - k);
+        double q = 0.0;
+        for (int a = 0; a < k; ++a) {
+            double t = 0.0;
+            for (int b = 0; b < k; ++b) t += G[a * k + b] * w[b];
+            q += w[a] * t;
+        }
+        v = theta[0] > 0.0 ? sqrt(q > 0.0 ? q : 0.0) / theta[0] : 0.0;
+        resid[i] = (float)v;
+    }
+    r[i] = v;
+    __syncthreads();
+    if (i == 0) {
+        double mx = 0.0;
+        for (int a = 0; a < k; ++a) mx = r[a] > mx ? r[a] : mx;
+        stat[2] = (float)mx;
+        if (!has_prev) { stat[0] = -1.f; stat[1] = 0.f; }
+    }
+}
+void launch_krylov_resid(const double* W, int m, int k, const double* G, const double* theta, float* resid, float* stat,
+                         int has_prev, hipStream_t st) {
+    hipLaunchKernelGGL(krylov_resid_kernel, dim3(1), dim3(64), 0, st, W, m, k, G, theta, resid, stat, has_prev);
+}
+
+// Eigenvalues w[k] of the residual block's Gram (descending): a direction whose singular value sqrt(w_i) is below
+// KRYLOV_DROP * theta_0 is fp32 noise of A = J^T J Q (which squares sigma) and becomes a zero row: w_i = 0, which
+// rotate_rows_kernel (mode 0) turns into a zero scale.  stat[3] = 1 when no direction is left (the space is invariant).
+__global__ void krylov_floor_kernel(double* w, int k, const double* theta, float* stat) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        const double lim = KRYLOV_DROP * theta[0];
+        int any = 0;
+        for (int i = 0; i < k; ++i) {
+            if (w[i] > 0.0 && sqrt(w[i]) >= lim) any = 1; else w[i] = 0.0;
+        }
+        stat[3] = any ? 0.f : 1.f;
+    }
+}
+void launch_krylov_floor(double* w, int k, const double* theta, float* stat, hipStream_t st) {
+    hipLaunchKernelGGL(krylov_floor_kernel, dim3(1), dim3(64), 0, st, w, k, theta, stat);
+}
+
+// s[i] = ||A_i||^2 in double: grid (segments <= 64, k) of fixed-order partial sums, then one thread per row
+__global__ __launch_bounds__(256) void row_sqnorm_partial_kernel(const float* A, long n, double* part) {
+    __shared__ double sm[4];
+    const float* row = A + (long)blockIdx.y * n;
+    double ss = 0.0;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) ss += (double)row[i] * (double)row[i];
+    ss = wsum(ss);
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = ss;
+    __syncthreads();
+    if (threadIdx.x == 0) part[(long)blockIdx.y * gridDim.x + blockIdx.x] = sm[0] + sm[1] + sm[2] + sm[3];
+}
+__global__ void row_sqnorm_final_kernel(const double* part, int nseg, int k, float* s) {
+    const int r = threadIdx.x;
+    if (r < k) {
+        double ss = 0.0;
+        for (int i = 0; i < nseg; ++i) ss += part[(long)r * nseg + i];
+        s[r] = (float)ss;
+    }
+}
+void launch_row_sqnorm(const float* A, int k, long n, float* s, double* scratch, hipStream_t st) {
+    int nseg = (int)((n + 255) / 256);
+    if (nseg > 64) nseg = 64;
+    hipLaunchKernelGGL(row_sqnorm_partial_kernel, dim3(nseg, k), dim3(256), 0, st, A, n, scratch);
+    hipLaunchKernelGGL(row_sqnorm_final_kernel, dim3(1), dim3(64), 0, st, scratch, nseg, k, s);
 }
 
 __global__ void edit_axpy_kernel(const float* x, const float* v, const float* alphas, long n, float* out) {

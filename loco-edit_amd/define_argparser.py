@@ -152,11 +152,17 @@ def build_parser():
                         "(fp32-faithful to ~2^-16, default), 'f16' single f16 MFMA with fp32 accumulate (2^-11 operands; opt-in: "
                         "operands are cast without range management, so tangent / cotangent entries below 6e-5 lose bits and "
                         "above 65504 overflow -- pinned on synthetic weights only)")
+    p.add_argument('--solver', type=str, default=None, choices=['power', 'krylov'],
+                   help="basis solver (sets LOCO_SOLVER): 'power' block power iteration (default, the reference's loop), 'krylov' "
+                        "block Krylov with Rayleigh-Ritz over all iterates: same two passes per step, stops on its own test, at most "
+                        "32 probes per solve; writes <basis name>_residual.json next to each basis it computes")
     return p
 
 
 def parse_args(argv=None):
     args = build_parser().parse_args(argv)
+    if args.solver:
+        os.environ["LOCO_SOLVER"] = args.solver
     if args.text_encoder_path and args.prompt_emb_path:
         raise ValueError("--text_encoder_path and --prompt_emb_path both give the prompt embeddings: pass one of them")
     if args.max_batch <= 0:

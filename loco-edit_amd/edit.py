@@ -95,6 +95,11 @@ class EditUncondDiffusion(object):
         if self.sharder.is_main:
             torch.save(obj, path)
 
+    def _save_residuals(self, basis_path, info):
+        """``<basis name>_residual.json`` next to a basis file the Krylov solver computed (solver.write_residuals)."""
+        if self.sharder.is_main:
+            solver.write_residuals(basis_path, info)
+
     def _exists(self, path):
         return self.sharder.agree(bool(path) and os.path.exists(path))
 
@@ -208,9 +213,11 @@ class EditUncondDiffusion(object):
         are accepted and ignored exactly as in the reference."""
         x = x.to(device=self.device, dtype=torch.float32).contiguous()
         at = self.scheduler.alpha_at(t)
+        self.last_solver_info = {}              # which solver ran (LOCO_SOLVER / --solver); the Krylov solver's residuals
         u, s, vT, self.last_n_iter = solver.local_basis(
             self.engine, x, t, at, pca_rank, mask=mask, noise=noise, min_iter=min_iter, max_iter=max_iter,
-            convergence_threshold=convergence_threshold, v0=v0, sharder=self.sharder, verbose=verbose)
+            convergence_threshold=convergence_threshold, v0=v0, sharder=self.sharder, verbose=verbose,
+            info=self.last_solver_info)
         return u, s, vT
 
     # ------------------------------------------------------------------ drivers
@@ -317,12 +324,16 @@ class EditUncondDiffusion(object):
                 # both bases are missing: one pass carries the probes of both solves (solver.local_basis_pair)
                 print('subspace solves: modify space + null space (shared probe batches)')
                 at = self.scheduler.alpha_at(t)
+                pair_info = []
                 (u_modify, s_modify, vT_modify, self.last_n_iter), (u_null, s_null, vT_null, self.last_n_iter_null) = \
                     solver.local_basis_pair(self.engine, xt.to(self.device, torch.float32), float(t), at, pca_rank, mask,
                                             pca_rank_null, ~mask, noise=encoder_decoder_by_et, min_iter=10, max_iter=50,
-                                            convergence_threshold=1e-4, sharder=self.sharder)
+                                            convergence_threshold=1e-4, sharder=self.sharder, info=pair_info)
                 self._save(vT_modify, vT_modify_path)
                 self._save(vT_null, vT_null_path)
+                if pair_info:
+                    self._save_residuals(vT_modify_path, pair_info[0])
+                    self._save_residuals(vT_null_path, pair_info[1])
             elif have_m:
                 vT_modify = self._load(vT_modify_path, map_location=self.device).to(self.device).type(self.dtype)
             else:
@@ -331,6 +342,7 @@ class EditUncondDiffusion(object):
                     x=xt, t=t, op=op, block_idx=block_idx, pca_rank=pca_rank,
                     min_iter=10, max_iter=50, convergence_threshold=1e-4, mask=mask, noise=encoder_decoder_by_et)
                 self._save(vT_modify, vT_modify_path)
+                self._save_residuals(vT_modify_path, self.last_solver_info)
 
             if vT_null is not None:
                 pass
@@ -342,6 +354,7 @@ class EditUncondDiffusion(object):
                     x=xt, t=t, op=op, block_idx=block_idx, pca_rank=pca_rank_null,
                     min_iter=10, max_iter=50, convergence_threshold=1e-4, mask=~mask, noise=encoder_decoder_by_et)
                 self._save(vT_null, vT_null_path)
+                self._save_residuals(vT_null_path, self.last_solver_info)
 
             if random_edit:
                 vT_modify = torch.randn_like(vT_modify)       # same generator state on every rank (seed broadcast in main)

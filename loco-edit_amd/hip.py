@@ -27,7 +27,7 @@ SYMBOLS = [
     "loco_version", "loco_device_count", "loco_create", "loco_fork", "loco_destroy", "loco_last_error",
     "loco_load_param", "loco_params_missing", "loco_unet_forward", "loco_ddim_step", "loco_sched_step",
     "loco_pmp_primal", "loco_pmp_set_second_mask", "loco_pmp_jvp", "loco_pmp_vjp", "loco_orthonormalize", "loco_qr_rows",
-    "loco_convergence", "loco_convergence_rows", "loco_null_project", "loco_edit_axpy", "loco_mask_gather", "loco_mask_count",
+    "loco_convergence", "loco_convergence_rows", "loco_krylov_extend", "loco_krylov_ritz", "loco_krylov_left", "loco_null_project", "loco_edit_axpy", "loco_mask_gather", "loco_mask_count",
     "loco_unet_flops", "loco_workspace_bytes", "loco_clock_stamp", "loco_set_side_stream", "loco_timer_start", "loco_timer_stop",
     "loco_profile_enable", "loco_profile_report", "loco_set_precision", "loco_get_precision", "loco_set_streams", "loco_set_chip_share",
     "loco_set_cond", "loco_set_context", "loco_lincomb", "loco_masked_axpby", "loco_latent_sample",
@@ -148,6 +148,9 @@ def load_library():
     lib.loco_qr_rows.argtypes = [vp, vp, i32, i64, vp]
     lib.loco_convergence.argtypes = [vp, vp, vp, i64, f32, vp, vp]
     lib.loco_convergence_rows.argtypes = [vp, vp, vp, i32, i64, f32, vp, vp]
+    lib.loco_krylov_extend.argtypes = [vp, vp, i32, vp, i32, i64, vp, vp, i32, vp]
+    lib.loco_krylov_ritz.argtypes = [vp, vp, i32, i64, i32, vp, vp, f32, vp, vp, i32, vp]
+    lib.loco_krylov_left.argtypes = [vp, vp, i32, i64, i32, vp, vp, i32, vp]
     lib.loco_null_project.argtypes = [vp, vp, i32, vp, i32, i64, vp, vp]
     lib.loco_edit_axpy.argtypes = [vp, vp, vp, C.POINTER(f32), i32, i64, vp, vp]
     lib.loco_mask_gather.argtypes = [vp, vp, i32, vp, vp]
@@ -471,6 +474,39 @@ class LocoEngine:
         self._check(self.lib.loco_convergence_rows(self._ctx, _ptr(Vprev), _ptr(V), k, n, float(atol), _ptr(out),
                                                    _stream()), "loco_convergence_rows")
         return out
+
+    # ---- block Krylov solver (solver.krylov_iteration drives these; include/loco_hip.h states the contract)
+    def krylov_extend(self, A, Q, m: int, nxt, stat, slot: int = 0):
+        """One step's n-wide algebra on A [k, n] = J^T J Q[m-k:m] against the first ``m`` rows of Q; ``nxt`` [k, n] (or None)
+        receives the next block; stat[3] is set."""
+        for t in (A, Q, stat) + ((nxt,) if nxt is not None else ()):
+            _chk_dev(t)
+        k, n = A.shape
+        if Q.shape[1] != n or Q.shape[0] < m or stat.numel() < 4 or (nxt is not None and tuple(nxt.shape) != (k, n)):
+            raise ValueError("krylov_extend: Q must hold m rows of A's width, nxt must have A's shape, stat 4 floats")
+        self._check(self.lib.loco_krylov_extend(self._ctx, _ptr(A), k, _ptr(Q), int(m), n, _ptr(nxt), _ptr(stat), int(slot),
+                                                _stream()), "loco_krylov_extend")
+
+    def krylov_ritz(self, Q, m: int, Y, Yprev, atol, resid, stat, slot: int = 0):
+        """Y [k, n] = top-k Ritz vectors over Q[:m]; resid [k]; stat[0..2] (loco_krylov_ritz)."""
+        for t in (Q, Y, resid, stat) + ((Yprev,) if Yprev is not None else ()):
+            _chk_dev(t)
+        k, n = Y.shape
+        if Q.shape[1] != n or Q.shape[0] < m or resid.numel() < k or stat.numel() < 4 or \
+                (Yprev is not None and tuple(Yprev.shape) != (k, n)):
+            raise ValueError("krylov_ritz: Q must hold m rows of Y's width, Yprev must have Y's shape, resid k and stat 4 floats")
+        self._check(self.lib.loco_krylov_ritz(self._ctx, _ptr(Q), int(m), n, k, _ptr(Y), _ptr(Yprev), float(atol), _ptr(resid),
+                                              _ptr(stat), int(slot), _stream()), "loco_krylov_ritz")
+
+    def krylov_left(self, Ustore, m: int, UY, s, slot: int = 0):
+        """UY [k, n_out] = the Ritz combination (and signs) of Ustore[:m]; s [k] = ||UY_i||^2 (loco_krylov_left)."""
+        for t in (Ustore, UY, s):
+            _chk_dev(t)
+        k, n_out = UY.shape
+        if Ustore.shape[1] != n_out or Ustore.shape[0] < m or s.numel() < k:
+            raise ValueError("krylov_left: Ustore must hold m rows of UY's width, s k floats")
+        self._check(self.lib.loco_krylov_left(self._ctx, _ptr(Ustore), int(m), n_out, k, _ptr(UY), _ptr(s), int(slot),
+                                              _stream()), "loco_krylov_left")
 
     def null_project(self, Vm, Vn=None) -> torch.Tensor:
         _chk_dev(Vm)

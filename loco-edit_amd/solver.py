@@ -8,6 +8,9 @@ the primal is evaluated once per solve, each iteration is one batched tangent
 pass + one batched cotangent pass + an on-device Gram/eig re-orthonormalisation,
 and at most one 2-float readback.
 
+``LOCO_SOLVER=krylov`` / ``solver="krylov"`` selects the block Krylov solver (``krylov_iteration``) instead: the same
+two passes per step, Rayleigh-Ritz over every stored block, a residual per returned direction.
+
 Multi-GPU: probes are sharded over ranks (``ProbeSharder``), each
 rank runs JVP+VJP on its rows, one all-gather of the A shards per iteration,
 the k x k algebra is replicated.
@@ -135,15 +138,174 @@ def subspace_iteration(op, algebra, V0: torch.Tensor, min_iter: int = 10, max_it
     return U, s, V, n_done
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# block Krylov solver (opt-in)
+KRYLOV_ROWS = 64          # rows of Q the eigensolver takes
+KRYLOV_MAX_PROBES = 32    # two blocks must fit
+
+
+def default_solver() -> str:
+    """``LOCO_SOLVER``: ``power`` (default; ``subspace_iteration``) or ``krylov`` (``krylov_iteration``)."""
+    name = os.environ.get("LOCO_SOLVER", "power")
+    if name not in ("power", "krylov"):
+        raise ValueError(f"LOCO_SOLVER must be 'power' or 'krylov', got {name!r}")
+    return name
+
+
+def _pick_solver(solver: Optional[str]) -> str:
+    name = solver or default_solver()
+    if name not in ("power", "krylov"):
+        raise ValueError(f"solver must be 'power' or 'krylov', got {name!r}")
+    return name
+
+
+class KrylovState:
+    """What one block Krylov solve keeps between steps: ``Q`` [cap, n] (orthonormal rows, blocks of k, block 0 = V0),
+    the rows ``J Q`` this rank computed, two buffers for the Ritz vectors of this step and the previous one, the
+    residuals and the four floats read back per step.  Allocated once per solve; ``slot`` names the context's own
+    small state (T, Ritz pairs, G), so that two solves can be in flight."""
+
+    def __init__(self, algebra, V0: torch.Tensor, n_out: int, local_rows: Tuple[int, int], slot: int = 0):
+        k, n = V0.shape
+        if k > KRYLOV_MAX_PROBES:
+            raise ValueError(f"the block Krylov solver keeps at least two blocks in {KRYLOV_ROWS} rows: {k} probes > "
+                             f"{KRYLOV_MAX_PROBES}; use solver='power' for this probe count")
+        self.algebra, self.k, self.n, self.n_out, self.slot = algebra, k, n, n_out, slot
+        self.cap = (KRYLOV_ROWS // k) * k
+        self.lo, self.hi = local_rows
+        self.Q = V0.new_zeros(self.cap, n)
+        self.Q[:k] = V0
+        self.Uloc = V0.new_zeros(self.cap // k, self.hi - self.lo, n_out)      # block b: rows lo..hi of J Q_b
+        self.Y = [V0.new_empty(k, n), V0.new_empty(k, n)]
+        self.resid = V0.new_zeros(k)
+        self.stat = V0.new_zeros(4)
+        self.m = k              # rows of Q in use, the current block last
+        self.steps = 0
+        self.m_ritz = 0         # rows the last Ritz vectors were computed over
+        self.reason = None      # why the solve ended: invariant | converged | full | max_iter
+        self.dist = -1.0
+        self.max_resid = float("nan")
+
+    def block(self) -> torch.Tensor:
+        return self.Q[self.m - self.k:self.m]
+
+    def advance(self, U_loc: torch.Tensor, A: torch.Tensor, thr: float, last: bool) -> bool:
+        """Take this step's J Q_j rows (this rank's) and A = J^T J Q_j (all rows; overwritten).  True: the solve ends."""
+        k, m = self.k, self.m
+        self.Uloc[m // k - 1].copy_(U_loc)
+        room = m + k <= self.cap and not last
+        nxt = self.Q[m:m + k] if room else None
+        self.algebra.krylov_extend(A, self.Q, m, nxt, self.stat, self.slot)
+        Y, Yprev = self.Y[self.steps % 2], (self.Y[(self.steps + 1) % 2] if self.steps >= 1 else None)
+        self.algebra.krylov_ritz(self.Q, m, Y, Yprev, thr, self.resid, self.stat, self.slot)
+        self.dist, flag, self.max_resid, all_zero = self.stat.tolist()         # the one readback of the step
+        self.steps += 1
+        self.m_ritz = m
+        if room and all_zero > 0.5:
+            self.reason = "invariant"
+        elif Yprev is not None and flag > 0.5:
+            self.reason = "converged"
+        elif not room:
+            self.reason = "max_iter" if last else "full"
+        else:
+            self.m = m + k
+        return self.reason is not None
+
+    def finish(self, sharder: ProbeSharder):
+        """-> (U [k, n_out] = J V, s [k] = ||U_i||^2, V [k, n], resid [k])."""
+        k, nb = self.k, self.m_ritz // self.k
+        if sharder.active:      # the stored rows are gathered once, here: [rows, blocks * n_out] keeps all_gather_rows' layout
+            loc = self.Uloc[:nb].permute(1, 0, 2).reshape(self.hi - self.lo, nb * self.n_out)
+            Ustore = sharder.all_gather_rows(loc, k).view(k, nb, self.n_out).permute(1, 0, 2).reshape(nb * k, self.n_out)
+            Ustore = Ustore.contiguous()
+        else:
+            Ustore = self.Uloc.view(self.cap, self.n_out)
+        UY = self.Q.new_empty(k, self.n_out)
+        s = self.Q.new_empty(k)
+        self.algebra.krylov_left(Ustore, self.m_ritz, UY, s, self.slot)
+        return UY, s, self.Y[(self.steps - 1) % 2], self.resid
+
+
+def krylov_iteration(op, algebra, V0: torch.Tensor, max_iter: int = 100, convergence_threshold: float = 1e-3,
+                     sharder: Optional[ProbeSharder] = None, verbose: bool = True, info: Optional[dict] = None
+                     ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, int]:
+    """Block Krylov counterpart of ``subspace_iteration`` on orthonormal rows ``V0`` [k, n], k <= 32 (DESIGN.md "Block
+    Krylov solver").  Every step pays the same one batched J V and one batched J^T U; the blocks of all steps are kept
+    (at most 64 rows) and the returned rows are the top-k Ritz vectors of J^T J over their span.  After j steps that span
+    is V0, (J^T J) V0 ... (J^T J)^(j-1) V0: the newest block A_j enters T and the residual, and the basis one step later.
+
+    ``algebra`` provides krylov_extend / krylov_ritz / krylov_left (the HIP engine; tests substitute a float64 double).
+    Returns (U [k, n_out], s [k], V [k, n], n_steps) with ``subspace_iteration``'s conventions -- callers take
+    ``s.sqrt()`` and ``op.gather(U)`` -- except that U = J V of the RETURNED V (the power loop returns it one iteration
+    behind) and s_i = ||U_i||^2.  ``info`` (a dict) receives ``residual`` (list of k floats: ||J^T J v_i - theta_i v_i||
+    / theta_0 as estimated from the last residual block), ``reason`` and ``rows``.
+
+    The solve ends when the next block is entirely below 1e-6 of the largest Ritz value (the space is invariant: the
+    result is exact), when every row is allclose(``convergence_threshold``) to +-its predecessor (tested from the second
+    step on; a negative threshold switches this exit off), when another block would not fit in 64 rows, or after
+    ``max_iter`` steps.  The reference's ``min_iter`` is not consulted: the drivers pass 10, which would forbid the early
+    stop this solver exists for."""
+    sharder = sharder or ProbeSharder(None)
+    k = V0.shape[0]
+    st = KrylovState(algebra, V0, _n_out(op, V0), sharder.rows(k))
+    lo, hi = st.lo, st.hi
+    for j in range(max_iter):
+        blk = st.block()
+        if hi > lo:
+            U_loc = op.jvp(blk[lo:hi].contiguous())
+            A_loc = op.vjp(U_loc)
+        else:                                           # more ranks than probes: this rank only joins the gathers
+            A_loc = blk[0:0].contiguous()
+            U_loc = blk.new_empty(0, st.n_out)
+        A = sharder.all_gather_rows(A_loc, k)           # the one collective per step
+        done = st.advance(U_loc, A, convergence_threshold, last=(j == max_iter - 1))
+        if verbose:
+            print(f'block krylov : {j}-th step ({st.m_ritz} rows) convergence : {st.dist}  residual : {st.max_resid}')
+        if done:
+            break
+    if verbose:
+        print(f'block krylov : ended after {st.steps} steps ({st.reason})')
+    U, s, V, resid = st.finish(sharder)
+    if info is not None:
+        info.update(residual=[float(r) for r in resid.tolist()], reason=st.reason, rows=st.m_ritz, solver="krylov")
+    return U, s, V, st.steps
+
+
+def solve_basis(op, algebra, V0: torch.Tensor, min_iter: int = 10, max_iter: int = 100, convergence_threshold: float = 1e-3,
+                sharder: Optional[ProbeSharder] = None, verbose: bool = True, stop_rule: Optional[str] = None,
+                solver: Optional[str] = None, info: Optional[dict] = None):
+    """The solver picked by ``solver`` (default ``LOCO_SOLVER``, default ``power``) -> (U, s, V, n_iter).  ``power`` is
+    ``subspace_iteration`` called exactly as before; ``krylov`` ignores ``min_iter`` and ``stop_rule`` and fills ``info``."""
+    if _pick_solver(solver) == "krylov":
+        return krylov_iteration(op, algebra, V0, max_iter, convergence_threshold, sharder=sharder, verbose=verbose, info=info)
+    if info is not None:
+        info.update(solver="power")
+    return subspace_iteration(op, algebra, V0, min_iter, max_iter, convergence_threshold, sharder=sharder, verbose=verbose,
+                              stop_rule=stop_rule)
+
+
+def write_residuals(basis_path: str, info: Optional[dict]):
+    """``<basis name>_residual.json`` next to a basis file, for a solve that produced residuals (the Krylov solver)."""
+    if not info or "residual" not in info:
+        return None
+    import json
+    path = os.path.splitext(basis_path)[0] + "_residual.json"
+    with open(path, "w") as f:
+        json.dump({k: info[k] for k in ("solver", "residual", "reason", "rows") if k in info}, f)
+    return path
+
+
 def local_basis(engine, x, t, at, pca_rank: int, mask=None, noise=False, min_iter=10, max_iter=100,
                 convergence_threshold=1e-3, v0: Optional[torch.Tensor] = None,
-                sharder: Optional[ProbeSharder] = None, verbose=True, stop_rule: Optional[str] = None):
+                sharder: Optional[ProbeSharder] = None, verbose=True, stop_rule: Optional[str] = None,
+                solver: Optional[str] = None, info: Optional[dict] = None):
     """Top-``pca_rank`` right singular subspace of J (edit.py:2406-2504).
 
     ``v0``: optional [n, k] Gaussian matrix standing in for the ``torch.randn``
     draw of edit.py:2435 (parity tests inject it).  Returns (u [L,k], s [k],
     vT [k,n], n_iter) with the reference's conventions: ``s`` is the square
-    root of the singular values of A = U^T J (edit.py:2500).
+    root of the singular values of A = U^T J (edit.py:2500).  ``solver``: ``power`` | ``krylov`` (``solve_basis``);
+    ``info`` receives the Krylov solver's residuals.
     """
     n = engine.n
     dev = x.device
@@ -153,19 +315,20 @@ def local_basis(engine, x, t, at, pca_rank: int, mask=None, noise=False, min_ite
     V = v0.to(device=dev, dtype=torch.float32).T.contiguous()               # rows = probes
     engine.qr_rows_(V)                                                       # edit.py:2436 (thin QR)
     op = JacobianOperator(engine, x, t, at, mask, noise)
-    U, s, V, n_iter = subspace_iteration(op, engine, V, min_iter, max_iter, convergence_threshold,
-                                         sharder=sharder, verbose=verbose, stop_rule=stop_rule)
+    U, s, V, n_iter = solve_basis(op, engine, V, min_iter, max_iter, convergence_threshold, sharder=sharder,
+                                  verbose=verbose, stop_rule=stop_rule, solver=solver, info=info)
     op.check_mask()
     u = op.gather(U).T.contiguous()                                          # [L, k]  (edit.py:2500-2502)
     if verbose:
         torch.cuda.synchronize()
-        print('power method runtime ==', time.time() - time_s)
+        print('power method runtime ==' if _pick_solver(solver) == "power" else 'block krylov runtime ==', time.time() - time_s)
     return u, s.sqrt(), V, n_iter
 
 
 def local_basis_pair(engine, x, t, at, rank_a: int, mask_a, rank_b: int, mask_b, noise=False, min_iter=10, max_iter=100,
                      convergence_threshold=1e-3, v0_a: Optional[torch.Tensor] = None, v0_b: Optional[torch.Tensor] = None,
-                     sharder: Optional[ProbeSharder] = None, verbose=True, stop_rule: Optional[str] = None):
+                     sharder: Optional[ProbeSharder] = None, verbose=True, stop_rule: Optional[str] = None,
+                     solver: Optional[str] = None, info: Optional[list] = None):
     """The two solves of ``run_edit_null_space_projection`` -- modify space on ``mask_a``, null space on ``mask_b`` (its
     complement), same ``x``, ``t`` (edit.py:2290-2310) -- with their probes in ONE batch per pass.
 
@@ -174,8 +337,14 @@ def local_basis_pair(engine, x, t, at, rank_a: int, mask_a, rank_b: int, mask_b,
     changes is that a pass carries rank_a + rank_b probes, which fills the deep levels of the network better (5 + 5
     probes: 14 % less time per probe than 5).  ``loco_pmp_set_second_mask`` tells the engine from which row of a call the
     second mask applies; once one solve has converged the other continues alone.  Returns
-    ``((u_a, s_a, vT_a, n_iter_a), (u_b, s_b, vT_b, n_iter_b))`` with ``local_basis``'s conventions."""
+    ``((u_a, s_a, vT_a, n_iter_a), (u_b, s_b, vT_b, n_iter_b))`` with ``local_basis``'s conventions.
+
+    ``solver``: ``power`` | ``krylov`` (default ``LOCO_SOLVER``).  With ``krylov`` each solve keeps its own basis, context
+    slot and exits (``_krylov_pair``); ``info`` (a list) receives one dict per solve (``krylov_iteration``'s ``info``)."""
     sharder = sharder or ProbeSharder(None)
+    if _pick_solver(solver) == "krylov":
+        return _krylov_pair(engine, x, t, at, rank_a, mask_a, rank_b, mask_b, noise, max_iter, convergence_threshold,
+                            v0_a, v0_b, sharder, verbose, info)
     n, dev = engine.n, x.device
     rule = stop_rule or default_stop_rule()
     may_stop = [rule == "aligned" or rank_a == 1, rule == "aligned" or rank_b == 1]
@@ -249,4 +418,77 @@ def local_basis_pair(engine, x, t, at, rank_a: int, mask_a, rank_b: int, mask_b,
     if verbose:
         torch.cuda.synchronize()
         print('power method runtime (both solves) ==', time.time() - time_s)
+    return out[0], out[1]
+
+
+def _krylov_pair(engine, x, t, at, rank_a, mask_a, rank_b, mask_b, noise, max_iter, convergence_threshold, v0_a, v0_b,
+                 sharder, verbose, info):
+    """``local_basis_pair`` with the block Krylov solver: the current blocks of both solves share one batch per pass, each
+    solve has its own ``KrylovState`` (context slot 0 and 1) and ends by its own exits; once one has ended the other
+    continues alone.  With probes sharded over ranks the two solves run one after the other instead (each sharded as
+    ``krylov_iteration`` shards it): a rank's rows of a joint batch are not a contiguous share of either solve."""
+    n, dev = engine.n, x.device
+    time_s = time.time()
+    if v0_a is None:
+        v0_a = torch.randn(n, rank_a, device=dev, dtype=torch.float32)          # edit.py:2435, first solve
+    if v0_b is None:
+        v0_b = torch.randn(n, rank_b, device=dev, dtype=torch.float32)          # edit.py:2435, second solve
+    infos = [{}, {}]
+    if sharder.active:
+        out = [local_basis(engine, x, t, at, r, mask=m, noise=noise, max_iter=max_iter, convergence_threshold=convergence_threshold,
+                           v0=v0, sharder=sharder, verbose=verbose, solver="krylov", info=infos[j])
+               for j, (r, m, v0) in enumerate(((rank_a, mask_a, v0_a), (rank_b, mask_b, v0_b)))]
+        if info is not None:
+            info.extend(infos)
+        return out[0], out[1]
+    ranks = (rank_a, rank_b)
+    states = []
+    for j, v0 in enumerate((v0_a, v0_b)):
+        V = v0.to(device=dev, dtype=torch.float32).T.contiguous()
+        engine.qr_rows_(V)
+        states.append(KrylovState(engine, V, engine.n_out, (0, ranks[j]), slot=j))
+    op = JacobianOperator(engine, x, t, at, mask_a, noise)
+    m8_b = mask_b.to(device=dev, dtype=torch.uint8).contiguous().view(-1)
+    mask_state = None
+    active = [True, True]
+    names = ("modify", "null")
+    for i in range(max_iter):
+        idx = [j for j in (0, 1) if active[j]]
+        if not idx:
+            break
+        Vin = torch.cat([states[j].block() for j in idx]) if len(idx) == 2 else states[idx[0]].block()
+        if tuple(idx) != mask_state:                             # only when the set of running solves changes
+            if len(idx) == 2:
+                engine.pmp_set_second_mask(m8_b, rank_a)
+            elif idx[0] == 1:
+                engine.pmp_set_second_mask(m8_b, 0)              # only the null-space solve is still running
+            else:
+                engine.pmp_set_second_mask(None)
+            mask_state = tuple(idx)
+        U = op.jvp(Vin)
+        A = op.vjp(U)
+        off = 0
+        for j in idx:
+            st = states[j]
+            done = st.advance(U[off:off + ranks[j]], A[off:off + ranks[j]], convergence_threshold, last=(i == max_iter - 1))
+            if verbose:
+                print(f'block krylov [{names[j]}] : {i}-th step ({st.m_ritz} rows) convergence : {st.dist}  residual : {st.max_resid}')
+            if done:
+                active[j] = False
+            off += ranks[j]
+    engine.pmp_set_second_mask(None)
+    out = []
+    for j, m in ((0, mask_a), (1, mask_b)):
+        mflat = m.to(dev).reshape(-1)
+        if not bool(mflat.any()):
+            raise ValueError("empty mask: J = d x0_hat[mask] / d x_t has no rows")
+        st = states[j]
+        U, s, V, resid = st.finish(sharder)
+        infos[j].update(residual=[float(r) for r in resid.tolist()], reason=st.reason, rows=st.m_ritz, solver="krylov")
+        out.append((U[:, mflat].T.contiguous(), s.sqrt(), V, st.steps))
+    if info is not None:
+        info.extend(infos)
+    if verbose:
+        torch.cuda.synchronize()
+        print('block krylov runtime (both solves) ==', time.time() - time_s)
     return out[0], out[1]

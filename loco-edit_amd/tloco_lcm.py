@@ -268,8 +268,9 @@ class EditLatentConsistency(EditStableDiffusion):
         V = v0.to(self.device, torch.float32).T.contiguous()
         self.engine.qr_rows_(V)                                                            # :313
         opj = self._operator(zt, for_prompt, t, mask)
-        U, s, V, self.last_n_iter = solver.subspace_iteration(opj, self.engine, V, min_iter, max_iter, convergence_threshold,
-                                                              sharder=self.sharder, verbose=verbose)
+        self.last_solver_info = {}              # solver.solve_basis: which solver ran; the Krylov solver's residuals
+        U, s, V, self.last_n_iter = solver.solve_basis(opj, self.engine, V, min_iter, max_iter, convergence_threshold,
+                                                       sharder=self.sharder, verbose=verbose, info=self.last_solver_info)
         opj.check_mask()
         u = opj.gather(U).T.contiguous()
         return u, s.sqrt(), V

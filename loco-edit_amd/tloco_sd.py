@@ -289,8 +289,9 @@ class EditStableDiffusion(EditDeepFloydIF):
         V = v0.to(self.device, torch.float32).T.contiguous()
         self.engine.qr_rows_(V)                                                            # :859
         opj = self._operator(zt, t, mask, mode)
-        U, s, V, self.last_n_iter = solver.subspace_iteration(opj, self.engine, V, min_iter, max_iter,
-                                                              convergence_threshold, sharder=self.sharder, verbose=verbose)
+        self.last_solver_info = {}              # solver.solve_basis: which solver ran; the Krylov solver's residuals
+        U, s, V, self.last_n_iter = solver.solve_basis(opj, self.engine, V, min_iter, max_iter, convergence_threshold,
+                                                       sharder=self.sharder, verbose=verbose, info=self.last_solver_info)
         opj.check_mask()
         u = opj.gather(U).T.contiguous()
         return u, s.sqrt(), V
@@ -371,17 +372,20 @@ class EditStableDiffusion(EditDeepFloydIF):
             vT_null = self._load(paths["vn"], map_location=self.device).to(self.device).type(self.dtype)
         else:
             print('subspace solve: CFG-combined Jacobian')
+            self.last_solver_info = None            # modify_fn may take its direction from a gradient: no solve, no residuals
             u_modify, vT_modify = modify_fn()
             if self.sharder.is_main:
                 if u_modify is not None:
                     torch.save(u_modify, paths["um"])
                 torch.save(vT_modify, paths["vm"])
+                solver.write_residuals(paths["vm"], self.last_solver_info)
             if null_space_projection:
                 u_null, s_null, vT_null = self.local_encoder_decoder_pullback_zt(
                     zt, t, t_idx, F, E, N, op=op, block_idx=block_idx, pca_rank=pca_rank_null, chunk_size=5, min_iter=10,
                     max_iter=50, convergence_threshold=1e-3, mask=~mask, mode="null+(for-null)")
                 if self.sharder.is_main:
                     torch.save(u_null, paths["un"]); torch.save(vT_null, paths["vn"])
+                    solver.write_residuals(paths["vn"], self.last_solver_info)
         return self.engine.null_project(vT_modify.contiguous(),
                                         vT_null[:pca_rank_null, :].contiguous() if null_space_projection else None)
 
