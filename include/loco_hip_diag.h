@@ -84,6 +84,52 @@ typedef struct loco_conv_desc {
 } loco_conv_desc;
 int  loco_debug_conv(loco_ctx* ctx, const loco_conv_desc* desc, char* plan, int64_t cap, void* stream);
 
+/* Test hook: ONE pass of ONE attention stage on caller-supplied tensors, through the functions the engine's passes call
+ * (attn_forward / attn_tangent / attn_cotangent, xa_forward / xa_linear), route selection included
+ * (tests/test_gpu_attn_oracle.py compares it with a float64 reference, tests/attn_oracle.py).
+ *
+ * Every operand is a DEVICE pointer to contiguous fp32 in the engine's [channel][token] layout; C = NH * CH, head h owns the
+ * channels h CH ... h CH + CH - 1.  Samples / probes are dense ([B][...]).
+ *
+ * kind 0, the self-attention core:  P = softmax_j(scale q^T [K_text | k]),  o = [V_text | v] P^T,  scale = CH^-1/2.
+ *   Lt = 0: no text keys.  Lt > 0 (a multiple of 64): kt, vt [C][Lt], L <= Lt real columns, the rest zero and masked out of the
+ *   softmax; a score row is [Lt text columns | T image columns], Tk = Lt + T.
+ *   pair = 1: the AttentionBlock form (the tangent may K-concatenate its two product pairs); 0: the transformer form.
+ *   pass 0 forward:    reads q, k, v [B][C][T] (kt, vt); writes P [B][NH][T][Tk] and o [B][C][T].
+ *   pass 1 tangent:    reads the primal q, k, v [C][T], P [NH][T][Tk], o [C][T] (B = 1) and dq, dk, dv [B][C][T]; writes out = do [B][C][T].
+ *   pass 2 cotangent:  reads the primal q, k, v, P, o and go [B][C][T]; writes gq, gk, gv [B][C][T].
+ *   no_workspace = 1 withholds the record workspace of the flash kernels: they then take the kernels that convert their operands
+ *   themselves, as the product does when its workspace is too small.
+ * kind 1, the text cross-attention:  P = softmax_l(scale q^T K_ctx),  o = V_ctx P^T  over L real context rows,
+ *   Lp = 64 ceil(L / 64) padded ones: kt = K_ctx, vt = V_ctx [C][Lp], zero beyond L; k, v, Lt, pair are ignored.
+ *   pass 0: reads q [B][C][T]; writes P [B][NH][T][Lp] (padding columns zero) and o [B][C][T].
+ *   pass 1: reads P (B = 1) and dq [B][C][T]; writes out = do.      pass 2: reads P and go [B][C][T]; writes gq.
+ *
+ * P and o of the linear passes come from the caller, so each pass is one unit under test.  Scratch (per-probe score matrices, the
+ * flash cotangent's delta, the record workspace, the column mask built from L) is this call's, allocated and freed per call.
+ *
+ * Refused with an error before any launch: T not a multiple of 64, Lt not a multiple of 64, L > Lt, CH < 1, NH or B < 1, a null
+ * required operand.
+ *
+ * route (cap bytes, may be null) receives one line per launch, in launch order:
+ *   "kernel=<name>\n"  for attn_split, flash_dma_tan|cotq|cotk, flash_tan|cotq|cotk, softmax_rows, softmax_jac, xattn_fused_fwd|lin
+ *   "kernel=<name> M=m N=n K=k batch=b heads=h kcat=0|1\n"  for gemm_rec, gemm_bf16x3, gemm_f32
+ * Returns 0; < 0 on errors. */
+typedef struct loco_attn_desc {
+    int32_t struct_size;
+    int32_t kind, pass;
+    int32_t T, NH, CH, B;
+    int32_t Lt, L, pair, no_workspace;
+    const float *q, *k, *v;
+    const float *kt, *vt;
+    float *P, *o;                                               /* written by pass 0, read by passes 1 and 2 */
+    const float *dq, *dk, *dv;
+    float* out;
+    const float* go;
+    float *gq, *gk, *gv;
+} loco_attn_desc;
+int  loco_debug_attn(loco_ctx* ctx, const loco_attn_desc* desc, char* route, int64_t cap, void* stream);
+
 /* Debug / test hook: copy an internal primal activation ("down.0.block.0" ...)
  * of the last forward/primal call into dst (device), returns element count or <0. */
 int64_t loco_debug_tensor(loco_ctx* ctx, const char* name, float* dst, int64_t cap, void* stream);

@@ -764,9 +764,12 @@ static void attn_flash_launch_n(int mode, const AttnFlashArgs& a, hipStream_t st
 }
 
 // ---- the DMA-fed kernels: workspace layout, the split pass, the launches -------------------------------------------------
-static int flash_dma_on() {          // LOCO_FLASH_DMA=0: the kernels that convert their operands themselves (A/B switch; read per launch)
+bool attn_flash_dma_enabled() {      // LOCO_FLASH_DMA=0: the kernels that convert their operands themselves (A/B switch; read per launch)
     const char* e = getenv("LOCO_FLASH_DMA");
-    return e ? atoi(e) : 1;
+    return e ? atoi(e) != 0 : true;
+}
+static bool flash_dma(const AttnFlashArgs& a) {
+    return attn_flash_dma_route(a.ws, a.ws_bytes, attn_flash_ws_bytes(a), attn_flash_dma_enabled());
 }
 static void flash_shape(int CH, bool txt, int& nck, int& nct) {
     if (txt) { nck = 4; nct = 2; }
@@ -862,7 +865,7 @@ static void attn_flash_dma_n(int mode, const AttnFlashArgs& a, hipStream_t st) {
 }
 
 static void attn_flash_launch(int mode, const AttnFlashArgs& a, hipStream_t st) {
-    if (a.ws && flash_dma_on() && attn_flash_ws_bytes(a) <= a.ws_bytes && (mode == M_TAN || mode == M_COTQ)) {
+    if (flash_dma(a) && (mode == M_TAN || mode == M_COTQ)) {
         if (a.Lt > 0) attn_flash_dma_n<4, 2, true>(mode, a, st);
         else if (a.CH <= 48) attn_flash_dma_n<3, 2>(mode, a, st);
         else if (a.CH <= 64) attn_flash_dma_n<4, 2>(mode, a, st);
@@ -879,7 +882,7 @@ static void attn_flash_launch(int mode, const AttnFlashArgs& a, hipStream_t st) 
 
 void launch_attn_flash_tangent(const AttnFlashArgs& a, hipStream_t st) { attn_flash_launch(M_TAN, a, st); }
 void launch_attn_flash_cotangent(const AttnFlashArgs& a, hipStream_t st) {
-    if (a.ws && flash_dma_on() && attn_flash_ws_bytes(a) <= a.ws_bytes) { attn_flash_launch(M_COTQ, a, st); return; }    // (the pair)
+    if (flash_dma(a)) { attn_flash_launch(M_COTQ, a, st); return; }    // (the pair)
     attn_flash_launch(M_COTQ, a, st);      // g_q and delta_i (read by the second kernel: the kernel boundary orders them)
     attn_flash_launch(M_COTK, a, st);      // g_k, g_v
 }

@@ -142,6 +142,7 @@ struct loco_ctx {
     const float* bench_out = nullptr; int64_t bench_out_count = 0;      // diag: output tensor of the last loco_bench_conv
 #ifdef LOCO_DIAG
     std::string* plan_log = nullptr;                                    // diag: run_conv appends the text of every plan it executes (loco_debug_conv)
+    std::string* attn_log = nullptr;                                    // diag: the attention stages append one line per launch (loco_debug_attn)
 #endif
     float *tact = nullptr, *tproj = nullptr;
     float* eps_buf = nullptr;      // [max_batch][n]
@@ -613,12 +614,33 @@ inline unsigned char* gemm_ws_get(loco_ctx* c, size_t need, hipStream_t st) {
     c->gemm_ws[l] = static_cast<unsigned char*>(p); c->gemm_ws_bytes[l] = need; c->bytes += need;
     return c->gemm_ws[l];
 }
+// diag (loco_debug_attn): one line per launch of an attention stage, the counterpart of run_conv's plan_log
+inline void attn_note(loco_ctx* c, const char* kernel, const GemmArgs* g = nullptr) {
+#ifdef LOCO_DIAG
+    if (!c->attn_log) return;
+    char line[192];
+    if (g) snprintf(line, sizeof(line), "kernel=%s M=%d N=%d K=%d batch=%d heads=%d kcat=%d\n", kernel, g->M, g->N, g->K, g->batch,
+                    g->batch2 > 0 ? g->batch2 : 1, g->A2 ? 1 : 0);
+    else snprintf(line, sizeof(line), "kernel=%s\n", kernel);
+    *c->attn_log += line;
+#else
+    (void)c; (void)kernel; (void)g;
+#endif
+}
 inline bool attn_gemm_rec(const loco_ctx* c, const GemmArgs& g) { return c->prec >= 1 && c->gemm_lowp && gemm_rec_eligible(g); }
+inline void attn_gemm_f32(loco_ctx* c, const GemmArgs& g, hipStream_t st) { attn_note(c, "gemm_f32", &g); launch_gemm(g, st); }
 inline void attn_gemm(loco_ctx* c, const GemmArgs& g, hipStream_t st) {
     if (attn_gemm_rec(c, g)) {        // both operands pre-split into records, LDS-DMA fed (gemm_rec.hip)
-        if (unsigned char* ws = gemm_ws_get(c, gemm_rec_ws_bytes(g), st)) { launch_gemm_rec(g, ws, st); return; }
+        if (unsigned char* ws = gemm_ws_get(c, gemm_rec_ws_bytes(g), st)) { attn_note(c, "gemm_rec", &g); launch_gemm_rec(g, ws, st); return; }
     }
-    if (c->prec >= 1 && c->gemm_lowp && gemm_prefers_bf16x3(g)) launch_gemm_bf16x3(g, st); else launch_gemm(g, st);
+    if (c->prec >= 1 && c->gemm_lowp && gemm_prefers_bf16x3(g)) { attn_note(c, "gemm_bf16x3", &g); launch_gemm_bf16x3(g, st); }
+    else attn_gemm_f32(c, g, st);
+}
+inline void attn_softmax_rows(loco_ctx* c, float* S, long rows, int T, hipStream_t st, int B, long bs) {
+    attn_note(c, "softmax_rows"); launch_softmax_rows(S, rows, T, st, B, bs);
+}
+inline void attn_softmax_jac(loco_ctx* c, float* dS, const float* P, long rows, int T, float scale, hipStream_t st, int B, long bs) {
+    attn_note(c, "softmax_jac"); launch_softmax_jac(dS, P, rows, T, rows, scale, st, B, bs);
 }
 
 void conv_defaults(ConvArgs& a) {
@@ -833,15 +855,20 @@ void gn_forward_stats(const Pass& p, const NormP& n, const float* x, long xbs, i
 // out = xmid + proj(o),  o = V_ctx P^T,  P = softmax_l(scale q^T K_ctx),  q = Wq GN(xmid); K_ctx / V_ctx [C][Lp] are the
 // projected encoder states (loco_set_context), constant with respect to the image, so the tangent / cotangent only
 // travel through q.  Generic GEMM + row kernels: the score rows are only Lp (<= 128) long.
-struct XA {                     // tensors of one pass: `a` = the arena holding this pass's values, `ap` = the primal arena
-    loco_ctx* c; const Op* op; hipStream_t st; int B; int C, T, NH, CH, Lp;
+struct XA {                     // shape and constants of one stage; the tensors of a pass are arguments of xa_forward / xa_linear
+    loco_ctx* c; hipStream_t st; int B; int C, T, NH, CH, L, Lp;       // L real context rows of the Lp padded ones
     float scale;
+    const float *xK, *xV;       // K_ctx, V_ctx [C][Lp]
+    const float* colbias;       // [Lp]: 0 / -1e30, the key padding of the forward scores
+    long xs, ss;                // sample stride of the [C][T] tensors (q, o, their tangents / cotangents) and of the score matrices
 };
 XA xa_of(loco_ctx* c, const Op& op, int B, hipStream_t st) {
-    XA x; x.c = c; x.op = &op; x.st = st; x.B = B;
+    XA x; x.c = c; x.st = st; x.B = B;
     const Tens& t = c->tens[op.in];
-    x.C = t.C; x.T = t.H * t.W; x.NH = op.heads; x.CH = x.C / x.NH; x.Lp = c->prog->ctx_Lp;
+    x.C = t.C; x.T = t.H * t.W; x.NH = op.heads; x.CH = x.C / x.NH; x.L = c->cfg.context_len; x.Lp = c->prog->ctx_Lp;
     x.scale = 1.0f / std::sqrt((float)x.CH);
+    x.xK = op.xK; x.xV = op.xV; x.colbias = c->ctx_colbias;
+    x.xs = x.ss = c->prog->per_sample;
     return x;
 }
 // S[b][h][i][l] = alpha * sum_c X[b][h*CH+c][i] K[h*CH+c][l]      (X: q / dq / g_o, K: K_ctx or V_ctx)
@@ -851,8 +878,8 @@ void xa_scores(const XA& x, const float* X, long x_bs, const float* K, float* S,
     g.Bm = K; g.sbk = x.Lp; g.sbn = 1; g.sbb = 0; g.sbh = (long)x.CH * x.Lp;
     g.C = S; g.scm = x.Lp; g.scn = 1; g.scb = s_bs; g.sch = (long)x.T * x.Lp;
     g.M = x.T; g.N = x.Lp; g.K = x.CH; g.batch = x.B; g.batch2 = x.NH; g.alpha = alpha; g.beta = 0.f;
-    g.colbias = mask ? x.c->ctx_colbias : nullptr;
-    launch_gemm(g, x.st);
+    g.colbias = mask ? x.colbias : nullptr;
+    attn_gemm_f32(x.c, g, x.st);
 }
 // O[b][h*CH+c][i] = sum_l K[h*CH+c][l] S[b][h][i][l]              (K: V_ctx or K_ctx, S: P / dP / g_S)
 void xa_values(const XA& x, const float* K, const float* S, long s_bs, float* O, long o_bs) {
@@ -861,7 +888,7 @@ void xa_values(const XA& x, const float* K, const float* S, long s_bs, float* O,
     g.Bm = S; g.sbk = 1; g.sbn = x.Lp; g.sbb = s_bs; g.sbh = (long)x.T * x.Lp;
     g.C = O; g.scm = x.T; g.scn = 1; g.scb = o_bs; g.sch = (long)x.CH * x.T;
     g.M = x.CH; g.N = x.T; g.K = x.Lp; g.batch = x.B; g.batch2 = x.NH; g.alpha = 1.f; g.beta = 0.f;
-    launch_gemm(g, x.st);
+    attn_gemm_f32(x.c, g, x.st);
 }
 // the three steps of one pass (scores, row operation, values) as one kernel where the shape allows (LOCO_FUSE_XATTN=0: off)
 //   kind 0 forward: P = softmax(scale X^T K1) -> Pout (per sample), O = K2 P^T
@@ -869,29 +896,28 @@ void xa_values(const XA& x, const float* K, const float* S, long s_bs, float* O,
 bool xa_fused(const XA& x, int kind, const float* X, long x_bs, const float* K1, const float* K2, float* P, long p_bs,
               float* O, long o_bs) {
     loco_ctx* c = x.c;
-    if (!c->fuse_xattn || !xattn_fused_supported(x.T, x.CH, c->cfg.context_len, x.Lp)) return false;
+    if (!c->fuse_xattn || !xattn_fused_supported(x.T, x.CH, x.L, x.Lp)) return false;
     XAttnArgs a; std::memset(&a, 0, sizeof(a));
-    a.T = x.T; a.NH = x.NH; a.B = x.B; a.CH = x.CH; a.L = c->cfg.context_len; a.Lp = x.Lp; a.fwd = kind == 0;
+    a.T = x.T; a.NH = x.NH; a.B = x.B; a.CH = x.CH; a.L = x.L; a.Lp = x.Lp; a.fwd = kind == 0;
     a.alpha = x.scale; a.X = X; a.x_bs = x_bs; a.K1 = K1; a.K2 = K2; a.P = P; a.p_bs = p_bs; a.O = O; a.o_bs = o_bs;
+    attn_note(c, kind == 0 ? "xattn_fused_fwd" : "xattn_fused_lin");
     launch_xattn_fused(a, x.st);
     return true;
 }
 // the row step of one pass, fused where the shape allows: P = softmax(scale Xq^T K_ctx) per sample, O = V_ctx P^T
-void xa_forward(const XA& x, const float* Xq, float* P, float* O, long bs) {
-    const Op& op = *x.op;
-    if (xa_fused(x, 0, Xq, bs, op.xK, op.xV, P, bs, O, bs)) return;
-    xa_scores(x, Xq, bs, op.xK, P, bs, x.scale, true);
-    launch_softmax_rows(P, (long)x.NH * x.T, x.Lp, x.st, x.B, bs);
-    xa_values(x, op.xV, P, bs, O, bs);
+void xa_forward(const XA& x, const float* Xq, float* P, float* O) {
+    if (xa_fused(x, 0, Xq, x.xs, x.xK, x.xV, P, x.ss, O, x.xs)) return;
+    xa_scores(x, Xq, x.xs, x.xK, P, x.ss, x.scale, true);
+    attn_softmax_rows(x.c, P, (long)x.NH * x.T, x.Lp, x.st, x.B, x.ss);
+    xa_values(x, x.xV, P, x.ss, O, x.xs);
 }
 // ... and of the two linear passes, per probe through the softmax Jacobian at the primal P (B = 1), S = this pass's scores:
 // tangent X = dq, K1 = K_ctx, K2 = V_ctx -> O = do;  cotangent X = g_o, K1 = V_ctx, K2 = K_ctx -> O = g_q
 void xa_linear(const XA& x, const float* X, const float* K1, const float* K2, float* P, float* S, float* O) {
-    const long PS = x.c->prog->per_sample;
-    if (xa_fused(x, 1, X, PS, K1, K2, P, 0, O, PS)) return;
-    xa_scores(x, X, PS, K1, S, PS, 1.f, false);
-    launch_softmax_jac(S, P, (long)x.NH * x.T, x.Lp, (long)x.NH * x.T, x.scale, x.st, x.B, PS);
-    xa_values(x, K2, S, PS, O, PS);
+    if (xa_fused(x, 1, X, x.xs, K1, K2, P, 0, O, x.xs)) return;
+    xa_scores(x, X, x.xs, K1, S, x.ss, 1.f, false);
+    attn_softmax_jac(x.c, S, P, (long)x.NH * x.T, x.Lp, x.scale, x.st, x.B, x.ss);
+    xa_values(x, K2, S, x.ss, O, x.xs);
 }
 
 // ------------------------------ multi-head self-attention core ------------------------------
@@ -902,24 +928,43 @@ void xa_linear(const XA& x, const float* X, const float* K1, const float* K2, fl
 // K_text / V_text [C][Lt] are constants of the prompt (loco_set_context), so tangents / cotangents reach them through q only.
 // Strided products on column ranges of one score matrix S [NH][T][Tk] per sample, the text columns first.
 struct Attn {
-    loco_ctx* c; const Op* op; hipStream_t st;
+    loco_ctx* c; hipStream_t st;
     int B, T, NH, CH, Lt, Tk;       // Lt text key columns (0: none) ahead of the T image ones, Tk = Lt + T
-    long HS, SS, OS, KS;            // head strides: q / k / v inside op.qkv, S, o, K_text / V_text
+    long HS, SS, OS, KS;            // head strides: q / k / v (inside op.qkv in the engine), S, o, K_text / V_text
     float scale;
     bool pair;                      // the tangent may K-concatenate its two product pairs (attn_tangent)
-    float* at(float* arena, int id) const { return arena + c->tens[id].off; }
+    // the primal (B = 1) q, k, v, P = softmax, o -- read by the tangent and the cotangent
+    const float *q, *k, *v, *P, *o;
+    // this pass's tensors, B samples / probes: the forward's q, k, v -> S (scores, then P), o; the tangent's dq, dk, dv -> do with
+    // the scratch dS; the cotangent's g_o -> g_q, g_k, g_v with the scratch g_S.  Sample strides: bq (q-like), bS (scores), bo (o-like)
+    float *tq, *tk, *tv, *tS, *to;
+    long bq, bS, bo;
+    const float *kt, *vt;           // K_text, V_text [NH][CH][Lt] (Lt > 0)
+    const float* colbias;           // [Lt]: 0 / -1e30, the key padding of the forward text scores
+    float* delta;                   // scratch [B][NH][T] of the flash cotangent
+    unsigned char* ws; size_t ws_bytes;      // record workspace of the flash kernels (nullptr / too small: the converting kernels)
     // the tangent / cotangent kernels of attn_flash.hip take this shape (no [T x Tk] matrix per probe)
     bool flash() const {
         return c->flash_attn && c->prec >= 1 && (Lt ? attn_flash_text_supported(T, CH, Lt) : attn_flash_supported(T, CH));
     }
 };
-Attn attn_of(loco_ctx* c, const Op& op, int B, hipStream_t st) {
-    Attn s; s.c = c; s.op = &op; s.st = st; s.B = B;
+// `arena` holds this pass's tensors, `bs` apart per sample: the forward's own arena, else (nullptr) the tangent / cotangent arena
+Attn attn_of(loco_ctx* c, const Op& op, int B, hipStream_t st, float* arena = nullptr, long bs = 0) {
+    Attn s; s.c = c; s.st = st; s.B = B;
     const Tens& t = c->tens[op.in];
     s.T = t.H * t.W; s.NH = op.heads; s.CH = t.C / op.heads; s.Lt = op.added_kv ? c->prog->ctx_Lp : 0; s.Tk = s.Lt + s.T;
     s.HS = 3L * s.CH * s.T; s.SS = (long)s.T * s.Tk; s.OS = (long)s.CH * s.T; s.KS = (long)s.CH * s.Lt;
     s.scale = 1.0f / std::sqrt((float)s.CH);
     s.pair = op.kind == OP_ATTN && !op.added_kv;
+    if (!arena) { arena = c->arenaT; bs = c->prog->per_sample; }
+    s.q = c->arenaP + c->tens[op.qkv].off; s.k = s.q + s.OS; s.v = s.k + s.OS;
+    s.P = c->arenaP + c->tens[op.S].off; s.o = c->arenaP + c->tens[op.o].off;
+    s.tq = arena + c->tens[op.qkv].off; s.tk = s.tq + s.OS; s.tv = s.tk + s.OS;
+    s.tS = arena + c->tens[op.S].off; s.to = arena + c->tens[op.o].off;
+    s.bq = s.bS = s.bo = bs;
+    s.kt = s.Lt ? op.xK : nullptr; s.vt = s.Lt ? op.xV : nullptr; s.colbias = c->ctx_colbias;
+    s.delta = c->attn_delta;
+    s.ws = reinterpret_cast<unsigned char*>(c->partial); s.ws_bytes = c->partial_floats * sizeof(float);
     return s;
 }
 // The three products.  `text`: over the Lt text columns of S, against K_text / V_text ([CH][Lt] per head, KS apart) -- these go
@@ -936,7 +981,7 @@ GemmArgs attn_scores(const Attn& s, bool text, const float* X, long xb, long xh,
     g.Bm = K; g.sbk = n; g.sbn = 1; g.sbb = kb; g.sbh = text ? s.KS : s.HS;
     g.C = S + (text ? 0 : s.Lt); g.scm = s.Tk; g.scn = 1; g.scb = sb; g.sch = s.SS;
     g.M = s.T; g.N = n; g.K = s.CH; g.batch = s.B; g.batch2 = s.NH; g.alpha = alpha; g.beta = beta;
-    g.colbias = mask ? s.c->ctx_colbias : nullptr;            // key padding of the prompt: forward text scores only
+    g.colbias = mask ? s.colbias : nullptr;                   // key padding of the prompt: forward text scores only
     g.A2 = X2; g.sab2 = xb2; g.Bm2 = K2; g.sbb2 = kb2;
     return g;
 }
@@ -964,35 +1009,43 @@ GemmArgs attn_keys(const Attn& s, const float* X, long xb, long xh, const float*
 // what the flash tangent and cotangent share: the shape, the primal q / k / v / P / o and the text keys / values; the caller
 // adds its per-probe tensors
 AttnFlashArgs attn_flash_args(const Attn& s) {
-    loco_ctx* c = s.c; const Op& op = *s.op;
     AttnFlashArgs fa; std::memset(&fa, 0, sizeof(fa));
-    fa.ws = reinterpret_cast<unsigned char*>(c->partial); fa.ws_bytes = c->partial_floats * sizeof(float);      // (records of the operands: attn_flash.hip)
+    fa.ws = s.ws; fa.ws_bytes = s.ws_bytes;      // (records of the operands: attn_flash.hip)
     fa.T = s.T; fa.NH = s.NH; fa.B = s.B; fa.CH = s.CH; fa.scale = s.scale;
-    fa.q = s.at(c->arenaP, op.qkv); fa.k = fa.q + s.OS; fa.v = fa.k + s.OS; fa.hs = s.HS;
-    fa.P = s.at(c->arenaP, op.S); fa.o = s.at(c->arenaP, op.o);
-    if (s.Lt) { fa.Lt = s.Lt; fa.kt = op.xK; fa.vt = op.xV; }
+    fa.q = s.q; fa.k = s.k; fa.v = s.v; fa.hs = s.HS;
+    fa.P = s.P; fa.o = s.o;
+    if (s.Lt) { fa.Lt = s.Lt; fa.kt = s.kt; fa.vt = s.vt; }
     return fa;
 }
-void attn_forward(const Attn& s, float* arena, long bs) {      // q, k, v in arena(qkv) -> P in arena(S), o in arena(o)
-    loco_ctx* c = s.c; const Op& op = *s.op;
-    float* q = s.at(arena, op.qkv); float* k = q + s.OS; float* v = k + s.OS;
-    float* S = s.at(arena, op.S); float* o = s.at(arena, op.o);
-    if (s.Lt) launch_gemm(attn_scores(s, TEXT, q, bs, s.HS, op.xK, 0, S, bs, s.scale, 0.f, true), s.st);
-    attn_gemm(c, attn_scores(s, IMAGE, q, bs, s.HS, k, bs, S, bs, s.scale, 0.f), s.st);
-    launch_softmax_rows(S, (long)s.NH * s.T, s.Tk, s.st, s.B, bs);
-    attn_gemm(c, attn_values(s, IMAGE, v, bs, S, bs, o, bs, s.OS, 0.f), s.st);
-    if (s.Lt) launch_gemm(attn_values(s, TEXT, op.xV, 0, S, bs, o, bs, s.OS, 1.f), s.st);
+// diag: the kernels a flash launch takes, by the launchers' own predicate (attn_flash_dma_route)
+inline void attn_note_flash(loco_ctx* c, const AttnFlashArgs& fa, bool tan) {
+#ifdef LOCO_DIAG
+    if (!c->attn_log) return;
+    const bool dma = attn_flash_dma_route(fa.ws, fa.ws_bytes, attn_flash_ws_bytes(fa), attn_flash_dma_enabled());
+    if (dma) attn_note(c, "attn_split");
+    if (tan) attn_note(c, dma ? "flash_dma_tan" : "flash_tan");
+    else { attn_note(c, dma ? "flash_dma_cotq" : "flash_cotq"); attn_note(c, dma ? "flash_dma_cotk" : "flash_cotk"); }
+#else
+    (void)c; (void)fa; (void)tan;
+#endif
 }
-void attn_tangent(const Attn& s) {      // dq, dk, dv in arenaT(qkv) -> do in arenaT(o); primal in arenaP (B = 1)
-    loco_ctx* c = s.c; const Op& op = *s.op;
-    const long PS = c->prog->per_sample;
-    float* q = s.at(c->arenaP, op.qkv); float* k = q + s.OS; float* v = k + s.OS;
-    float* dq = s.at(c->arenaT, op.qkv); float* dk = dq + s.OS; float* dv = dk + s.OS;
-    float* SP = s.at(c->arenaP, op.S); float* ST = s.at(c->arenaT, op.S);
-    float* oT = s.at(c->arenaT, op.o);
+void attn_forward(const Attn& s) {      // q, k, v (s.tq, s.tk, s.tv) -> P in s.tS, o in s.to
+    loco_ctx* c = s.c;
+    float *q = s.tq, *k = s.tk, *v = s.tv, *S = s.tS, *o = s.to;
+    if (s.Lt) attn_gemm_f32(c, attn_scores(s, TEXT, q, s.bq, s.HS, s.kt, 0, S, s.bS, s.scale, 0.f, true), s.st);
+    attn_gemm(c, attn_scores(s, IMAGE, q, s.bq, s.HS, k, s.bq, S, s.bS, s.scale, 0.f), s.st);
+    attn_softmax_rows(c, S, (long)s.NH * s.T, s.Tk, s.st, s.B, s.bS);
+    attn_gemm(c, attn_values(s, IMAGE, v, s.bq, S, s.bS, o, s.bo, s.OS, 0.f), s.st);
+    if (s.Lt) attn_gemm_f32(c, attn_values(s, TEXT, s.vt, 0, S, s.bS, o, s.bo, s.OS, 1.f), s.st);
+}
+void attn_tangent(const Attn& s) {      // dq, dk, dv (s.tq, s.tk, s.tv) -> do in s.to; the primal q, k, v, P, o: B = 1
+    loco_ctx* c = s.c;
+    const float *q = s.q, *k = s.k, *v = s.v, *SP = s.P;
+    float *dq = s.tq, *dk = s.tk, *dv = s.tv, *ST = s.tS, *oT = s.to;
     if (s.flash()) {        // do from dq, dk, dv and the primal P / o in one kernel
         AttnFlashArgs fa = attn_flash_args(s);
-        fa.dq = dq; fa.dk = dk; fa.dv = dv; fa.bs_d = PS; fa.out = oT; fa.bs_out = PS;
+        fa.dq = dq; fa.dk = dk; fa.dv = dv; fa.bs_d = s.bq; fa.out = oT; fa.bs_out = s.bo;
+        attn_note_flash(c, fa, true);
         launch_attn_flash_tangent(fa, s.st);
         return;
     }
@@ -1002,42 +1055,40 @@ void attn_tangent(const Attn& s) {      // dq, dk, dv in arenaT(qkv) -> do in ar
     // -- and where the record GEMM takes the product (the decoder's 4096-token head): one write of dS instead of a write
     // and a read-modify-write (500 vs 276 + 586 us, tests/diag/gemm_rec_bench.hip)
     // The AttentionBlock without text keys only (s.pair): the others always issue two launches.
-    const GemmArgs dS2 = attn_scores(s, IMAGE, dq, PS, s.HS, k, 0, ST, PS, 1.f, 0.f, false, q, 0, dk, PS);
+    const GemmArgs dS2 = attn_scores(s, IMAGE, dq, s.bq, s.HS, k, 0, ST, s.bS, 1.f, 0.f, false, q, 0, dk, s.bq);
     const bool kcat = s.pair && (s.T <= 256 || attn_gemm_rec(c, dS2));
-    if (s.Lt) launch_gemm(attn_scores(s, TEXT, dq, PS, s.HS, op.xK, 0, ST, PS, 1.f, 0.f), s.st);        // dS_text = dq^T K_text
+    if (s.Lt) attn_gemm_f32(c, attn_scores(s, TEXT, dq, s.bq, s.HS, s.kt, 0, ST, s.bS, 1.f, 0.f), s.st);      // dS_text = dq^T K_text
     if (kcat) attn_gemm(c, dS2, s.st);                                                                  // dS = dq^T k + q^T dk
     else {
-        attn_gemm(c, attn_scores(s, IMAGE, dq, PS, s.HS, k, 0, ST, PS, 1.f, 0.f), s.st);                // dS_img = dq^T k
-        attn_gemm(c, attn_scores(s, IMAGE, q, 0, s.HS, dk, PS, ST, PS, 1.f, 1.f), s.st);                //        + q^T dk
+        attn_gemm(c, attn_scores(s, IMAGE, dq, s.bq, s.HS, k, 0, ST, s.bS, 1.f, 0.f), s.st);            // dS_img = dq^T k
+        attn_gemm(c, attn_scores(s, IMAGE, q, 0, s.HS, dk, s.bq, ST, s.bS, 1.f, 1.f), s.st);            //        + q^T dk
     }
-    launch_softmax_jac(ST, SP, (long)s.NH * s.T, s.Tk, (long)s.NH * s.T, s.scale, s.st, s.B, PS);
-    if (kcat) attn_gemm(c, attn_values(s, IMAGE, dv, PS, SP, 0, oT, PS, s.OS, 0.f, v, 0, ST, PS), s.st);   // do = dv P^T + v dP^T
+    attn_softmax_jac(c, ST, SP, (long)s.NH * s.T, s.Tk, s.scale, s.st, s.B, s.bS);
+    if (kcat) attn_gemm(c, attn_values(s, IMAGE, dv, s.bq, SP, 0, oT, s.bo, s.OS, 0.f, v, 0, ST, s.bS), s.st);   // do = dv P^T + v dP^T
     else {
-        attn_gemm(c, attn_values(s, IMAGE, dv, PS, SP, 0, oT, PS, s.OS, 0.f), s.st);                    // do = dv P_img^T
-        attn_gemm(c, attn_values(s, IMAGE, v, 0, ST, PS, oT, PS, s.OS, 1.f), s.st);                     //    + v dP_img^T
+        attn_gemm(c, attn_values(s, IMAGE, dv, s.bq, SP, 0, oT, s.bo, s.OS, 0.f), s.st);                // do = dv P_img^T
+        attn_gemm(c, attn_values(s, IMAGE, v, 0, ST, s.bS, oT, s.bo, s.OS, 1.f), s.st);                 //    + v dP_img^T
     }
-    if (s.Lt) launch_gemm(attn_values(s, TEXT, op.xV, 0, ST, PS, oT, PS, s.OS, 1.f), s.st);             //    + V_text dP_text^T
+    if (s.Lt) attn_gemm_f32(c, attn_values(s, TEXT, s.vt, 0, ST, s.bS, oT, s.bo, s.OS, 1.f), s.st);     //    + V_text dP_text^T
 }
-void attn_cotangent(const Attn& s) {    // g_o in arenaT(o) -> g_q, g_k, g_v in arenaT(qkv)
-    loco_ctx* c = s.c; const Op& op = *s.op;
-    const long PS = c->prog->per_sample;
-    float* q = s.at(c->arenaP, op.qkv); float* k = q + s.OS; float* v = k + s.OS;
-    float* gq = s.at(c->arenaT, op.qkv); float* gk = gq + s.OS; float* gv = gk + s.OS;
-    float* SP = s.at(c->arenaP, op.S); float* SG = s.at(c->arenaT, op.S);
-    float* oG = s.at(c->arenaT, op.o);
+void attn_cotangent(const Attn& s) {    // g_o in s.to -> g_q, g_k, g_v in s.tq, s.tk, s.tv
+    loco_ctx* c = s.c;
+    const float *q = s.q, *k = s.k, *v = s.v, *SP = s.P;
+    float *gq = s.tq, *gk = s.tk, *gv = s.tv, *SG = s.tS, *oG = s.to;
     if (s.flash()) {        // g_q, g_k, g_v from g_o and the primal q / k / v / P / o
         AttnFlashArgs fa = attn_flash_args(s);
-        fa.go = oG; fa.bs_go = PS; fa.gq = gq; fa.gk = gk; fa.gv = gv; fa.bs_g = PS; fa.delta = c->attn_delta;
+        fa.go = oG; fa.bs_go = s.bo; fa.gq = gq; fa.gk = gk; fa.gv = gv; fa.bs_g = s.bq; fa.delta = s.delta;
+        attn_note_flash(c, fa, false);
         launch_attn_flash_cotangent(fa, s.st);
         return;
     }
-    attn_gemm(c, attn_keys(s, oG, PS, s.OS, SP, 0, gv, PS), s.st);                                      // g_v = g_o P_img
-    if (s.Lt) launch_gemm(attn_scores(s, TEXT, oG, PS, s.OS, op.xV, 0, SG, PS, 1.f, 0.f), s.st);        // g_P_text = g_o^T V_text
-    attn_gemm(c, attn_scores(s, IMAGE, oG, PS, s.OS, v, 0, SG, PS, 1.f, 0.f), s.st);                    // g_P_img = g_o^T v
-    launch_softmax_jac(SG, SP, (long)s.NH * s.T, s.Tk, (long)s.NH * s.T, s.scale, s.st, s.B, PS);
-    attn_gemm(c, attn_values(s, IMAGE, k, 0, SG, PS, gq, PS, s.HS, 0.f), s.st);                         // g_q = k g_S_img^T
-    if (s.Lt) launch_gemm(attn_values(s, TEXT, op.xK, 0, SG, PS, gq, PS, s.HS, 1.f), s.st);             //     + K_text g_S_text^T
-    attn_gemm(c, attn_keys(s, q, 0, s.HS, SG, PS, gk, PS), s.st);                                       // g_k = q g_S_img
+    attn_gemm(c, attn_keys(s, oG, s.bo, s.OS, SP, 0, gv, s.bq), s.st);                                  // g_v = g_o P_img
+    if (s.Lt) attn_gemm_f32(c, attn_scores(s, TEXT, oG, s.bo, s.OS, s.vt, 0, SG, s.bS, 1.f, 0.f), s.st);      // g_P_text = g_o^T V_text
+    attn_gemm(c, attn_scores(s, IMAGE, oG, s.bo, s.OS, v, 0, SG, s.bS, 1.f, 0.f), s.st);                // g_P_img = g_o^T v
+    attn_softmax_jac(c, SG, SP, (long)s.NH * s.T, s.Tk, s.scale, s.st, s.B, s.bS);
+    attn_gemm(c, attn_values(s, IMAGE, k, 0, SG, s.bS, gq, s.bq, s.HS, 0.f), s.st);                     // g_q = k g_S_img^T
+    if (s.Lt) attn_gemm_f32(c, attn_values(s, TEXT, s.kt, 0, SG, s.bS, gq, s.bq, s.HS, 1.f), s.st);     //     + K_text g_S_text^T
+    attn_gemm(c, attn_keys(s, q, 0, s.HS, SG, s.bS, gk, s.bq), s.st);                                   // g_k = q g_S_img
 }
 
 // y[Cout][T] (+ bias, + residual) = W x[Cin][T] as a 1x1 conv; dgrad: the transposed map
@@ -1154,7 +1205,7 @@ int forward_pass(loco_ctx* c, const float* x, float t, int B, float* arena, floa
                 // per head h: q = qkv[h*3*CH ...], k = +CH, v = +2CH channels (QKVAttentionLegacy, unet.py:346;
                 // with one head this is the [q|k|v] stacking of the fused DDPM projection)
                 if (op.added_kv && !c->has_ctx) { c->err = "this architecture attends over the prompt's states: call loco_set_context first"; return -1; }
-                attn_forward(attn_of(c, op, B, st), arena, p.bs());
+                attn_forward(attn_of(c, op, B, st, arena, p.bs()));
                 ConvArgs pr; conv_defaults(pr);
                 pr.in = p.T(op.o); pr.in_bs = p.bs(); pr.Cin = C; pr.Hin = to.H; pr.Win = to.W;
                 setw(pr, op.proj, false); pr.bias = op.proj.bias; pr.pad = 0;
@@ -1176,7 +1227,7 @@ int forward_pass(loco_ctx* c, const float* x, float t, int B, float* arena, floa
                     qa.mode = CM_GN; qa.sc = sx.sc; qa.sh = sx.sh; qa.scsh_bs = SB;
                     qa.out = p.T(op.xq); qa.out_bs = p.bs(); qa.Cout = C; qa.Hout = to.H; qa.Wout = to.W; qa.B = B;
                     run_conv(c, qa, 1, st);
-                    xa_forward(x, p.T(op.xq), p.T(op.xS), p.T(op.xo), p.bs());
+                    xa_forward(x, p.T(op.xq), p.T(op.xS), p.T(op.xo));
                     const StatReq rqx = next_fwd(op.out);
                     lin1x1(c, op.xproj, false, p.T(op.xo), p.bs(), C, p.T(op.out), p.bs(), C, to.H, to.W, B,
                            p.T(op.xmid), p.bs(), true, st, &rqx);
@@ -1203,12 +1254,12 @@ int forward_pass(loco_ctx* c, const float* x, float t, int B, float* arena, floa
                 // x = x + attn1(LN1(x))
                 launch_ln_fwd(X(X_H0), PSb, B, C, T, op.lng[0], op.lnb[0], 1e-5f, X(X_A1), PSb, X(X_LN1), PSb, st);
                 lin1x1(c, op.qkvc, false, X(X_A1), PSb, C, X(X_QKV), PSb, 3 * C, H, W, B, nullptr, 0, false, st);
-                attn_forward(attn_of(c, op, B, st), arena, PSb);
+                attn_forward(attn_of(c, op, B, st, arena, PSb));
                 lin1x1(c, op.to_out1, false, X(X_O), PSb, C, X(X_H1), PSb, C, H, W, B, X(X_H0), PSb, true, st);
                 // x = x + attn2(LN2(x), context)
                 launch_ln_fwd(X(X_H1), PSb, B, C, T, op.lng[1], op.lnb[1], 1e-5f, X(X_A2), PSb, X(X_LN2), PSb, st);
                 lin1x1(c, op.xqc, false, X(X_A2), PSb, C, X(X_XQ), PSb, C, H, W, B, nullptr, 0, false, st);
-                xa_forward(xa, X(X_XQ), X(X_XS), X(X_XO), PSb);
+                xa_forward(xa, X(X_XQ), X(X_XS), X(X_XO));
                 lin1x1(c, op.to_out2, false, X(X_XO), PSb, C, X(X_H2), PSb, C, H, W, B, X(X_H1), PSb, true, st);
                 // x = x + Linear(GEGLU(LN3(x)))
                 launch_ln_fwd(X(X_H2), PSb, B, C, T, op.lng[2], op.lnb[2], 1e-5f, X(X_A3), PSb, X(X_LN3), PSb, st);
@@ -2781,6 +2832,98 @@ int loco_debug_conv(loco_ctx* c, const loco_conv_desc* d, char* plan, int64_t ca
         std::memcpy(plan, text.c_str(), text.size() + 1);
     }
     if (d->cot_d && !rode) { c->err = "debug_conv: norm-cotangent term declined"; return 1; }
+    return 0;
+}
+
+// loco_debug_attn: one pass of one attention stage on the caller's tensors, through attn_forward / attn_tangent / attn_cotangent or
+// xa_forward / xa_linear -- the engine's own functions, so the route (flash, record GEMM, bf16x3, fused cross-attention) is the
+// product's.  Only the descriptor -> Attn / XA mapping and the scratch live here.
+int loco_debug_attn(loco_ctx* c, const loco_attn_desc* d, char* route, int64_t cap, void* stream) {
+    if (!c) return -2;
+    if (!d || d->struct_size != (int32_t)sizeof(loco_attn_desc)) { c->err = "debug_attn: descriptor size mismatch"; return -2; }
+    hipStream_t st = (hipStream_t)stream;
+    const int T = d->T, NH = d->NH, CH = d->CH, B = d->B, L = d->L;
+    const bool cross = d->kind == 1;
+    if ((d->kind != 0 && d->kind != 1) || d->pass < 0 || d->pass > 2) { c->err = "debug_attn: kind is 0 / 1, pass 0 / 1 / 2"; return -2; }
+    if (CH < 1) { c->err = "debug_attn: CH < 1"; return -2; }
+    if (T < 64 || T % 64) { c->err = "debug_attn: T must be a multiple of 64 (the row kernels and the tiles of the fused kernels)"; return -2; }
+    if (NH < 1 || B < 1) { c->err = "debug_attn: NH and B must be positive"; return -2; }
+    if (!cross && (d->Lt < 0 || d->Lt % 64)) { c->err = "debug_attn: Lt must be a multiple of 64"; return -2; }
+    if (!cross && (L < 0 || L > d->Lt || (d->Lt > 0 && L < 1))) { c->err = "debug_attn: L must lie in 1 ... Lt"; return -2; }
+    if (cross && L < 1) { c->err = "debug_attn: the cross-attention needs L >= 1 context rows"; return -2; }
+    const int Lt = cross ? ((L + 63) / 64) * 64 : d->Lt;        // cross: Lp, the padded row length (program.hip: ctx_Lp)
+    const bool text = cross || Lt > 0;
+    bool have = d->P && (!text || (d->kt && d->vt));
+    if (!cross) have = have && d->q && d->k && d->v && d->o;
+    if (d->pass == 0) have = have && d->o;
+    if (d->pass == 0) have = have && d->q;
+    if (d->pass == 1) have = have && d->dq && d->out && (cross || (d->dk && d->dv));
+    if (d->pass == 2) have = have && d->go && d->gq && (cross || (d->gk && d->gv));
+    if (!have) { c->err = "debug_attn: a required operand is null"; return -2; }
+    const long CT = (long)NH * CH * T, SB = (long)NH * T * (cross ? Lt : Lt + T);
+    const size_t owned0 = c->owned.size(), bytes0 = c->bytes;
+    auto release = [&]() {      // what this call allocated
+        (void)hipStreamSynchronize(st);
+        while (c->owned.size() > owned0) { (void)hipFree(c->owned.back()); c->owned.pop_back(); }
+        c->bytes = bytes0;
+    };
+    float* colbias = nullptr;
+    if (text) {
+        std::vector<float> cb((size_t)Lt, 0.f);
+        for (int l = L; l < Lt; ++l) cb[l] = -1e30f;
+        if (upload(c, &colbias, cb)) { release(); return -1; }
+    }
+    std::string text_log;
+    float* scratch = nullptr;
+    if (cross) {
+        XA x; x.c = c; x.st = st; x.B = B; x.C = NH * CH; x.T = T; x.NH = NH; x.CH = CH; x.L = L; x.Lp = Lt;
+        x.scale = 1.0f / std::sqrt((float)CH);
+        x.xK = d->kt; x.xV = d->vt; x.colbias = colbias; x.xs = CT; x.ss = SB;
+        if (d->pass != 0 && dalloc(c, &scratch, (size_t)B * SB)) { release(); return -1; }
+        c->attn_log = &text_log;
+        if (d->pass == 0) xa_forward(x, d->q, d->P, d->o);
+        else if (d->pass == 1) xa_linear(x, d->dq, x.xK, x.xV, d->P, scratch, d->out);        // dq -> do
+        else xa_linear(x, d->go, x.xV, x.xK, d->P, scratch, d->gq);                             // g_o -> g_q
+    } else {
+        Attn s; s.c = c; s.st = st; s.B = B; s.T = T; s.NH = NH; s.CH = CH; s.Lt = Lt; s.Tk = Lt + T;
+        s.HS = (long)CH * T; s.SS = (long)T * s.Tk; s.OS = (long)CH * T; s.KS = (long)CH * Lt;      // q, k, v: tensors of their own
+        s.scale = 1.0f / std::sqrt((float)CH);
+        s.pair = d->pair != 0;
+        s.q = d->q; s.k = d->k; s.v = d->v; s.P = d->P; s.o = d->o;
+        s.bq = CT; s.bS = SB; s.bo = CT;
+        s.kt = d->kt; s.vt = d->vt; s.colbias = colbias;
+        s.delta = nullptr; s.ws = nullptr; s.ws_bytes = 0;
+        s.tq = s.tk = s.tv = s.tS = s.to = nullptr;
+        if (d->pass == 0) {
+            s.tq = const_cast<float*>(d->q); s.tk = const_cast<float*>(d->k); s.tv = const_cast<float*>(d->v); s.tS = d->P; s.to = d->o;
+        } else {
+            if (d->pass == 1) { s.tq = const_cast<float*>(d->dq); s.tk = const_cast<float*>(d->dk); s.tv = const_cast<float*>(d->dv); s.to = d->out; }
+            else { s.tq = d->gq; s.tk = d->gk; s.tv = d->gv; s.to = const_cast<float*>(d->go); }
+            if (s.flash()) {
+                AttnFlashArgs fa = attn_flash_args(s);
+                const size_t need = attn_flash_ws_bytes(fa);
+                float* wsf = nullptr;
+                if (dalloc(c, &s.delta, (size_t)B * NH * T) || (!d->no_workspace && dalloc(c, &wsf, need / sizeof(float) + 16384))) { release(); return -1; }
+                if (wsf) { s.ws = reinterpret_cast<unsigned char*>(wsf); s.ws_bytes = need; }
+            } else {
+                if (dalloc(c, &scratch, (size_t)B * SB)) { release(); return -1; }
+                s.tS = scratch;
+            }
+        }
+        c->attn_log = &text_log;
+        if (d->pass == 0) attn_forward(s);
+        else if (d->pass == 1) attn_tangent(s);
+        else attn_cotangent(s);
+    }
+    c->attn_log = nullptr;
+    hipError_t he = hipGetLastError();
+    release();
+    if (he == hipSuccess) he = hipGetLastError();
+    if (he != hipSuccess) { c->err = std::string("debug_attn: ") + hipGetErrorString(he); return -1; }
+    if (route && cap > 0) {
+        if ((int64_t)text_log.size() + 1 > cap) { c->err = "debug_attn: route buffer too small"; return -4; }
+        std::memcpy(route, text_log.c_str(), text_log.size() + 1);
+    }
     return 0;
 }
 

@@ -274,6 +274,12 @@ struct AttnFlashArgs {
     unsigned char* ws; size_t ws_bytes;
 };
 size_t attn_flash_ws_bytes(const AttnFlashArgs& a);
+// DMA-fed kernels (operands pre-split into records in `ws`) or the converting ones: the one decision of the launchers, also read by
+// the diagnostics route log.  need = attn_flash_ws_bytes(a); dma_on = the LOCO_FLASH_DMA switch (attn_flash_dma_enabled)
+inline bool attn_flash_dma_route(const unsigned char* ws, size_t ws_bytes, size_t need, bool dma_on) {
+    return ws != nullptr && dma_on && need <= ws_bytes;
+}
+bool attn_flash_dma_enabled();                // LOCO_FLASH_DMA != 0, read per launch
 bool attn_flash_supported(int T, int CH);     // heads of <= 96 channels, token counts that are multiples of 128
 bool attn_flash_text_supported(int T, int CH, int Lt);   // the [text ; image] form: heads of <= 64 channels
 void launch_attn_flash_tangent(const AttnFlashArgs& a, hipStream_t st);

@@ -20,7 +20,7 @@ _LIB_PATH = os.environ.get("LOCO_HIP_LIB") or os.path.join(os.path.dirname(os.pa
 _lib = None
 
 # diagnostics of include/loco_hip_diag.h: only in a -DLOCO_DIAG build (make -C loco-edit_amd/csrc diag)
-DIAG_SYMBOLS = ["loco_bench_conv", "loco_debug_conv", "loco_debug_tensor"]
+DIAG_SYMBOLS = ["loco_bench_conv", "loco_debug_conv", "loco_debug_attn", "loco_debug_tensor"]
 
 # every symbol include/loco_hip.h declares
 SYMBOLS = [
@@ -72,6 +72,14 @@ class LocoConvDesc(C.Structure):
                 [(k, C.c_int32) for k in ("Cin", "Cout", "Hin", "Win", "B", "taps", "stride", "upsample", "zins", "mode", "cpg",
                                           "transposed", "accumulate", "in_arena", "pad", "Cin2", "cot_cpg")] +
                 [("res_scale", C.c_float), ("st_cpg", C.c_int32)] + [(k, C.c_void_p) for k in _PTRS] + [("pool2", C.c_int32)])
+
+
+class LocoAttnDesc(C.Structure):
+    """loco_attn_desc of include/loco_hip_diag.h (loco_debug_attn): one pass of one attention stage on caller-supplied tensors."""
+    _PTRS = ("q", "k", "v", "kt", "vt", "P", "o", "dq", "dk", "dv", "out", "go", "gq", "gk", "gv")
+    _fields_ = ([("struct_size", C.c_int32)] +
+                [(k, C.c_int32) for k in ("kind", "pass_", "T", "NH", "CH", "B", "Lt", "L", "pair", "no_workspace")] +
+                [(k, C.c_void_p) for k in _PTRS])
 
 
 class LocoTextCfg(C.Structure):
@@ -241,6 +249,8 @@ def load_library():
         lib.loco_debug_tensor.restype = i64
     if hasattr(lib, "loco_debug_conv"):
         lib.loco_debug_conv.argtypes = [vp, C.POINTER(LocoConvDesc), C.c_char_p, i64, vp]
+    if hasattr(lib, "loco_debug_attn"):
+        lib.loco_debug_attn.argtypes = [vp, C.POINTER(LocoAttnDesc), C.c_char_p, i64, vp]
     _lib = lib
     return lib
 
@@ -801,6 +811,31 @@ class LocoEngine:
             rec = dict(f.split("=", 1) for f in line.split(" "))
             plan.append({k: (v if k == "kernel" else int(v)) for k, v in rec.items()})
         return plan, rc == 0
+
+    def debug_attn(self, **desc):
+        """One pass of one attention stage on caller-supplied tensors through the engine's own attn_* / xa_* functions
+        (loco_debug_attn, include/loco_hip_diag.h).  `desc`: the fields of loco_attn_desc (`pass_` for the pass); every tensor a
+        contiguous float32 device tensor.  Returns the route: one dict per launch (kernel, and M, N, K, batch, heads, kcat of a GEMM)."""
+        self._need_diag("loco_debug_attn")
+        d = LocoAttnDesc()
+        d.struct_size = C.sizeof(LocoAttnDesc)
+        keep = []
+        for k, v in desc.items():
+            if k not in LocoAttnDesc._PTRS:
+                if not hasattr(d, k) or k == "struct_size":
+                    raise TypeError(f"debug_attn: no descriptor field {k!r}")
+                setattr(d, k, v)
+            elif v is not None:
+                _chk_dev(v)
+                keep.append(v)
+                setattr(d, k, v.data_ptr())
+        buf = C.create_string_buffer(1 << 12)
+        self._check(self.lib.loco_debug_attn(self._ctx, C.byref(d), buf, len(buf), _stream()), "loco_debug_attn")
+        route = []
+        for line in buf.value.decode().splitlines():
+            rec = dict(f.split("=", 1) for f in line.split(" "))
+            route.append({k: (v if k == "kernel" else int(v)) for k, v in rec.items()})
+        return route
 
     def profile_enable(self, on):
         """True/1: per kernel variant; 2: per layer shape; False: off."""
