@@ -56,12 +56,28 @@ int  loco_bench_conv(loco_ctx* ctx, int32_t cin, int32_t cout, int32_t H, int32_
  *   {mean, rstd} of that norm's groups.  st_out [2][B][Cout / st_cpg][2] receives {m1, m2} per (sample, group): [0] merged from
  *   the kept partials (all-ones bit patterns, i.e. NaN, where the launch kept none), [1] by the standalone pass over the finished tensor.
  *
+ *   statistics request with a consuming norm (st_kind = 1 ST_FWD, 2 ST_TAN, 3 ST_COT; 0: the kept-partials request above): the
+ *   launch carries the StatReq the engine's passes attach for the norm that consumes the output tensor, and the route is whatever
+ *   plan_conv picks (epilogue partials + finalize, the split-K epilogue, the standalone kernels, both across a tail-probe split).
+ *   The norm has the ENGINE's group count G = cfg.gn_groups (run_conv takes it from there): st_gamma, st_beta [Cout], st_eps, and
+ *   for ST_FWD optionally st_ss_scale, st_ss_shift [Cout]; for ST_TAN / ST_COT the primal st_prim [Cout][Hout][Wout] of the output
+ *   tensor and that norm's primal st_sc, st_sh [Cout], st_mr [G][2] (the {S, xhat} records of ST_COT are built by launch_gn_cache).
+ *   What the statistics arena receives per sample is copied out: ST_FWD st_o_mr [B][G][2], st_o_sc, st_o_sh [B][Cout];
+ *   ST_TAN / ST_COT st_o_tst [B][G][2], st_o_tc [B][Cout][2] (all-ones bit patterns where nothing was written).
+ *   st_keep = 1 (ST_FWD, ST_TAN): the launch finishes one part of a concatenation; the row-tile partials it kept are copied to
+ *   st_keep_out [B][Cout][keep_ntile][2] (st_keep_cap floats, fewer than were kept: -4 after the launch; keep_ntile is in the plan's
+ *   closing line, 0: none kept).
+ *   Refused before any launch: Cout not a multiple of G, 4 Cout + 4 G floats beyond a sample's statistics slot, Hout Wout not a
+ *   multiple of 4, B beyond max_batch, ST_COT records beyond the record cache.  (Another cpg: an engine with another gn_groups.)
+ *
  * in_arena = 1: `in` (and in2, prim, cot_d) are copied into the engine's padded arenas, as every inner conv sees them;
  * in_arena = 0: the kernel reads the caller's `in` (ConvArgs::in_padded = 0: the network's first conv on the user's tensor).
  *
  * plan (cap bytes, may be null) receives one line per launch and part, as planned by plan_conv:
  *   "launch=L part=P kernel=<conv_variant_name> tile=T nsplit=S B=b s0=first sample gemm=0|1 gemm_tm=M pair=0|1 Cin2=C
- *    sc_first=0|1 cot=0|1\n"      (a shortcut that runs first is a launch of its own, listed first)
+ *    sc_first=0|1 cot=0|1 stats=none|epi|splitk|alone|keep ntile=N\n"   (a shortcut that runs first is a plan of its own, listed first)
+ *   and one closing line per plan: "stats_all=0|1 keep_ntile=N\n" (a standalone statistics pass over the whole batch follows;
+ *   tiles per row of the kept partials)
  * Returns 0, or 1 when a norm-cotangent term was asked for and the planner declined it (out then holds the plain result and
  * loco_last_error says "declined"); < 0 on errors (shapes that exceed the arenas or the workspace among them). */
 typedef struct loco_conv_desc {
@@ -81,6 +97,15 @@ typedef struct loco_conv_desc {
     const float *st_prim, *st_mr;                                /* tangent statistics request, see above */
     float* st_out;
     int32_t pool2;                                               /* 1: a 2x2 sum-pool follows the conv, see above */
+    /* statistics request WITH a consuming norm (st_kind 1, 2, 3; see above).  All zero: none of it, the call is what it was. */
+    int32_t st_kind, st_keep;
+    float   st_eps;                                              /* 0: the engine's gn_eps */
+    int32_t st_keep_cap;                                         /* floats st_keep_out can take */
+    const float *st_gamma, *st_beta, *st_ss_scale, *st_ss_shift; /* the consuming norm, [Cout]; scale-shift optional (FWD) */
+    const float *st_sc, *st_sh;                                  /* TAN / COT: the norm's primal sc, sh [Cout] (with st_prim, st_mr) */
+    float *st_o_mr, *st_o_sc, *st_o_sh;                          /* FWD: [B][G][2], [B][Cout], [B][Cout] */
+    float *st_o_tst, *st_o_tc;                                   /* TAN / COT: [B][G][2], [B][Cout][2] */
+    float *st_keep_out;                                          /* st_keep: [B][Cout][keep_ntile][2] */
 } loco_conv_desc;
 int  loco_debug_conv(loco_ctx* ctx, const loco_conv_desc* desc, char* plan, int64_t cap, void* stream);
 
@@ -129,6 +154,30 @@ typedef struct loco_attn_desc {
     float *gq, *gk, *gv;
 } loco_attn_desc;
 int  loco_debug_attn(loco_ctx* ctx, const loco_attn_desc* desc, char* route, int64_t cap, void* stream);
+
+/* Test hook: ONE launch of ONE standalone GroupNorm launcher (kernels.h) on caller-supplied DEVICE tensors
+ * (tests/test_gpu_stats_oracle.py compares it with the float64 reference of tests/stats_oracle.py).  Strides are in floats and the
+ * caller's; scratch is the engine's reduction buffer where the launcher wants one.
+ *   op 0 launch_gn_stats:              x [B][C][HW] (x_bs), gamma, beta, eps, ss_scale / ss_shift or null -> o_mr, o_sc, o_sh (o_bs)
+ *   op 1 launch_gn_tstats:             kind 0 / 1 / 2, act; d (d_bs), x (x_bs, 0: broadcast), sc, sh (pbs_c), mr (pbs_g) -> o_tst, o_tc (o_bs)
+ *   op 2 launch_gn_apply:              kind 0 - 5, act; d, x, base (base_bs, base_scale), sc, sh, mr, tst (t_bs), accumulate -> out (out_bs)
+ *   op 3 launch_gn_cache:              x [C][HW], sc, sh, mr, act -> out [C][HW][2]
+ *   op 4 launch_gn_fused_finalize:     partA [B][C][ntA][2] -> o_mr, o_sc, o_sh
+ *   op 5 launch_gn_fused_finalize_cat: partA [B][C1][ntA][2], partB [B][C - C1][ntB][2] -> o_mr, o_sc, o_sh
+ *   op 6 launch_gn_lin_fused_finalize: kind 2 (ST_TAN) / 3 (ST_COT); partA (C1, ntA), partB or null (then C1 = C), mr [G][2] -> o_tst, o_tc
+ *   op 7 launch_ctx_groupnorm:         x = tok [HW = L][C = D], gamma, beta, eps -> out [L][D]
+ * Refused before any launch: C not a multiple of G, HW not a multiple of 4 (ops 0 - 6), more than 256 channels per group (the
+ * kernels expand per channel with one thread each), B G > 8192 (the reduction buffer), a kind out of the launcher's range, tile
+ * counts that do not divide HW, C1 outside (0, C), one of ss_scale / ss_shift without the other, a null required operand. */
+typedef struct loco_norm_desc {
+    int32_t struct_size;
+    int32_t op, kind, act, B, C, HW, G, C1, ntA, ntB, accumulate;
+    float   eps, base_scale;
+    int64_t x_bs, d_bs, base_bs, out_bs, pbs_c, pbs_g, o_bs, t_bs;
+    const float *x, *d, *base, *gamma, *beta, *ss_scale, *ss_shift, *sc, *sh, *mr, *tst, *partA, *partB;
+    float *o_mr, *o_sc, *o_sh, *o_tst, *o_tc, *out;
+} loco_norm_desc;
+int  loco_debug_norm(loco_ctx* ctx, const loco_norm_desc* desc, void* stream);
 
 /* Debug / test hook: copy an internal primal activation ("down.0.block.0" ...)
  * of the last forward/primal call into dst (device), returns element count or <0. */

@@ -2712,11 +2712,39 @@ int loco_debug_conv(loco_ctx* c, const loco_conv_desc* d, char* plan, int64_t ca
     const int G = lin ? d->Cin / d->cpg : 0;
     const long tbs = up64(2L * G) + up64(2L * d->Cin);
     // tangent statistics request (st_prim): kept row partials, a zeroed sc / sh pair for the standalone pass
-    const bool st_req = d->st_prim != nullptr;
+    const bool st_req = d->st_kind == 0 && d->st_prim != nullptr;
     if (st_req && (!d->st_mr || !d->st_out || d->st_cpg < 1 || d->Cout % d->st_cpg || d->cot_d || d->Cin2 > 0)) {
         c->err = "debug_conv: the statistics request needs st_prim, st_mr, st_out and st_cpg (no second operator, no cot_d)"; return -2;
     }
-    const long keep_n = st_req ? up64((long)B * d->Cout * ((long)Hout * Wout / 64 + 1) * 2) : 0;
+    // statistics request with a consuming norm (st_kind = ST_FWD / ST_TAN / ST_COT): run_conv takes the group count, the slot
+    // layout and the arenas from the engine, so what does not fit them is refused here
+    const int stk = d->st_kind, Gs = c->cfg.gn_groups;
+    const bool st_norm = stk != 0, st_lin = stk == ST_TAN || stk == ST_COT;
+    const long SBs = c->prog->stats_per_sample;
+    const long sx_st = need_sx;      // ST_COT: the norm's {S, xhat} records over the output tensor, behind the other records
+    if (st_norm) {
+        if (stk < ST_FWD || stk > ST_COT) { c->err = "debug_conv: st_kind is 0, 1 (FWD), 2 (TAN) or 3 (COT)"; return -2; }
+        if (Gs < 1 || d->Cout % Gs) { c->err = "debug_conv: statistics request: Cout must be a multiple of the engine's gn_groups"; return -2; }
+        if (4L * d->Cout + 4L * Gs > SBs) { c->err = "debug_conv: statistics request: 4 Cout + 4 G exceeds a sample's statistics slot"; return -2; }
+        if (((long)Hout * Wout) % 4) { c->err = "debug_conv: statistics request: Hout Wout must be a multiple of 4"; return -2; }
+        if (B > c->cfg.max_batch) { c->err = "debug_conv: statistics request: B exceeds max_batch"; return -2; }
+        if (!d->st_gamma || !d->st_beta) { c->err = "debug_conv: statistics request: st_gamma and st_beta are required"; return -2; }
+        if (stk == ST_FWD && (!d->st_o_mr || !d->st_o_sc || !d->st_o_sh || (!d->st_ss_scale != !d->st_ss_shift))) {
+            c->err = "debug_conv: ST_FWD needs st_o_mr, st_o_sc, st_o_sh (and st_ss_scale with st_ss_shift)"; return -2;
+        }
+        if (st_lin && (!d->st_prim || !d->st_sc || !d->st_sh || !d->st_mr || !d->st_o_tst || !d->st_o_tc)) {
+            c->err = "debug_conv: ST_TAN / ST_COT need st_prim, st_sc, st_sh, st_mr, st_o_tst and st_o_tc"; return -2;
+        }
+        if (stk == ST_COT && (!c->sxcache || sx_st + out_e > c->prog->sx_total)) {
+            c->err = "debug_conv: ST_COT: the norm's records exceed the record cache"; return -2;
+        }
+        if (d->st_keep && (stk == ST_COT || !d->st_keep_out || d->st_keep_cap < 1)) {
+            c->err = "debug_conv: st_keep goes with ST_FWD / ST_TAN and needs st_keep_out, st_keep_cap"; return -2;
+        }
+        if (d->pool2) { c->err = "debug_conv: statistics request: not with pool2"; return -2; }
+    }
+    const bool st_kept = st_norm && d->st_keep;
+    const long keep_n = (st_req || st_kept) ? up64((long)B * d->Cout * ((long)Hout * Wout / 64 + 1) * 2) : 0;
     const long small_n = (lin ? (long)B * tbs : 0) + (d->cot_d ? (long)B * up64(2L * d->Cout) : 0) + 64 + keep_n + (st_req ? up64(2L * d->Cout) : 0);
     const size_t owned0 = c->owned.size();
     const size_t bytes0 = c->bytes;
@@ -2807,9 +2835,42 @@ int loco_debug_conv(loco_ctx* c, const loco_conv_desc* d, char* plan, int64_t ca
     if (st_req) {      // as next_tan asks for one part of a concatenation: the raw row partials stay in `keep`
         srq.kind = ST_TAN; srq.prim = d->st_prim; srq.keep = keep_buf; srq.keep_floats = (size_t)keep_n; srq.keep_ntile = &kept_ntile;
     }
-    const bool rode = run_conv(c, a, taps, st, st_req ? &srq : nullptr, d->Cin2 > 0 ? &n2 : nullptr);
+    NormP stn;      // the consuming norm of a statistics request: slot 0 of the arenas, its records behind the launch's own
+    if (st_norm) {
+        stn.C = d->Cout; stn.soff = 0; stn.eps = d->st_eps;
+        stn.gamma = const_cast<float*>(d->st_gamma); stn.beta = const_cast<float*>(d->st_beta);
+        srq.kind = stk; srq.n = &stn; srq.stats = c->statsT;
+        srq.ss_scale = d->st_ss_scale; srq.ss_shift = d->st_ss_shift;
+        (void)hipMemsetAsync(c->statsT, 0xff, (size_t)B * SBs * sizeof(float), st);      // an unwritten slot reads as NaN
+        if (st_lin) {
+            NS sp = nstats(c, c->statsP, stn);
+            (void)copy(sp.sc, d->st_sc, d->Cout); (void)copy(sp.sh, d->st_sh, d->Cout); (void)copy(sp.mr, d->st_mr, 2L * Gs);
+            srq.prim = d->st_prim;
+            if (stk == ST_COT) {
+                stn.sx_off = sx_st;
+                launch_gn_cache(d->st_prim, d->Cout, Hout * Wout, d->Cout / Gs, sp.sc, sp.sh, sp.mr, c->sxcache + sx_st, st, c->cfg.act);
+            }
+        }
+        if (st_kept) { srq.keep = keep_buf; srq.keep_floats = (size_t)keep_n; srq.keep_ntile = &kept_ntile; }
+    }
+    bool keep_short = false;      // the kept partials did not fit st_keep_out
+    const bool rode = run_conv(c, a, taps, st, (st_req || st_norm) ? &srq : nullptr, d->Cin2 > 0 ? &n2 : nullptr);
     c->plan_log = nullptr;
     c->cfg.act = act0;
+    if (st_norm) {      // what the arena's slots received, per sample
+        NS so = nstats(c, c->statsT, stn);
+        auto rows = [&](float* dst, const float* src, long w) {
+            return hipMemcpy2DAsync(dst, (size_t)w * sizeof(float), src, (size_t)SBs * sizeof(float), (size_t)w * sizeof(float), (size_t)B,
+                                    hipMemcpyDeviceToDevice, st);
+        };
+        if (stk == ST_FWD) { (void)rows(d->st_o_mr, so.mr, 2L * Gs); (void)rows(d->st_o_sc, so.sc, d->Cout); (void)rows(d->st_o_sh, so.sh, d->Cout); }
+        else { (void)rows(d->st_o_tst, so.tst, 2L * Gs); (void)rows(d->st_o_tc, so.tc, 2L * d->Cout); }
+        if (st_kept && kept_ntile > 0) {
+            const long n = (long)B * d->Cout * kept_ntile * 2;
+            if (n <= d->st_keep_cap) (void)copy(d->st_keep_out, keep_buf, n);
+            else keep_short = true;
+        }
+    }
     if (st_req) {
         // st_out[0]: {m1, m2} per (sample, group) from the partials the launch kept (NaN where it kept none); st_out[1]: the
         // standalone pass over the finished tensor
@@ -2831,7 +2892,85 @@ int loco_debug_conv(loco_ctx* c, const loco_conv_desc* d, char* plan, int64_t ca
         if ((int64_t)text.size() + 1 > cap) { c->err = "debug_conv: plan buffer too small"; return -4; }
         std::memcpy(plan, text.c_str(), text.size() + 1);
     }
+    if (keep_short) { c->err = "debug_conv: st_keep_out too small for the kept partials (B Cout keep_ntile 2 floats)"; return -4; }
     if (d->cot_d && !rode) { c->err = "debug_conv: norm-cotangent term declined"; return 1; }
+    return 0;
+}
+
+// loco_debug_norm: one launch of one standalone GroupNorm launcher on the caller's tensors.  Only the descriptor -> argument
+// mapping and the launchers' shape contract (checked here, before the launch) live here.
+int loco_debug_norm(loco_ctx* c, const loco_norm_desc* d, void* stream) {
+    if (!c) return -2;
+    if (!d || d->struct_size != (int32_t)sizeof(loco_norm_desc)) { c->err = "debug_norm: descriptor size mismatch"; return -2; }
+    if (finalize_params(c)) return -3;
+    hipStream_t st = (hipStream_t)stream;
+    const int op = d->op, B = d->B, C = d->C, HW = d->HW, G = d->G;
+    if (op < 0 || op > 7) { c->err = "debug_norm: op is 0 ... 7"; return -2; }
+    if (C < 1 || HW < 1 || G < 1 || C % G) { c->err = "debug_norm: C must be a positive multiple of G"; return -2; }
+    if (op != 7 && op != 3 && B < 1) { c->err = "debug_norm: B < 1"; return -2; }
+    if (op != 7 && (HW % 4)) { c->err = "debug_norm: HW must be a multiple of 4 (16-byte loads)"; return -2; }
+    if (C / G > 256) { c->err = "debug_norm: more than 256 channels per group"; return -2; }
+    if (op != 7 && op != 3 && (long)B * G > 8192) { c->err = "debug_norm: B G exceeds the reduction buffer"; return -2; }
+    auto need = [&](std::initializer_list<const void*> ps) { for (const void* p : ps) if (!p) return false; return true; };
+    const char* null_op = "debug_norm: a required operand is null";
+    {   // kind, tile counts, the split of a concatenation and the scale-shift pair, each under its own name
+        static const int kind_lo[8] = {0, 0, 0, 0, 0, 0, ST_TAN, 0}, kind_hi[8] = {0, 2, 5, 0, 0, 0, ST_COT, 0};
+        if ((op == 1 || op == 2 || op == 6) && (d->kind < kind_lo[op] || d->kind > kind_hi[op])) {
+            c->err = "debug_norm: kind out of range (gn_tstats 0 - 2, gn_apply 0 - 5, gn_lin_fused_finalize 2 / 3)"; return -2;
+        }
+        const bool two = op == 5 || (op == 6 && d->partB);
+        if ((op == 4 || op == 5 || op == 6) && (d->ntA < 1 || HW % d->ntA || (two && (d->ntB < 1 || HW % d->ntB)))) {
+            c->err = "debug_norm: tile counts must be positive and divide HW"; return -2;
+        }
+        if (two && (d->C1 < 1 || d->C1 >= C)) { c->err = "debug_norm: C1 must lie inside (0, C)"; return -2; }
+        if ((op == 0 || op == 4) && (!d->ss_scale != !d->ss_shift)) { c->err = "debug_norm: ss_scale goes with ss_shift"; return -2; }
+    }
+    switch (op) {
+        case 0:
+            if (!need({d->x, d->gamma, d->beta, d->o_mr, d->o_sc, d->o_sh})) { c->err = null_op; return -2; }
+            launch_gn_stats(d->x, d->x_bs, B, C, HW, G, d->eps, d->gamma, d->beta, d->o_mr, d->o_sc, d->o_sh, d->o_bs, c->red, st,
+                            d->ss_scale, d->ss_shift);
+            break;
+        case 1:
+            if (!need({d->d, d->x, d->sc, d->sh, d->mr, d->o_tst})) { c->err = null_op; return -2; }
+            launch_gn_tstats(d->d, d->d_bs, d->x, d->x_bs, B, C, HW, G, d->sc, d->sh, d->mr, d->pbs_c, d->pbs_g, d->kind, d->o_tst,
+                             d->o_tc, d->o_bs, c->red, st, d->act);
+            break;
+        case 2: {
+            const bool lin = d->kind != 0 && d->kind != 4;
+            if (!need({d->x, d->sc, d->sh, d->out}) || (lin && !need({d->d, d->mr, d->tst}))) { c->err = null_op; return -2; }
+            launch_gn_apply(d->kind, d->d, d->d_bs, d->x, d->x_bs, d->base, d->base_bs, d->out, d->out_bs, d->accumulate, B, C, HW, G,
+                            d->sc, d->sh, d->mr, d->pbs_c, d->pbs_g, d->tst, d->t_bs, st, d->act, d->base_scale);
+            break;
+        }
+        case 3:
+            if (!need({d->x, d->sc, d->sh, d->mr, d->out})) { c->err = null_op; return -2; }
+            launch_gn_cache(d->x, C, HW, C / G, d->sc, d->sh, d->mr, reinterpret_cast<float2*>(d->out), st, d->act);
+            break;
+        case 4:
+            if (!need({d->partA, d->gamma, d->beta, d->o_mr, d->o_sc, d->o_sh})) { c->err = null_op; return -2; }
+            launch_gn_fused_finalize(d->partA, d->ntA, B, C, HW, G, d->eps, d->gamma, d->beta, d->o_mr, d->o_sc, d->o_sh, d->o_bs,
+                                     d->ss_scale, d->ss_shift, st);
+            break;
+        case 5:
+            if (!need({d->partA, d->partB, d->gamma, d->beta, d->o_mr, d->o_sc, d->o_sh})) { c->err = null_op; return -2; }
+            launch_gn_fused_finalize_cat(d->partA, d->C1, d->ntA, d->partB, d->ntB, B, C, HW, G, d->eps, d->gamma, d->beta, d->o_mr,
+                                         d->o_sc, d->o_sh, d->o_bs, st);
+            break;
+        case 6: {
+            const int C1 = d->partB ? d->C1 : C;
+            if (!need({d->partA, d->mr, d->o_tst})) { c->err = null_op; return -2; }
+            launch_gn_lin_fused_finalize(d->kind, d->partA, C1, d->ntA, d->partB, d->ntB, B, C, HW, G, d->mr, d->o_tst, d->o_tc, d->o_bs, st);
+            break;
+        }
+        default:
+            if (!need({d->x, d->gamma, d->beta, d->out})) { c->err = null_op; return -2; }
+            launch_ctx_groupnorm(d->x, HW, C, G, d->eps, d->gamma, d->beta, d->out, st);
+            break;
+    }
+    hipError_t he = hipStreamSynchronize(st);
+    if (he == hipSuccess) he = hipGetLastError();
+    if (he != hipSuccess) { c->err = std::string("debug_norm: ") + hipGetErrorString(he); return -1; }
     return 0;
 }
 

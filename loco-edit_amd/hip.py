@@ -20,7 +20,7 @@ _LIB_PATH = os.environ.get("LOCO_HIP_LIB") or os.path.join(os.path.dirname(os.pa
 _lib = None
 
 # diagnostics of include/loco_hip_diag.h: only in a -DLOCO_DIAG build (make -C loco-edit_amd/csrc diag)
-DIAG_SYMBOLS = ["loco_bench_conv", "loco_debug_conv", "loco_debug_attn", "loco_debug_tensor"]
+DIAG_SYMBOLS = ["loco_bench_conv", "loco_debug_conv", "loco_debug_attn", "loco_debug_norm", "loco_debug_tensor"]
 
 # every symbol include/loco_hip.h declares
 SYMBOLS = [
@@ -67,11 +67,29 @@ class LocoConvDesc(C.Structure):
     """loco_conv_desc of include/loco_hip_diag.h (loco_debug_conv): one conv launch on caller-supplied operands."""
     _PTRS = ("weight", "bias", "in", "bias2", "res", "prim", "sc", "sh", "mr", "gamma", "tst", "tc", "in2", "w2", "bias2nd",
              "cot_d", "cot_prim", "cot_sc", "cot_sh", "cot_mr", "cot_tc", "out", "st_prim", "st_mr", "st_out")
+    _ST_PTRS = ("st_gamma", "st_beta", "st_ss_scale", "st_ss_shift", "st_sc", "st_sh", "st_o_mr", "st_o_sc", "st_o_sh", "st_o_tst",
+                "st_o_tc", "st_keep_out")
     _HOST = ("weight", "bias", "w2", "bias2nd")
     _fields_ = ([("struct_size", C.c_int32)] +
                 [(k, C.c_int32) for k in ("Cin", "Cout", "Hin", "Win", "B", "taps", "stride", "upsample", "zins", "mode", "cpg",
                                           "transposed", "accumulate", "in_arena", "pad", "Cin2", "cot_cpg")] +
-                [("res_scale", C.c_float), ("st_cpg", C.c_int32)] + [(k, C.c_void_p) for k in _PTRS] + [("pool2", C.c_int32)])
+                [("res_scale", C.c_float), ("st_cpg", C.c_int32)] + [(k, C.c_void_p) for k in _PTRS] + [("pool2", C.c_int32)] +
+                [("st_kind", C.c_int32), ("st_keep", C.c_int32), ("st_eps", C.c_float), ("st_keep_cap", C.c_int32)] +
+                [(k, C.c_void_p) for k in _ST_PTRS])
+    _PTRS = _PTRS + _ST_PTRS
+
+
+class LocoNormDesc(C.Structure):
+    """loco_norm_desc of include/loco_hip_diag.h (loco_debug_norm): one launch of one standalone GroupNorm launcher."""
+    OPS = {"gn_stats": 0, "gn_tstats": 1, "gn_apply": 2, "gn_cache": 3, "gn_fused_finalize": 4, "gn_fused_finalize_cat": 5,
+           "gn_lin_fused_finalize": 6, "ctx_groupnorm": 7}
+    _PTRS = ("x", "d", "base", "gamma", "beta", "ss_scale", "ss_shift", "sc", "sh", "mr", "tst", "partA", "partB",
+             "o_mr", "o_sc", "o_sh", "o_tst", "o_tc", "out")
+    _fields_ = ([("struct_size", C.c_int32)] +
+                [(k, C.c_int32) for k in ("op", "kind", "act", "B", "C", "HW", "G", "C1", "ntA", "ntB", "accumulate")] +
+                [("eps", C.c_float), ("base_scale", C.c_float)] +
+                [(k, C.c_int64) for k in ("x_bs", "d_bs", "base_bs", "out_bs", "pbs_c", "pbs_g", "o_bs", "t_bs")] +
+                [(k, C.c_void_p) for k in _PTRS])
 
 
 class LocoAttnDesc(C.Structure):
@@ -251,6 +269,8 @@ def load_library():
         lib.loco_debug_conv.argtypes = [vp, C.POINTER(LocoConvDesc), C.c_char_p, i64, vp]
     if hasattr(lib, "loco_debug_attn"):
         lib.loco_debug_attn.argtypes = [vp, C.POINTER(LocoAttnDesc), C.c_char_p, i64, vp]
+    if hasattr(lib, "loco_debug_norm"):
+        lib.loco_debug_norm.argtypes = [vp, C.POINTER(LocoNormDesc), vp]
     _lib = lib
     return lib
 
@@ -778,11 +798,12 @@ class LocoEngine:
                                              _stream()), "loco_bench_conv")
         return float(ms.value)
 
-    def debug_conv(self, out: torch.Tensor, **desc):
+    def debug_conv(self, out: torch.Tensor, with_closing: bool = False, **desc):
         """One conv launch on caller-supplied operands through run_conv -> plan_conv (loco_debug_conv, include/loco_hip_diag.h).
         `desc`: the fields of loco_conv_desc; weight / bias / w2 / bias2nd are CPU float32 tensors, every other operand a
         contiguous float32 device tensor.  Writes `out` and returns (plan, cot_rode): the plan as a list of dicts, one per
-        launch and part, and whether a requested norm-cotangent term rode in the epilogue."""
+        launch and part, and whether a requested norm-cotangent term rode in the epilogue.  with_closing: a third value, the closing
+        line of the (main operator's) plan as a dict (stats_all, keep_ntile)."""
         self._need_diag("loco_debug_conv")
         d = LocoConvDesc()
         d.struct_size = C.sizeof(LocoConvDesc)
@@ -807,10 +828,35 @@ class LocoEngine:
         if rc not in (0, 1):
             self._check(rc, "loco_debug_conv")
         plan = []
+        closing = None
         for line in buf.value.decode().splitlines():
             rec = dict(f.split("=", 1) for f in line.split(" "))
-            plan.append({k: (v if k == "kernel" else int(v)) for k, v in rec.items()})
-        return plan, rc == 0
+            rec = {k: (v if k in ("kernel", "stats") else int(v)) for k, v in rec.items()}
+            if "launch" in rec:
+                plan.append(rec)
+            else:
+                closing = rec
+        return (plan, rc == 0, closing) if with_closing else (plan, rc == 0)
+
+    def debug_norm(self, op: str, **desc):
+        """One launch of one standalone GroupNorm launcher (loco_debug_norm, include/loco_hip_diag.h).  `desc`: the fields of
+        loco_norm_desc; a tensor operand is a contiguous float32 device tensor (or a view into one: strides are the caller's)."""
+        self._need_diag("loco_debug_norm")
+        d = LocoNormDesc()
+        d.struct_size = C.sizeof(LocoNormDesc)
+        d.op, d.base_scale, d.B = LocoNormDesc.OPS[op], 1.0, 1
+        keep = []
+        for k, v in desc.items():
+            if k not in LocoNormDesc._PTRS:
+                if not hasattr(d, k) or k in ("struct_size", "op"):
+                    raise TypeError(f"debug_norm: no descriptor field {k!r}")
+                setattr(d, k, v)
+            elif v is not None:
+                if not (v.is_cuda and v.dtype == torch.float32):
+                    raise TypeError(f"debug_norm: {k} must be a float32 device tensor")
+                keep.append(v)
+                setattr(d, k, v.data_ptr())
+        self._check(self.lib.loco_debug_norm(self._ctx, C.byref(d), _stream()), "loco_debug_norm")
 
     def debug_attn(self, **desc):
         """One pass of one attention stage on caller-supplied tensors through the engine's own attn_* / xa_* functions

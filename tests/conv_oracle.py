@@ -548,11 +548,14 @@ def check_plan(plan, exp, d) -> List[str]:
 
 
 def parse_plan(text: str) -> List[dict]:
-    """the lines of conv_plan_text.h (what loco_debug_conv returns) as dicts; everything but `kernel` is an integer"""
+    """the launch lines of conv_plan_text.h (what loco_debug_conv returns) as dicts; everything but `kernel` and `stats` is an
+    integer.  A plan's closing line (stats_all, keep_ntile; tests/stats_oracle.parse_plan reads it) is no launch and is left out;
+    texts from before the statistics words parse as they did."""
     plan = []
     for line in text.splitlines():
-        rec = dict(f.split("=", 1) for f in line.split(" "))
-        plan.append({k: (v if k == "kernel" else int(v)) for k, v in rec.items()})
+        rec = dict(f.split("=", 1) for f in line.split(" ") if f)
+        if "launch" in rec:
+            plan.append({k: (v if k in ("kernel", "stats") else int(v)) for k, v in rec.items()})
     return plan
 
 
