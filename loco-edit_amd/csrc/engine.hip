@@ -636,6 +636,14 @@ inline void attn_gemm(loco_ctx* c, const GemmArgs& g, hipStream_t st) {
     if (c->prec >= 1 && c->gemm_lowp && gemm_prefers_bf16x3(g)) { attn_note(c, "gemm_bf16x3", &g); launch_gemm_bf16x3(g, st); }
     else attn_gemm_f32(c, g, st);
 }
+// two independent products of one pass: one launch where both are exact-fp32 launches of the small tiling (launch_gemm_pair);
+// the route text has its line per product either way
+inline void attn_gemm_pair(loco_ctx* c, const GemmArgs& g0, const GemmArgs& g1, hipStream_t st) {
+    auto f32 = [&](const GemmArgs& g) { return !attn_gemm_rec(c, g) && !(c->prec >= 1 && c->gemm_lowp && gemm_prefers_bf16x3(g)); };
+    if (!f32(g0) || !f32(g1)) { attn_gemm(c, g0, st); attn_gemm(c, g1, st); return; }
+    attn_note(c, "gemm_f32", &g0); attn_note(c, "gemm_f32", &g1);
+    launch_gemm_pair(g0, g1, st);
+}
 inline void attn_softmax_rows(loco_ctx* c, float* S, long rows, int T, hipStream_t st, int B, long bs) {
     attn_note(c, "softmax_rows"); launch_softmax_rows(S, rows, T, st, B, bs);
 }
@@ -1080,6 +1088,14 @@ void attn_cotangent(const Attn& s) {    // g_o in s.to -> g_q, g_k, g_v in s.tq,
         fa.go = oG; fa.bs_go = s.bo; fa.gq = gq; fa.gk = gk; fa.gv = gv; fa.bs_g = s.bq; fa.delta = s.delta;
         attn_note_flash(c, fa, false);
         launch_attn_flash_cotangent(fa, s.st);
+        return;
+    }
+    if (!s.Lt) {            // g_v, g_P depend on g_o alone and g_q, g_k on g_S alone: one launch per pair where the launches are small
+        attn_gemm_pair(c, attn_keys(s, oG, s.bo, s.OS, SP, 0, gv, s.bq),                                // g_v = g_o P
+                       attn_scores(s, IMAGE, oG, s.bo, s.OS, v, 0, SG, s.bS, 1.f, 0.f), s.st);          // g_P = g_o^T v
+        attn_softmax_jac(c, SG, SP, (long)s.NH * s.T, s.Tk, s.scale, s.st, s.B, s.bS);
+        attn_gemm_pair(c, attn_values(s, IMAGE, k, 0, SG, s.bS, gq, s.bq, s.HS, 0.f),                   // g_q = k g_S^T
+                       attn_keys(s, q, 0, s.HS, SG, s.bS, gk, s.bq), s.st);                             // g_k = q g_S
         return;
     }
     attn_gemm(c, attn_keys(s, oG, s.bo, s.OS, SP, 0, gv, s.bq), s.st);                                  // g_v = g_o P_img

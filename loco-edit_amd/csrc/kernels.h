@@ -240,6 +240,9 @@ struct GemmArgs {
     const float* A2; long sab2; const float* Bm2; long sbb2;
 };
 void launch_gemm(const GemmArgs& g, hipStream_t st);              // exact fp32 (f32-input MFMA)
+// two independent products (no A2 / B2; neither reads what the other writes) as launch_gemm would compute them: one grid
+// when both take the pipelined small tiling (gemm.hip; LOCO_GEMM_GROUP=0: never), else two launches in this order
+void launch_gemm_pair(const GemmArgs& g0, const GemmArgs& g1, hipStream_t st);
 // the same exact-fp32 product on the 64 x 64 tiling whatever the shape, so every output element is the same chain of MFMAs
 // whatever N and the batch are (launch_gemm picks its tiling by grid size), with an activation after the bias (GemmAct;
 // the fc1 of the CLIP text encoder, textenc.hip).  A2 / B2 take no activation.
