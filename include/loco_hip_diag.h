@@ -179,6 +179,48 @@ typedef struct loco_norm_desc {
 } loco_norm_desc;
 int  loco_debug_norm(loco_ctx* ctx, const loco_norm_desc* desc, void* stream);
 
+/* Test hook: ONE call of ONE strided batched GEMM launcher (kernels.h, gemm.hip / gemm_rec.hip) on caller-supplied DEVICE tensors
+ * (tests/test_gpu_gemm_oracle.py compares it with the float64 reference of tests/gemm_oracle.py).
+ *   op 0 launch_gemm          op 1 launch_gemm_fixed (with act: 0 none, 1 quick-GELU, 2 GELU)      op 2 launch_gemm_bf16x3
+ *   op 3 launch_gemm_rec      (the workspace of gemm_rec_ws_bytes is allocated and freed by the call)
+ *   op 4 launch_gemm_pair     (problem slots 0 and 1; every other op uses slot 0)
+ * A problem slot is GemmArgs field by field: out(b, h, m, n) = act(alpha (A B + A2 B2) + beta C + bias[m] + colbias[n] + R), every
+ * stride in floats; A2 / B2 share the row, k and head strides of A / B and have batch strides of their own; R shares C's row, column
+ * and head strides and has its batch stride srb; batch2 (heads) < 1 counts as 1.  n_* is the number of floats the caller owns from
+ * the pointer on.
+ * Refused with an error before any launch: M, N, K or batch < 1; a null A, B or C, A2 without B2; a stride that is negative or
+ * beyond 2^28; an operand whose largest addressed offset (from the dimensions and strides) is not below its n_*; act with A2
+ * (launch_gemm_fixed drops the activation there); op 3 with bias, colbias or R, or with K < 256, M < 128 or N < 256 (the structural
+ * part of gemm_rec_eligible -- its 4e9-MAC threshold is a performance rule and not applied); op 4 with A2 in either slot or with
+ * outputs whose address ranges overlap.
+ *
+ * route (cap bytes, may be null) receives one line per launch, in launch order, written from the predicates the launchers
+ * themselves branch on (gemm_f32_variant, gemm_pair_grouped, gemm_bf16x3_tile, gemm_rec_route):
+ *   "kernel=<name> M=m N=n K=k batch=b heads=h nseg=1|2 akm=0|1 bkm=0|1 tm=t ksplit=s\n"   (akm / bkm: unit stride along m / n;
+ *    tm, ksplit: 0 except for gemm_rec) for gemm_f32_64, gemm_f32_small, gemm_f32_small_pipe, gemm_f32_fixed, gemm_bf16x3_64,
+ *    gemm_bf16x3_128, gemm_rec, and for gemm_f32_pair: the ONE launch of a grouped pair has one such line per problem slot;
+ *   "kernel=rec_split operand=0|1|2|3 kcontig=0|1 z=count\n"  before gemm_rec, per record set (A, B, A2, B2);
+ *   "kernel=gemm_rec_reduce ksplit=s\n"  after a gemm_rec with a K split.
+ * Returns 0; < 0 on errors. */
+typedef struct loco_gemm_prob {
+    const float *A, *B, *A2, *B2, *bias, *colbias, *R;
+    float* C;
+    int64_t sam, sak, sab, sah;
+    int64_t sbk, sbn, sbb, sbh;
+    int64_t scm, scn, scb, sch;
+    int64_t srb, sab2, sbb2;
+    int64_t n_A, n_B, n_A2, n_B2, n_bias, n_colbias, n_R, n_C;
+    int32_t M, N, K, batch, batch2;
+    float   alpha, beta;
+    int32_t pad_;
+} loco_gemm_prob;
+typedef struct loco_gemm_desc {
+    int32_t struct_size;
+    int32_t op, act, pad_;
+    loco_gemm_prob p[2];
+} loco_gemm_desc;
+int  loco_debug_gemm(loco_ctx* ctx, const loco_gemm_desc* desc, char* route, int64_t cap, void* stream);
+
 /* Debug / test hook: copy an internal primal activation ("down.0.block.0" ...)
  * of the last forward/primal call into dst (device), returns element count or <0. */
 int64_t loco_debug_tensor(loco_ctx* ctx, const char* name, float* dst, int64_t cap, void* stream);

@@ -3082,6 +3082,100 @@ int loco_debug_attn(loco_ctx* c, const loco_attn_desc* d, char* route, int64_t c
     return 0;
 }
 
+// loco_debug_gemm: one call of one GEMM launcher on the caller's tensors.  Only the descriptor -> GemmArgs mapping, the bounds of
+// every operand (checked here, before the launch) and the route text live here; the text is written from the functions the
+// launchers branch on.
+int loco_debug_gemm(loco_ctx* c, const loco_gemm_desc* d, char* route, int64_t cap, void* stream) {
+    if (!c) return -2;
+    if (!d || d->struct_size != (int32_t)sizeof(loco_gemm_desc)) { c->err = "debug_gemm: descriptor size mismatch"; return -2; }
+    hipStream_t st = (hipStream_t)stream;
+    const int op = d->op;
+    if (op < 0 || op > 4) { c->err = "debug_gemm: op is 0 ... 4"; return -2; }
+    if (d->act < 0 || d->act > 2 || (d->act && op != 1)) { c->err = "debug_gemm: act is 0 / 1 / 2 and goes with op 1 only"; return -2; }
+    const int nprob = op == 4 ? 2 : 1;
+    GemmArgs g[2];
+    int64_t c_span[2] = {0, 0};
+    for (int i = 0; i < nprob; ++i) {
+        const loco_gemm_prob& p = d->p[i];
+        if (p.M < 1 || p.N < 1 || p.K < 1 || p.batch < 1) { c->err = "debug_gemm: M, N, K and batch must be positive"; return -2; }
+        if (!p.A || !p.B || !p.C || (!p.A2 != !p.B2)) { c->err = "debug_gemm: a required operand is null"; return -2; }
+        const int64_t nb2 = p.batch2 > 0 ? p.batch2 : 1;
+        const int64_t strides[] = {p.sam, p.sak, p.sab, p.sah, p.sbk, p.sbn, p.sbb, p.sbh, p.scm, p.scn, p.scb, p.sch, p.srb, p.sab2, p.sbb2};
+        for (int64_t s : strides)
+            if (s < 0 || s > ((int64_t)1 << 28)) { c->err = "debug_gemm: a stride is negative or beyond 2^28"; return -2; }      // (offsets stay far inside int64)
+        const int64_t M1 = p.M - 1, N1 = p.N - 1, K1 = p.K - 1, B1 = p.batch - 1, H1 = nb2 - 1;
+        const int64_t c_last = M1 * p.scm + N1 * p.scn + H1 * p.sch;
+        auto inside = [&](const void* ptr, int64_t last, int64_t count) { return !ptr || (count > 0 && last < count); };
+        if (!inside(p.A, M1 * p.sam + K1 * p.sak + H1 * p.sah + B1 * p.sab, p.n_A) ||
+            !inside(p.B, K1 * p.sbk + N1 * p.sbn + H1 * p.sbh + B1 * p.sbb, p.n_B) ||
+            !inside(p.A2, M1 * p.sam + K1 * p.sak + H1 * p.sah + B1 * p.sab2, p.n_A2) ||
+            !inside(p.B2, K1 * p.sbk + N1 * p.sbn + H1 * p.sbh + B1 * p.sbb2, p.n_B2) ||
+            !inside(p.C, c_last + B1 * p.scb, p.n_C) || !inside(p.R, c_last + B1 * p.srb, p.n_R) ||
+            !inside(p.bias, M1, p.n_bias) || !inside(p.colbias, N1, p.n_colbias)) {
+            c->err = "debug_gemm: an operand's largest addressed offset is outside its buffer"; return -2;
+        }
+        c_span[i] = c_last + B1 * p.scb + 1;
+        if (d->act && p.A2) { c->err = "debug_gemm: launch_gemm_fixed applies no activation to a two-segment product (act with A2)"; return -2; }
+        if (op == 3 && (p.bias || p.colbias || p.R)) { c->err = "debug_gemm: launch_gemm_rec has no bias, colbias or R"; return -2; }
+        if (op == 3 && (p.K < 256 || p.M < 128 || p.N < 256)) { c->err = "debug_gemm: launch_gemm_rec needs K >= 256, M >= 128, N >= 256"; return -2; }
+        if (op == 4 && p.A2) { c->err = "debug_gemm: launch_gemm_pair takes single-segment problems (A2 set)"; return -2; }
+        GemmArgs& a = g[i];
+        std::memset(&a, 0, sizeof(a));
+        a.A = p.A; a.sam = p.sam; a.sak = p.sak; a.sab = p.sab;
+        a.Bm = p.B; a.sbk = p.sbk; a.sbn = p.sbn; a.sbb = p.sbb;
+        a.C = p.C; a.scm = p.scm; a.scn = p.scn; a.scb = p.scb;
+        a.bias = p.bias; a.colbias = p.colbias; a.R = p.R; a.srb = p.srb;
+        a.M = p.M; a.N = p.N; a.K = p.K; a.batch = p.batch; a.alpha = p.alpha; a.beta = p.beta;
+        a.batch2 = p.batch2; a.sah = p.sah; a.sbh = p.sbh; a.sch = p.sch;
+        a.A2 = p.A2; a.sab2 = p.sab2; a.Bm2 = p.B2; a.sbb2 = p.sbb2;
+    }
+    if (op == 4) {
+        const float *lo0 = g[0].C, *hi0 = lo0 + c_span[0], *lo1 = g[1].C, *hi1 = lo1 + c_span[1];
+        if (lo0 < hi1 && lo1 < hi0) { c->err = "debug_gemm: the outputs of the two problems overlap"; return -2; }
+    }
+    std::string text;
+    auto note = [&](const char* kernel, const GemmArgs& a, int tm, int ksplit) {
+        char line[224];
+        snprintf(line, sizeof(line), "kernel=%s M=%d N=%d K=%d batch=%d heads=%d nseg=%d akm=%d bkm=%d tm=%d ksplit=%d\n", kernel, a.M, a.N,
+                 a.K, a.batch, a.batch2 > 0 ? a.batch2 : 1, a.A2 ? 2 : 1, a.sam == 1 ? 1 : 0, a.sbn == 1 ? 1 : 0, tm, ksplit);
+        text += line;
+    };
+    static const char* const f32_name[3] = {"gemm_f32_64", "gemm_f32_small", "gemm_f32_small_pipe"};
+    void* ws = nullptr;
+    switch (op) {
+        case 0: note(f32_name[gemm_f32_variant(g[0])], g[0], 0, 0); launch_gemm(g[0], st); break;
+        case 1: note("gemm_f32_fixed", g[0], 0, 0); launch_gemm_fixed(g[0], d->act, st); break;
+        case 2: note(gemm_bf16x3_tile(g[0]) == 128 ? "gemm_bf16x3_128" : "gemm_bf16x3_64", g[0], 0, 0); launch_gemm_bf16x3(g[0], st); break;
+        case 3: {
+            const GemmRecRoute rt = gemm_rec_route(g[0]);
+            char line[96];
+            for (int o = 0; o < (g[0].A2 ? 4 : 2); ++o) {
+                snprintf(line, sizeof(line), "kernel=rec_split operand=%d kcontig=%d z=%d\n", o, rt.kcontig[o], rt.z[o]);
+                text += line;
+            }
+            note("gemm_rec", g[0], rt.tm, rt.ksplit);
+            if (rt.ksplit > 1) { snprintf(line, sizeof(line), "kernel=gemm_rec_reduce ksplit=%d\n", rt.ksplit); text += line; }
+            if (hipMalloc(&ws, gemm_rec_ws_bytes(g[0])) != hipSuccess) { (void)hipGetLastError(); c->err = "debug_gemm: workspace allocation failed"; return -1; }
+            launch_gemm_rec(g[0], static_cast<unsigned char*>(ws), st);
+            break;
+        }
+        default:
+            if (gemm_pair_grouped(g[0], g[1])) { note("gemm_f32_pair", g[0], 0, 0); note("gemm_f32_pair", g[1], 0, 0); }
+            else { note(f32_name[gemm_f32_variant(g[0])], g[0], 0, 0); note(f32_name[gemm_f32_variant(g[1])], g[1], 0, 0); }
+            launch_gemm_pair(g[0], g[1], st);
+            break;
+    }
+    hipError_t he = hipStreamSynchronize(st);
+    if (ws) (void)hipFree(ws);
+    if (he == hipSuccess) he = hipGetLastError();
+    if (he != hipSuccess) { c->err = std::string("debug_gemm: ") + hipGetErrorString(he); return -1; }
+    if (route && cap > 0) {
+        if ((int64_t)text.size() + 1 > cap) { c->err = "debug_gemm: route buffer too small"; return -4; }
+        std::memcpy(route, text.c_str(), text.size() + 1);
+    }
+    return 0;
+}
+
 #endif
 
 int loco_set_streams(loco_ctx* c, int32_t n) {

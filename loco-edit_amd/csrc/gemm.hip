@@ -501,10 +501,16 @@ bool gemm_prefers_bf16x3(const GemmArgs& g) {
     return g.K >= 256 && macs >= 4e9;
 }
 
-void launch_gemm_bf16x3(const GemmArgs& g, hipStream_t st) {
+// the 128 x 128 tile where it still gives two rounds of the chip, else 64 x 64
+int gemm_bf16x3_tile(const GemmArgs& g) {
     const int nb = g.batch * (g.batch2 > 0 ? g.batch2 : 1);
     const long big = (long)((g.N + 127) / 128) * ((g.M + 127) / 128) * nb;
-    if (big >= 512 && g.M >= 128 && g.N >= 128) {
+    return big >= 512 && g.M >= 128 && g.N >= 128 ? 128 : 64;
+}
+
+void launch_gemm_bf16x3(const GemmArgs& g, hipStream_t st) {
+    const int nb = g.batch * (g.batch2 > 0 ? g.batch2 : 1);
+    if (gemm_bf16x3_tile(g) == 128) {
         dim3 grid((g.N + 127) / 128, (g.M + 127) / 128, nb);
         if (g.A2) hipLaunchKernelGGL((gemm_bf16x3_kernel<128, 128, 2>), grid, dim3(256), 0, st, g);
         else hipLaunchKernelGGL((gemm_bf16x3_kernel<128, 128, 1>), grid, dim3(256), 0, st, g);
@@ -556,11 +562,18 @@ static void launch_small_pipe2(const GemmArgs& g0, const GemmArgs& g1, dim3 sg, 
     else hipLaunchKernelGGL((gemm_f32_small_pipe2_kernel<AKM0, BKM0, false, false>), sg, dim3(256), 0, st, g0, g1, nz0);
 }
 
-void launch_gemm_pair(const GemmArgs& g0, const GemmArgs& g1, hipStream_t st) {
+int gemm_f32_variant(const GemmArgs& g) {
+    if (!gemm_small_taken(g)) return GEMM_F32_64;
+    return gemm_small_pipe_eligible(g) ? GEMM_F32_SMALL_PIPE : GEMM_F32_SMALL;
+}
+bool gemm_pair_grouped(const GemmArgs& g0, const GemmArgs& g1) {
     static int group_on = -1;      // LOCO_GEMM_GROUP=0: two launches (A/B)
     if (group_on < 0) { const char* e = getenv("LOCO_GEMM_GROUP"); group_on = e ? (atoi(e) != 0) : 1; }
-    if (!group_on || g0.A2 || g1.A2 || !gemm_small_taken(g0) || !gemm_small_taken(g1) || !gemm_small_pipe_eligible(g0) ||
-        !gemm_small_pipe_eligible(g1)) {
+    return group_on && !g0.A2 && !g1.A2 && gemm_f32_variant(g0) == GEMM_F32_SMALL_PIPE && gemm_f32_variant(g1) == GEMM_F32_SMALL_PIPE;
+}
+
+void launch_gemm_pair(const GemmArgs& g0, const GemmArgs& g1, hipStream_t st) {
+    if (!gemm_pair_grouped(g0, g1)) {
         launch_gemm(g0, st);
         launch_gemm(g1, st);
         return;
@@ -576,16 +589,17 @@ void launch_gemm_pair(const GemmArgs& g0, const GemmArgs& g1, hipStream_t st) {
 
 void launch_gemm(const GemmArgs& g, hipStream_t st) {
     const int nz = g.batch * (g.batch2 > 0 ? g.batch2 : 1);
-    if (gemm_small_taken(g)) {
+    const int variant = gemm_f32_variant(g);
+    if (variant != GEMM_F32_64) {
         dim3 sg((g.N + SBN - 1) / SBN, (g.M + SBM - 1) / SBM, nz);
-        if (gemm_small_pipe_eligible(g)) {
+        if (variant == GEMM_F32_SMALL_PIPE) {
             if (g.A2) launch_small_pipe<2>(g, sg, st);
             else launch_small_pipe<1>(g, sg, st);
         } else if (g.A2) hipLaunchKernelGGL(gemm_f32_small_kernel<2>, sg, dim3(256), 0, st, g);
         else hipLaunchKernelGGL(gemm_f32_small_kernel<1>, sg, dim3(256), 0, st, g);
         return;
     }
-    dim3 grid((g.N + GBN - 1) / GBN, (g.M + GBM - 1) / GBM, g.batch * (g.batch2 > 0 ? g.batch2 : 1));
+    dim3 grid((g.N + GBN - 1) / GBN, (g.M + GBM - 1) / GBM, nz);
     if (g.A2) hipLaunchKernelGGL(gemm_f32_kernel<2>, grid, dim3(256), 0, st, g);
     else hipLaunchKernelGGL(gemm_f32_kernel<1>, grid, dim3(256), 0, st, g);
 }

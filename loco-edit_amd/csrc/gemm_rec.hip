@@ -285,10 +285,11 @@ RecPlan rec_plan(const GemmArgs& g) {
     return p;
 }
 
-void split_operand(const float* X, long sr, long sk, long sb, long sh, int R, int K, int zb, int nb2, unsigned char* rec, hipStream_t st) {
+void split_operand(const float* X, long sr, long sk, long sb, long sh, int R, int K, int zb, int nb2, bool kcontig, unsigned char* rec,
+                   hipStream_t st) {
     RecSplitArgs a{X, sr, sk, sb, sh, R, K, nb2, rec};
     dim3 grid((R + 255) / 256, (K + 15) / 16, zb);
-    if (sk == 1) hipLaunchKernelGGL(rec_split_kernel<true>, grid, dim3(256), 0, st, a);
+    if (kcontig) hipLaunchKernelGGL(rec_split_kernel<true>, grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL(rec_split_kernel<false>, grid, dim3(256), 0, st, a);
 }
 
@@ -313,16 +314,27 @@ bool gemm_rec_eligible(const GemmArgs& g) {
 }
 size_t gemm_rec_ws_bytes(const GemmArgs& g) { return rec_plan(g).total; }
 
+GemmRecRoute gemm_rec_route(const GemmArgs& g) {
+    const RecPlan p = rec_plan(g);
+    GemmRecRoute r{};
+    r.tm = p.tm; r.ksplit = p.ksplit;
+    r.z[0] = p.za; r.z[1] = p.zb; r.z[2] = p.za2; r.z[3] = p.zb2;
+    r.kcontig[0] = g.sak == 1; r.kcontig[1] = g.sbk == 1;
+    if (g.A2) { r.kcontig[2] = r.kcontig[0]; r.kcontig[3] = r.kcontig[1]; }
+    return r;
+}
+
 void launch_gemm_rec(const GemmArgs& g, unsigned char* ws, hipStream_t st) {
     const RecPlan p = rec_plan(g);
+    const GemmRecRoute rt = gemm_rec_route(g);
     const int nb2 = g.batch2 > 0 ? g.batch2 : 1;
     unsigned char *ra = ws, *rb = ra + p.a1, *ra2 = rb + p.b1, *rb2 = ra2 + p.a2;
     float* part = reinterpret_cast<float*>(rb2 + p.b2);
-    split_operand(g.A, g.sam, g.sak, g.sab, g.sah, g.M, g.K, p.za, nb2, ra, st);
-    split_operand(g.Bm, g.sbn, g.sbk, g.sbb, g.sbh, g.N, g.K, p.zb, nb2, rb, st);
+    split_operand(g.A, g.sam, g.sak, g.sab, g.sah, g.M, g.K, rt.z[0], nb2, rt.kcontig[0], ra, st);
+    split_operand(g.Bm, g.sbn, g.sbk, g.sbb, g.sbh, g.N, g.K, rt.z[1], nb2, rt.kcontig[1], rb, st);
     if (g.A2) {
-        split_operand(g.A2, g.sam, g.sak, g.sab2, g.sah, g.M, g.K, p.za2, nb2, ra2, st);
-        split_operand(g.Bm2, g.sbn, g.sbk, g.sbb2, g.sbh, g.N, g.K, p.zb2, nb2, rb2, st);
+        split_operand(g.A2, g.sam, g.sak, g.sab2, g.sah, g.M, g.K, rt.z[2], nb2, rt.kcontig[2], ra2, st);
+        split_operand(g.Bm2, g.sbn, g.sbk, g.sbb2, g.sbh, g.N, g.K, rt.z[3], nb2, rt.kcontig[3], rb2, st);
     }
     GemmRecArgs r{};
     const long hbA = (long)p.nck * g.M * 64, hbB = (long)p.nck * g.N * 64;      // bytes of one z of records
@@ -334,11 +346,11 @@ void launch_gemm_rec(const GemmArgs& g, unsigned char* ws, hipStream_t st) {
     }
     r.M = g.M; r.N = g.N; r.nst1 = p.nck; r.nst2 = g.A2 ? p.nck : 0; r.nb2 = nb2; r.Z = g.batch * nb2;
     r.C = g.C; r.scm = g.scm; r.scn = g.scn; r.scb = g.scb; r.sch = g.sch; r.alpha = g.alpha; r.beta = g.beta;
-    r.ksplit = p.ksplit; r.part = part;
-    if (p.tm == 4) launch_rec_tm<4>(r, st); else launch_rec_tm<2>(r, st);
-    if (p.ksplit > 1) {
+    r.ksplit = rt.ksplit; r.part = part;
+    if (rt.tm == 4) launch_rec_tm<4>(r, st); else launch_rec_tm<2>(r, st);
+    if (rt.ksplit > 1) {
         const long MN = (long)g.M * g.N;
-        hipLaunchKernelGGL(gemm_rec_reduce, dim3((unsigned)((MN + 255) / 256), r.Z), dim3(256), 0, st, part, p.ksplit, r.Z, nb2, g.M, g.N,
+        hipLaunchKernelGGL(gemm_rec_reduce, dim3((unsigned)((MN + 255) / 256), r.Z), dim3(256), 0, st, part, rt.ksplit, r.Z, nb2, g.M, g.N,
                            g.C, g.scm, g.scn, g.scb, g.sch, g.alpha, g.beta);
     }
 }

@@ -255,6 +255,16 @@ bool gemm_prefers_bf16x3(const GemmArgs& g);                      // long contra
 bool gemm_rec_eligible(const GemmArgs& g);
 size_t gemm_rec_ws_bytes(const GemmArgs& g);
 void launch_gemm_rec(const GemmArgs& g, unsigned char* ws, hipStream_t st);
+// The launchers' routing decisions as pure host functions: the launchers above branch on exactly these, and the route text of
+// loco_debug_gemm (include/loco_hip_diag.h) is written from them.
+enum GemmF32Variant : int { GEMM_F32_64 = 0, GEMM_F32_SMALL = 1, GEMM_F32_SMALL_PIPE = 2 };
+int  gemm_f32_variant(const GemmArgs& g);                          // the kernel launch_gemm runs
+bool gemm_pair_grouped(const GemmArgs& g0, const GemmArgs& g1);    // launch_gemm_pair: one grid (else two launch_gemm)
+int  gemm_bf16x3_tile(const GemmArgs& g);                          // launch_gemm_bf16x3: 64 or 128
+// launch_gemm_rec: rows per workgroup / 64, K splits (> 1: a reduce pass follows), and per operand record set (A, B, A2, B2; the
+// last two zero without a second segment) the z count it is split for and whether it takes the k-contiguous split kernel
+struct GemmRecRoute { int tm, ksplit, z[4], kcontig[4]; };
+GemmRecRoute gemm_rec_route(const GemmArgs& g);
 
 // ---- tangent / cotangent of multi-head self-attention without per-probe [T x T] matrices (attn_flash.hip) ----
 // All tensors [channel][token] with the engine's strides; q / k / v (and their tangents / cotangents) of head h start

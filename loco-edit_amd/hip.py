@@ -20,7 +20,7 @@ _LIB_PATH = os.environ.get("LOCO_HIP_LIB") or os.path.join(os.path.dirname(os.pa
 _lib = None
 
 # diagnostics of include/loco_hip_diag.h: only in a -DLOCO_DIAG build (make -C loco-edit_amd/csrc diag)
-DIAG_SYMBOLS = ["loco_bench_conv", "loco_debug_conv", "loco_debug_attn", "loco_debug_norm", "loco_debug_tensor"]
+DIAG_SYMBOLS = ["loco_bench_conv", "loco_debug_conv", "loco_debug_attn", "loco_debug_norm", "loco_debug_gemm", "loco_debug_tensor"]
 
 # every symbol include/loco_hip.h declares
 SYMBOLS = [
@@ -98,6 +98,22 @@ class LocoAttnDesc(C.Structure):
     _fields_ = ([("struct_size", C.c_int32)] +
                 [(k, C.c_int32) for k in ("kind", "pass_", "T", "NH", "CH", "B", "Lt", "L", "pair", "no_workspace")] +
                 [(k, C.c_void_p) for k in _PTRS])
+
+
+class LocoGemmProb(C.Structure):
+    """loco_gemm_prob of include/loco_hip_diag.h: one problem slot of loco_debug_gemm, GemmArgs field by field."""
+    _PTRS = ("A", "B", "A2", "B2", "bias", "colbias", "R", "C")
+    _STRIDES = ("sam", "sak", "sab", "sah", "sbk", "sbn", "sbb", "sbh", "scm", "scn", "scb", "sch", "srb", "sab2", "sbb2")
+    _fields_ = ([(k, C.c_void_p) for k in _PTRS] + [(k, C.c_int64) for k in _STRIDES] +
+                [("n_" + k, C.c_int64) for k in ("A", "B", "A2", "B2", "bias", "colbias", "R", "C")] +
+                [(k, C.c_int32) for k in ("M", "N", "K", "batch", "batch2")] + [("alpha", C.c_float), ("beta", C.c_float), ("pad_", C.c_int32)])
+
+
+class LocoGemmDesc(C.Structure):
+    """loco_gemm_desc of include/loco_hip_diag.h (loco_debug_gemm): one call of one GEMM launcher on caller-supplied tensors."""
+    OPS = {"gemm": 0, "gemm_fixed": 1, "gemm_bf16x3": 2, "gemm_rec": 3, "gemm_pair": 4}
+    ACTS = {"none": 0, "quick_gelu": 1, "gelu": 2}
+    _fields_ = [("struct_size", C.c_int32), ("op", C.c_int32), ("act", C.c_int32), ("pad_", C.c_int32), ("p", LocoGemmProb * 2)]
 
 
 class LocoTextCfg(C.Structure):
@@ -271,6 +287,8 @@ def load_library():
         lib.loco_debug_attn.argtypes = [vp, C.POINTER(LocoAttnDesc), C.c_char_p, i64, vp]
     if hasattr(lib, "loco_debug_norm"):
         lib.loco_debug_norm.argtypes = [vp, C.POINTER(LocoNormDesc), vp]
+    if hasattr(lib, "loco_debug_gemm"):
+        lib.loco_debug_gemm.argtypes = [vp, C.POINTER(LocoGemmDesc), C.c_char_p, i64, vp]
     _lib = lib
     return lib
 
@@ -877,6 +895,39 @@ class LocoEngine:
                 setattr(d, k, v.data_ptr())
         buf = C.create_string_buffer(1 << 12)
         self._check(self.lib.loco_debug_attn(self._ctx, C.byref(d), buf, len(buf), _stream()), "loco_debug_attn")
+        route = []
+        for line in buf.value.decode().splitlines():
+            rec = dict(f.split("=", 1) for f in line.split(" "))
+            route.append({k: (v if k == "kernel" else int(v)) for k, v in rec.items()})
+        return route
+
+    def debug_gemm(self, op: str, problems, act: str = "none"):
+        """One call of one GEMM launcher (loco_debug_gemm, include/loco_hip_diag.h).  `problems`: one dict per problem slot (two for
+        "gemm_pair") with the fields of loco_gemm_prob; an operand is a (tensor, offset) pair: a flat float32 device tensor and the
+        float offset of the operand's base inside it -- the pointer is the tensor's plus the offset, n_* what is left of the tensor
+        from there.  Returns the route: one dict per launch line (kernel, and the numbers of that line)."""
+        self._need_diag("loco_debug_gemm")
+        d = LocoGemmDesc()
+        d.struct_size = C.sizeof(LocoGemmDesc)
+        d.op, d.act = LocoGemmDesc.OPS[op], LocoGemmDesc.ACTS[act]
+        keep = []
+        for slot, prob in enumerate(problems):
+            p = d.p[slot]
+            p.alpha, p.batch, p.batch2 = 1.0, 1, 1
+            for k, v in prob.items():
+                if k not in LocoGemmProb._PTRS:
+                    if not hasattr(p, k) or k.startswith("n_"):
+                        raise TypeError(f"debug_gemm: no descriptor field {k!r}")
+                    setattr(p, k, v)
+                elif v is not None:
+                    t, off = v
+                    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 1 and 0 <= off < t.numel()):
+                        raise TypeError(f"debug_gemm: {k} must be (flat float32 device tensor, offset inside it)")
+                    keep.append(t)
+                    setattr(p, k, t.data_ptr() + 4 * off)
+                    setattr(p, "n_" + k, t.numel() - off)
+        buf = C.create_string_buffer(1 << 12)
+        self._check(self.lib.loco_debug_gemm(self._ctx, C.byref(d), buf, len(buf), _stream()), "loco_debug_gemm")
         route = []
         for line in buf.value.decode().splitlines():
             rec = dict(f.split("=", 1) for f in line.split(" "))
