@@ -221,6 +221,52 @@ typedef struct loco_gemm_desc {
 } loco_gemm_desc;
 int  loco_debug_gemm(loco_ctx* ctx, const loco_gemm_desc* desc, char* route, int64_t cap, void* stream);
 
+/* Test hook: ONE launch of ONE token-wise or pointwise launcher (kernels.h; xfmr.hip, misc.hip) on caller-supplied DEVICE tensors
+ * (tests/test_gpu_token_oracle.py compares it with the float64 reference of tests/token_oracle.py).  Strides are in floats and the
+ * caller's; null = absent.  LayerNorm and GEGLU tensors are in the engine's [channel][token] layout.
+ *   op 0  launch_ln_fwd:        x [B][C][T] (in_bs), gamma, beta [C], eps -> out [B][C][T] (out_bs), out2 = stats [B][2][T] (st_bs)
+ *                               = {mean, rstd} per token; out == x with out_bs == in_bs is the in-place call
+ *   op 1  launch_ln_tan:        x = dx [B][C][T] (in_bs), y = the primal [C][T], stats [2][T] (B = 1), gamma -> out [B][C][T] (out_bs)
+ *   op 2  launch_ln_cot:        x = gy (in_bs), y = the primal, stats, gamma, base [B][C][T] (aux_bs) or null -> out = gx (out_bs)
+ *   op 3  launch_geglu:         kind 0: x = f [B][2 count] (in_bs) = [value | gate] -> out [B][count] (out_bs)
+ *                               kind 1: x = df [B][2 count], y = the primal f [2 count] -> out [B][count]
+ *                               kind 2: x = g [B][count], y = the primal f -> out [B][2 count] = [g gelu(gate) | g value gelu'(gate)]
+ *   op 4  launch_temb:          C = ch, n = temb_ch, t, freq [ch / 2], w0 [n][ch], b0 [n], w1 [n][n], b1 [n], add [n] or null,
+ *                               add_in [ch] or null, act (0 SiLU, 1 GELU), cos_first -> out [n].  t_dev (one float) non-null: the call
+ *                               fills it with t (launch_set_scalar) and the kernel reads the timestep from there
+ *   op 5  launch_temb_proj:     x = tact [n], w0 = w [C = cout][n], b0 = bias [cout] or null -> out [cout]
+ *   op 6  launch_pool2x2_sum:   x [B][C][2 H][2 W] (in_bs) -> out [B][C][H][W] (out_bs) (+)= scale * the 2x2 sums; H, W of the OUTPUT
+ *   op 7  launch_upsample2x:    x [B][C][H][W] (in_bs) -> out [B][C][2 H][2 W] (out_bs) (+)= scale * nearest; H, W of the INPUT
+ *   op 8  launch_copy:          x [B][count] (in_bs) -> out [B][count] (out_bs) (+)= x
+ *   op 9  launch_masked_axpby:  x = V [k][count] or null, y = dE [k][count], mask, mask2 [count] (uint8) or null, split, cv, ce -> out = U
+ *   op 10 launch_cot_seed:      x = U [k][count], mask, mask2, split, cv, ce -> out = gE [k][count], out2 = gX0 [k][count] or null
+ *   op 11 launch_ddim_step:     x, y = eps, base = noise or null [count]; f[0 ... 4] = c_x0_x, c_x0_e, c_next_x0, c_next_e, c_noise
+ *                               -> out [count], out2 = x0_out [count] or null
+ *   op 12 launch_latent_sample: x = moments [B][2 count] (mean | logvar), base = noise [B][count] or null, scale -> out = z [B][count]
+ *   op 13 launch_lincomb:       src[0 ... n - 1] [count], f[0 ... n - 1] the coefficients -> out [count]; a source may be out itself
+ *   op 14 launch_add:           x, y [count] -> out [count]
+ * Refused before any launch: an op outside 0 ... 14; B, C, count or k < 1 where the op uses them; a negative stride; a null required
+ * operand.  LayerNorm: T not a positive multiple of 16, st_bs < 2 T with B > 1, an output that overlaps an input (the in-place
+ * ln_fwd excepted).  GEGLU: kind outside 0 ... 2, in_bs / out_bs (B > 1) smaller than the kind reads / writes.  temb: ch + temb_ch
+ * floats beyond the 64 KiB of LDS a workgroup takes without opting in.  pool2x2 / upsample2x: H or W < 1; pool2x2: an odd in_bs or an
+ * x not aligned to 8 bytes (float2 loads).  copy: count, in_bs or out_bs not a multiple of 4, or a pointer not aligned to 16 bytes
+ * (float4).  lincomb: n outside 1 ... 4, a pointer not aligned to 16 bytes.  masked_axpby / cot_seed: split outside [0, k], mask2
+ * without mask. */
+typedef struct loco_pointwise_desc {
+    int32_t struct_size;
+    int32_t op, kind, act, B, C, T, H, W, n, k, accumulate, cos_first;
+    float   eps, scale, t, cv, ce;
+    float   f[5];
+    int32_t pad_;
+    int64_t count, split, in_bs, out_bs, aux_bs, st_bs;
+    const float *x, *y, *stats, *gamma, *beta, *base;
+    const float *freq, *w0, *b0, *w1, *b1, *add, *add_in;
+    const float *src[4];
+    const uint8_t *mask, *mask2;
+    float *out, *out2, *t_dev;
+} loco_pointwise_desc;
+int  loco_debug_pointwise(loco_ctx* ctx, const loco_pointwise_desc* desc, void* stream);
+
 /* Debug / test hook: copy an internal primal activation ("down.0.block.0" ...)
  * of the last forward/primal call into dst (device), returns element count or <0. */
 int64_t loco_debug_tensor(loco_ctx* ctx, const char* name, float* dst, int64_t cap, void* stream);

@@ -2990,6 +2990,125 @@ int loco_debug_norm(loco_ctx* c, const loco_norm_desc* d, void* stream) {
     return 0;
 }
 
+// loco_debug_pointwise: one launch of one token-wise / pointwise launcher on the caller's tensors.  Only the descriptor -> argument
+// mapping and the launchers' contract (checked here, before the launch) live here.
+int loco_debug_pointwise(loco_ctx* c, const loco_pointwise_desc* d, void* stream) {
+    if (!c) return -2;
+    if (!d || d->struct_size != (int32_t)sizeof(loco_pointwise_desc)) { c->err = "debug_pointwise: descriptor size mismatch"; return -2; }
+    hipStream_t st = (hipStream_t)stream;
+    const int op = d->op, B = d->B, C = d->C, T = d->T;
+    const long count = d->count;
+    auto fail = [&](const char* why) { c->err = std::string("debug_pointwise: ") + why; return -2; };
+    auto need = [&](std::initializer_list<const void*> ps) { for (const void* p : ps) if (!p) return false; return true; };
+    auto aligned = [](const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; };
+    // [p, p + n) and [q, q + m) floats share an address
+    auto overlap = [](const float* p, long n, const float* q, long m) { return p && q && p < q + m && q < p + n; };
+    const char* null_op = "a required operand is null";
+    if (op < 0 || op > 14) return fail("op is 0 ... 14");
+    if (d->in_bs < 0 || d->out_bs < 0 || d->aux_bs < 0 || d->st_bs < 0) return fail("a stride is negative");
+    const bool batched = op <= 3 || (op >= 6 && op <= 8) || op == 12;
+    if (batched && B < 1) return fail("B < 1");
+    const bool counted = op == 3 || op >= 8;
+    if (counted && count < 1) return fail("count < 1");
+    switch (op) {
+        case 0: case 1: case 2: {
+            if (C < 1) return fail("C < 1");
+            if (T < 16 || T % 16) return fail("T must be a positive multiple of 16 (a workgroup owns 16 tokens)");
+            if (!need({d->x, d->gamma, d->out}) || (op == 0 ? !need({d->beta, d->out2}) : !need({d->y, d->stats}))) return fail(null_op);
+            const long ext = (long)C * T, xe = (long)(B - 1) * d->in_bs + ext, oe = (long)(B - 1) * d->out_bs + ext;
+            const bool in_place = op == 0 && d->out == d->x && d->out_bs == d->in_bs;
+            if (!in_place && overlap(d->out, oe, d->x, xe)) return fail("the output overlaps an input (only ln_fwd runs in place, out == x with equal strides)");
+            if (op == 0) {
+                if (B > 1 && d->st_bs < 2L * T) return fail("st_bs below 2 T: the statistics of two samples overlap");
+                const long se = (long)(B - 1) * d->st_bs + 2L * T;
+                if (overlap(d->out2, se, d->x, xe) || overlap(d->out2, se, d->out, oe)) return fail("the statistics overlap a tensor");
+                launch_ln_fwd(d->x, d->in_bs, B, C, T, d->gamma, d->beta, d->eps, d->out, d->out_bs, d->out2, d->st_bs, st);
+            } else {
+                if (overlap(d->out, oe, d->y, ext) || overlap(d->out, oe, d->stats, 2L * T)
+                    || overlap(d->out, oe, d->base, (long)(B - 1) * d->aux_bs + ext))
+                    return fail("the output overlaps an input (only ln_fwd runs in place, out == x with equal strides)");
+                if (op == 1) launch_ln_tan(d->x, d->in_bs, d->y, d->stats, B, C, T, d->gamma, d->out, d->out_bs, st);
+                else launch_ln_cot(d->x, d->in_bs, d->y, d->stats, B, C, T, d->gamma, d->base, d->aux_bs, d->out, d->out_bs, st);
+            }
+            break;
+        }
+        case 3: {
+            if (d->kind < 0 || d->kind > 2) return fail("geglu kind is 0 ... 2");
+            if (!need({d->x, d->out}) || (d->kind != 0 && !d->y)) return fail(null_op);
+            const long rd = d->kind == 2 ? count : 2 * count, wr = d->kind == 2 ? 2 * count : count;
+            if (B > 1 && (d->in_bs < rd || d->out_bs < wr)) return fail("in_bs / out_bs smaller than the kind reads / writes (2 n4 or n4)");
+            launch_geglu(d->kind, d->x, d->in_bs, d->y, B, count, d->out, d->out_bs, st);
+            break;
+        }
+        case 4: {
+            if (C < 1 || d->n < 1) return fail("ch or temb_ch < 1");
+            if ((long)C + d->n > 16384) return fail("ch + temb_ch floats exceed the 64 KiB of LDS a workgroup may take");
+            if (d->act != ACT_SILU && d->act != ACT_GELU) return fail("act is 0 (SiLU) or 1 (GELU)");
+            if (!need({d->w0, d->b0, d->w1, d->b1, d->out}) || (C > 1 && !d->freq)) return fail(null_op);
+            if (d->t_dev) launch_set_scalar(d->t_dev, d->t, st);
+            launch_temb(d->t_dev ? 0.f : d->t, C, d->n, d->freq, d->w0, d->b0, d->w1, d->b1, d->out, st, d->cos_first, d->add, d->t_dev,
+                        d->act, d->add_in);
+            break;
+        }
+        case 5:
+            if (C < 1 || d->n < 1) return fail("cout or temb_ch < 1");
+            if (!need({d->x, d->w0, d->out})) return fail(null_op);
+            launch_temb_proj(d->x, d->n, d->w0, d->b0, C, d->out, st);
+            break;
+        case 6: case 7:
+            if (C < 1 || d->H < 1 || d->W < 1) return fail("C, H and W must be positive");
+            if (!need({d->x, d->out})) return fail(null_op);
+            if (op == 6) {
+                if ((d->in_bs & 1) || !aligned(d->x, 8)) return fail("pool2x2 reads float2 pairs: in_bs must be even and x aligned to 8 bytes");
+                launch_pool2x2_sum(d->x, d->in_bs, d->out, d->out_bs, d->accumulate, B, C, d->H, d->W, st, d->scale);
+            } else {
+                launch_upsample2x(d->x, d->in_bs, d->out, d->out_bs, d->accumulate, d->scale, B, C, d->H, d->W, st);
+            }
+            break;
+        case 8:
+            if (!need({d->x, d->out})) return fail(null_op);
+            if ((count | d->in_bs | d->out_bs) & 3) return fail("copy moves float4: per_sample, in_bs and out_bs must be multiples of 4");
+            if (!aligned(d->x, 16) || !aligned(d->out, 16)) return fail("copy moves float4: x and out must be aligned to 16 bytes");
+            launch_copy(d->x, d->in_bs, d->out, d->out_bs, d->accumulate, B, count, st);
+            break;
+        case 9: case 10:
+            if (d->k < 1) return fail("k < 1");
+            if (d->split < 0 || d->split > d->k) return fail("split outside [0, k]");
+            if (d->mask2 && !d->mask) return fail("mask2 without mask");
+            if (!need({d->out}) || (op == 9 ? !d->y : !d->x)) return fail(null_op);
+            if (op == 9) launch_masked_axpby(d->x, d->y, d->mask, d->cv, d->ce, d->out, d->k, count, st, d->mask2, d->split);
+            else launch_cot_seed(d->x, d->mask, d->cv, d->ce, d->out, d->out2, d->k, count, st, d->mask2, d->split);
+            break;
+        case 11:
+            if (!need({d->x, d->y, d->out})) return fail(null_op);
+            launch_ddim_step(d->x, d->y, d->base, d->out, d->out2, count, d->f[0], d->f[1], d->f[2], d->f[3], d->f[4], st);
+            break;
+        case 12:
+            if (!need({d->x, d->out})) return fail(null_op);
+            launch_latent_sample(d->x, d->base, d->scale, d->out, B, count, st);
+            break;
+        case 13: {
+            if (d->n < 1 || d->n > 4) return fail("lincomb takes n = 1 ... 4 sources");
+            if (!d->out) return fail(null_op);
+            if (!aligned(d->out, 16)) return fail("lincomb moves float4: every pointer must be aligned to 16 bytes");
+            for (int i = 0; i < d->n; ++i) {
+                if (!d->src[i]) return fail(null_op);
+                if (!aligned(d->src[i], 16)) return fail("lincomb moves float4: every pointer must be aligned to 16 bytes");
+            }
+            launch_lincomb(d->src, d->f, d->n, d->out, count, st);
+            break;
+        }
+        default:
+            if (!need({d->x, d->y, d->out})) return fail(null_op);
+            launch_add(d->x, d->y, d->out, count, st);
+            break;
+    }
+    hipError_t he = hipStreamSynchronize(st);
+    if (he == hipSuccess) he = hipGetLastError();
+    if (he != hipSuccess) { c->err = std::string("debug_pointwise: ") + hipGetErrorString(he); return -1; }
+    return 0;
+}
+
 // loco_debug_attn: one pass of one attention stage on the caller's tensors, through attn_forward / attn_tangent / attn_cotangent or
 // xa_forward / xa_linear -- the engine's own functions, so the route (flash, record GEMM, bf16x3, fused cross-attention) is the
 // product's.  Only the descriptor -> Attn / XA mapping and the scratch live here.

@@ -870,6 +870,7 @@ __global__ void pool2x2_kernel(const float* in, long in_bs, float* out, long out
         *o = v;
     }
 }
+// contract: the kernel reads float2 pairs -- `in` aligned to 8 bytes and in_bs even (the arenas' 16-byte slots satisfy both)
 void launch_pool2x2_sum(const float* in, long in_bs, float* out, long out_bs, int accumulate, int B, int C,
                         int Hout, int Wout, hipStream_t st, float scale) {
     long per = (long)C * Hout * Wout;
@@ -917,6 +918,7 @@ __global__ void copy_kernel(const float* in, long in_bs, float* out, long out_bs
         *o = v;
     }
 }
+// contract: the kernel moves float4 -- both pointers aligned to 16 bytes, per_sample and both batch strides multiples of 4
 void launch_copy(const float* in, long in_bs, float* out, long out_bs, int accumulate, int B, long per_sample,
                  hipStream_t st) {
     int blocks = (int)((per_sample / 4 + 255) / 256);
@@ -1034,6 +1036,7 @@ __global__ void lincomb_kernel(LinComb lc, float* out, long count) {
         }
     }
 }
+// contract: 1 <= n <= 4 and every pointer aligned to 16 bytes (float4 body; the scalar tail takes count % 4)
 void launch_lincomb(const float* const* src, const float* coef, int n, float* out, long count, hipStream_t st) {
     LinComb lc;
     lc.n = n;

@@ -20,7 +20,8 @@ _LIB_PATH = os.environ.get("LOCO_HIP_LIB") or os.path.join(os.path.dirname(os.pa
 _lib = None
 
 # diagnostics of include/loco_hip_diag.h: only in a -DLOCO_DIAG build (make -C loco-edit_amd/csrc diag)
-DIAG_SYMBOLS = ["loco_bench_conv", "loco_debug_conv", "loco_debug_attn", "loco_debug_norm", "loco_debug_gemm", "loco_debug_tensor"]
+DIAG_SYMBOLS = ["loco_bench_conv", "loco_debug_conv", "loco_debug_attn", "loco_debug_norm", "loco_debug_gemm", "loco_debug_pointwise",
+                "loco_debug_tensor"]
 
 # every symbol include/loco_hip.h declares
 SYMBOLS = [
@@ -90,6 +91,20 @@ class LocoNormDesc(C.Structure):
                 [("eps", C.c_float), ("base_scale", C.c_float)] +
                 [(k, C.c_int64) for k in ("x_bs", "d_bs", "base_bs", "out_bs", "pbs_c", "pbs_g", "o_bs", "t_bs")] +
                 [(k, C.c_void_p) for k in _PTRS])
+
+
+class LocoPointwiseDesc(C.Structure):
+    """loco_pointwise_desc of include/loco_hip_diag.h (loco_debug_pointwise): one launch of one token-wise / pointwise launcher."""
+    OPS = {"ln_fwd": 0, "ln_tan": 1, "ln_cot": 2, "geglu": 3, "temb": 4, "temb_proj": 5, "pool2x2_sum": 6, "upsample2x": 7, "copy": 8,
+           "masked_axpby": 9, "cot_seed": 10, "ddim_step": 11, "latent_sample": 12, "lincomb": 13, "add": 14}
+    _PTRS = ("x", "y", "stats", "gamma", "beta", "base", "freq", "w0", "b0", "w1", "b1", "add", "add_in")
+    _MASKS = ("mask", "mask2")
+    _OUTS = ("out", "out2", "t_dev")
+    _fields_ = ([("struct_size", C.c_int32)] +
+                [(k, C.c_int32) for k in ("op", "kind", "act", "B", "C", "T", "H", "W", "n", "k", "accumulate", "cos_first")] +
+                [(k, C.c_float) for k in ("eps", "scale", "t", "cv", "ce")] + [("f", C.c_float * 5), ("pad_", C.c_int32)] +
+                [(k, C.c_int64) for k in ("count", "split", "in_bs", "out_bs", "aux_bs", "st_bs")] +
+                [(k, C.c_void_p) for k in _PTRS] + [("src", C.c_void_p * 4)] + [(k, C.c_void_p) for k in _MASKS + _OUTS])
 
 
 class LocoAttnDesc(C.Structure):
@@ -287,6 +302,8 @@ def load_library():
         lib.loco_debug_attn.argtypes = [vp, C.POINTER(LocoAttnDesc), C.c_char_p, i64, vp]
     if hasattr(lib, "loco_debug_norm"):
         lib.loco_debug_norm.argtypes = [vp, C.POINTER(LocoNormDesc), vp]
+    if hasattr(lib, "loco_debug_pointwise"):
+        lib.loco_debug_pointwise.argtypes = [vp, C.POINTER(LocoPointwiseDesc), vp]
     if hasattr(lib, "loco_debug_gemm"):
         lib.loco_debug_gemm.argtypes = [vp, C.POINTER(LocoGemmDesc), C.c_char_p, i64, vp]
     _lib = lib
@@ -875,6 +892,38 @@ class LocoEngine:
                 keep.append(v)
                 setattr(d, k, v.data_ptr())
         self._check(self.lib.loco_debug_norm(self._ctx, C.byref(d), _stream()), "loco_debug_norm")
+
+    def debug_pointwise(self, op: str, **desc):
+        """One launch of one token-wise / pointwise launcher (loco_debug_pointwise, include/loco_hip_diag.h).  `desc`: the fields of
+        loco_pointwise_desc; a tensor operand is a float32 device tensor (uint8 for mask / mask2) or a view into one: strides are
+        the caller's.  `f` and `src` are sequences of up to 5 floats / 4 tensors."""
+        self._need_diag("loco_debug_pointwise")
+        P = LocoPointwiseDesc
+        d = P()
+        d.struct_size = C.sizeof(P)
+        d.op, d.B, d.scale = (P.OPS[op] if isinstance(op, str) else int(op)), 1, 1.0
+        keep = []
+
+        def addr(k, v, dtype):
+            if not (torch.is_tensor(v) and v.is_cuda and v.dtype == dtype):
+                raise TypeError(f"debug_pointwise: {k} must be a {dtype} device tensor")
+            keep.append(v)
+            return v.data_ptr()
+        for k, v in desc.items():
+            if k == "f":
+                for i, fv in enumerate(v):
+                    d.f[i] = fv
+            elif k == "src":
+                for i, sv in enumerate(v):
+                    d.src[i] = None if sv is None else addr(k, sv, torch.float32)
+            elif k in P._PTRS or k in P._OUTS or k in P._MASKS:
+                if v is not None:
+                    setattr(d, k, addr(k, v, torch.uint8 if k in P._MASKS else torch.float32))
+            elif not hasattr(d, k) or k in ("struct_size", "op", "pad_"):
+                raise TypeError(f"debug_pointwise: no descriptor field {k!r}")
+            else:
+                setattr(d, k, v)
+        self._check(self.lib.loco_debug_pointwise(self._ctx, C.byref(d), _stream()), "loco_debug_pointwise")
 
     def debug_attn(self, **desc):
         """One pass of one attention stage on caller-supplied tensors through the engine's own attn_* / xa_* functions
