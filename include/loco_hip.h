@@ -167,6 +167,34 @@ int  loco_pmp_jvp(loco_ctx* ctx, const float* V, int32_t k, float* U, void* stre
  * U: dense [k, n] (entries outside the mask are ignored); A: [k, n]. */
 int  loco_pmp_vjp(loco_ctx* ctx, const float* U, int32_t k, float* A, void* stream);
 
+/* --- h-space tap: the U-Net bottleneck h of a denoiser (arch 0 / 1) ---
+ * h is the output of the middle block's last op, PullBackDDPM.get_h(x, t, op='mid', block_idx=0)
+ * (models/ddpm/diffusion.py:203-260); n_h = C*H*W.  The latent decoder and encoder (arch 2 / 3) have no tap: every
+ * entry below refuses them (-2, text in loco_last_error).  Eager launches only: no captured-graph variant. */
+int  loco_h_dims(loco_ctx* ctx, int32_t* C, int32_t* H, int32_t* W);
+/* h_out [B, n_h] = get_h(x, t): the ops up to the tap only.  Invalidates the cached primal, like loco_unet_forward. */
+int  loco_unet_get_h(loco_ctx* ctx, const float* x, float t, int32_t B, float* h_out, void* stream);
+/* eps = PullBackDDPM.forward(x, t, u=dh, op='mid', block_idx=0) (diffusion.py:145-200): h[b] += dh[b] between the tap
+ * op and the op behind it; everything behind the tap sees the shifted h, its GroupNorm statistics included.
+ * dh: device [B, n_h], 16-byte aligned (it is read as float4, like every row the engine copies), NULL = plain forward.
+ * Invalidates the cached primal. */
+int  loco_unet_forward_dh(loco_ctx* ctx, const float* x, float t, int32_t B, const float* dh, float* eps, void* stream);
+/* loco_pmp_primal with the operator that the later loco_pmp_jvp / loco_pmp_vjp calls apply; the next
+ * loco_pmp_primal* call replaces it.
+ *   tap 0: exactly loco_pmp_primal.
+ *   tap 1 (encoder): J = d h / d x_t, [n_h x n_in] (local_encoder_pullback_xt, diffusion.py:484-560).  mask must be
+ *          NULL; at and use_et are not read.  jvp: V [k, n_in] -> U [k, n_h]; vjp: U [k, n_h] -> A [k, n_in].
+ *   tap 2 (decoder): J = mask . c . d eps / d h with x_t, the skip tensors and the embedding held fixed, [n_out x n_h]
+ *          (what get_h_to_e differentiates).  use_et != 0: c = 1 (local_decoder_pullback_xt); use_et == 0:
+ *          c = -sqrt(1 - at) / sqrt(at) (local_x0_decoder_pullback_xt: the x_t term of x0 does not depend on h).
+ *          mask (optional) selects outputs.  jvp: V [k, n_h] -> U [k, n_out]; vjp: U [k, n_out] -> A [k, n_h].
+ * The solver algebra (loco_orthonormalize, loco_qr_rows, loco_convergence_rows, loco_krylov_*) takes rows of up to
+ * max(n_in, n_out, n_h) elements on a context with a tap.  loco_mask_count / loco_mask_gather follow the operator's
+ * output: without a mask L = n_h and rows of n_h floats after a tap 1 primal, n_out otherwise.  V, U and A rows are
+ * read and written as float4: 16-byte aligned pointers. */
+int  loco_pmp_primal_tap(loco_ctx* ctx, const float* x, float t, float at, const uint8_t* mask, int32_t use_et,
+                         int32_t tap, void* stream);
+
 /* Thin SVD re-orthonormalisation of the k x n block (replaces torch.linalg.svd
  * at edit.py:2482): on return A holds Vh (orthonormal rows, descending
  * singular value, sign: largest-|.| entry of each row positive), s[k] the
@@ -199,7 +227,7 @@ int  loco_convergence_rows(loco_ctx* ctx, const float* Vprev, const float* V, in
  * = the QR'd start) and Ustore [m, n_out] (the rows J Q); the context keeps, per `slot` (0 or 1: two solves may be in
  * flight, e.g. the modify-space and null-space solves of one edit), T = Q J^T J Q^T, its Ritz pairs, the Gram of the
  * residual block and the signs of the returned rows, all in double.  1 <= k <= 32, m a multiple of k, m <= 64,
- * n <= C*H*W of the context; every pointer is device memory of the caller; nothing is allocated and the only values
+ * n <= C*H*W of the context (max(C*H*W, n_h) on a context with an h-space tap); every pointer is device memory of the caller; nothing is allocated and the only values
  * meant to be read back per step are the four floats of `stat`:
  *   stat[0], stat[1]  distance and allclose flag of loco_convergence_rows between Y and Yprev (-1, 0 without Yprev)
  *   stat[2]           the largest residual estimate of this step

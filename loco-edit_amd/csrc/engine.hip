@@ -168,6 +168,8 @@ struct loco_ctx {
     // PMP state
     bool primal_ok = false;
     float p_cv = 0.f, p_ce = 0.f;
+    int tap = 0;                   // operator of the cached primal (loco_pmp_primal_tap): 0 x_t -> x0 / eps, 1 x_t -> h, 2 h -> eps
+    long n_ws = 0;                 // longest row the solver algebra takes: max(n_in, n_out, n_h) of a denoiser (n_in where there is no tap)
     uint8_t* mask = nullptr;       // device, [n] (owned copy)
     bool has_mask = false;
     uint8_t* mask2 = nullptr;      // device, [n] (owned copy): mask of the probe rows >= mask2_from (loco_pmp_set_second_mask)
@@ -1120,8 +1122,12 @@ void lin1x1(loco_ctx* c, const ConvP& w, bool dgrad, const float* in, long in_bs
 }
 
 // ------------------------------ forward ------------------------------------
+// `op_hi` >= 0: stop after that op (the encoder half of loco_unet_get_h and of the encoder tap's primal).  `dh` [B][n_h]: added to
+// the tap tensor h as the tap op writes it -- the op is an identity-shortcut ResBlock, out = conv2(..) + in, so conv2 takes
+// in + dh (staged in the block's cotangent scratch a1, idle in a forward pass) as its residual and the statistics its epilogue
+// delivers or keeps for the norm over cat([h, skip]) are those of the modified h, on the launch list of the plain forward.
 int forward_pass(loco_ctx* c, const float* x, float t, int B, float* arena, float* stats, hipStream_t st,
-                 const float* t_ptr = nullptr) {
+                 const float* t_ptr = nullptr, int op_hi = -1, const float* dh = nullptr) {
     const loco_unet_cfg& cfg = c->cfg;
     Pass p{c, st, B, arena, stats};
     const long SB = c->prog->stats_per_sample;
@@ -1132,7 +1138,9 @@ int forward_pass(loco_ctx* c, const float* x, float t, int B, float* arena, floa
                     c->has_cond ? c->cond_add : nullptr, t_ptr, cfg.act, c->has_tcond ? c->cond_in : nullptr);
         launch_temb_proj(c->tact, cfg.ch * 4, c->wts->tp_w, c->wts->tp_b, (int)c->wts->tproj_total, c->tproj, st);
     }
-    for (auto& op : c->ops) {
+    const int op_end = op_hi >= 0 ? op_hi : (int)c->ops.size() - 1;
+    for (int oi = 0; oi <= op_end; ++oi) {
+        Op& op = c->ops[oi];
         const Tens& to = c->tens[op.out];
         const int HW = to.H * to.W;
         switch (op.kind) {
@@ -1191,6 +1199,10 @@ int forward_pass(loco_ctx* c, const float* x, float t, int B, float* arena, floa
                 }
                 NS s2 = nstats(c, stats, op.n2);
                 const float* xin = op.updown ? p.T(op.xu) : p.T(op.in);   // shortcut input after x_upd
+                if (dh && oi == c->prog->h_last_op) {                     // h + dh: (xin + dh / res_scale + conv2) * res_scale
+                    launch_add_rows(xin, p.bs(), dh, c->prog->n_h, 1.f / c->prog->res_scale, p.T(op.a1), p.bs(), B, c->prog->n_h, st);
+                    xin = p.T(op.a1);
+                }
                 ConvArgs n; conv_defaults(n);                             // the 1x1 shortcut (diffusion.py:887-912), if any
                 if (op.has_nin) {
                     n.in = xin; n.in_bs = p.bs(); n.Cin = ti.C; n.Hin = to.H; n.Win = to.W;
@@ -1337,7 +1349,9 @@ void set_tan(loco_ctx* c, ConvArgs& a, const NormP& n, const float* prim) {
 
 constexpr size_t RED_BYTES = (size_t)4 << 20;   // reduction scratch (GN partial sums)
 
-int tangent_pass(loco_ctx* c, const float* V, int B, hipStream_t st) {
+// ops op_lo..op_hi (op_hi < 0: the last).  A pass that starts behind the encoder half (op_lo > 0: the decoder tap) finds the
+// tangent of h and of the skip tensors in arena T (loco_pmp_jvp puts them there); V is not read.
+int tangent_pass(loco_ctx* c, const float* V, int B, hipStream_t st, int op_lo = 0, int op_hi = -1) {
     const loco_unet_cfg& cfg = c->cfg;
     const long PS = c->prog->per_sample;
     auto TP = [&](int id) { return c->arenaP + c->tens[id].off; };   // primal
@@ -1354,7 +1368,9 @@ int tangent_pass(loco_ctx* c, const float* V, int B, hipStream_t st) {
         }
         return r;
     };
-    for (auto& op : c->ops) {
+    const int op_end = op_hi >= 0 ? op_hi : (int)c->ops.size() - 1;
+    for (int oi = op_lo; oi <= op_end; ++oi) {
+        Op& op = c->ops[oi];
         const Tens& to = c->tens[op.out];
         const int HW = to.H * to.W;
         switch (op.kind) {
@@ -1529,7 +1545,10 @@ void cot_stats(loco_ctx* c, const NormP& n, const float* d, long dbs, const floa
 }
 
 // ge: cotangent of eps [B][n]; result A[B][n] = conv_in^T(...) + gx0
-int cotangent_pass(loco_ctx* c, const float* ge, const float* gx0, float* Aout, int B, hipStream_t st) {
+// ops op_hi (< 0: the last) down to op_lo.  A pass that starts at the tap (op_hi = h_last_op) finds the cotangent of h and zeros in
+// the skip slots in arena T; one that stops behind it (op_lo = h_last_op + 1) leaves the cotangent of h there (loco_pmp_vjp).
+int cotangent_pass(loco_ctx* c, const float* ge, const float* gx0, float* Aout, int B, hipStream_t st, int op_lo = 0,
+                   int op_hi = -1) {
     const loco_unet_cfg& cfg = c->cfg;
     const long PS = c->prog->per_sample;
     const int G = cfg.gn_groups;
@@ -1539,7 +1558,7 @@ int cotangent_pass(loco_ctx* c, const float* ge, const float* gx0, float* Aout, 
     auto GO = [&](const Op& o) -> const float* { return o.out == c->prog->eps_t ? ge : TG(o.out); };
     auto GOS = [&](const Op& o) -> long { return o.out == c->prog->eps_t ? (long)c->prog->n_out : PS; };
     clear_ready(c);
-    for (int oi = (int)c->ops.size() - 1; oi >= 0; --oi) {
+    for (int oi = op_hi >= 0 ? op_hi : (int)c->ops.size() - 1; oi >= op_lo; --oi) {
         Op& op = c->ops[oi];
         const Tens& to = c->tens[op.out];
         const int HW = to.H * to.W;
@@ -1794,6 +1813,13 @@ int run_lanes(loco_ctx* c, int B, hipStream_t st, F body) {      // body(first s
     HIPCHK(c, hipStreamWaitEvent(st, c->ev_join, 0));
     return 0;
 }
+// The skip tensors' rows of arena T (this lane's samples) set to zero, for the passes over half of the program: the decoder tangent
+// pass reads them as the skips' tangents (x_t fixed: zero), the encoder cotangent pass accumulates into them (nothing wrote them first).
+void tap_zero_skips(loco_ctx* c, int B, hipStream_t st) {
+    for (const Tens& t : c->tens)
+        if (t.cat_of >= 0 && c->tens[t.cat_of].cat_b == (int)(&t - c->tens.data()))
+            launch_zero_rows(c->arenaT + t.off, c->prog->per_sample, B, (long)t.C * t.H * t.W, st);
+}
 // Per-context state of the program's tensors and ops, in this context's views of them: the one place that allocates it, for a
 // created and a forked context alike.
 int alloc_state(loco_ctx* c) {
@@ -1855,10 +1881,11 @@ int create_ctx(loco_ctx* c, const loco_unet_cfg* cfg, std::shared_ptr<const Prog
     if (dalloc(c, &c->xin_buf, MB * c->prog->n_in) || dalloc(c, &c->t_dev, 4)) return -1;
     if (dalloc(c, &c->eps_buf, MB * c->prog->n_out) || dalloc(c, &c->gx0, MB * c->prog->n_in) || dalloc(c, &c->ge, MB * c->prog->n_out))
         return -1;
-    if (dalloc(c, &c->tmpA, (size_t)64 * c->prog->n_in)) return -1;
+    c->n_ws = std::max((long)c->prog->n_in, (long)c->prog->n_h);      // (a network with a tap is a denoiser: n_out = n_in)
+    if (dalloc(c, &c->tmpA, (size_t)64 * c->n_ws)) return -1;
     if (dalloc(c, &c->G, 64 * 64) || dalloc(c, &c->Q, 64 * 64) || dalloc(c, &c->W, SOLVER_W_GATE + 1)) return -1;
     {
-        size_t nblk = ((size_t)c->prog->n_in + 255) / 256;
+        size_t nblk = ((size_t)c->n_ws + 255) / 256;
         if (dalloc(c, &c->gscratch, nblk * 64 * 64 + 4096)) return -1;
     }
     if (dalloc(c, &c->kry[0], KRY_STATE) || dalloc(c, &c->kry[1], KRY_STATE)) return -1;
@@ -2035,6 +2062,55 @@ int loco_unet_forward(loco_ctx* c, const float* x, float t, int32_t B, float* ep
     return 0;
 }
 
+// ---- h-space tap: the bottleneck tensor h of a denoiser, read, shifted, and differentiated to and from ----
+static int tap_refuse(loco_ctx* c, const char* who) {
+    if (c->prog->h_t >= 0) return 0;
+    c->err = std::string(who) + ": this network has no h-space tap (the latent decoder and encoder, arch 2 / 3, have no U-Net bottleneck)";
+    return -2;
+}
+
+int loco_h_dims(loco_ctx* c, int32_t* C_, int32_t* H, int32_t* W) {
+    if (!c) return -2;
+    if (tap_refuse(c, "loco_h_dims")) return -2;
+    const TensPlan& t = c->prog->tens[c->prog->h_t];
+    if (C_) *C_ = t.C;
+    if (H) *H = t.H;
+    if (W) *W = t.W;
+    return 0;
+}
+
+int loco_unet_get_h(loco_ctx* c, const float* x, float t, int32_t B, float* h_out, void* stream) {
+    if (!c) return -2;
+    if (tap_refuse(c, "loco_unet_get_h")) return -2;
+    if (B < 1 || B > c->cfg.max_batch) { c->err = "batch exceeds max_batch"; return -2; }
+    if (finalize_params(c)) return -3;
+    hipStream_t st = (hipStream_t)stream;
+    c->primal_ok = false;
+    if (forward_pass(c, x, t, B, c->arenaP, c->statsP, st, nullptr, c->prog->h_last_op)) return -1;
+    c->primal_B = 0;      // no whole forward pass in the arena: the tensors behind the tap were not written
+    launch_copy(c->arenaP + c->tens[c->prog->h_t].off, c->prog->per_sample, h_out, c->prog->n_h, 0, B, c->prog->n_h, st);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+int loco_unet_forward_dh(loco_ctx* c, const float* x, float t, int32_t B, const float* dh, float* eps, void* stream) {
+    if (!c) return -2;
+    if (tap_refuse(c, "loco_unet_forward_dh")) return -2;
+    if (B < 1 || B > c->cfg.max_batch) { c->err = "batch exceeds max_batch"; return -2; }
+    if (finalize_params(c)) return -3;
+    {
+        const Op& op = c->ops[c->prog->h_last_op];
+        if (op.kind != OP_RES || op.has_nin || op.updown) { c->err = "loco_unet_forward_dh: the tap op is not an identity-shortcut ResBlock"; return -2; }
+    }
+    hipStream_t st = (hipStream_t)stream;
+    c->primal_ok = false;
+    if (forward_pass(c, x, t, B, c->arenaP, c->statsP, st, nullptr, -1, dh)) return -1;
+    c->primal_B = B;
+    launch_copy(c->arenaP + c->tens[c->prog->eps_t].off, c->prog->per_sample, eps, c->prog->n_out, 0, B, c->prog->n_out, st);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
 static void sched_coeffs(float at, float at_next, float eta, float* s1, float* s2, float* s3, float* ce, float* cn) {
     // fp32 arithmetic in the op order of reference utils.py:362-374
     *s1 = std::sqrt(1.0f - at); *s2 = std::sqrt(at); *s3 = std::sqrt(at_next);
@@ -2072,19 +2148,32 @@ int loco_ddim_step(loco_ctx* c, const float* x, float t, float at, float at_next
 
 int loco_pmp_primal(loco_ctx* c, const float* x, float t, float at, const uint8_t* mask, int32_t use_et,
                     void* stream) {
+    return loco_pmp_primal_tap(c, x, t, at, mask, use_et, 0, stream);
+}
+
+int loco_pmp_primal_tap(loco_ctx* c, const float* x, float t, float at, const uint8_t* mask, int32_t use_et, int32_t tap,
+                        void* stream) {
     if (!c) return -2;
+    if (tap < 0 || tap > 2) { c->err = "loco_pmp_primal_tap: tap must be 0 (x_t -> x0 / eps), 1 (encoder, x_t -> h) or 2 (decoder, h -> eps)"; return -2; }
+    if (tap && tap_refuse(c, "loco_pmp_primal_tap")) return -2;
+    if (tap == 1 && mask) { c->err = "loco_pmp_primal_tap: the encoder tap (x_t -> h) takes no mask: h has no pixel positions to select"; return -2; }
     if (finalize_params(c)) return -3;
+    if (tap == 1) use_et = 1;     // (no x0 combination at the tap: `at` and use_et are not read)
     if (c->prog->n_out != c->prog->n_in && !use_et) {
         c->err = "loco_pmp_primal: a network whose output size differs from its input has no x0 combination; use_et = 1 "
                  "(raw network Jacobian)";
         return -2;
     }
     hipStream_t st = (hipStream_t)stream;
-    if (forward_pass(c, x, t, 1, c->arenaP, c->statsP, st)) return -1;
+    // the ops whose linearisation the products of this primal run: all, the encoder half, or the decoder half (whose primal needs
+    // the whole forward pass)
+    const int op_lo = tap == 2 ? c->prog->h_last_op + 1 : 0, op_hi = tap == 1 ? c->prog->h_last_op : (int)c->ops.size() - 1;
+    if (forward_pass(c, x, t, 1, c->arenaP, c->statsP, st, nullptr, tap == 1 ? op_hi : -1)) return -1;
     c->primal_B = 1;
     if (c->prec >= 1) {
         // {S, xhat} cache for the tangent / cotangent staging of the split-bf16 convs
-        for (auto& op : c->ops) {
+        for (int oi = op_lo; oi <= op_hi; ++oi) {
+            Op& op = c->ops[oi];
             if (op.kind != OP_RES && op.kind != OP_OUT) continue;
             const Tens& ti = c->tens[op.in];
             const int HW = ti.H * ti.W, G = c->cfg.gn_groups;
@@ -2101,9 +2190,11 @@ int loco_pmp_primal(loco_ctx* c, const float* x, float t, float at, const uint8_
     }
     if (use_et) { c->p_cv = 0.f; c->p_ce = 1.f; }
     else { c->p_cv = 1.0f / std::sqrt(at); c->p_ce = -std::sqrt(1.0f - at) / std::sqrt(at); }
+    if (tap == 2) c->p_cv = 0.f;   // x0 = (x_t - sqrt(1 - at) eps) / sqrt(at): the x_t term does not depend on h
+    c->tap = tap;
     c->has_mask = (mask != nullptr);
     c->has_mask2 = false;
-    c->mask_L = c->prog->n_out;
+    c->mask_L = tap == 1 ? c->prog->n_h : c->prog->n_out;      // width of the rows of J V without a mask
     if (mask) {
         // masked-latent gather list built on the device (ordered prefix-sum compaction, one launch, no host sync);
         // L is read back lazily by loco_mask_count / loco_mask_gather
@@ -2137,6 +2228,21 @@ int loco_pmp_jvp(loco_ctx* c, const float* V, int32_t k, float* U, void* stream)
     for (int b0 = 0; b0 < k; b0 += MB) {
         int B = (k - b0 < MB) ? k - b0 : MB;
         int rc = run_lanes(c, B, st, [&](int s0, int nb, hipStream_t ls) -> int {
+            const Program& P = *c->prog;
+            if (c->tap == 1) {         // x_t -> h: the encoder half, then the tap tangent out of the arena
+                if (tangent_pass(c, V + (long)(b0 + s0) * P.n_in, nb, ls, 0, P.h_last_op)) return -1;
+                launch_copy(c->arenaT + c->tens[P.h_t].off, P.per_sample, U + (long)(b0 + s0) * P.n_h, P.n_h, 0, nb, P.n_h, ls);
+                return 0;
+            }
+            if (c->tap == 2) {         // h -> eps with x_t, the skips and the embedding fixed: V is the tap tangent, the skips' are zero
+                tap_zero_skips(c, nb, ls);
+                launch_copy(V + (long)(b0 + s0) * P.n_h, P.n_h, c->arenaT + c->tens[P.h_t].off, P.per_sample, 0, nb, P.n_h, ls);
+                if (tangent_pass(c, nullptr, nb, ls, P.h_last_op + 1)) return -1;
+                launch_copy(c->arenaT + c->tens[P.eps_t].off, P.per_sample, c->eps_buf, P.n_out, 0, nb, P.n_out, ls);
+                launch_masked_axpby(nullptr, c->eps_buf, c->has_mask ? c->mask : nullptr, 0.f, c->p_ce, U + (long)(b0 + s0) * P.n_out, nb,
+                                    P.n_out, ls, c->has_mask2 ? c->mask2 : nullptr, (long)c->mask2_from - (b0 + s0));
+                return 0;
+            }
             const float* Vc = V + (long)(b0 + s0) * c->prog->n_in;
             if (tangent_pass(c, Vc, nb, ls)) return -1;
             // U = mask * (cv*V + ce*dEps); dEps lives strided in arena T -> gather through eps_buf
@@ -2160,6 +2266,19 @@ int loco_pmp_vjp(loco_ctx* c, const float* U, int32_t k, float* A, void* stream)
     for (int b0 = 0; b0 < k; b0 += MB) {
         int B = (k - b0 < MB) ? k - b0 : MB;
         int rc = run_lanes(c, B, st, [&](int s0, int nb, hipStream_t ls) -> int {
+            const Program& P = *c->prog;
+            if (c->tap == 1) {         // h -> x_t: U seeds the tap cotangent; the skip slots the encoder ops accumulate into start at zero
+                tap_zero_skips(c, nb, ls);
+                launch_copy(U + (long)(b0 + s0) * P.n_h, P.n_h, c->arenaT + c->tens[P.h_t].off, P.per_sample, 0, nb, P.n_h, ls);
+                return cotangent_pass(c, nullptr, nullptr, A + (long)(b0 + s0) * P.n_in, nb, ls, 0, P.h_last_op);
+            }
+            if (c->tap == 2) {         // eps -> h: the decoder half, then the tap cotangent out of the arena
+                launch_cot_seed(U + (long)(b0 + s0) * P.n_out, c->has_mask ? c->mask : nullptr, 0.f, c->p_ce, c->ge, nullptr, nb, P.n_out,
+                                ls, c->has_mask2 ? c->mask2 : nullptr, (long)c->mask2_from - (b0 + s0));
+                if (cotangent_pass(c, c->ge, nullptr, nullptr, nb, ls, P.h_last_op + 1)) return -1;
+                launch_copy(c->arenaT + c->tens[P.h_t].off, P.per_sample, A + (long)(b0 + s0) * P.n_h, P.n_h, 0, nb, P.n_h, ls);
+                return 0;
+            }
             const bool same = c->prog->n_out == c->prog->n_in;
             launch_cot_seed(U + (long)(b0 + s0) * c->prog->n_out, c->has_mask ? c->mask : nullptr, c->p_cv, c->p_ce, c->ge,
                             same ? c->gx0 : nullptr, nb, c->prog->n_out, ls, c->has_mask2 ? c->mask2 : nullptr,
@@ -2174,7 +2293,7 @@ int loco_pmp_vjp(loco_ctx* c, const float* U, int32_t k, float* A, void* stream)
 
 int loco_orthonormalize(loco_ctx* c, float* A, int32_t k, int64_t n, float* s, void* stream) {
     if (!c) return -2;
-    if (k < 1 || k > 64 || n > c->prog->n_in) { c->err = "orthonormalize: need k <= 64 and n <= C*H*W"; return -2; }
+    if (k < 1 || k > 64 || n > c->n_ws) { c->err = "orthonormalize: need k <= 64 and n <= max(C*H*W, n_h) of the context"; return -2; }
     hipStream_t st = (hipStream_t)stream;
     launch_gram(A, k, n, c->G, c->gscratch, st);
     launch_jacobi_eig(c->G, k, c->W, c->Q, st);
@@ -2197,7 +2316,7 @@ int loco_orthonormalize(loco_ctx* c, float* A, int32_t k, int64_t n, float* s, v
 
 int loco_qr_rows(loco_ctx* c, float* A, int32_t k, int64_t n, void* stream) {
     if (!c) return -2;
-    if (k < 1 || k > 64 || n > c->prog->n_in) { c->err = "qr_rows: need k <= 64 and n <= C*H*W"; return -2; }
+    if (k < 1 || k > 64 || n > c->n_ws) { c->err = "qr_rows: need k <= 64 and n <= max(C*H*W, n_h) of the context"; return -2; }
     hipStream_t st = (hipStream_t)stream;
     for (int rep = 0; rep < 2; ++rep) {   // CholeskyQR2
         launch_gram(A, k, n, c->G, c->gscratch, st);
@@ -2222,10 +2341,10 @@ int loco_convergence_rows(loco_ctx* c, const float* Vprev, const float* V, int32
     if (!c) return -2;
     if (k < 1 || k > 64 || n < 1) { c->err = "convergence_rows: need 1 <= k <= 64"; return -2; }
     // the kernel leaves k * min(64, ceil(n / 256)) * 4 doubles in gscratch, which is sized for rows of the context's own width
-    if (n > c->prog->n_in) { c->err = "convergence_rows: rows longer than the context's input"; return -2; }
+    if (n > c->n_ws) { c->err = "convergence_rows: rows longer than max(C*H*W, n_h) of the context"; return -2; }
     {
         const size_t nseg = (size_t)((n + 255) / 256) < 64 ? (size_t)((n + 255) / 256) : 64;
-        const size_t cap = (((size_t)c->prog->n_in + 255) / 256) * 64 * 64 + 4096;       // doubles in gscratch (finalize_params)
+        const size_t cap = (((size_t)c->n_ws + 255) / 256) * 64 * 64 + 4096;       // doubles in gscratch (finalize_params)
         if ((size_t)k * nseg * 4 > cap) { c->err = "convergence_rows: k rows of this length exceed the reduction workspace"; return -2; }
     }
     launch_convergence_rows(Vprev, V, k, n, atol, 1e-5f, out2, c->gscratch, (hipStream_t)stream);
@@ -2239,7 +2358,7 @@ static const char* krylov_sizes(loco_ctx* c, int32_t k, int32_t m, int64_t n, in
     if (k < 1 || k > KRYLOV_MAX_BLOCK) return "krylov: need 1 <= k <= 32 (two blocks must fit in 64 rows)";
     if (m < k || m > 64 || m % k != 0) return "krylov: m must be a multiple of k with k <= m <= 64";
     if (n < 1) return "krylov: empty rows";
-    if (n_is_input && n > c->prog->n_in) return "krylov: rows longer than the context's input";
+    if (n_is_input && n > c->n_ws) return "krylov: rows longer than max(C*H*W, n_h) of the context";
     return nullptr;
 }
 
@@ -2351,8 +2470,9 @@ int loco_mask_gather(loco_ctx* c, const float* U, int32_t k, float* out, void* s
     if (!c) return -2;
     if (!c->primal_ok) { c->err = "loco_pmp_primal has not been called"; return -2; }
     hipStream_t st = (hipStream_t)stream;
-    if (!c->has_mask) {
-        HIPCHK(c, hipMemcpyAsync(out, U, (size_t)k * c->prog->n_out * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (!c->has_mask) {      // rows of J V as they are: n_h wide for the encoder tap (which takes no mask), else n_out
+        const size_t w = c->tap == 1 ? c->prog->n_h : c->prog->n_out;
+        HIPCHK(c, hipMemcpyAsync(out, U, (size_t)k * w * sizeof(float), hipMemcpyDeviceToDevice, st));
         return 0;
     }
     const long L = mask_count_lazy(c);

@@ -402,6 +402,10 @@ void launch_upsample2x(const float* in, long in_bs, float* out, long out_bs, int
 // strided copy / add of [B][C][HW] tensors
 void launch_copy(const float* in, long in_bs, float* out, long out_bs, int accumulate,
                  int B, long per_sample, hipStream_t st);
+// out[b] = in[b] + scale * add[b], and out[b] = 0: B rows of per_sample floats with their own batch strides (launch_copy's float4 contract)
+void launch_add_rows(const float* in, long in_bs, const float* add, long add_bs, float scale, float* out, long out_bs, int B,
+                     long per_sample, hipStream_t st);
+void launch_zero_rows(float* out, long out_bs, int B, long per_sample, hipStream_t st);
 
 // ---- DDIM / x0 algebra --------------------------------------------------------
 void launch_ddim_step(const float* x, const float* eps, const float* noise, float* out, float* x0_out, long count,

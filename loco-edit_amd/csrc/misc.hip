@@ -928,6 +928,37 @@ void launch_copy(const float* in, long in_bs, float* out, long out_bs, int accum
                        per_sample);
 }
 
+// h-space tap (loco_unet_forward_dh, the tap operators of loco_pmp_jvp / loco_pmp_vjp): out[b] = in[b] + scale * add[b] over
+// rows with their own batch strides, and the zero-fill of one tensor's rows in an arena.  Same float4 contract as launch_copy.
+__global__ void add_rows_kernel(const float* in, long in_bs, const float* add, long add_bs, float scale, float* out, long out_bs,
+                                long per) {
+    const int b = blockIdx.y;
+    for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < per; i += (long)gridDim.x * blockDim.x * 4) {
+        const float4 v = *reinterpret_cast<const float4*>(in + (long)b * in_bs + i);
+        const float4 d = *reinterpret_cast<const float4*>(add + (long)b * add_bs + i);
+        *reinterpret_cast<float4*>(out + (long)b * out_bs + i) =
+            make_float4(v.x + scale * d.x, v.y + scale * d.y, v.z + scale * d.z, v.w + scale * d.w);
+    }
+}
+void launch_add_rows(const float* in, long in_bs, const float* add, long add_bs, float scale, float* out, long out_bs, int B,
+                     long per_sample, hipStream_t st) {
+    int blocks = (int)((per_sample / 4 + 255) / 256);
+    if (blocks > 2048) blocks = 2048;
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(add_rows_kernel, dim3(blocks, B), dim3(256), 0, st, in, in_bs, add, add_bs, scale, out, out_bs, per_sample);
+}
+__global__ void zero_rows_kernel(float* out, long out_bs, long per) {
+    const int b = blockIdx.y;
+    for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < per; i += (long)gridDim.x * blockDim.x * 4)
+        *reinterpret_cast<float4*>(out + (long)b * out_bs + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+void launch_zero_rows(float* out, long out_bs, int B, long per_sample, hipStream_t st) {
+    int blocks = (int)((per_sample / 4 + 255) / 256);
+    if (blocks > 2048) blocks = 2048;
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(zero_rows_kernel, dim3(blocks, B), dim3(256), 0, st, out, out_bs, per_sample);
+}
+
 // ---------------------------------------------------------------------------
 // DDIM update, op order of reference utils.py:362-374:
 //   P = (x - e*c_x0_e)/c_x0_x ; next = c_next_x0*P + c_next_e*e (+ c_noise*noise)

@@ -74,6 +74,11 @@ struct Program {
     int n_in = 0;                  // C*H*W of the network input (image / latent)
     int n_out = 0;                 // C*H*W of the network output (= n_in for the denoisers; the decoded image for arch 2)
     int eps_t = -1;                // tensor id of the network output
+    // h-space tap (the reference's get_h(op='mid', block_idx=0)): the output of the middle block's last op, which is the first part
+    // of the first up-path concatenation.  -1 / -1 / 0 for the latent decoder and encoder (arch 2, 3), which have no tap.
+    int h_t = -1;                  // tensor id of h
+    int h_last_op = -1;            // index of the op that writes it: ops 0..h_last_op are the encoder half, the rest the decoder half
+    int n_h = 0;                   // C*H*W of h
     int ctx_Lp = 0;                // context length padded to a multiple of 64 (score row length of the cross-attention)
     long attn_dmax = 1;            // heads * tokens of the largest attention
     long max_tensor = 0;           // C*H*W of the largest tensor

@@ -59,6 +59,11 @@ struct Builder {
         return false;
     }
     int push(const OpPlan& op) { p.ops.push_back(op); return op.out; }
+    // the h-space tap: `tid` is the output of the op pushed last (the middle block's last op)
+    void tap(int tid) {
+        const TensPlan& t = p.tens[tid];
+        p.h_t = tid; p.h_last_op = (int)p.ops.size() - 1; p.n_h = t.C * t.H * t.W;
+    }
 
     // plain conv ops: CONV_IN (in = -1), CONV, DOWN, UP; the parameter stem is the op's name
     OpPlan conv_op(OpKind kind, const std::string& name, int in_t, int out_t) {
@@ -219,6 +224,7 @@ bool Builder::ddpm(std::string* err) {
         cur = attn("mid.attn_1", cur, a_out);
     }
     cur = resblock("mid.block_2", cur, s.hprev[0]);
+    tap(cur);
     int j = 0;
     for (int l = nres - 1; l >= 0; --l) {
         const int block_out = ch * cfg.ch_mult[l];
@@ -281,6 +287,7 @@ bool Builder::adm_unet(std::string* err) {
         cur = attn("middle_block.1", cur, a_out);
     }
     cur = resblock("middle_block.2", cur, s.hprev[0]);
+    tap(cur);
     int j = 0;
     for (int l = nlev - 1; l >= 0; --l) {
         for (int i = 0; i < cfg.num_res_blocks + 1; ++i, ++j) {

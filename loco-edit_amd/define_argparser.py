@@ -156,6 +156,12 @@ def build_parser():
                    help="basis solver (sets LOCO_SOLVER): 'power' block power iteration (default, the reference's loop), 'krylov' "
                         "block Krylov with Rayleigh-Ritz over all iterates: same two passes per step, stops on its own test, at most "
                         "32 probes per solve; writes <basis name>_residual.json next to each basis it computes")
+    p.add_argument('--jacobian_target', type=str, default='x0', choices=['x0', 'h'],
+                   help="--run_edit_null_space_projection: what the modify-space basis is the pullback of. 'x0' (default): the "
+                        "masked posterior mean, LOCO. 'h': the U-Net bottleneck (the Pullback baseline, d h / d x_t, no mask in that "
+                        "solve); the null-space solve, projection, edit walk and --vT_path are the same, basis and result names "
+                        "gain an -hspace tag. Unconditional models, --run_edit_null_space_projection and the power "
+                        "solver only: refused with another driver or with --solver krylov")
     return p
 
 
@@ -163,6 +169,15 @@ def parse_args(argv=None):
     args = build_parser().parse_args(argv)
     if args.solver:
         os.environ["LOCO_SOLVER"] = args.solver
+    if args.jacobian_target == 'h':
+        if any(s in args.model_name for s in ('stable-diffusion', 'DeepFloyd', 'LCM')):
+            raise ValueError("--jacobian_target h is built for the unconditional models (the T-LOCO classes differentiate a "
+                             "classifier-free-guidance combination)")
+        if not args.run_edit_null_space_projection:
+            raise ValueError("--jacobian_target h is read by --run_edit_null_space_projection only: no other driver solves for a basis")
+        if os.environ.get("LOCO_SOLVER", "power") == "krylov":
+            raise ValueError("--jacobian_target h runs the power iteration: the block Krylov solver (--solver krylov / LOCO_SOLVER) "
+                             "is not wired to the h-space operators")
     if args.text_encoder_path and args.prompt_emb_path:
         raise ValueError("--text_encoder_path and --prompt_emb_path both give the prompt embeddings: pass one of them")
     if args.max_batch <= 0:
@@ -170,7 +185,8 @@ def parse_args(argv=None):
         # sized by what actually shares a pass: the probes of the modify-space and null-space solves when they run as a
         # pair (solver.local_basis_pair; not with LOCO_PAIR_SOLVES=0, without projection or with a loaded basis), and the
         # edited frames of all shown directions in the decode (vis_num_pc x (2 vis_num + 1) frames at most)
-        pair = (args.null_space_projection and not args.vT_path and os.environ.get("LOCO_PAIR_SOLVES", "1") != "0")
+        pair = (args.null_space_projection and not args.vT_path and os.environ.get("LOCO_PAIR_SOLVES", "1") != "0"
+                and args.jacobian_target == 'x0')
         probes = args.pca_rank + (args.pca_rank_null if pair else 0)
         frames = args.pca_rank * (2 * max(int(args.vis_num), 1) + 1)     # main.py passes vis_num_pc = pca_rank
         args.max_batch = 8 if t2i else min(32, max(8, probes, frames))

@@ -220,6 +220,50 @@ class EditUncondDiffusion(object):
             info=self.last_solver_info)
         return u, s, vT
 
+    # h-space baselines of the reference's own denoiser class (models/ddpm/diffusion.py:484-707): Pullback (x_t -> h) and the
+    # decoder Jacobians h -> eps / h -> x0 with x_t and the skips fixed.  Argument names as there; ``op`` / ``block_idx`` must
+    # name the bottleneck ('mid', 0: the only tap the reference's get_h_to_e implements), ``chunk_size`` is accepted and ignored
+    # (the engine chunks by its max_batch).  ``s`` is sigma of J, as local_encoder_decoder_pullback_xt returns it.
+    def _h_pullback(self, target, x, t, op, block_idx, pca_rank, min_iter, max_iter, convergence_threshold, mask, noise, v0,
+                    verbose):
+        if op not in (None, 'mid') or block_idx not in (None, 0):
+            raise NotImplementedError(f"h-space tap (op, block_idx) = ({op!r}, {block_idx!r}): only ('mid', 0) is built")
+        x = x.to(device=self.device, dtype=torch.float32).contiguous()
+        at = self.scheduler.alpha_at(t)
+        self.last_solver_info = {}
+        u, s, vT, self.last_n_iter = solver.local_basis(
+            self.engine, x, t, at, pca_rank, mask=mask, noise=noise, min_iter=min_iter, max_iter=max_iter,
+            convergence_threshold=convergence_threshold, v0=v0, sharder=self.sharder, verbose=verbose,
+            info=self.last_solver_info, target=target)      # (LOCO_SOLVER=krylov: refused by local_basis for these targets)
+        return u, s, vT
+
+    def local_encoder_pullback_xt(self, x=None, t=None, op=None, block_idx=None, pca_rank=16, chunk_size=25,
+                                  min_iter=10, max_iter=100, convergence_threshold=1e-3, v0=None, verbose=True):
+        """diffusion.py:484-556 -> (u [n_h, k] = (J V_prev)^T, s [k], vT [k, n]) for J = d h / d x_t."""
+        return self._h_pullback("h_enc", x, t, op, block_idx, pca_rank, min_iter, max_iter, convergence_threshold, None, True, v0,
+                                verbose)
+
+    def local_decoder_pullback_xt(self, x=None, t=None, op=None, block_idx=None, pca_rank=50, chunk_size=10,
+                                  min_iter=10, max_iter=100, convergence_threshold=1e-3, mask=None, v0=None, verbose=True):
+        """diffusion.py:558-632 for J = d eps / d h -> (u, s, vT) with the reference's swapped names: ``u`` [n_h, k] are the
+        h-space directions (the right singular rows, transposed), ``vT`` [k, n_out] the rows J V_prev (:631).  ``mask``
+        (an extension) selects outputs: ``vT`` is then [k, L]."""
+        eT, s, hT = self._h_pullback("h_dec", x, t, op, block_idx, pca_rank, min_iter, max_iter, convergence_threshold, mask, True,
+                                     v0, verbose)
+        return hT.T.contiguous(), s, eT.T.contiguous()
+
+    def local_x0_decoder_pullback_xt(self, x=None, t=None, at=None, op=None, block_idx=None, pca_rank=50, chunk_size=10,
+                                     num_chunk=None, min_iter=10, max_iter=100, convergence_threshold=1e-3, mask=None, v0=None,
+                                     verbose=True):
+        """diffusion.py:634-707 for J = d x0_hat / d h = -sqrt(1 - at) / sqrt(at) . d eps / d h; names as
+        ``local_decoder_pullback_xt``.  ``at`` is the scheduler's alpha-bar at ``t`` (the argument is accepted for the
+        reference's signature and must agree with it when given)."""
+        if at is not None and abs(float(at) - float(self.scheduler.alpha_at(t))) > 1e-6:
+            raise ValueError(f"at = {float(at)} is not the scheduler's alpha-bar at t ({float(self.scheduler.alpha_at(t))})")
+        eT, s, hT = self._h_pullback("h_dec", x, t, op, block_idx, pca_rank, min_iter, max_iter, convergence_threshold, mask, False,
+                                     v0, verbose)
+        return hT.T.contiguous(), s, eT.T.contiguous()
+
     # ------------------------------------------------------------------ drivers
     @torch.no_grad()
     def group_edit_null_space_projection(self, idx, **kwargs):
@@ -315,12 +359,16 @@ class EditUncondDiffusion(object):
             tag = self.args.choose_sem if self.dataset_name in ("CelebA_HQ_mask", "Synthetic") else self.args.mask_index
             save_dir = os.path.join(self.result_folder, "basis", f'local_basis-{self.edit_t}T-select-mask-{tag}')
             os.makedirs(save_dir, exist_ok=True)
-            vT_modify_path = os.path.join(save_dir, f'vT-modify-pca-rank-{pca_rank}.pt')
+            # --jacobian_target h: the modify space is the Pullback basis (right singular rows of d h / d x_t, no mask); its
+            # files carry a tag so that a cached x0 basis is never taken for it.  The null-space solve is the x0 one either way.
+            hspace = getattr(self.args, "jacobian_target", "x0") == "h"
+            htag = "-hspace" if hspace else ""
+            vT_modify_path = os.path.join(save_dir, f'vT-modify-pca-rank-{pca_rank}{htag}.pt')
             vT_null_path = os.path.join(save_dir, f'vT-null-{pca_rank_null}.pt')
 
             vT_null = None
             have_m, have_n = self._exists(vT_modify_path), self._exists(vT_null_path)
-            if null_space_projection and mask is not None and not have_m and not have_n and self.pair_solves:
+            if null_space_projection and mask is not None and not have_m and not have_n and self.pair_solves and not hspace:
                 # both bases are missing: one pass carries the probes of both solves (solver.local_basis_pair)
                 print('subspace solves: modify space + null space (shared probe batches)')
                 at = self.scheduler.alpha_at(t)
@@ -336,6 +384,11 @@ class EditUncondDiffusion(object):
                     self._save_residuals(vT_null_path, pair_info[1])
             elif have_m:
                 vT_modify = self._load(vT_modify_path, map_location=self.device).to(self.device).type(self.dtype)
+            elif hspace:
+                print('subspace solve: modify space (h-space pullback, d h / d x_t)')
+                u_modify, s_modify, vT_modify = self.local_encoder_pullback_xt(
+                    x=xt, t=t, op=op, block_idx=block_idx, pca_rank=pca_rank, min_iter=10, max_iter=50, convergence_threshold=1e-4)
+                self._save(vT_modify, vT_modify_path)
             else:
                 print('subspace solve: modify space')
                 u_modify, s_modify, vT_modify = self.local_encoder_decoder_pullback_xt(
@@ -365,7 +418,7 @@ class EditUncondDiffusion(object):
             else:
                 vT = self.engine.null_project(vT_modify.contiguous(), vT_null[:pca_rank_null, :].contiguous())
             BASIS_NAME = (f"{encoder_decoder_by_et}_{tag}-edit_{self.edit_t}T_null_proj_{null_space_projection}"
-                          f"_rank{pca_rank_null}_scale_{self.x_space_guidance_scale}")
+                          f"_rank{pca_rank_null}_scale_{self.x_space_guidance_scale}{htag}")
             # the reference loops range(max(vis_num_pc, vT.shape[0])) (edit.py:2329) and would raise
             # IndexError for vis_num_pc > rank; main.py always passes vis_num_pc == pca_rank
             for pc_idx in range(min(max(vis_num_pc, vT.shape[0]), vT.shape[0])):

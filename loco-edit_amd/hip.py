@@ -35,6 +35,7 @@ SYMBOLS = [
     "loco_text_create", "loco_text_load_param", "loco_text_params_missing", "loco_text_encode", "loco_text_last_error",
     "loco_text_destroy", "loco_t5_create", "loco_text_encode_masked",
     "loco_diffedit_mask", "loco_cfg_masked_step", "loco_set_time_cond", "loco_lcm_step",
+    "loco_h_dims", "loco_unet_get_h", "loco_unet_forward_dh", "loco_pmp_primal_tap",
     "loco_sam_create", "loco_sam_load_param", "loco_sam_params_missing", "loco_sam_encode", "loco_sam_profile",
     "loco_sam_profile_read", "loco_sam_last_error", "loco_sam_destroy",
     "loco_samdec_create", "loco_samdec_load_param", "loco_samdec_params_missing", "loco_samdec_set_image", "loco_samdec_predict",
@@ -44,6 +45,9 @@ SYMBOLS = [
     "loco_quality_create", "loco_quality_load_param", "loco_quality_params_missing", "loco_quality_lpips", "loco_quality_ssim",
     "loco_quality_masked_mse", "loco_quality_last_error", "loco_quality_destroy",
 ]
+
+# operators of loco_pmp_primal_tap (include/loco_hip.h): None x_t -> x0 / eps, "enc" x_t -> h, "dec" h -> eps
+TAPS = {None: 0, "enc": 1, "dec": 2}
 
 # threshold rules of loco_diffedit_mask (include/loco_hip.h)
 DIFFEDIT_RULES = {"reference": 0, "intended": 1}
@@ -199,6 +203,10 @@ def load_library():
     lib.loco_sched_step.argtypes = [vp, vp, vp, f32, f32, f32, vp, i64, vp, vp, vp]
     lib.loco_pmp_primal.argtypes = [vp, vp, f32, f32, vp, i32, vp]
     lib.loco_pmp_set_second_mask.argtypes = [vp, vp, i32, vp]
+    lib.loco_h_dims.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    lib.loco_unet_get_h.argtypes = [vp, vp, f32, i32, vp, vp]
+    lib.loco_unet_forward_dh.argtypes = [vp, vp, f32, i32, vp, vp, vp]
+    lib.loco_pmp_primal_tap.argtypes = [vp, vp, f32, f32, vp, i32, i32, vp]
     lib.loco_pmp_jvp.argtypes = [vp, vp, i32, vp, vp]
     lib.loco_pmp_vjp.argtypes = [vp, vp, i32, vp, vp]
     lib.loco_orthonormalize.argtypes = [vp, vp, i32, i64, vp, vp]
@@ -369,6 +377,7 @@ class LocoEngine:
             raise RuntimeError(f"loco_create failed ({rc}): {msg}")
         self.n = cfg.n              # elements of the network input (image / latent)
         self.n_out = cfg.n_out      # elements of its output (= n for the denoisers; the decoded image for arch "dec")
+        self._tap = None            # operator of the cached primal (pmp_primal(tap=...)): the row widths of pmp_jvp / pmp_vjp
 
     def fork(self, max_batch: Optional[int] = None) -> "LocoEngine":
         """A second engine context on THIS engine's parameters (loco_fork): shares the device copies of the weights in every
@@ -378,6 +387,7 @@ class LocoEngine:
         child.lib, child.cfg, child.device = self.lib, self.cfg, self.device
         child.max_batch = int(max_batch or self.max_batch)
         child.n, child.n_out = self.n, self.n_out
+        child._tap = None
         for k, v in self.__dict__.items():      # host-side settings (stream mode ...) that __init__ derives from the arguments
             if k not in child.__dict__ and k != "_ctx":
                 child.__dict__[k] = v
@@ -423,9 +433,45 @@ class LocoEngine:
         if x.dim() != 4 or tuple(x.shape[1:]) != want:
             raise ValueError(f"input must be [B, {want[0]}, {want[1]}, {want[2]}], got {tuple(x.shape)}")
 
-    def unet_forward(self, x: torch.Tensor, t: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    # ---- h-space tap (loco_hip.h "h-space tap"): the U-Net bottleneck of a denoiser
+    @property
+    def h_shape(self):
+        """(C, H, W) of the bottleneck tensor h = get_h(x, t, 'mid', 0); the latent decoder / encoder have none (RuntimeError)."""
+        d = [C.c_int32(), C.c_int32(), C.c_int32()]
+        self._check(self.lib.loco_h_dims(self._ctx, *[C.byref(v) for v in d]), "loco_h_dims")
+        return tuple(int(v.value) for v in d)
+
+    @property
+    def n_h(self) -> int:
+        c, h, w = self.h_shape
+        return c * h * w
+
+    def get_h(self, x: torch.Tensor, t: float) -> torch.Tensor:
+        """h [B, C, H, W] of ``x`` [B, in_channels, R, R]: the ops up to the tap only."""
         _chk_dev(x)
         self._chk_input(x)
+        h = torch.empty(x.shape[0], *self.h_shape, device=x.device, dtype=torch.float32)
+        self._check(self.lib.loco_unet_get_h(self._ctx, _ptr(x), float(t), x.shape[0], _ptr(h), _stream()), "loco_unet_get_h")
+        return h
+
+    def _rows(self, side: str) -> int:
+        """Row width of the operator of the cached primal: ``in`` of pmp_jvp's V and pmp_vjp's A, ``out`` of the other two."""
+        if self._tap == "enc":
+            return self.n if side == "in" else self.n_h
+        if self._tap == "dec":
+            return self.n_h if side == "in" else self.n_out
+        return self.n if side == "in" else self.n_out
+
+    def unet_forward(self, x: torch.Tensor, t: float, out: Optional[torch.Tensor] = None,
+                     dh: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``dh`` [B, n_h] (any shape with B * n_h elements): added to the bottleneck tensor of each sample, the reference's
+        ``forward(x, t, u=dh, op='mid', block_idx=0)``."""
+        _chk_dev(x)
+        self._chk_input(x)
+        if dh is not None:
+            _chk_dev(dh)
+            if dh.numel() != x.shape[0] * self.n_h:
+                raise ValueError(f"dh must hold {x.shape[0]} x {self.n_h} elements, got {tuple(dh.shape)}")
         if out is not None:
             _chk_dev(out)
             if out.numel() != x.shape[0] * self.n_out:
@@ -436,6 +482,10 @@ class LocoEngine:
                               device=x.device, dtype=torch.float32)
         else:
             eps = torch.empty_like(x)
+        if dh is not None:
+            self._check(self.lib.loco_unet_forward_dh(self._ctx, _ptr(x), float(t), x.shape[0], _ptr(dh), _ptr(eps), _stream()),
+                        "loco_unet_forward_dh")
+            return eps
         self._check(self.lib.loco_unet_forward(self._ctx, _ptr(x), float(t), x.shape[0], _ptr(eps), _stream()),
                     "loco_unet_forward")
         return eps
@@ -461,7 +511,11 @@ class LocoEngine:
         return out, x0
 
     # ---- PMP-Jacobian operator
-    def pmp_primal(self, x, t, at, mask: Optional[torch.Tensor] = None, use_et: bool = False):
+    def pmp_primal(self, x, t, at, mask: Optional[torch.Tensor] = None, use_et: bool = False, tap: Optional[str] = None):
+        """``tap``: None (J = d x0_hat[mask] / d x_t), ``"enc"`` (J = d h / d x_t, no mask) or ``"dec"`` (J = mask . c . d eps / d h);
+        pmp_jvp / pmp_vjp take and return rows of that operator's widths until the next pmp_primal."""
+        if tap not in TAPS:
+            raise ValueError(f"tap must be None, 'enc' or 'dec', got {tap!r}")
         _chk_dev(x)
         if x.numel() != self.n:
             raise ValueError(f"the linearisation point is one sample of {self.n} elements, got {tuple(x.shape)}")
@@ -471,6 +525,12 @@ class LocoEngine:
             if m8.numel() != self.n_out:
                 raise ValueError("mask must have C*H*W elements (of the network output)")
         self._mask_keepalive = m8
+        if tap is not None:
+            self._check(self.lib.loco_pmp_primal_tap(self._ctx, _ptr(x), float(t), float(at), _ptr(m8), int(use_et), TAPS[tap],
+                                                     _stream()), "loco_pmp_primal_tap")
+            self._tap = tap
+            return
+        self._tap = None
         self._check(self.lib.loco_pmp_primal(self._ctx, _ptr(x), float(t), float(at), _ptr(m8), int(use_et),
                                              _stream()), "loco_pmp_primal")
 
@@ -489,22 +549,28 @@ class LocoEngine:
         stream first, so no allocation happens under the side stream)."""
         _chk_dev(V)
         k = V.shape[0]
-        U = torch.empty(k, self.n_out, device=V.device, dtype=torch.float32) if out is None else out
+        n_out = self._rows("out")
+        if self._tap is not None and (V.dim() != 2 or V.shape[1] != self._rows("in")):
+            raise ValueError(f"V must be [k, {self._rows('in')}] for the '{self._tap}' tap, got {tuple(V.shape)}")
+        U = torch.empty(k, n_out, device=V.device, dtype=torch.float32) if out is None else out
         if out is not None:
             _chk_dev(out)
-            if tuple(out.shape) != (k, self.n_out):
-                raise ValueError(f"out must be {(k, self.n_out)}, got {tuple(out.shape)}")
+            if tuple(out.shape) != (k, n_out):
+                raise ValueError(f"out must be {(k, n_out)}, got {tuple(out.shape)}")
         self._check(self.lib.loco_pmp_jvp(self._ctx, _ptr(V), k, _ptr(U), _stream()), "loco_pmp_jvp")
         return U
 
     def pmp_vjp(self, U: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         _chk_dev(U)
         k = U.shape[0]
-        A = torch.empty(k, self.n, device=U.device, dtype=torch.float32) if out is None else out
+        n_in = self._rows("in")
+        if self._tap is not None and (U.dim() != 2 or U.shape[1] != self._rows("out")):
+            raise ValueError(f"U must be [k, {self._rows('out')}] for the '{self._tap}' tap, got {tuple(U.shape)}")
+        A = torch.empty(k, n_in, device=U.device, dtype=torch.float32) if out is None else out
         if out is not None:
             _chk_dev(out)
-            if tuple(out.shape) != (k, self.n):
-                raise ValueError(f"out must be {(k, self.n)}, got {tuple(out.shape)}")
+            if tuple(out.shape) != (k, n_in):
+                raise ValueError(f"out must be {(k, n_in)}, got {tuple(out.shape)}")
         self._check(self.lib.loco_pmp_vjp(self._ctx, _ptr(U), k, _ptr(A), _stream()), "loco_pmp_vjp")
         return A
 

@@ -57,14 +57,22 @@ def _converged(algebra, V_prev, V, thr):
 
 
 class JacobianOperator:
-    """J and J^T products on the HIP engine for a fixed (x, t, mask)."""
+    """J and J^T products on the HIP engine for a fixed (x, t, mask).
 
-    def __init__(self, engine, x: torch.Tensor, t, at: float, mask: Optional[torch.Tensor], noise: bool = False):
+    ``tap``: None -- J = d x0_hat[mask] / d x_t; ``"enc"`` -- J = d h / d x_t (rows of J V have the bottleneck's width n_h, no
+    mask); ``"dec"`` -- J = mask . c . d eps / d h with x_t and the skips fixed (rows of V and J^T U have the width n_h)."""
+
+    def __init__(self, engine, x: torch.Tensor, t, at: float, mask: Optional[torch.Tensor], noise: bool = False,
+                 tap: Optional[str] = None):
         self.engine = engine
-        self.n = engine.n
-        self.n_out = engine.n_out      # width of the rows of J V (= n for the pixel-space denoisers)
+        self.tap = tap
+        self.n = engine.n_h if tap == "dec" else engine.n
+        self.n_out = engine.n_h if tap == "enc" else engine.n_out      # width of the rows of J V (= n for the pixel-space denoisers)
         self.masked = mask is not None
-        engine.pmp_primal(x.contiguous(), float(t), at, mask, use_et=noise)
+        if tap is None:
+            engine.pmp_primal(x.contiguous(), float(t), at, mask, use_et=noise)
+        else:
+            engine.pmp_primal(x.contiguous(), float(t), at, mask, use_et=noise, tap=tap)
 
     def check_mask(self):
         """The gather list is built on the device and its length L is read back lazily (no host sync at the start
@@ -295,11 +303,21 @@ def write_residuals(basis_path: str, info: Optional[dict]):
     return path
 
 
+# local_basis targets -> the engine's tap
+H_TARGETS = {"x0": None, "h_enc": "enc", "h_dec": "dec"}
+
+
 def local_basis(engine, x, t, at, pca_rank: int, mask=None, noise=False, min_iter=10, max_iter=100,
                 convergence_threshold=1e-3, v0: Optional[torch.Tensor] = None,
                 sharder: Optional[ProbeSharder] = None, verbose=True, stop_rule: Optional[str] = None,
-                solver: Optional[str] = None, info: Optional[dict] = None):
+                solver: Optional[str] = None, info: Optional[dict] = None, target: str = "x0"):
     """Top-``pca_rank`` right singular subspace of J (edit.py:2406-2504).
+
+    ``target``: ``"x0"`` -- J = d x0_hat[mask] / d x_t (``noise``: d eps instead); ``"h_enc"`` -- J = d h / d x_t, the
+    reference's ``local_encoder_pullback_xt`` (models/ddpm/diffusion.py:484-556; no mask; ``u`` is [n_h, k]); ``"h_dec"`` --
+    J = mask . d eps / d h with ``noise`` (``local_decoder_pullback_xt``, :558-632) or mask . d x0_hat / d h without
+    (``local_x0_decoder_pullback_xt``, :634-707); ``vT`` is [k, n_h] and ``u`` [L, k] (n_out without a mask).  The h-space
+    targets run the power iteration only: ``solver="krylov"`` is refused for them.
 
     ``v0``: optional [n, k] Gaussian matrix standing in for the ``torch.randn``
     draw of edit.py:2435 (parity tests inject it).  Returns (u [L,k], s [k],
@@ -307,14 +325,24 @@ def local_basis(engine, x, t, at, pca_rank: int, mask=None, noise=False, min_ite
     root of the singular values of A = U^T J (edit.py:2500).  ``solver``: ``power`` | ``krylov`` (``solve_basis``);
     ``info`` receives the Krylov solver's residuals.
     """
-    n = engine.n
+    if target not in H_TARGETS:
+        raise ValueError(f"target must be one of {sorted(H_TARGETS)}, got {target!r}")
+    tap = H_TARGETS[target]
+    if tap is not None and _pick_solver(solver) == "krylov":
+        raise ValueError("the block Krylov solver is not wired to the h-space operators (its stores are sized for x_t -> x0); "
+                         "use solver='power' for target 'h_enc' / 'h_dec'")
+    if tap == "enc" and mask is not None:
+        raise ValueError("target 'h_enc' takes no mask: h has no pixel positions to select")
+    n = engine.n_h if tap == "dec" else engine.n
     dev = x.device
     time_s = time.time()
     if v0 is None:
         v0 = torch.randn(n, pca_rank, device=dev, dtype=torch.float32)      # edit.py:2435
+    if tuple(v0.shape) != (n, pca_rank) and tap is not None:
+        raise ValueError(f"v0 must be [{n}, {pca_rank}] for target {target!r}, got {tuple(v0.shape)}")
     V = v0.to(device=dev, dtype=torch.float32).T.contiguous()               # rows = probes
     engine.qr_rows_(V)                                                       # edit.py:2436 (thin QR)
-    op = JacobianOperator(engine, x, t, at, mask, noise)
+    op = JacobianOperator(engine, x, t, at, mask, noise) if tap is None else JacobianOperator(engine, x, t, at, mask, noise, tap=tap)
     U, s, V, n_iter = solve_basis(op, engine, V, min_iter, max_iter, convergence_threshold, sharder=sharder,
                                   verbose=verbose, stop_rule=stop_rule, solver=solver, info=info)
     op.check_mask()
