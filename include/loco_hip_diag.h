@@ -1,8 +1,9 @@
 /* Diagnostics of libloco_hip -- NOT part of the drop-in boundary (include/loco_hip.h).
  *
- * These entry points exist only in a library built with -DLOCO_DIAG (`make -C loco-edit_amd/csrc diag` ->
- * loco-edit_amd/libloco_hip_diag.so); the by-hand tuning scripts under tests/ load that build through LOCO_HIP_LIB.  The
- * shipped libloco_hip.so does not export them. */
+ * These entry points live in their own unit, loco-edit_amd/csrc/engine_diag.hip, which is linked only into the diagnostics
+ * library (`make -C loco-edit_amd/csrc diag` -> loco-edit_amd/libloco_hip_diag.so: the product's objects + that unit, every unit
+ * that includes this header built with -DLOCO_DIAG); the by-hand tuning scripts under tests/ load that build through
+ * LOCO_HIP_LIB.  The shipped libloco_hip.so does not export them. */
 #ifndef LOCO_HIP_DIAG_H
 #define LOCO_HIP_DIAG_H
 #include "loco_hip.h"

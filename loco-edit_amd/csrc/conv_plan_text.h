@@ -1,6 +1,6 @@
 // A conv plan (conv_plan.hip) as text: one line per launch (`part` is always 0: a launch is one kernel) and one closing line
-// about the statistics of the whole plan.  Shared by the diagnostics entry point loco_debug_conv (engine.hip) and the host-only
-// plan printer of the tests (tests/c/conv_plan_cases.cpp), so that both speak of a plan in the same words.  Host code only;
+// about the statistics of the whole plan.  Shared by run_conv (engine.hip: appends it to loco_ctx::plan_log where the diagnostics
+// entry point loco_debug_conv, engine_diag.hip, has set one) and the host-only plan printer of the tests (tests/c/conv_plan_cases.cpp), so that both speak of a plan in the same words.  Host code only;
 // reads the plan, decides nothing.
 #pragma once
 #include "kernels.h"

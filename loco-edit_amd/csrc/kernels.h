@@ -1,4 +1,5 @@
-// Internal launch interface between the engine (engine.hip: passes and C ABI; the
+// Internal launch interface between the engine (engine.hip: passes and C ABI; engine_params.hip: host-side weight packing;
+// engine_diag.hip: the diagnostics hooks; engine_internal.h: what the three share; the
 // U-Net program it runs is built by program.hip) and the gfx950 kernels.  All tensors are fp32 NCHW with an explicit batch stride so that a
 // tensor may live inside a wider (concatenated) buffer and a primal (B=1)
 // tensor can be broadcast over a probe batch with stride 0.

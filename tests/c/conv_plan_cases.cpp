@@ -1,5 +1,5 @@
 // Host-only plan printer for the case table of tests/conv_oracle.py (tests/test_conv_oracle_host.py): builds the ConvArgs of
-// each case as loco_debug_conv + run_conv (engine.hip) do, asks plan_conv (conv_plan.hip, compiled with plain g++) and prints the
+// each case as loco_debug_conv (engine_diag.hip) + run_conv (engine.hip) do, asks plan_conv (conv_plan.hip, compiled with plain g++) and prints the
 // plan in the words of conv_plan_text.h -- the text loco_debug_conv returns on the GPU.
 //
 // stdin, one case per line:
