@@ -194,6 +194,9 @@ int  loco_unet_forward_dh(loco_ctx* ctx, const float* x, float t, int32_t B, con
  * read and written as float4: 16-byte aligned pointers. */
 int  loco_pmp_primal_tap(loco_ctx* ctx, const float* x, float t, float at, const uint8_t* mask, int32_t use_et,
                          int32_t tap, void* stream);
+/* eps[n_out] = the network output the last loco_pmp_primal / _tap (tap 0 or 2) evaluated at its linearisation point: a copy
+ * out of the cached state, no second evaluation.  Valid until the next call that runs the network on this context. */
+int  loco_pmp_primal_eps(loco_ctx* ctx, float* eps, void* stream);
 
 /* Thin SVD re-orthonormalisation of the k x n block (replaces torch.linalg.svd
  * at edit.py:2482): on return A holds Vh (orthonormal rows, descending
@@ -590,6 +593,30 @@ int  loco_clipvis_preprocess(loco_clipvis* t, const uint8_t* frames_dev, int32_t
  * pooler_output (post_layernorm of the class token).  Each image's rows are bit-identical whatever n and its position. */
 int  loco_clipvis_encode(loco_clipvis* t, const float* pixel_values, int32_t n, float* embeds_dev, float* hidden_dev, float* pooled_dev,
                          void* stream);
+/* --- cotangent of the image tower with respect to the pixels (the text guidance of the Blended Diffusion baseline) ---
+ * on != 0: allocates, per layer, the records a backward pass reads -- the layer input and the residual stream after the
+ * attention [D][Tp], qkv [3 D][Tp], the attention output [D][Tp], the statistics of both LayerNorms, the softmax row max and
+ * row sum per head and token -- and the gradient workspace, (6 D + 4 + 2 heads) Tp floats per layer (ViT-L/14 at max_images 8:
+ * 51 MB per layer, 1.3 GB with the workspace; loco_clipvis_grad_bytes tells).  The fc1 pre-activation is recomputed, not kept.
+ * From then on every loco_clipvis_encode keeps the records of its call; its three outputs stay bit-identical to those of a
+ * handle without grad.  on == 0 frees them.  A handle that never calls this allocates and computes what it always did. */
+int  loco_clipvis_enable_grad(loco_clipvis* t, int32_t on);
+int64_t loco_clipvis_grad_bytes(loco_clipvis* t);
+/* g_pixel_dev[n][3][S][S] = (d image_embeds / d pixel_values)^T g_embeds_dev[n][P] for the images of the last kept
+ * loco_clipvis_encode (n must be that call's).  No weight gradients.  Exact fp32, no atomics: an image's gradient is the same
+ * bits whatever n and its position, and from call to call.  Refused without grad enabled or before a kept encode. */
+int  loco_clipvis_encode_vjp(loco_clipvis* t, const float* g_embeds_dev, int32_t n, float* g_pixel_dev, void* stream);
+/* The differentiable preprocessing: out_dev[n][3][S][S] from fp32 frames_dev[nf][3][H][W] in [-1, 1], nf = 1 (one frame seen
+ * through n windows) or n.  boxes_dev: int32 [n][4] = (top, left, h, w) on the device, or NULL for the centred largest square
+ * of every frame; a box that leaves the frame is refused (the boxes are read back: the call waits for the stream).  A window is
+ * resized straight to S x S, each axis through the tap rule of loco_clipvis_preprocess on the window's extent (antialiased
+ * bicubic, a = -0.5, positions and weight sums in double; no tap reads outside the window), then (v / 2 + 1 / 2 - mean) / std. */
+int  loco_clipvis_preprocess_f32(loco_clipvis* t, const float* frames_dev, int32_t nf, const int32_t* boxes_dev, int32_t n, int32_t H,
+                                 int32_t W, float* out_dev, void* stream);
+/* Its exact transpose, two gather passes without atomics: g_frames_dev[nf][3][H][W] (every pixel written; with nf = 1 the n
+ * windows are summed in window order) from g_pixel_dev[n][3][S][S]. */
+int  loco_clipvis_preprocess_f32_vjp(loco_clipvis* t, const float* g_pixel_dev, const int32_t* boxes_dev, int32_t n, int32_t nf, int32_t H,
+                                     int32_t W, float* g_frames_dev, void* stream);
 /* Message of the last failed call on t; t == NULL: of the last failed loco_clipvis_create. */
 const char* loco_clipvis_last_error(loco_clipvis* t);
 void loco_clipvis_destroy(loco_clipvis* t);

@@ -210,7 +210,7 @@ class ClipScorer:
 
     def __init__(self, vision_cfg: ClipVisionConfig, vision_sd: Dict[str, torch.Tensor], text_cfg: te.TextConfig,
                  text_sd: Dict[str, torch.Tensor], text_projection: torch.Tensor, tokenizer: te.CLIPTokenizer, device=None,
-                 max_images: int = 8, preprocess: str = "device", model_path: str = ""):
+                 max_images: int = 8, preprocess: str = "device", model_path: str = "", grad: bool = False):
         from .hip import LocoClipVisionEngine, LocoTextEngine
         if preprocess not in PREPROCESS_MODES:
             raise ValueError(f"clip_preprocess choice: {', '.join(PREPROCESS_MODES)}")
@@ -222,7 +222,7 @@ class ClipScorer:
                              f"{(vision_cfg.projection_dim, text_cfg.width)}")
         self.vision_cfg, self.text_cfg, self.tokenizer = vision_cfg, text_cfg, tokenizer
         self.preprocess_mode, self.model_path = preprocess, model_path
-        self.vision = LocoClipVisionEngine(vision_cfg, max_images=max_images, device=device)
+        self.vision = LocoClipVisionEngine(vision_cfg, max_images=max_images, device=device, grad=grad)
         self.vision.load_state_dict(vision_sd)
         self.text = LocoTextEngine(text_cfg, max_prompts=4, device=device)
         self.text.load_state_dict(text_sd)
@@ -245,6 +245,38 @@ class ClipScorer:
         mi = self.vision.max_images
         outs = [self.vision.encode(pv[i:i + mi]) for i in range(0, pv.shape[0], mi)]
         return outs[0] if len(outs) == 1 else torch.cat(outs)
+
+    def text_guidance(self, frames: torch.Tensor, text_embed: torch.Tensor, boxes=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The text loss of a float frame seen through windows, and its pixel gradient (a ``grad=True`` scorer).
+
+        frames [nf, 3, H, W] fp32 in [-1, 1] (nf = 1: one frame through every window, or one frame per window); text_embed [P];
+        boxes integer [n, 4] = (top, left, h, w), or None for the centred largest square of every frame.  Returns
+        (loss [n] with loss_i = 1 - cos(E_I(window_i), text_embed), grad [nf, 3, H, W] = d sum_i loss_i / d frames), both on
+        the device.  The cosine and its derivative with respect to the embeddings are taken in float64 from the fp32
+        embeddings; the towers' forward and cotangent passes are the engine's."""
+        if not getattr(self.vision, "grad", False):
+            raise RuntimeError("text_guidance needs a scorer built with grad=True (load_clip(..., grad=True))")
+        fr = torch.as_tensor(frames)
+        if fr.dim() == 3:
+            fr = fr[None]
+        pv = self.vision.preprocess_float(fr, boxes)
+        n, nf, H, W = pv.shape[0], fr.shape[0], fr.shape[2], fr.shape[3]
+        tn = torch.as_tensor(text_embed).to(self.device).double().flatten()
+        if tn.numel() != self.vision_cfg.projection_dim:
+            raise ValueError(f"text_embed must hold {self.vision_cfg.projection_dim} values, got {tuple(text_embed.shape)}")
+        tn = tn / tn.norm()
+        loss, g_pv = [], []
+        mi = self.vision.max_images
+        for i in range(0, n, mi):
+            emb = self.vision.encode(pv[i:i + mi]).double()
+            norm = emb.norm(dim=1, keepdim=True)
+            en = emb / norm
+            cos = en @ tn
+            loss.append(1 - cos)
+            g_emb = -(tn[None] - cos[:, None] * en) / norm          # d (1 - cos) / d emb
+            g_pv.append(self.vision.encode_vjp(g_emb.to(torch.float32)))
+        grad = self.vision.preprocess_float_vjp(torch.cat(g_pv), boxes, nf, H, W)
+        return torch.cat(loss).to(torch.float32), grad
 
     def text_embeds_from_ids(self, ids: torch.Tensor) -> torch.Tensor:
         """ids [n, positions] -> un-normalised text_embeds [n, P] fp32 (host): final state at the first EOS id x text_projection."""
@@ -296,8 +328,10 @@ def read_clip_checkpoint(path: str):
     raise FileNotFoundError(path)
 
 
-def load_clip(path: str, tokenizer_path: Optional[str] = None, device=None, max_images: int = 8, preprocess: str = "device") -> ClipScorer:
-    """A ``CLIPModel`` folder or state-dict file -> a ``ClipScorer`` (both towers on the HIP engine)."""
+def load_clip(path: str, tokenizer_path: Optional[str] = None, device=None, max_images: int = 8, preprocess: str = "device",
+              grad: bool = False) -> ClipScorer:
+    """A ``CLIPModel`` folder or state-dict file -> a ``ClipScorer`` (both towers on the HIP engine).  ``grad``: the image tower
+    keeps the records of its cotangent pass (``ClipScorer.text_guidance``)."""
     if not path:
         raise NotImplementedError("the CLIP scores need a CLIPModel checkpoint, which is not available offline: pass --clip_model_path "
                                   "(a transformers CLIPModel folder or state-dict file)")
@@ -313,4 +347,4 @@ def load_clip(path: str, tokenizer_path: Optional[str] = None, device=None, max_
     if not tok_dir:
         raise ValueError(f"{path} holds no tokenizer (vocab.json, merges.txt): pass --tokenizer_path")
     return ClipScorer(vcfg, vision, tcfg, tsd, tproj, te.CLIPTokenizer.from_dir(tok_dir), device=device, max_images=max_images,
-                      preprocess=preprocess, model_path=path)
+                      preprocess=preprocess, model_path=path, grad=grad)

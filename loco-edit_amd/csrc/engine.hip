@@ -1621,6 +1621,16 @@ int loco_pmp_primal_tap(loco_ctx* c, const float* x, float t, float at, const ui
     return 0;
 }
 
+int loco_pmp_primal_eps(loco_ctx* c, float* eps, void* stream) {
+    if (!c) return -2;
+    if (!eps) { c->err = "loco_pmp_primal_eps: eps is NULL"; return -2; }
+    if (!c->primal_ok) { c->err = "loco_pmp_primal has not been called"; return -2; }
+    if (c->tap == 1) { c->err = "loco_pmp_primal_eps: the encoder tap's primal stops at h, there is no network output to hand out"; return -2; }
+    launch_copy(c->arenaP + c->tens[c->prog->eps_t].off, c->prog->per_sample, eps, c->prog->n_out, 0, 1, c->prog->n_out, (hipStream_t)stream);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
 int loco_pmp_set_second_mask(loco_ctx* c, const uint8_t* mask2, int32_t from_row, void* stream) {
     if (!c) return -2;
     if (!c->primal_ok) { c->err = "loco_pmp_primal has not been called"; return -2; }

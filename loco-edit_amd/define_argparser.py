@@ -65,7 +65,7 @@ _FLAGS = [
     ('run_edit_null_space_projection_zt_semantic', 'bool', 'False'),
     ('run_edit_null_space_projection_xt', 'bool', 'False'),
     ('run_edit_null_space_projection_xt_semantic', 'bool', 'False'),
-    ('group_edit_null_space_projection', 'bool', 'False'),
+    ('group_edit_null_space_projection', 'bool', 'False'), ('run_edit_blended_diffusion', 'bool', 'False'),
     ('vis_num', _I, 4), ('choose_sem', _S, 'hair'), ('null_space_projection', 'bool', 'False'),
     # mode
     ('debug_mode', 'bool', 'False'), ('sampling_mode', 'bool', 'False'), ('non_semantic', 'bool', 'False'),
@@ -162,7 +162,29 @@ def build_parser():
                         "solve); the null-space solve, projection, edit walk and --vT_path are the same, basis and result names "
                         "gain an -hspace tag. Unconditional models, --run_edit_null_space_projection and the power "
                         "solver only: refused with another driver or with --solver krylov")
+    p.add_argument('--clip_guidance_scale', type=float, default=1000.0,
+                   help='--run_edit_blended_diffusion: weight of the CLIP loss mean_i (1 - cos) (the released Blended Diffusion default)')
+    p.add_argument('--blended_num_aug', type=int, default=8,
+                   help='--run_edit_blended_diffusion: windows of the masked x0 estimate the CLIP loss averages over per step (the '
+                        'first is the whole frame, the others squares of 0.75 - 1 of the short side)')
+    p.add_argument('--blended_start_t', type=float, default=0.5,
+                   help='--run_edit_blended_diffusion: the noise level (fraction of the 1000 training steps) the source image is '
+                        'taken to; the run starts at the nearest timestep of the --for_steps schedule')
+    p.add_argument('--range_scale', type=float, default=50.0,
+                   help='--run_edit_blended_diffusion: weight of the range loss mean |x0 - clamp(x0, -1, 1)|')
     return p
+
+
+def check_blended_args(args, edit_prompt=None):
+    """--run_edit_blended_diffusion needs a CLIP model and an edit prompt: checked before any device work."""
+    if not getattr(args, "clip_model_path", ""):
+        raise ValueError("--run_edit_blended_diffusion needs --clip_model_path (the CLIP model whose score guides the edit)")
+    if not (args.edit_prompt if edit_prompt is None else edit_prompt):
+        raise ValueError("--run_edit_blended_diffusion needs --edit_prompt (the text the masked region is driven towards)")
+    if not 0.0 < float(args.blended_start_t) <= 1.0:
+        raise ValueError(f"--blended_start_t {args.blended_start_t}: a noise level in (0, 1]")
+    if int(args.blended_num_aug) < 1:
+        raise ValueError("--blended_num_aug must be at least 1")
 
 
 def parse_args(argv=None):
@@ -178,6 +200,10 @@ def parse_args(argv=None):
         if os.environ.get("LOCO_SOLVER", "power") == "krylov":
             raise ValueError("--jacobian_target h runs the power iteration: the block Krylov solver (--solver krylov / LOCO_SOLVER) "
                              "is not wired to the h-space operators")
+    if args.run_edit_blended_diffusion:
+        if any(s in args.model_name for s in ('stable-diffusion', 'DeepFloyd', 'LCM')):
+            raise ValueError("--run_edit_blended_diffusion edits with an unconditional DDPM: the text-to-image classes are not wired to it")
+        check_blended_args(args)
     if args.text_encoder_path and args.prompt_emb_path:
         raise ValueError("--text_encoder_path and --prompt_emb_path both give the prompt embeddings: pass one of them")
     if args.max_batch <= 0:

@@ -454,6 +454,51 @@ class EditUncondDiffusion(object):
             self._score_quality((dec / 2 + 0.5).clamp(0, 1), names[pc_idx], self._walk_alphas(vis_num), mask)
         return xt
 
+    @torch.no_grad()
+    def run_edit_blended_diffusion(self, idx, edit_prompt, clip_guidance_scale=1000.0, num_aug=8, start_t=0.5, range_scale=50.0):
+        """The Blended Diffusion baseline (blended.py): the text-driven edit of the source image inside the run's mask.  Writes
+        <EXP_NAME>_blended.png (source | mask | result), <EXP_NAME>_clip.json (the scorer's numbers of the source and the result)
+        and, with --quality_metrics, <EXP_NAME>_quality.json.  Returns the result [1, 3, H, W] in [-1, 1]."""
+        import json
+        from . import blended
+        from .clip_score import load_clip
+        from .define_argparser import check_blended_args
+        check_blended_args(self.args, edit_prompt)
+        xT, mask = self._get_xT_and_mask(idx, True)
+        if xT is None:
+            return None
+        if mask is None:
+            raise ValueError("Blended Diffusion edits inside a mask: this dataset / flag combination gave none")
+        if self.dataset_name == 'Random':
+            self.EXP_NAME = "original"
+            x_src = self.DDIMforwardsteps(xT, t_start_idx=0, t_end_idx=-1)
+        else:
+            x_src = self.dataset[idx]
+        x_src = x_src.to(self.device, torch.float32).reshape(1, self.c_in, self.image_size, self.image_size).clamp(-1, 1).contiguous()
+        self.scheduler.set_timesteps(self.for_steps, device=self.device)
+        scorer = load_clip(self.args.clip_model_path, tokenizer_path=getattr(self.args, "tokenizer_path", "") or None,
+                           device=self.device, max_images=max(int(num_aug), 1), preprocess=getattr(self.args, "clip_preprocess", "device"),
+                           grad=True)
+        print(f"CLIP image tower: {scorer.vision.grad_bytes >> 20} MiB of records and workspace for the pixel gradient")
+        text = scorer.text_embeds([edit_prompt])[0]
+        tag = self.args.choose_sem if self.dataset_name in ("CelebA_HQ_mask", "Synthetic") else self.args.mask_index
+        self.EXP_NAME = f'{idx}-Blended-mask_{tag}-start_{start_t}T-scale_{clip_guidance_scale}'
+        out = blended.run(self.engine, self.scheduler, scorer, x_src, mask, text, self.seed, start_t,
+                          clip_guidance_scale=clip_guidance_scale, range_scale=range_scale, num_aug=num_aug, verbose=True)
+        image = (torch.cat([x_src, out]) / 2 + 0.5).clamp(0, 1)
+        panel = torch.cat([image[:1], mask.to(self.device).float().view(1, self.c_in, self.image_size, self.image_size), image[1:]])
+        self._save_image(panel, os.path.join(self.result_folder, f'{self.EXP_NAME}_blended.png'), nrow=3)
+        if self.sharder.is_main:
+            frames = (image * 255).round().to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+            for_prompt = getattr(self.args, "for_prompt", "") or ""
+            recs = scorer.score(frames, 0, for_prompt, edit_prompt)
+            with open(os.path.join(self.result_folder, f"{self.EXP_NAME}_clip.json"), "w") as f:
+                json.dump({"clip_model_path": self.args.clip_model_path, "clip_preprocess": scorer.preprocess_mode,
+                           "for_prompt": for_prompt, "edit_prompt": edit_prompt, "exp_name": self.EXP_NAME,
+                           "original": "the source image", "original_frame": recs[0], "frames": [dict(alpha=None, **recs[1])]}, f, indent=1)
+        self._score_quality(image, self.EXP_NAME, None, mask, original_index=0)
+        return out
+
     def _score_quality(self, image, name, alphas, mask, original_index=None):
         """--quality_metrics: scores the decoded frames `image` [n,3,H,W] in [0, 1] (before they are quantised for the PNG) against
         the walk's alpha = 0 frame (or frame `original_index`) with quality.QualityScorer and writes

@@ -35,13 +35,15 @@ SYMBOLS = [
     "loco_text_create", "loco_text_load_param", "loco_text_params_missing", "loco_text_encode", "loco_text_last_error",
     "loco_text_destroy", "loco_t5_create", "loco_text_encode_masked",
     "loco_diffedit_mask", "loco_cfg_masked_step", "loco_set_time_cond", "loco_lcm_step",
-    "loco_h_dims", "loco_unet_get_h", "loco_unet_forward_dh", "loco_pmp_primal_tap",
+    "loco_h_dims", "loco_unet_get_h", "loco_unet_forward_dh", "loco_pmp_primal_tap", "loco_pmp_primal_eps",
     "loco_sam_create", "loco_sam_load_param", "loco_sam_params_missing", "loco_sam_encode", "loco_sam_profile",
     "loco_sam_profile_read", "loco_sam_last_error", "loco_sam_destroy",
     "loco_samdec_create", "loco_samdec_load_param", "loco_samdec_params_missing", "loco_samdec_set_image", "loco_samdec_predict",
     "loco_samdec_score", "loco_samdec_binarize", "loco_samdec_last_error", "loco_samdec_destroy",
     "loco_clipvis_create", "loco_clipvis_load_param", "loco_clipvis_params_missing", "loco_clipvis_preprocess",
     "loco_clipvis_encode", "loco_clipvis_last_error", "loco_clipvis_destroy",
+    "loco_clipvis_enable_grad", "loco_clipvis_grad_bytes", "loco_clipvis_encode_vjp", "loco_clipvis_preprocess_f32",
+    "loco_clipvis_preprocess_f32_vjp",
     "loco_quality_create", "loco_quality_load_param", "loco_quality_params_missing", "loco_quality_lpips", "loco_quality_ssim",
     "loco_quality_masked_mse", "loco_quality_last_error", "loco_quality_destroy",
 ]
@@ -207,6 +209,8 @@ def load_library():
     lib.loco_unet_get_h.argtypes = [vp, vp, f32, i32, vp, vp]
     lib.loco_unet_forward_dh.argtypes = [vp, vp, f32, i32, vp, vp, vp]
     lib.loco_pmp_primal_tap.argtypes = [vp, vp, f32, f32, vp, i32, i32, vp]
+    if hasattr(lib, "loco_pmp_primal_eps"):
+        lib.loco_pmp_primal_eps.argtypes = [vp, vp, vp]
     lib.loco_pmp_jvp.argtypes = [vp, vp, i32, vp, vp]
     lib.loco_pmp_vjp.argtypes = [vp, vp, i32, vp, vp]
     lib.loco_orthonormalize.argtypes = [vp, vp, i32, i64, vp, vp]
@@ -289,6 +293,13 @@ def load_library():
         lib.loco_clipvis_last_error.restype = C.c_char_p
         lib.loco_clipvis_destroy.argtypes = [vp]
         lib.loco_clipvis_destroy.restype = None
+    if hasattr(lib, "loco_clipvis_encode_vjp"):
+        lib.loco_clipvis_enable_grad.argtypes = [vp, i32]
+        lib.loco_clipvis_grad_bytes.argtypes = [vp]
+        lib.loco_clipvis_grad_bytes.restype = i64
+        lib.loco_clipvis_encode_vjp.argtypes = [vp, vp, i32, vp, vp]
+        lib.loco_clipvis_preprocess_f32.argtypes = [vp, vp, i32, vp, i32, i32, i32, vp, vp]
+        lib.loco_clipvis_preprocess_f32_vjp.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp]
     if hasattr(lib, "loco_quality_create"):
         lib.loco_quality_create.argtypes = [C.POINTER(LocoQualityCfg), i32, i32, C.POINTER(vp)]
         lib.loco_quality_load_param.argtypes = [vp, C.c_char_p, vp, C.POINTER(i64), i32]
@@ -533,6 +544,12 @@ class LocoEngine:
         self._tap = None
         self._check(self.lib.loco_pmp_primal(self._ctx, _ptr(x), float(t), float(at), _ptr(m8), int(use_et),
                                              _stream()), "loco_pmp_primal")
+
+    def pmp_primal_eps(self) -> torch.Tensor:
+        """The network output [n_out] the last ``pmp_primal`` evaluated at its linearisation point (no second evaluation)."""
+        eps = torch.empty(self.n_out, device=self.device, dtype=torch.float32)
+        self._check(self.lib.loco_pmp_primal_eps(self._ctx, _ptr(eps), _stream()), "loco_pmp_primal_eps")
+        return eps
 
     def pmp_set_second_mask(self, mask2: Optional[torch.Tensor], from_row: int = 0):
         """Rows >= from_row of later pmp_jvp / pmp_vjp calls use ``mask2`` (None: off)."""
@@ -1327,7 +1344,7 @@ class LocoClipVisionEngine(_EncoderEngine):
     without the ``vision_model.`` prefix (clip_score.split_clip_state_dict produces them)."""
     _prefix, _label = "loco_clipvis", "CLIP image encoder"
 
-    def __init__(self, cfg, max_images: int = 8, device: Optional[torch.device] = None):
+    def __init__(self, cfg, max_images: int = 8, device: Optional[torch.device] = None, grad: bool = False):
         self._open(device)
         self.cfg, self.max_images = cfg, int(max_images)
         c = LocoClipVisCfg(image_size=cfg.image_size, patch_size=cfg.patch_size, width=cfg.width, layers=cfg.layers, heads=cfg.heads,
@@ -1336,6 +1353,74 @@ class LocoClipVisionEngine(_EncoderEngine):
         for i in range(3):
             c.image_mean[i], c.image_std[i] = cfg.image_mean[i], cfg.image_std[i]
         self._create("loco_clipvis_create", c, self.max_images)
+        self.grad = bool(grad)
+        if self.grad:
+            with torch.cuda.device(self.device):
+                self._check(self.lib.loco_clipvis_enable_grad(self._t, 1), "loco_clipvis_enable_grad")
+
+    @property
+    def grad_bytes(self) -> int:
+        """Bytes of the per-layer records and the gradient workspace (0 without ``grad``)."""
+        return int(self.lib.loco_clipvis_grad_bytes(self._t))
+
+    def _boxes(self, boxes, n_default):
+        """-> (int32 [n, 4] on the device or None, n)"""
+        if boxes is None:
+            return None, n_default
+        b = torch.as_tensor(boxes)
+        if b.dim() != 2 or b.shape[1] != 4 or b.shape[0] < 1 or b.is_floating_point():
+            raise ValueError(f"boxes must be integer [n, 4] = (top, left, h, w), got {b.dtype} {tuple(b.shape)}")
+        return b.to(device=self.device, dtype=torch.int32).contiguous(), int(b.shape[0])
+
+    def preprocess_float(self, frames: torch.Tensor, boxes=None) -> torch.Tensor:
+        """frames [nf, 3, H, W] or [3, H, W] (fp32 in [-1, 1], host or device), boxes integer [n, 4] = (top, left, h, w) or None
+        (the centred largest square of every frame) -> pixel_values [n, 3, S, S] on the device; nf is 1 or n."""
+        fr = torch.as_tensor(frames)
+        if fr.dim() == 3:
+            fr = fr[None]
+        if fr.dim() != 4 or fr.shape[1] != 3 or not fr.is_floating_point() or 0 in fr.shape:
+            raise ValueError(f"frames must be floating point [nf, 3, H, W], got {fr.dtype} {tuple(fr.shape)}")
+        fr = fr.to(device=self.device, dtype=torch.float32).contiguous()
+        nf, H, W, S = fr.shape[0], fr.shape[2], fr.shape[3], self.cfg.image_size
+        bx, n = self._boxes(boxes, nf)
+        out = torch.empty(n, 3, S, S, device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.loco_clipvis_preprocess_f32(self._t, _ptr(fr), nf, _ptr(bx), n, H, W, _ptr(out), _stream()),
+                        "loco_clipvis_preprocess_f32")
+        return out
+
+    def preprocess_float_vjp(self, g_pixel_values: torch.Tensor, boxes, nf: int, H: int, W: int) -> torch.Tensor:
+        """The transpose of ``preprocess_float``: g_pixel_values [n, 3, S, S] -> the cotangent of the frames [nf, 3, H, W]."""
+        S = self.cfg.image_size
+        g = torch.as_tensor(g_pixel_values)
+        if g.dim() != 4 or tuple(g.shape[1:]) != (3, S, S) or g.shape[0] < 1:
+            raise ValueError(f"g_pixel_values must be [n, 3, {S}, {S}], got {tuple(g.shape)}")
+        g = g.to(device=self.device, dtype=torch.float32).contiguous()
+        bx, n = self._boxes(boxes, g.shape[0])
+        if n != g.shape[0]:
+            raise ValueError(f"{n} boxes for {g.shape[0]} gradients")
+        nf, H, W = int(nf), int(H), int(W)
+        if nf < 1 or H < 1 or W < 1:
+            raise ValueError("nf, H and W must be positive")
+        out = torch.empty(nf, 3, H, W, device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.loco_clipvis_preprocess_f32_vjp(self._t, _ptr(g), _ptr(bx), n, nf, H, W, _ptr(out), _stream()),
+                        "loco_clipvis_preprocess_f32_vjp")
+        return out
+
+    def encode_vjp(self, g_embeds: torch.Tensor) -> torch.Tensor:
+        """g_embeds [n, P] -> the cotangent of image_embeds with respect to the pixel_values [n, 3, S, S] of the last
+        ``encode`` (a ``grad=True`` engine keeps its records)."""
+        S, P = self.cfg.image_size, self.cfg.projection_dim
+        g = torch.as_tensor(g_embeds)
+        if g.dim() != 2 or g.shape[1] != P or g.shape[0] < 1:
+            raise ValueError(f"g_embeds must be [n, {P}], got {tuple(g.shape)}")
+        n = g.shape[0]
+        g = g.to(device=self.device, dtype=torch.float32).contiguous()
+        out = torch.empty(n, 3, S, S, device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.loco_clipvis_encode_vjp(self._t, _ptr(g), n, _ptr(out), _stream()), "loco_clipvis_encode_vjp")
+        return out
 
     @property
     def tokens(self) -> int:

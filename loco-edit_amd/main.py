@@ -71,6 +71,10 @@ def main(argv=None):
             idx=args.sample_idx, op='mid', block_idx=0, vis_num_pc=1, pca_rank=1, edit_prompt=args.edit_prompt,
             null_space_projection=args.null_space_projection, pca_rank_null=args.pca_rank_null,
             encoder_decoder_by_et=args.encoder_decoder_by_et)
+    if args.run_edit_blended_diffusion:          # the Blended Diffusion baseline (blended.py; not in the reference)
+        out = edit.run_edit_blended_diffusion(
+            idx=args.sample_idx, edit_prompt=args.edit_prompt, clip_guidance_scale=args.clip_guidance_scale,
+            num_aug=args.blended_num_aug, start_t=args.blended_start_t, range_scale=args.range_scale)
     if args.run_ddim_forward:                    # main.py:98-99
         edit.run_DDIMforward(num_samples=5)
     if args.run_ddim_inversion:                  # main.py:102-103
