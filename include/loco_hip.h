@@ -593,6 +593,13 @@ int  loco_clipvis_preprocess(loco_clipvis* t, const uint8_t* frames_dev, int32_t
  * pooler_output (post_layernorm of the class token).  Each image's rows are bit-identical whatever n and its position. */
 int  loco_clipvis_encode(loco_clipvis* t, const float* pixel_values, int32_t n, float* embeds_dev, float* hidden_dev, float* pooled_dev,
                          void* stream);
+/* The residual stream after chosen layers (the activations a CLIPSeg decoder reads): taps_dev[n_taps][n][T][D], token-major as
+ * hidden_dev, slot j = the output of layer layers[j] (0-based) = hidden_states[layers[j] + 1] of transformers.  `layers`: host
+ * array, strictly increasing, inside [0, cfg.layers).  The tower stops after the last tapped layer; no pooling, no records
+ * (a handle with grad enabled keeps those of its last loco_clipvis_encode).  The launches are those of loco_clipvis_encode:
+ * each image's taps are bit-identical whatever n and its position. */
+int  loco_clipvis_encode_taps(loco_clipvis* t, const float* pixel_values, int32_t n, const int32_t* layers, int32_t n_taps,
+                              float* taps_dev, void* stream);
 /* --- cotangent of the image tower with respect to the pixels (the text guidance of the Blended Diffusion baseline) ---
  * on != 0: allocates, per layer, the records a backward pass reads -- the layer input and the residual stream after the
  * attention [D][Tp], qkv [3 D][Tp], the attention output [D][Tp], the statistics of both LayerNorms, the softmax row max and
@@ -620,6 +627,57 @@ int  loco_clipvis_preprocess_f32_vjp(loco_clipvis* t, const float* g_pixel_dev, 
 /* Message of the last failed call on t; t == NULL: of the last failed loco_clipvis_create. */
 const char* loco_clipvis_last_error(loco_clipvis* t);
 void loco_clipvis_destroy(loco_clipvis* t);
+
+/* --- CLIPSeg decoder (text-prompted edit masks) ---
+ * The CLIPSegDecoder of transformers on the taps of the CLIP image tower (loco_clipvis_encode_taps) and one conditional
+ * embedding per mask: taps deepest first; at stage i the state becomes reduces[i](tap) + state; at i == conditional_layer
+ * film_mul(c) * x + film_add(c); then a post-norm block x = LN1(x + attn(x)), x = LN2(x + fc2(relu(fc1(x)))) (full attention,
+ * scale head_dim^-0.5); the class token is dropped and the head runs: one ConvTranspose2d(reduce_dim, 1, ps, stride ps), or
+ * (complex_head) Conv2d 3x3 pad 1, ReLU, ConvTranspose2d(rd, rd / 2, ps / 4, stride ps / 4), ReLU, ConvTranspose2d(rd / 2, 1,
+ * ps / 4, stride ps / 4).  Logit side: G ps (simple) or G (ps / 4)^2 (complex), as those layers give it.  Exact fp32
+ * (independent of loco_set_precision / LOCO_PRECISION), sums in a fixed order, no atomics: a mask's logits are bit-identical
+ * whatever M and its position.  Its own handle; the workspace for max_masks masks is allocated at create. */
+typedef struct loco_clipseg loco_clipseg;
+typedef struct loco_clipseg_cfg {
+    int32_t width;              /* D of the tower the taps come from */
+    int32_t grid;               /* G: the tower's token grid at the run size, T = 1 + G^2 <= 2048 */
+    int32_t patch_size;         /* ps of the tower (16); complex_head needs ps % 4 == 0 */
+    int32_t reduce_dim;         /* rd (64); even with complex_head */
+    int32_t heads;              /* decoder_num_attention_heads (4); head width rd / heads in {4, 8, 16, 32, 64} */
+    int32_t ffn;                /* decoder_intermediate_size (2048) */
+    int32_t n_taps;             /* len(extract_layers) = decoder blocks (3) */
+    int32_t conditional_layer;  /* stage at which FiLM is applied (0), inside [0, n_taps) */
+    int32_t projection_dim;     /* P: width of a conditional embedding (512) */
+    int32_t complex_head;       /* use_complex_transposed_convolution (rd64-refined: 1) */
+    float   ln_eps;             /* layer_norm_eps of the vision config (1e-5) */
+    int32_t max_masks;          /* the largest M one decode may carry */
+} loco_clipseg_cfg;
+int  loco_clipseg_create(const loco_clipseg_cfg* cfg, int32_t device, loco_clipseg** out);
+/* One call per entry of transformers' `decoder.*` without that prefix: film_mul.*, film_add.*, reduces.{i}.*,
+ * layers.{i}.{self_attn.{q,k,v,out}_proj,layer_norm1,mlp.fc1,mlp.fc2,layer_norm2}.*, transposed_convolution.{weight,bias}
+ * (simple head) or transposed_convolution.{0,2,4}.{weight,bias} (complex head).  `host`: fp32, a host or a device pointer. */
+int  loco_clipseg_load_param(loco_clipseg* t, const char* name, const float* host, const int64_t* shape, int32_t ndim);
+int  loco_clipseg_params_missing(loco_clipseg* t);
+/* The side of the logits: G ps or G (ps / 4)^2. */
+int32_t loco_clipseg_logit_size(loco_clipseg* t);
+/* logits_dev[M][s][s] from taps_dev[n_taps][n_images][T][D] (loco_clipvis_encode_taps), cond_dev[M][P] and image_of_mask[M]
+ * (host array: the image mask m looks at, inside [0, n_images)); 1 <= M <= max_masks.  The reduces run once per image. */
+int  loco_clipseg_decode(loco_clipseg* t, const float* taps_dev, int32_t n_images, const float* cond_dev, const int32_t* image_of_mask,
+                         int32_t M, float* logits_dev, void* stream);
+/* out_dev[n][3][S][S] (fp32) from frames_dev: is_u8 == 0: fp32 [n][3][H][W] in [-1, 1] (v / 2 + 1 / 2); else uint8 [n][H][W][3]
+ * (v / 255).  Each axis is resized to S on its own (no shortest-edge rule, no crop: ViTImageProcessor), antialiased, two
+ * passes with the tap rule of loco_clipvis_preprocess; resample 2: the triangle filter (PIL BILINEAR), 3: cubic a = -0.5
+ * (BICUBIC), any other value is refused; then (v - mean[c]) / stdev[c] (host arrays of 3). */
+int  loco_clipseg_preprocess(loco_clipseg* t, const void* frames_dev, int32_t is_u8, int32_t n, int32_t H, int32_t W, int32_t S,
+                             int32_t resample, const float* mean, const float* stdev, float* out_dev, void* stream);
+/* One launch: mask_dev[M][res][res] (uint8 0 / 1) = bilinear resize (align_corners = False, no antialias, positions and
+ * blend in double) of logits_dev[M][s][s] > threshold_logit (= log(thr / (1 - thr)), the caller's), area_dev[M] (int32) = the
+ * set pixels of every mask, counted in a fixed order by the workgroup that owns the mask. */
+int  loco_clipseg_masks(loco_clipseg* t, const float* logits_dev, int32_t M, int32_t s, int32_t res, double threshold_logit,
+                        uint8_t* mask_dev, int32_t* area_dev, void* stream);
+/* Message of the last failed call on t; t == NULL: of the last failed loco_clipseg_create. */
+const char* loco_clipseg_last_error(loco_clipseg* t);
+void loco_clipseg_destroy(loco_clipseg* t);
 
 /* --- Edit-quality scores of decoded frames (the unconditional drivers' --quality_metrics, eval.py --backend hip) ---
  * LPIPS with the AlexNet backbone, SSIM and mask-restricted MSE between the images of a[n] and b[n], pair by pair, as

@@ -664,6 +664,34 @@ int clipvis_check_windows(loco_clipvis* t, const char* fn, const int32_t* boxes_
     return 0;
 }
 
+// patch projection, class / position add, pre_layrnorm: pixel_values -> xe (the embeddings) -> h0
+void clipvis_embed_fwd(loco_clipvis* t, const float* pixel_values, int n, int Tp, float* xe, float* h0, float* st_pre, hipStream_t st) {
+    const loco_clipvis_cfg& c = t->cfg;
+    const int D = c.width, ps = c.patch_size, PK = 3 * ps * ps, G = t->G, T = t->T, nT = n * T;
+    hipLaunchKernelGGL(clipvis_patch_kernel, dim3(blocks256((long)PK * Tp)), dim3(256), 0, st, pixel_values, c.image_size, ps, G, T, nT, Tp,
+                       t->f);
+    launch_gemm_fixed(enc_linear(t->patch_w, nullptr, t->f, xe, nullptr, D, PK, Tp), GEMM_ACT_NONE, st);
+    hipLaunchKernelGGL(clipvis_embed_kernel, dim3(blocks256((long)D * nT)), dim3(256), 0, st, xe, t->cls, t->pos, D, T, nT, Tp);
+    launch_ln_fwd(xe, 0, 1, D, Tp, t->pre_g, t->pre_b, c.ln_eps, h0, 0, st_pre, 0, st);
+}
+
+// one block on the shared buffers (no records): t->h -> t->h
+void clipvis_layer_plain(loco_clipvis* t, const ClipVisLayer& ly, int n, int Tp, hipStream_t st) {
+    const loco_clipvis_cfg& c = t->cfg;
+    const int D = c.width, F = c.mlp_dim, T = t->T, hd = t->hd;
+    const float scale = 1.0f / std::sqrt((float)hd);
+    const int gact = c.act == 0 ? GEMM_ACT_QUICK_GELU : GEMM_ACT_GELU;
+    const dim3 attn_grid((T + CV_QB - 1) / CV_QB, c.heads, n);
+    launch_ln_fwd(t->h, 0, 1, D, Tp, ly.ln1_g, ly.ln1_b, c.ln_eps, t->x, 0, t->stats, 0, st);
+    launch_gemm_fixed(enc_linear(ly.wqkv, ly.bqkv, t->x, t->qkv, nullptr, 3 * D, D, Tp), GEMM_ACT_NONE, st);
+    hipLaunchKernelGGL(clipvis_attn_kernel<false>, attn_grid, dim3(CV_THREADS), clipvis_attn_lds_floats(hd) * sizeof(float), st, t->qkv,
+                       (long)Tp, D, hd, T, scale, t->attn, (float*)nullptr);
+    launch_gemm_fixed(enc_linear(ly.wo, ly.bo, t->attn, t->h, t->h, D, D, Tp), GEMM_ACT_NONE, st);
+    launch_ln_fwd(t->h, 0, 1, D, Tp, ly.ln2_g, ly.ln2_b, c.ln_eps, t->x, 0, t->stats, 0, st);
+    launch_gemm_fixed(enc_linear(ly.w1, ly.b1, t->x, t->f, nullptr, F, D, Tp), gact, st);
+    launch_gemm_fixed(enc_linear(ly.w2, ly.b2, t->f, t->h, t->h, D, F, Tp), GEMM_ACT_NONE, st);
+}
+
 int clipvis_grow_rows(loco_clipvis* t, const char* fn, size_t need) {
     if (need <= t->rows_floats) return 0;
     if (t->rows) (void)hipFree(t->rows);             // (waits for the launches that read it)
@@ -784,8 +812,8 @@ int loco_clipvis_encode(loco_clipvis* t, const float* pixel_values, int32_t n, f
     DeviceGuard dg(t->device);
     hipStream_t st = (hipStream_t)stream;
     const loco_clipvis_cfg& c = t->cfg;
-    const int D = c.width, F = c.mlp_dim, P = c.projection_dim, ps = c.patch_size, PK = 3 * ps * ps;
-    const int G = t->G, T = t->T, hd = t->hd, nT = n * T, Tp = (nT + 15) / 16 * 16, Np = (n + 15) / 16 * 16;
+    const int D = c.width, F = c.mlp_dim, P = c.projection_dim;
+    const int T = t->T, hd = t->hd, nT = n * T, Tp = (nT + 15) / 16 * 16, Np = (n + 15) / 16 * 16;
     const float scale = 1.0f / std::sqrt((float)hd);
     const int gact = c.act == 0 ? GEMM_ACT_QUICK_GELU : GEMM_ACT_GELU;
     // with grad enabled the same launches write the layer's tensors into its record instead of the shared buffers
@@ -794,22 +822,11 @@ int loco_clipvis_encode(loco_clipvis* t, const float* pixel_values, int32_t n, f
     const size_t attn_lds = clipvis_attn_lds_floats(hd) * sizeof(float);
     const dim3 attn_grid((T + CV_QB - 1) / CV_QB, c.heads, n);
     float* xe = keep ? t->xemb : t->x;
-    hipLaunchKernelGGL(clipvis_patch_kernel, dim3(blocks256((long)PK * Tp)), dim3(256), 0, st, pixel_values, c.image_size, ps, G, T, nT, Tp,
-                       t->f);
-    launch_gemm_fixed(enc_linear(t->patch_w, nullptr, t->f, xe, nullptr, D, PK, Tp), GEMM_ACT_NONE, st);
-    hipLaunchKernelGGL(clipvis_embed_kernel, dim3(blocks256((long)D * nT)), dim3(256), 0, st, xe, t->cls, t->pos, D, T, nT, Tp);
-    launch_ln_fwd(xe, 0, 1, D, Tp, t->pre_g, t->pre_b, c.ln_eps, keep ? t->rec[0].h_in : t->h, 0, keep ? t->st_pre : t->stats, 0, st);
+    clipvis_embed_fwd(t, pixel_values, n, Tp, xe, keep ? t->rec[0].h_in : t->h, keep ? t->st_pre : t->stats, st);
     for (size_t l = 0; l < t->layer.size(); ++l) {
         const ClipVisLayer& ly = t->layer[l];
         if (!keep) {
-            launch_ln_fwd(t->h, 0, 1, D, Tp, ly.ln1_g, ly.ln1_b, c.ln_eps, t->x, 0, t->stats, 0, st);
-            launch_gemm_fixed(enc_linear(ly.wqkv, ly.bqkv, t->x, t->qkv, nullptr, 3 * D, D, Tp), GEMM_ACT_NONE, st);
-            hipLaunchKernelGGL(clipvis_attn_kernel<false>, attn_grid, dim3(CV_THREADS), attn_lds, st, t->qkv, (long)Tp, D, hd, T, scale,
-                               t->attn, (float*)nullptr);
-            launch_gemm_fixed(enc_linear(ly.wo, ly.bo, t->attn, t->h, t->h, D, D, Tp), GEMM_ACT_NONE, st);
-            launch_ln_fwd(t->h, 0, 1, D, Tp, ly.ln2_g, ly.ln2_b, c.ln_eps, t->x, 0, t->stats, 0, st);
-            launch_gemm_fixed(enc_linear(ly.w1, ly.b1, t->x, t->f, nullptr, F, D, Tp), gact, st);
-            launch_gemm_fixed(enc_linear(ly.w2, ly.b2, t->f, t->h, t->h, D, F, Tp), GEMM_ACT_NONE, st);
+            clipvis_layer_plain(t, ly, n, Tp, st);
             continue;
         }
         const ClipVisRec& r = t->rec[l];
@@ -832,6 +849,37 @@ int loco_clipvis_encode(loco_clipvis* t, const float* pixel_values, int32_t n, f
     hipLaunchKernelGGL(clipvis_transpose_kernel, dim3(blocks256((long)n * P)), dim3(256), 0, st, t->emb, Np, n, P, embeds_dev);
     if (hipGetLastError() != hipSuccess) return t->fail("loco_clipvis_encode: kernel launch failed");
     if (keep) t->kept_n = n;
+    return 0;
+}
+
+int loco_clipvis_encode_taps(loco_clipvis* t, const float* pixel_values, int32_t n, const int32_t* layers, int32_t n_taps, float* taps_dev,
+                             void* stream) {
+    if (!t) return -1;
+    if (!pixel_values || !taps_dev || !layers) return t->fail("loco_clipvis_encode_taps: null pixel_values, layers or taps");
+    if (n <= 0 || n > t->max_images)
+        return t->fail("loco_clipvis_encode_taps: n = " + std::to_string(n) + " outside [1, max_images = " + std::to_string(t->max_images) + "]");
+    const int L = (int)t->layer.size();
+    if (n_taps <= 0 || n_taps > L) return t->fail("loco_clipvis_encode_taps: n_taps = " + std::to_string(n_taps) + " outside [1, layers = " + std::to_string(L) + "]");
+    for (int j = 0; j < n_taps; ++j) {
+        if (layers[j] < 0 || layers[j] >= L)
+            return t->fail("loco_clipvis_encode_taps: layer " + std::to_string(layers[j]) + " outside [0, " + std::to_string(L) + ")");
+        if (j && layers[j] <= layers[j - 1]) return t->fail("loco_clipvis_encode_taps: the layers must be strictly increasing");
+    }
+    if (t->table.missing(t->err)) return -1;
+    DeviceGuard dg(t->device);
+    hipStream_t st = (hipStream_t)stream;
+    const int D = t->cfg.width, T = t->T, nT = n * T, Tp = (nT + 15) / 16 * 16;
+    clipvis_embed_fwd(t, pixel_values, n, Tp, t->x, t->h, t->stats, st);
+    int j = 0;
+    for (int l = 0; l <= layers[n_taps - 1]; ++l) {
+        clipvis_layer_plain(t, t->layer[l], n, Tp, st);
+        if (l == layers[j]) {
+            hipLaunchKernelGGL(clipvis_transpose_kernel, dim3(blocks256((long)nT * D)), dim3(256), 0, st, t->h, Tp, nT, D,
+                               taps_dev + (size_t)j * nT * D);
+            ++j;
+        }
+    }
+    if (hipGetLastError() != hipSuccess) return t->fail("loco_clipvis_encode_taps: kernel launch failed");
     return 0;
 }
 

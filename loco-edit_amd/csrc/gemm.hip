@@ -90,6 +90,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs g) {
             if (g.R) v += g.R[(long)bz * g.srb + (long)hz * g.sch + off];
             if (EPI == GEMM_ACT_QUICK_GELU) v = v * (1.0f / (1.0f + expf(-1.702f * v)));
             else if (EPI == GEMM_ACT_GELU) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
+            else if (EPI == GEMM_ACT_RELU) v = fmaxf(v, 0.f);
             *c = v;
         }
     }
@@ -609,6 +610,7 @@ void launch_gemm_fixed(const GemmArgs& g, int act, hipStream_t st) {
     if (g.A2) hipLaunchKernelGGL(gemm_f32_kernel<2>, grid, dim3(256), 0, st, g);
     else if (act == GEMM_ACT_QUICK_GELU) hipLaunchKernelGGL((gemm_f32_kernel<1, GEMM_ACT_QUICK_GELU>), grid, dim3(256), 0, st, g);
     else if (act == GEMM_ACT_GELU) hipLaunchKernelGGL((gemm_f32_kernel<1, GEMM_ACT_GELU>), grid, dim3(256), 0, st, g);
+    else if (act == GEMM_ACT_RELU) hipLaunchKernelGGL((gemm_f32_kernel<1, GEMM_ACT_RELU>), grid, dim3(256), 0, st, g);
     else hipLaunchKernelGGL(gemm_f32_kernel<1>, grid, dim3(256), 0, st, g);
 }
 

@@ -247,7 +247,7 @@ void launch_gemm_pair(const GemmArgs& g0, const GemmArgs& g1, hipStream_t st);
 // the same exact-fp32 product on the 64 x 64 tiling whatever the shape, so every output element is the same chain of MFMAs
 // whatever N and the batch are (launch_gemm picks its tiling by grid size), with an activation after the bias (GemmAct;
 // the fc1 of the CLIP text encoder, textenc.hip).  A2 / B2 take no activation.
-enum GemmAct : int { GEMM_ACT_NONE = 0, GEMM_ACT_QUICK_GELU = 1, GEMM_ACT_GELU = 2 };
+enum GemmAct : int { GEMM_ACT_NONE = 0, GEMM_ACT_QUICK_GELU = 1, GEMM_ACT_GELU = 2, GEMM_ACT_RELU = 3 };
 void launch_gemm_fixed(const GemmArgs& g, int act, hipStream_t st);
 void launch_gemm_bf16x3(const GemmArgs& g, hipStream_t st);       // split-bf16 operands on the bf16 matrix pipe
 bool gemm_prefers_bf16x3(const GemmArgs& g);                      // long contraction, matrix-rate bound on the f32 MFMA

@@ -172,7 +172,35 @@ def build_parser():
                         'taken to; the run starts at the nearest timestep of the --for_steps schedule')
     p.add_argument('--range_scale', type=float, default=50.0,
                    help='--run_edit_blended_diffusion: weight of the range loss mean |x0 - clamp(x0, -1, 1)|')
+    p.add_argument('--mask_prompts', type=str, default='',
+                   help='text-prompted edit masks: a comma list such as "hair,eyes,mouth"; when mask/mask.pt is missing, CLIPSeg '
+                        '(--mask_prompt_model_path) writes one mask per entry, in order, so --mask_index selects a prompt')
+    p.add_argument('--mask_prompt_model_path', type=str, default='',
+                   help='CLIPSeg model behind --mask_prompts: a local CLIPSegForImageSegmentation folder (config.json + '
+                        'model.safetensors or pytorch_model.bin, tokenizer files or --tokenizer_path, optional '
+                        'preprocessor_config.json) or a state_dict file. Nothing is downloaded. Excludes --mask_model_path')
+    p.add_argument('--mask_prompt_threshold', type=float, default=0.5,
+                   help='--mask_prompts: a pixel belongs to the mask when sigmoid(logit) exceeds this (a user knob: lower it for a '
+                        'wider mask; a prompt whose mask comes out empty is an error)')
     return p
+
+
+def check_mask_prompt_args(args):
+    """The combinations of --mask_prompts / --mask_prompt_model_path / --mask_model_path / --mask_index that make no sense."""
+    prompts, model = getattr(args, "mask_prompts", ""), getattr(args, "mask_prompt_model_path", "")
+    if model and getattr(args, "mask_model_path", ""):
+        raise ValueError("--mask_model_path (Segment Anything) and --mask_prompt_model_path (CLIPSeg) both write mask/mask.pt: pass one")
+    if prompts and not model:
+        raise ValueError("--mask_prompts needs --mask_prompt_model_path (a local CLIPSegForImageSegmentation folder or state_dict file)")
+    if model and not prompts:
+        raise ValueError("--mask_prompt_model_path needs --mask_prompts (a comma list, one mask per entry)")
+    if not model:
+        return
+    from .prompt_mask import parse_prompts, threshold_logit
+    names = parse_prompts(prompts)
+    threshold_logit(args.mask_prompt_threshold)
+    if not 0 <= int(args.mask_index) < len(names):
+        raise ValueError(f"--mask_index {args.mask_index} is beyond the {len(names)} prompts of --mask_prompts {names}")
 
 
 def check_blended_args(args, edit_prompt=None):
@@ -204,6 +232,7 @@ def parse_args(argv=None):
         if any(s in args.model_name for s in ('stable-diffusion', 'DeepFloyd', 'LCM')):
             raise ValueError("--run_edit_blended_diffusion edits with an unconditional DDPM: the text-to-image classes are not wired to it")
         check_blended_args(args)
+    check_mask_prompt_args(args)
     if args.text_encoder_path and args.prompt_emb_path:
         raise ValueError("--text_encoder_path and --prompt_emb_path both give the prompt embeddings: pass one of them")
     if args.max_batch <= 0:

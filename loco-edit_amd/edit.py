@@ -16,6 +16,7 @@ import torch
 
 from . import solver
 from .dist import ProbeSharder
+from .mask_segmentation import wants_segmentation
 from .utils import get_custom_diffusion_model, get_custom_diffusion_scheduler, get_dataset
 from .utils import save_image as _save_image
 
@@ -308,7 +309,7 @@ class EditUncondDiffusion(object):
         if self.dataset_name == 'Random':
             xT = torch.randn(1, self.c_in, self.image_size, self.image_size, dtype=self.dtype, device=self.device)
             mpath = os.path.join(self.result_folder, "mask/mask.pt")
-            if getattr(self.args, "mask_model_path", "") and not self._exists(mpath):
+            if wants_segmentation(self.args) and not self._exists(mpath):
                 self.EXP_NAME = "original"                     # edit.py:2236-2241: sample, then segment the sample
                 masks = self._segment(lambda: self.DDIMforwardsteps(xT, t_start_idx=0, t_end_idx=-1))
             else:
@@ -327,7 +328,7 @@ class EditUncondDiffusion(object):
             return xT, (mask if use_mask or self.dataset_name == "CelebA_HQ_mask" else None)
         # FFHQ / AFHQ / ... : SAM masks cached as mask/mask.pt, bool [N,res,res] (edit.py:2252-2267)
         mpath = os.path.join(self.result_folder, "mask/mask.pt")
-        if getattr(self.args, "mask_model_path", "") and not self._exists(mpath):
+        if wants_segmentation(self.args) and not self._exists(mpath):
             masks = self._segment(lambda: self.dataset[idx])    # edit.py:2253-2257: the dataset image
         else:
             if not os.path.exists(mpath):

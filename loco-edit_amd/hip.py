@@ -43,7 +43,9 @@ SYMBOLS = [
     "loco_clipvis_create", "loco_clipvis_load_param", "loco_clipvis_params_missing", "loco_clipvis_preprocess",
     "loco_clipvis_encode", "loco_clipvis_last_error", "loco_clipvis_destroy",
     "loco_clipvis_enable_grad", "loco_clipvis_grad_bytes", "loco_clipvis_encode_vjp", "loco_clipvis_preprocess_f32",
-    "loco_clipvis_preprocess_f32_vjp",
+    "loco_clipvis_preprocess_f32_vjp", "loco_clipvis_encode_taps",
+    "loco_clipseg_create", "loco_clipseg_load_param", "loco_clipseg_params_missing", "loco_clipseg_logit_size", "loco_clipseg_decode",
+    "loco_clipseg_preprocess", "loco_clipseg_masks", "loco_clipseg_last_error", "loco_clipseg_destroy",
     "loco_quality_create", "loco_quality_load_param", "loco_quality_params_missing", "loco_quality_lpips", "loco_quality_ssim",
     "loco_quality_masked_mse", "loco_quality_last_error", "loco_quality_destroy",
 ]
@@ -168,6 +170,12 @@ class LocoClipVisCfg(C.Structure):
     _fields_ = [("image_size", C.c_int32), ("patch_size", C.c_int32), ("width", C.c_int32), ("layers", C.c_int32),
                 ("heads", C.c_int32), ("mlp_dim", C.c_int32), ("projection_dim", C.c_int32), ("act", C.c_int32),
                 ("ln_eps", C.c_float), ("image_mean", C.c_float * 3), ("image_std", C.c_float * 3)]
+
+
+class LocoClipSegCfg(C.Structure):
+    _fields_ = [("width", C.c_int32), ("grid", C.c_int32), ("patch_size", C.c_int32), ("reduce_dim", C.c_int32), ("heads", C.c_int32),
+                ("ffn", C.c_int32), ("n_taps", C.c_int32), ("conditional_layer", C.c_int32), ("projection_dim", C.c_int32),
+                ("complex_head", C.c_int32), ("ln_eps", C.c_float), ("max_masks", C.c_int32)]
 
 
 class LocoQualityCfg(C.Structure):
@@ -300,6 +308,20 @@ def load_library():
         lib.loco_clipvis_encode_vjp.argtypes = [vp, vp, i32, vp, vp]
         lib.loco_clipvis_preprocess_f32.argtypes = [vp, vp, i32, vp, i32, i32, i32, vp, vp]
         lib.loco_clipvis_preprocess_f32_vjp.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp]
+    if hasattr(lib, "loco_clipseg_create"):
+        lib.loco_clipvis_encode_taps.argtypes = [vp, vp, i32, C.POINTER(i32), i32, vp, vp]
+        lib.loco_clipseg_create.argtypes = [C.POINTER(LocoClipSegCfg), i32, C.POINTER(vp)]
+        lib.loco_clipseg_load_param.argtypes = [vp, C.c_char_p, vp, C.POINTER(i64), i32]
+        lib.loco_clipseg_params_missing.argtypes = [vp]
+        lib.loco_clipseg_logit_size.argtypes = [vp]
+        lib.loco_clipseg_logit_size.restype = i32
+        lib.loco_clipseg_decode.argtypes = [vp, vp, i32, vp, C.POINTER(i32), i32, vp, vp]
+        lib.loco_clipseg_preprocess.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, vp]
+        lib.loco_clipseg_masks.argtypes = [vp, vp, i32, i32, i32, C.c_double, vp, vp, vp]
+        lib.loco_clipseg_last_error.argtypes = [vp]
+        lib.loco_clipseg_last_error.restype = C.c_char_p
+        lib.loco_clipseg_destroy.argtypes = [vp]
+        lib.loco_clipseg_destroy.restype = None
     if hasattr(lib, "loco_quality_create"):
         lib.loco_quality_create.argtypes = [C.POINTER(LocoQualityCfg), i32, i32, C.POINTER(vp)]
         lib.loco_quality_load_param.argtypes = [vp, C.c_char_p, vp, C.POINTER(i64), i32]
@@ -1460,6 +1482,101 @@ class LocoClipVisionEngine(_EncoderEngine):
             self._check(self.lib.loco_clipvis_encode(self._t, _ptr(pv), n, _ptr(emb), _ptr(hid), _ptr(pool), _stream()),
                         "loco_clipvis_encode")
         return (emb, hid, pool) if want_hidden else emb
+
+    def encode_taps(self, pixel_values: torch.Tensor, layers) -> torch.Tensor:
+        """pixel_values [n, 3, S, S], n <= max_images; layers: strictly increasing 0-based layer indices -> the residual stream
+        after each of them [n_taps, n, T, D] (slot j = ``hidden_states[layers[j] + 1]`` of transformers).  The tower stops
+        after the last tapped layer."""
+        S, D = self.cfg.image_size, self.cfg.width
+        pv = torch.as_tensor(pixel_values)
+        if pv.dim() != 4 or tuple(pv.shape[1:]) != (3, S, S) or pv.shape[0] < 1:
+            raise ValueError(f"pixel_values must be [n, 3, {S}, {S}], got {tuple(pv.shape)}")
+        layers = [int(v) for v in layers]
+        n = pv.shape[0]
+        pv = pv.to(device=self.device, dtype=torch.float32).contiguous()
+        out = torch.empty(max(len(layers), 1), n, self.tokens, D, device=self.device, dtype=torch.float32)
+        arr = (C.c_int32 * max(len(layers), 1))(*layers)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.loco_clipvis_encode_taps(self._t, _ptr(pv), n, arr, len(layers), _ptr(out), _stream()),
+                        "loco_clipvis_encode_taps")
+        return out
+
+
+class LocoClipSegDecoder(_EncoderEngine):
+    """The CLIPSeg decoder (= loco_clipseg, include/loco_hip.h, csrc/clipseg.hip): parameters and the workspace of `max_masks`
+    masks on the device.  `cfg` is a ``prompt_mask.ClipSegDecoderConfig``.  ``decode`` turns the taps of
+    ``LocoClipVisionEngine.encode_taps`` and one conditional embedding per mask into logits, ``preprocess`` resizes frames the
+    way ViTImageProcessor does for CLIPSeg, ``masks`` resizes logits bilinearly and thresholds them.  ``load_state_dict``
+    takes the names of transformers' ``decoder.*`` without the prefix."""
+    _prefix, _label = "loco_clipseg", "CLIPSeg decoder"
+
+    def __init__(self, cfg, device: Optional[torch.device] = None):
+        self._open(device)
+        self.cfg = cfg
+        c = LocoClipSegCfg(width=cfg.width, grid=cfg.grid, patch_size=cfg.patch_size, reduce_dim=cfg.reduce_dim, heads=cfg.heads,
+                           ffn=cfg.ffn, n_taps=cfg.n_taps, conditional_layer=cfg.conditional_layer, projection_dim=cfg.projection_dim,
+                           complex_head=int(bool(cfg.complex_head)), ln_eps=cfg.ln_eps, max_masks=cfg.max_masks)
+        self._create("loco_clipseg_create", c)
+        self.logit_size = int(self.lib.loco_clipseg_logit_size(self._t))
+
+    def decode(self, taps: torch.Tensor, cond: torch.Tensor, image_of_mask=None) -> torch.Tensor:
+        """taps [n_taps, n, T, D] (device), cond [M, P], image_of_mask: M image indices (None: mask m looks at image m) ->
+        logits [M, s, s] on the device."""
+        cfg, T = self.cfg, 1 + self.cfg.grid ** 2
+        taps = torch.as_tensor(taps)
+        if taps.dim() != 4 or taps.shape[0] != cfg.n_taps or tuple(taps.shape[2:]) != (T, cfg.width) or taps.shape[1] < 1:
+            raise ValueError(f"taps must be [{cfg.n_taps}, n, {T}, {cfg.width}], got {tuple(taps.shape)}")
+        cond = torch.as_tensor(cond)
+        if cond.dim() != 2 or cond.shape[1] != cfg.projection_dim:
+            raise ValueError(f"cond must be [M, {cfg.projection_dim}], got {tuple(cond.shape)}")
+        M, n = cond.shape[0], taps.shape[1]
+        iom = list(range(M)) if image_of_mask is None else [int(v) for v in image_of_mask]
+        if len(iom) != M:
+            raise ValueError(f"image_of_mask must hold {M} indices, got {len(iom)}")
+        taps = taps.to(device=self.device, dtype=torch.float32).contiguous()
+        cond = cond.to(device=self.device, dtype=torch.float32).contiguous()
+        s = self.logit_size
+        out = torch.empty(M, s, s, device=self.device, dtype=torch.float32)
+        arr = (C.c_int32 * max(M, 1))(*iom)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.loco_clipseg_decode(self._t, _ptr(taps), n, _ptr(cond), arr, M, _ptr(out), _stream()),
+                        "loco_clipseg_decode")
+        return out
+
+    def preprocess(self, frames: torch.Tensor, size: int, resample: int, mean, std) -> torch.Tensor:
+        """frames fp32 [n, 3, H, W] in [-1, 1] or uint8 [n, H, W, 3] -> pixel_values [n, 3, size, size] on the device."""
+        fr = torch.as_tensor(frames)
+        if fr.dtype == torch.uint8:
+            if fr.dim() != 4 or fr.shape[-1] != 3 or 0 in fr.shape:
+                raise ValueError(f"uint8 frames must be [n, H, W, 3], got {tuple(fr.shape)}")
+            n, H, W, u8 = fr.shape[0], fr.shape[1], fr.shape[2], 1
+            fr = fr.to(self.device).contiguous()
+        else:
+            if fr.dim() != 4 or fr.shape[1] != 3 or not fr.is_floating_point() or 0 in fr.shape:
+                raise ValueError(f"frames must be uint8 [n, H, W, 3] or floating point [n, 3, H, W], got {fr.dtype} {tuple(fr.shape)}")
+            n, H, W, u8 = fr.shape[0], fr.shape[2], fr.shape[3], 0
+            fr = fr.to(device=self.device, dtype=torch.float32).contiguous()
+        size = int(size)
+        out = torch.empty(n, 3, max(size, 1), max(size, 1), device=self.device, dtype=torch.float32)
+        m3, s3 = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
+        with torch.cuda.device(self.device):
+            self._check(self.lib.loco_clipseg_preprocess(self._t, _ptr(fr), u8, n, H, W, size, int(resample), m3, s3, _ptr(out), _stream()),
+                        "loco_clipseg_preprocess")
+        return out
+
+    def masks(self, logits: torch.Tensor, resolution: int, threshold_logit: float):
+        """logits [M, s, s] -> (mask uint8 [M, res, res], area int32 [M]) on the device."""
+        lg = torch.as_tensor(logits)
+        if lg.dim() != 3 or lg.shape[1] != lg.shape[2] or 0 in lg.shape:
+            raise ValueError(f"logits must be [M, s, s], got {tuple(lg.shape)}")
+        lg = lg.to(device=self.device, dtype=torch.float32).contiguous()
+        M, s, res = lg.shape[0], lg.shape[1], int(resolution)
+        mask = torch.empty(M, max(res, 1), max(res, 1), device=self.device, dtype=torch.uint8)
+        area = torch.empty(M, device=self.device, dtype=torch.int32)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.loco_clipseg_masks(self._t, _ptr(lg), M, s, res, float(threshold_logit), _ptr(mask), _ptr(area), _stream()),
+                        "loco_clipseg_masks")
+        return mask, area
 
 
 class LocoQualityEngine(_EncoderEngine):

@@ -775,15 +775,26 @@ class SAM(object):
         Image.fromarray(total).save(os.path.join(self.log_dir, "total_mask.png"))
 
 
+def wants_segmentation(args) -> bool:
+    """Whether a driver is to produce mask/mask.pt itself when it is missing: --mask_model_path (Segment Anything) or
+    --mask_prompt_model_path (CLIPSeg, one mask per entry of --mask_prompts)."""
+    return bool(getattr(args, "mask_model_path", "") or getattr(args, "mask_prompt_model_path", ""))
+
+
 def segment_for_driver(args, result_folder, sharder, image_fn, resolution: int):
-    """The drivers' SAM step when mask/mask.pt is missing and --mask_model_path is set: every rank produces the image (the
-    sampler is the same flow on all of them), rank 0 segments it and writes the cache, every rank receives the masks
-    (bool [N, res, res], on the host); a failure on rank 0 raises on all."""
+    """The drivers' segmentation step when mask/mask.pt is missing and a mask model is set (``wants_segmentation``): every rank
+    produces the image (the sampler is the same flow on all of them), rank 0 segments it -- Segment Anything with
+    --mask_model_path, the prompt masker (prompt_mask.prompt_masks_for_driver) with --mask_prompt_model_path -- and writes the
+    cache, every rank receives the masks (bool [N, res, res], on the host); a failure on rank 0 raises on all."""
     image = image_fn()
     masks, err = None, None
     if sharder.is_main:
         try:
-            masks = SAM(args, result_folder).mask_segmentation(image, resolution=resolution)
+            if getattr(args, "mask_prompt_model_path", ""):
+                from .prompt_mask import prompt_masks_for_driver
+                masks = prompt_masks_for_driver(args, result_folder, image, resolution)
+            else:
+                masks = SAM(args, result_folder).mask_segmentation(image, resolution=resolution)
         except Exception as ex:
             if not sharder.active:
                 raise

@@ -44,6 +44,7 @@ from . import solver
 from .config import UNetConfig, synth_params
 from .dist import ProbeSharder
 from .hip import LocoEngine
+from .mask_segmentation import wants_segmentation
 from .scheduler import SchedulerOutput
 from .utils import save_image as _save_image
 
@@ -712,7 +713,7 @@ class EditDeepFloydIF(object):
         """The cached SAM masks; without a cache and with --mask_model_path, `image_fn()` (uint8 [H, W, 3]) is segmented."""
         mpath = os.path.join(self.result_folder, "mask/mask.pt")
         if not self._exists(mpath):
-            if getattr(self.args, "mask_model_path", "") and image_fn is not None:
+            if wants_segmentation(self.args) and image_fn is not None:
                 from .mask_segmentation import segment_for_driver
                 print("Creating masks......")
                 return segment_for_driver(self.args, self.result_folder, self.sharder, image_fn, resolution)

@@ -31,6 +31,7 @@ import torch
 
 from . import solver
 from .hip import LocoEngine
+from .mask_segmentation import wants_segmentation
 from .tloco import BranchStreams
 from .tloco_sd import LATENT_SCALE, EditStableDiffusion, LatentCFGJacobianOperator, SDScheduler
 from .utils import save_image as _save_image
@@ -292,7 +293,7 @@ class EditLatentConsistency(EditStableDiffusion):
         self.scheduler.set_timesteps(self.num_inference_steps, device=self.device)
         zT = self._zT()
         self.EXP_NAME = "original"
-        segment = bool(getattr(self.args, "mask_model_path", "")) and not self._exists(os.path.join(self.result_folder, "mask/mask.pt"))
+        segment = wants_segmentation(self.args) and not self._exists(os.path.join(self.result_folder, "mask/mask.pt"))
         x0 = None
         if self.sharder.agree(not os.path.exists(os.path.join(self.result_folder, "original.png"))) or segment:
             print("Generating images and creating masks......")

@@ -44,6 +44,7 @@ import torch
 from . import solver
 from .config import UNetConfig, synth_params
 from .hip import LocoEngine
+from .mask_segmentation import wants_segmentation
 from .tloco import BranchStreams, EditDeepFloydIF, IFScheduler, cfg_weights
 from .utils import save_image as _save_image
 
@@ -395,7 +396,7 @@ class EditStableDiffusion(EditDeepFloydIF):
         self.EXP_NAME = "original"
         F, E, N = self.for_prompt_emb, self.edit_prompt_emb, self.null_prompt_emb
         x0 = None
-        segment = bool(getattr(self.args, "mask_model_path", "")) and not self._exists(os.path.join(self.result_folder, "mask/mask.pt"))
+        segment = wants_segmentation(self.args) and not self._exists(os.path.join(self.result_folder, "mask/mask.pt"))
         if self.sharder.agree(not os.path.exists(os.path.join(self.result_folder, "original.png"))) or segment:
             _, x0 = self.DDIMforwardsteps(zT, t_start_idx=0, t_end_idx=-1, for_prompt_emb=F, edit_prompt_emb=E, null_prompt_emb=N,
                                           mode="null+(for-null)")         # the image SAM segments (edit.py:942-948)
