@@ -720,6 +720,48 @@ int  loco_quality_masked_mse(loco_quality* q, const float* a_dev, const float* b
 const char* loco_quality_last_error(loco_quality* q);
 void loco_quality_destroy(loco_quality* q);
 
+/* --- Randomized, centred low-rank PCA of a sample matrix on the device (the h-space PCA baselines, hspace_pca.py) ---
+ * Its own handle: the sample store H [n_max][d] (fp32), its centred copy and every workspace are allocated at create.
+ * Algorithm, with Omega [d][q] from the caller (so the result is a deterministic function of the store and Omega):
+ *     Q = orth(Hc Omega);  niter times: Z = orth(Hc^T Q), Q = orth(Hc Z);  B = Hc^T Q;  B^T B = E diag(lambda) E^T;
+ *     s = sqrt(lambda) descending, V = B E / s, every column of V flipped so that its entry of largest magnitude is positive.
+ * Hc = fp32(H - mean) formed in double from column means summed in double; orth = CholeskyQR2 with the Gram summed in double
+ * over parts of the long dimension whose boundaries depend on its length alone, joined in order (no atomics); the q x q
+ * Cholesky, its inverse and the eigendecomposition run in double on the host (each call synchronises `stream` for them).  The
+ * products are exact fp32.  Independent of loco_set_precision / LOCO_PRECISION.  Results are bit-identical from call to
+ * call and whatever chunks the rows arrived in.  The unit's limit for q is 512. */
+typedef struct loco_pca loco_pca;
+int  loco_pca_create(int32_t device, int64_t n_max, int64_t d, int32_t q_max, loco_pca** out);
+/* Forget the rows (the capacity stays). */
+int  loco_pca_reset(loco_pca* p);
+/* The rows held, or -1. */
+int64_t loco_pca_rows(loco_pca* p);
+/* Appends rows_dev [b][d] (device, fp32).  Refused, with the bytes in the message: d other than the handle's, more rows
+ * than n_max in all. */
+int  loco_pca_add_rows(loco_pca* p, const float* rows_dev, int64_t b, int64_t d, void* stream);
+/* s_dev [q], v_dev [d][q], mean_dev [d] (optional; zeros when center == 0) of the rows held.  omega_dev [d][q].  Refused: q
+ * above min(N - 1, d) with centring or min(N, d) without, q above q_max or 512, niter < 0; a pivot of a Cholesky
+ * factor below 2^-30 of its column's squared norm (or such an eigenvalue of B^T B): the message names the numerical rank
+ * and q, and no output is written. */
+int  loco_pca_fit(loco_pca* p, int32_t q, int32_t niter, const float* omega_dev, int32_t center, float* s_dev, float* v_dev, float* mean_dev,
+                  void* stream);
+/* The parts of loco_pca_fit on their own (tests, profiles).  loco_pca_center: centered_dev [N][d] and mean_dev [d] (either may be
+ * NULL) of the rows held; center == 0: the rows as they are, mean 0.  loco_pca_gram: g_dev [q][q] (double) = y_dev^T y_dev for
+ * y_dev [rows][q], rows <= max(n_max, d).  loco_pca_project: out_dev [N][q] = Hc w_dev (w_dev [d][q]) or, transpose != 0,
+ * out_dev [d][q] = Hc^T w_dev (w_dev [N][q]). */
+int  loco_pca_center(loco_pca* p, int32_t center, float* centered_dev, float* mean_dev, void* stream);
+int  loco_pca_gram(loco_pca* p, const float* y_dev, int64_t rows, int32_t q, double* g_dev, void* stream);
+int  loco_pca_project(loco_pca* p, const float* w_dev, int32_t q, int32_t transpose, int32_t center, float* out_dev, void* stream);
+/* Route of the two large products: 0 = launch_gemm where the 64 x 64 output grid has 256 tiles or more, else the
+ * split-contraction kernel (default); 1 = launch_gemm always; 2 = the split-contraction kernel always. */
+int  loco_pca_set_route(loco_pca* p, int32_t route);
+/* The routes the last loco_pca_fit / loco_pca_project took, "HW:<route> HtQ:<route>" with gemm, split (contraction in parts)
+ * or tile (one part). */
+const char* loco_pca_routes(loco_pca* p);
+/* Message of the last failed call on p; p == NULL: of the last failed loco_pca_create. */
+const char* loco_pca_last_error(loco_pca* p);
+void loco_pca_destroy(loco_pca* p);
+
 #ifdef __cplusplus
 }
 #endif

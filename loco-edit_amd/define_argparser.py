@@ -172,6 +172,22 @@ def build_parser():
                         'taken to; the run starts at the nearest timestep of the --for_steps schedule')
     p.add_argument('--range_scale', type=float, default=50.0,
                    help='--run_edit_blended_diffusion: weight of the range loss mean |x0 - clamp(x0, -1, 1)|')
+    p.add_argument('--run_edit_hspace_pca', type=str2bool, default=False,
+                   help='edit along unsupervised h-space directions: PCA of the U-Net bottleneck h at --edit_t, computed on the '
+                        'device (the global / local h-space PCA baselines). Unconditional models only; --pca_rank directions are '
+                        'shown, --vis_num frames each side')
+    p.add_argument('--hspace_pca', type=str, default='global', choices=['global', 'local'],
+                   help="--run_edit_hspace_pca: 'global' = PCA of h over --hspace_pca_samples fresh x_T taken to --edit_t; 'local' = "
+                        "PCA of h over that many unit-norm perturbations of the inverted image's x_t")
+    p.add_argument('--hspace_pca_samples', type=int, default=1000,
+                   help='--run_edit_hspace_pca: samples of h the PCA is taken over (the reference default is 50000)')
+    p.add_argument('--hspace_pca_rank', type=int, default=50,
+                   help='--run_edit_hspace_pca: rank of the PCA, at most min(samples - 1, 512); --pca_rank of them are shown')
+    p.add_argument('--hspace_edit', type=str, default='h', choices=['h', 'x'],
+                   help="--run_edit_hspace_pca: 'h' adds alpha * scale * s_k / sqrt(N - 1) * u_k to h at every remaining step of the "
+                        "decode; 'x' moves x_t along inv_jac_xt(u_k) as --run_edit_null_space_projection moves it along its basis")
+    p.add_argument('--hspace_edit_scale', type=float, default=1.0,
+                   help='--run_edit_hspace_pca --hspace_edit h: multiplies the walk, in standard deviations of h along the direction')
     p.add_argument('--mask_prompts', type=str, default='',
                    help='text-prompted edit masks: a comma list such as "hair,eyes,mouth"; when mask/mask.pt is missing, CLIPSeg '
                         '(--mask_prompt_model_path) writes one mask per entry, in order, so --mask_index selects a prompt')
@@ -215,10 +231,42 @@ def check_blended_args(args, edit_prompt=None):
         raise ValueError("--blended_num_aug must be at least 1")
 
 
+HSPACE_PCA_Q_LIMIT = 512          # hip.LocoPca.Q_LIMIT (not imported here: parsing needs no device library)
+
+
+def check_hspace_pca_args(args):
+    """--run_edit_hspace_pca and its flags: checked before any device work."""
+    given = [f for f, d in (('hspace_pca', 'global'), ('hspace_pca_samples', 1000), ('hspace_pca_rank', 50), ('hspace_edit', 'h'),
+                            ('hspace_edit_scale', 1.0)) if getattr(args, f) != d]
+    if not args.run_edit_hspace_pca:
+        if given:
+            raise ValueError(f"--{given[0]} is read by --run_edit_hspace_pca only")
+        return
+    if any(s in args.model_name for s in ('stable-diffusion', 'DeepFloyd', 'LCM')):
+        raise ValueError("--run_edit_hspace_pca is built for the unconditional models (the T-LOCO classes have no h-space tap "
+                         "on their classifier-free-guidance combination)")
+    if args.hspace_pca_samples < 3:
+        raise ValueError(f"--hspace_pca_samples {args.hspace_pca_samples}: a centred PCA needs at least 3 samples")
+    most = min(args.hspace_pca_samples - 1, HSPACE_PCA_Q_LIMIT)
+    if not 1 <= args.hspace_pca_rank <= most:
+        raise ValueError(f"--hspace_pca_rank {args.hspace_pca_rank} must lie in [1, min(samples - 1, {HSPACE_PCA_Q_LIMIT})] = [1, {most}]")
+    if args.pca_rank > args.hspace_pca_rank:
+        raise ValueError(f"--pca_rank {args.pca_rank} directions are shown, the PCA has only --hspace_pca_rank {args.hspace_pca_rank}")
+    if not args.hspace_edit_scale > 0 or not np.isfinite(args.hspace_edit_scale):
+        raise ValueError(f"--hspace_edit_scale {args.hspace_edit_scale} must be positive and finite")
+    if args.hspace_edit == 'x' and args.hspace_edit_scale != 1.0:
+        raise ValueError("--hspace_edit_scale scales the h-space walk (--hspace_edit h); the x-space walk is scaled by "
+                         "--x_space_guidance_scale")
+    if args.vT_path:
+        raise ValueError("--vT_path loads an x-space basis for --run_edit_null_space_projection; --run_edit_hspace_pca keeps its "
+                         "own basis file")
+
+
 def parse_args(argv=None):
     args = build_parser().parse_args(argv)
     if args.solver:
         os.environ["LOCO_SOLVER"] = args.solver
+    check_hspace_pca_args(args)
     if args.jacobian_target == 'h':
         if any(s in args.model_name for s in ('stable-diffusion', 'DeepFloyd', 'LCM')):
             raise ValueError("--jacobian_target h is built for the unconditional models (the T-LOCO classes differentiate a "

@@ -265,7 +265,145 @@ class EditUncondDiffusion(object):
                                      v0, verbose)
         return hT.T.contiguous(), s, eT.T.contiguous()
 
+    # h-space PCA baselines of the same class (models/ddpm/diffusion.py:347-482): the unsupervised h-space directions LOCO is
+    # compared against.  The samples stay on the device (hip.LocoPca, csrc/pca.hip) instead of going to ``pca_device``.
+    def _h_tap_only(self, op, block_idx):
+        if op not in (None, 'mid') or block_idx not in (None, 0):
+            raise NotImplementedError(f"h-space tap (op, block_idx) = ({op!r}, {block_idx!r}): only ('mid', 0) is built")
+
+    def _pca_generator(self, generator):
+        return generator if generator is not None else torch.Generator().manual_seed(int(self.seed) % (2 ** 63))
+
+    @torch.no_grad()
+    def inv_jac_xt(self, x=None, t=None, op=None, block_idx=None, u=None, perturb_h=1e-1):
+        """diffusion.py:347-377 -> vT [k, n] for u [n_h, k] (or [n_h]: k = 1).  The reference differentiates
+        ``|| h + perturb_h u - get_h(x) ||`` at the ``x`` where that difference is ``perturb_h u``: row i is
+        ``-J^T u_i / (|J^T u_i| + 1e-6)`` with J = d h / d x_t -- the NEGATIVE pullback of u_i, and independent of
+        ``perturb_h`` (accepted for the signature).  One encoder primal and one cotangent pass per row."""
+        self._h_tap_only(op, block_idx)
+        x = x.to(device=self.device, dtype=torch.float32).contiguous()
+        u = u.to(device=self.device, dtype=torch.float32)
+        rows = (u.reshape(1, -1) if u.dim() == 1 else u.T).contiguous()
+        self.engine.pmp_primal(x, float(t), self.scheduler.alpha_at(t), None, tap="enc")
+        g = self.engine.pmp_vjp(rows)
+        return -g / (g.norm(dim=1, keepdim=True) + 1e-6)
+
+    @torch.no_grad()
+    def local_pca_xt(self, x=None, t=None, op=None, block_idx=None, memory_bound=5, num_pca_samples=50000, pca_rank=512,
+                     pca_device='cpu', return_x_direction=True, perturb_h=1e-1, noise=None, generator=None):
+        """diffusion.py:379-436 -> (u [n_h, q], s [q], vT [q, n] | None): PCA (niter = 2) of ``get_h(x + eps / (|eps| + 1e-6))``
+        over ``num_pca_samples`` Gaussian draws.  ``s`` are the singular values of the centred sample matrix, as
+        ``torch.pca_lowrank`` returns them.  ``memory_bound`` is accepted (the engine chunks by its ``max_batch``);
+        ``pca_device`` is accepted and ignored: the samples never leave the device.  Extensions: ``noise`` [N, C, R, R] injects
+        the draws, ``generator`` seeds the range finder (default: a CPU generator seeded with the run's seed)."""
+        from . import hspace_pca
+        self._h_tap_only(op, block_idx)
+        n = int(num_pca_samples)
+        x = x.to(device=self.device, dtype=torch.float32).contiguous()
+        if noise is not None and (noise.dim() != 4 or noise.shape[0] != n or tuple(noise.shape[1:]) != tuple(x.shape[1:])):
+            raise ValueError(f"noise must be [{n}, {', '.join(str(v) for v in x.shape[1:])}], got {tuple(noise.shape)}")
+        store = hspace_pca.LocoPca(n, self.engine.n_h, int(pca_rank), device=self.device)
+        mb = self.engine.max_batch
+        for b0 in range(0, n, mb):
+            b = min(mb, n - b0)
+            eps = (torch.randn(b, *x.shape[1:], device=self.device, dtype=torch.float32) if noise is None
+                   else noise[b0:b0 + b].to(device=self.device, dtype=torch.float32))
+            hspace_pca.sample_h(self.engine, x + hspace_pca.normalize_wrt_batch(eps), t, store)
+        s, u, mean = hspace_pca.pca_lowrank_device(store, int(pca_rank), 2, self._pca_generator(generator), center=True)
+        self.last_pca = {"mean": mean, "n_samples": n, "routes": store.routes()}
+        vT = self.inv_jac_xt(x=x, t=t, op=op, block_idx=block_idx, u=u, perturb_h=perturb_h) if return_x_direction else None
+        return u, s, vT
+
+    @torch.no_grad()
+    def global_pca_xt(self, x=None, t=None, op=None, block_idx=None, memory_bound=5, pca_rank=512, pca_device='cpu',
+                      generator=None):
+        """diffusion.py:438-482 -> (u [n_h, q], s [q]): PCA (niter = 5) of ``get_h`` over the rows of ``x`` [N, C, R, R] (x_t of N
+        independent x_T).  ``memory_bound`` / ``pca_device`` / ``generator``: as ``local_pca_xt``."""
+        from . import hspace_pca
+        self._h_tap_only(op, block_idx)
+        store = hspace_pca.sample_h(self.engine, x, t, q_max=int(pca_rank))
+        s, u, mean = hspace_pca.pca_lowrank_device(store, int(pca_rank), 5, self._pca_generator(generator), center=True)
+        self.last_pca = {"mean": mean, "n_samples": int(x.shape[0]), "routes": store.routes()}
+        return u, s
+
     # ------------------------------------------------------------------ drivers
+    @torch.no_grad()
+    def run_edit_hspace_pca(self, idx, vis_num, vis_num_pc=5, pca_rank=50, kind='global', num_samples=1000, edit='h', scale=1.0,
+                            op='mid', block_idx=0, use_mask=True, **kwargs):
+        """--run_edit_hspace_pca: edits along the unsupervised h-space directions (not in the reference's CLI; its class has the
+        three functions only).  ``kind`` 'global': PCA of h at ``edit_t`` over ``num_samples`` fresh x_T; 'local': around the
+        inverted image's x_t.  The basis ``{u, s, mean, t, kind, n_samples}`` is saved next to the other basis files and reused
+        when present.  ``edit`` 'h': every remaining step of the decode gets ``alpha scale s_k / sqrt(N - 1) u_k`` added to the
+        bottleneck (all frames of a walk in one batch); 'x': ``vT = inv_jac_xt(u)`` and the x-space walk of
+        ``run_edit_null_space_projection``.  Grids and quality scores as there.  The sampling runs on every rank alike (no
+        sharding)."""
+        from . import hspace_pca
+        if kind not in ('global', 'local') or edit not in ('h', 'x'):
+            raise ValueError(f"kind must be 'global' or 'local' and edit 'h' or 'x', got {kind!r}, {edit!r}")
+        n_s, q = int(num_samples), int(pca_rank)
+        if q < 1 or q > min(n_s - 1, self.engine.n_h, hspace_pca.LocoPca.Q_LIMIT):
+            raise ValueError(f"--hspace_pca_rank {q} must lie in [1, min(samples - 1, n_h, {hspace_pca.LocoPca.Q_LIMIT})] = "
+                             f"[1, {min(n_s - 1, self.engine.n_h, hspace_pca.LocoPca.Q_LIMIT)}]")
+        xT, mask = self._get_xT_and_mask(idx, use_mask)
+        if xT is None:
+            return None
+        xt, t, t_idx = self.DDIMforwardsteps(xT, t_start_idx=0, t_end_idx=self.edit_t_idx)
+        assert t_idx == self.edit_t_idx
+        save_dir = os.path.join(self.result_folder, "basis", f'hspace_pca-{self.edit_t}T')
+        os.makedirs(save_dir, exist_ok=True)
+        basis_path = os.path.join(save_dir, f'hspace-pca-{kind}-rank-{q}-samples-{n_s}.pt')
+        if self._exists(basis_path):
+            print(f'loading the h-space PCA basis {basis_path}')
+            basis = torch.load(basis_path, map_location="cpu") if self.sharder.is_main else None
+            if self.sharder.active:
+                basis = self.sharder.agree(basis)
+            self.hspace_pca_reloaded = True
+        else:
+            self.hspace_pca_reloaded = False
+            print(f'h-space PCA ({kind}): {n_s} samples of h at t = {int(t)}, rank {q}')
+            gen = torch.Generator().manual_seed(int(self.seed) % (2 ** 63))
+            if kind == 'global':
+                shape = (self.c_in, self.image_size, self.image_size)
+                mb = self.engine.max_batch
+                store = hspace_pca.LocoPca(n_s, self.engine.n_h, q, device=self.device)
+                for b0 in range(0, n_s, mb):
+                    x_T = torch.randn(min(mb, n_s - b0), *shape, generator=gen).to(self.device)
+                    x_t, _, _ = self.DDIMforwardsteps(x_T, t_start_idx=0, t_end_idx=self.edit_t_idx)
+                    hspace_pca.sample_h(self.engine, x_t, t, store)
+                s, u, mean = hspace_pca.pca_lowrank_device(store, q, 5, gen, center=True)
+            else:
+                u, s, _ = self.local_pca_xt(x=xt, t=t, op=op, block_idx=block_idx, num_pca_samples=n_s, pca_rank=q,
+                                            return_x_direction=False, generator=gen,
+                                            noise=torch.randn(n_s, *xt.shape[1:], generator=gen))
+                mean = self.last_pca["mean"]
+            basis = {"u": u.cpu(), "s": s.cpu(), "mean": mean.cpu(), "t": int(t), "kind": kind, "n_samples": n_s}
+            self._save(basis, basis_path)
+        u, s = basis["u"].to(self.device, torch.float32), basis["s"].to(self.device, torch.float32)
+        n_pc = min(int(vis_num_pc), u.shape[1])
+        alphas = self._walk_alphas(vis_num)
+        BASIS_NAME = f"hspace-pca-{kind}-edit_{self.edit_t}T-{edit}-rank{q}-scale_{scale}"
+        names = [f'{idx}-Edit-hspace_pca-{BASIS_NAME}-pc_{pc_idx:0=3d}' for pc_idx in range(n_pc)]
+        original_xt = xt.detach()
+        if edit == 'x':
+            vT = self.inv_jac_xt(x=original_xt, t=t, op=op, block_idx=block_idx, u=u[:, :n_pc].contiguous())
+            frames = [self.edit_batch(original_xt, vT[pc_idx, :], vis_num) for pc_idx in range(n_pc)]
+            per = frames[0].shape[0]
+            dec = self._decode_frames(torch.cat(frames, dim=0), n_pc, per)
+        else:
+            per = len(alphas)
+            sigma = s[:n_pc] / float(basis["n_samples"] - 1) ** 0.5             # standard deviation of h along u_k
+            a = torch.tensor(alphas, device=self.device, dtype=torch.float32)
+            # dh [n_pc, per, n_h] = alpha_j scale sigma_k u_k
+            dh = (float(scale) * sigma)[:, None, None] * a[None, :, None] * u[:, :n_pc].T[:, None, :]
+            dec = hspace_pca.decode_with_dh(self, original_xt.expand(n_pc * per, -1, -1, -1), self.edit_t_idx,
+                                            dh.reshape(n_pc * per, -1), performance_boosting=True)
+        for pc_idx, name in enumerate(names):
+            self.EXP_NAME = name
+            image = (dec[pc_idx * per:(pc_idx + 1) * per] / 2 + 0.5).clamp(0, 1)
+            self._save_image(image, os.path.join(self.result_folder, f'{name}.png'), nrow=image.size(0))
+            self._score_quality(image, name, alphas, mask)
+        return dec
+
     @torch.no_grad()
     def group_edit_null_space_projection(self, idx, **kwargs):
         """edit.py:2171-2212: compose two saved directions."""

@@ -48,6 +48,8 @@ SYMBOLS = [
     "loco_clipseg_preprocess", "loco_clipseg_masks", "loco_clipseg_last_error", "loco_clipseg_destroy",
     "loco_quality_create", "loco_quality_load_param", "loco_quality_params_missing", "loco_quality_lpips", "loco_quality_ssim",
     "loco_quality_masked_mse", "loco_quality_last_error", "loco_quality_destroy",
+    "loco_pca_create", "loco_pca_reset", "loco_pca_rows", "loco_pca_add_rows", "loco_pca_fit", "loco_pca_center", "loco_pca_gram",
+    "loco_pca_project", "loco_pca_set_route", "loco_pca_routes", "loco_pca_last_error", "loco_pca_destroy",
 ]
 
 # operators of loco_pmp_primal_tap (include/loco_hip.h): None x_t -> x0 / eps, "enc" x_t -> h, "dec" h -> eps
@@ -333,6 +335,23 @@ def load_library():
         lib.loco_quality_last_error.restype = C.c_char_p
         lib.loco_quality_destroy.argtypes = [vp]
         lib.loco_quality_destroy.restype = None
+    if hasattr(lib, "loco_pca_create"):
+        lib.loco_pca_create.argtypes = [i32, i64, i64, i32, C.POINTER(vp)]
+        lib.loco_pca_reset.argtypes = [vp]
+        lib.loco_pca_rows.argtypes = [vp]
+        lib.loco_pca_rows.restype = i64
+        lib.loco_pca_add_rows.argtypes = [vp, vp, i64, i64, vp]
+        lib.loco_pca_fit.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, vp]
+        lib.loco_pca_center.argtypes = [vp, i32, vp, vp, vp]
+        lib.loco_pca_gram.argtypes = [vp, vp, i64, i32, vp, vp]
+        lib.loco_pca_project.argtypes = [vp, vp, i32, i32, i32, vp, vp]
+        lib.loco_pca_set_route.argtypes = [vp, i32]
+        lib.loco_pca_routes.argtypes = [vp]
+        lib.loco_pca_routes.restype = C.c_char_p
+        lib.loco_pca_last_error.argtypes = [vp]
+        lib.loco_pca_last_error.restype = C.c_char_p
+        lib.loco_pca_destroy.argtypes = [vp]
+        lib.loco_pca_destroy.restype = None
     if hasattr(lib, "loco_bench_conv"):          # diag build only
         lib.loco_bench_conv.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(f32), vp]
         lib.loco_debug_tensor.argtypes = [vp, C.c_char_p, vp, i64, vp]
@@ -1645,3 +1664,111 @@ class LocoQualityEngine(_EncoderEngine):
         if bool((cnt == 0).any()):
             raise ValueError("empty mask")
         return s / cnt.double()
+
+
+class LocoPca(_EncoderEngine):
+    """Randomized, centred low-rank PCA of a sample matrix that stays on the device (= loco_pca, include/loco_hip.h): the
+    sample store ``[n_max, d]`` (fp32) and every workspace live in the handle.  ``add_rows`` appends, ``fit`` returns
+    ``(s [q], V [d, q], mean [d])`` as a deterministic function of the store and ``omega``.  ``ValueError`` for arguments
+    that are refused here (dtype, device, shapes), ``RuntimeError`` with the library's message for what it refuses
+    (capacity, q, numerical rank)."""
+    _prefix, _label = "loco_pca", "device PCA"
+    ROUTES = {"auto": 0, "gemm": 1, "split": 2}
+    Q_LIMIT = 512
+
+    def __init__(self, n_max: int, d: int, q_max: int, device: Optional[torch.device] = None):
+        self._open(device)
+        self.n_max, self.d, self.q_max = int(n_max), int(d), int(q_max)
+        if self.q_max > self.Q_LIMIT:
+            raise ValueError(f"q_max = {self.q_max} is above the unit's limit of {self.Q_LIMIT}")
+        with torch.cuda.device(self.device):
+            rc = self.lib.loco_pca_create(self.device.index, self.n_max, self.d, self.q_max, C.byref(self._t))
+        if rc != 0:
+            raise RuntimeError(f"loco_pca_create failed ({rc}): {self.lib.loco_pca_last_error(None).decode()}")
+
+    def _chk(self, t: torch.Tensor, what: str, shape=None, dtype=torch.float32) -> torch.Tensor:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{what}: expected a tensor")
+        if t.dtype != dtype:
+            raise ValueError(f"{what}: expected {dtype}, got {t.dtype}")
+        if t.device != self.device:
+            raise ValueError(f"{what}: expected a tensor on {self.device}, got one on {t.device}")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{what}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+        return t.contiguous()
+
+    @property
+    def rows(self) -> int:
+        return int(self.lib.loco_pca_rows(self._t))
+
+    def reset(self):
+        self._check(self.lib.loco_pca_reset(self._t), "loco_pca_reset")
+
+    def set_route(self, route: str):
+        """'auto' (launch_gemm where the output grid fills the chip, else the split-contraction kernel), 'gemm', 'split'."""
+        if route not in self.ROUTES:
+            raise ValueError(f"route must be one of {sorted(self.ROUTES)}, got {route!r}")
+        self._check(self.lib.loco_pca_set_route(self._t, self.ROUTES[route]), "loco_pca_set_route")
+
+    def routes(self) -> str:
+        return self.lib.loco_pca_routes(self._t).decode()
+
+    def add_rows(self, rows: torch.Tensor):
+        """Appends ``rows [b, d]`` (fp32, on the handle's device)."""
+        if not isinstance(rows, torch.Tensor) or rows.dim() != 2:
+            raise ValueError("add_rows: expected rows [b, d]")
+        rows = self._chk(rows, "add_rows")
+        if rows.shape[0] == 0:
+            return
+        with torch.cuda.device(self.device):
+            self._check(self.lib.loco_pca_add_rows(self._t, _ptr(rows), rows.shape[0], rows.shape[1], _stream()), "loco_pca_add_rows")
+            torch.cuda.current_stream().synchronize()       # `rows` may be a temporary of the caller
+
+    def fit(self, q: int, niter: int, omega: torch.Tensor, center: bool = True):
+        """``(s [q], V [d, q], mean [d])`` of the rows held; ``omega [d, q]`` is the caller's random test matrix."""
+        q, niter = int(q), int(niter)
+        if q < 1:
+            raise ValueError(f"fit: q = {q} must be positive")
+        omega = self._chk(omega, "fit: omega", (self.d, q))
+        s = torch.zeros(q, device=self.device, dtype=torch.float32)
+        V = torch.zeros(self.d, q, device=self.device, dtype=torch.float32)
+        mean = torch.zeros(self.d, device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.loco_pca_fit(self._t, q, niter, _ptr(omega), int(bool(center)), _ptr(s), _ptr(V), _ptr(mean), _stream()),
+                        "loco_pca_fit")
+        return s, V, mean
+
+    def center(self, center: bool = True):
+        """Forms the centred store inside the handle (what ``fit`` does first), without copying it out."""
+        with torch.cuda.device(self.device):
+            self._check(self.lib.loco_pca_center(self._t, int(bool(center)), None, None, _stream()), "loco_pca_center")
+
+    def centered(self, center: bool = True):
+        """``(Hc [N, d], mean [d])``: the centred store as ``fit`` reads it."""
+        Hc = torch.empty(self.rows, self.d, device=self.device, dtype=torch.float32)
+        mean = torch.empty(self.d, device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.loco_pca_center(self._t, int(bool(center)), _ptr(Hc), _ptr(mean), _stream()), "loco_pca_center")
+        return Hc, mean
+
+    def gram(self, Y: torch.Tensor) -> torch.Tensor:
+        """``Y^T Y [q, q]`` in float64 for ``Y [rows, q]`` (fp32), summed as ``fit`` sums its Gram matrices."""
+        if not isinstance(Y, torch.Tensor) or Y.dim() != 2:
+            raise ValueError("gram: expected Y [rows, q]")
+        Y = self._chk(Y, "gram: Y")
+        G = torch.empty(Y.shape[1], Y.shape[1], device=self.device, dtype=torch.float64)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.loco_pca_gram(self._t, _ptr(Y), Y.shape[0], Y.shape[1], _ptr(G), _stream()), "loco_pca_gram")
+        return G
+
+    def project(self, W: torch.Tensor, transpose: bool = False, center: bool = True) -> torch.Tensor:
+        """``Hc W [N, q]`` for ``W [d, q]``, or with ``transpose`` ``Hc^T W [d, q]`` for ``W [N, q]``."""
+        if not isinstance(W, torch.Tensor) or W.dim() != 2:
+            raise ValueError("project: expected W [rows, q]")
+        n = self.rows
+        W = self._chk(W, "project: W", (n if transpose else self.d, W.shape[1]))
+        out = torch.empty(self.d if transpose else n, W.shape[1], device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.loco_pca_project(self._t, _ptr(W), W.shape[1], int(bool(transpose)), int(bool(center)), _ptr(out), _stream()),
+                        "loco_pca_project")
+        return out

@@ -75,6 +75,11 @@ def main(argv=None):
         out = edit.run_edit_blended_diffusion(
             idx=args.sample_idx, edit_prompt=args.edit_prompt, clip_guidance_scale=args.clip_guidance_scale,
             num_aug=args.blended_num_aug, start_t=args.blended_start_t, range_scale=args.range_scale)
+    if args.run_edit_hspace_pca:                 # the h-space PCA baselines (hspace_pca.py; the reference's CLI does not reach them)
+        out = edit.run_edit_hspace_pca(
+            idx=args.sample_idx, op='mid', block_idx=0, vis_num=args.vis_num, vis_num_pc=args.pca_rank,
+            pca_rank=args.hspace_pca_rank, kind=args.hspace_pca, num_samples=args.hspace_pca_samples, edit=args.hspace_edit,
+            scale=args.hspace_edit_scale, use_mask=args.use_mask)
     if args.run_ddim_forward:                    # main.py:98-99
         edit.run_DDIMforward(num_samples=5)
     if args.run_ddim_inversion:                  # main.py:102-103
