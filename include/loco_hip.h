@@ -146,6 +146,13 @@ int  loco_sched_step(loco_ctx* ctx, const float* x, const float* et, float at, f
                      float eta, const float* noise, int64_t count, float* x_next, float* x0_out,
                      void* stream);
 
+/* The eta = 0 scheduler update with two network outputs (Asyrp's asymmetric step, asyrp.py): the x0 estimate from et_edit,
+ * the direction term from et_src,
+ *     x0 = (x - sqrt(1 - at) et_edit) / sqrt(at),   x_next = sqrt(at_next) x0 + sqrt(1 - at_next) et_src.
+ * One launch; with et_edit == et_src bit-identical to loco_sched_step(eta = 0).  x0_out (optional) receives x0. */
+int  loco_sched_step_asym(loco_ctx* ctx, const float* x, const float* et_edit, const float* et_src, float at, float at_next,
+                          int64_t count, float* x_next, float* x0_out, void* stream);
+
 /* --- PMP-Jacobian operator J = d x0_hat[mask] / d x_t  (edit.py:2369-2391) ---
  * loco_pmp_primal evaluates the denoiser once at (x,t), caching what the
  * tangent and cotangent passes need; `mask` is uint8 [C*H*W] (nullptr = all
@@ -194,6 +201,14 @@ int  loco_unet_forward_dh(loco_ctx* ctx, const float* x, float t, int32_t B, con
  * read and written as float4: 16-byte aligned pointers. */
 int  loco_pmp_primal_tap(loco_ctx* ctx, const float* x, float t, float at, const uint8_t* mask, int32_t use_et,
                          int32_t tap, void* stream);
+/* The tap 2 (decoder) primal of loco_pmp_primal_tap at a SHIFTED bottleneck: the forward pass runs with h <- h + dh, dh [n_h]
+ * injected where loco_unet_forward_dh injects it, so every record the later loco_pmp_jvp / loco_pmp_vjp / loco_pmp_primal_eps
+ * read -- the tensors behind the tap and the GroupNorm statistics over them -- is taken at h + dh: J = mask . c . d eps / d h
+ * at h(x_t) + dh, and loco_pmp_primal_eps returns what loco_unet_forward_dh(x, t, dh) returns.  dh == NULL: exactly
+ * loco_pmp_primal_tap(.., tap = 2).  Refused like loco_unet_forward_dh: a network without a tap, a tap op that is not an
+ * identity-shortcut ResBlock. */
+int  loco_pmp_primal_tap_dh(loco_ctx* ctx, const float* x, float t, float at, const uint8_t* mask, int32_t use_et,
+                            const float* dh, void* stream);
 /* eps[n_out] = the network output the last loco_pmp_primal / _tap (tap 0 or 2) evaluated at its linearisation point: a copy
  * out of the cached state, no second evaluation.  Valid until the next call that runs the network on this context. */
 int  loco_pmp_primal_eps(loco_ctx* ctx, float* eps, void* stream);
@@ -761,6 +776,46 @@ const char* loco_pca_routes(loco_pca* p);
 /* Message of the last failed call on p; p == NULL: of the last failed loco_pca_create. */
 const char* loco_pca_last_error(loco_pca* p);
 void loco_pca_destroy(loco_pca* p);
+
+/* --- The trainable h-space block f_t of the Asyrp baseline (asyrp.py) ---
+ * For h [B][C][H][W] (the U-Net bottleneck) and a time vector e [E], with a scalar s per call:
+ *     a1 = swish(GroupNorm32(h; g1, b1));   y1 = W1 a1 + c1 + (Wt swish(e) + ct);
+ *     a2 = swish(GroupNorm32(y1; g2, b2));  dh = s (W2 a2 + c2)
+ * Parameters (loco_asyrp_load_param names): g1 b1 c1 ct g2 b2 c2 [C], W1 W2 [C][C] (1x1 convs), Wt [C][E].  Its own handle:
+ * the parameters, their gradient store, Adam's two moments (zero at create) and the records of the last forward live on
+ * the device.  Exact fp32 products; every contraction, GroupNorm moment and per-channel sum is accumulated in double in a
+ * fixed order and rounded once (no atomics): two identical call sequences give bit-identical results.  Independent of
+ * loco_set_precision / LOCO_PRECISION.  Refused at create: C not a positive multiple of 32 or above 2048, a map outside
+ * 1 x 1 .. 64 x 64, E outside [1, 8192], max_batch outside [1, 64], gn_eps <= 0. */
+typedef struct loco_asyrp loco_asyrp;
+int  loco_asyrp_create(int32_t device, int32_t C, int32_t H, int32_t W, int32_t E, int32_t max_batch, float gn_eps, loco_asyrp** out);
+/* fp32 values behind a host or a device pointer; shape as listed above. */
+int  loco_asyrp_load_param(loco_asyrp* p, const char* name, const float* data, const int64_t* shape, int32_t ndim);
+/* The count of parameters not loaded yet (0: complete); the first one's name goes to the last error. */
+int  loco_asyrp_params_missing(loco_asyrp* p);
+/* Copies parameter `name` / its accumulated gradient to dst (host or device, `count` floats = the parameter's size) after
+ * waiting for the device. */
+int  loco_asyrp_read_param(loco_asyrp* p, const char* name, float* dst, int64_t count);
+int  loco_asyrp_read_grad(loco_asyrp* p, const char* name, float* dst, int64_t count);
+/* dh_dev [B][C][H][W] = f_t(h_dev [B][C][H][W], e_dev [E]) scaled by s.  keep_records != 0: the records loco_asyrp_backward
+ * reads (the repacked h, a1, y1, a2, both norms' statistics, swish(e), B and s) stay valid until the next forward;
+ * keep_records == 0 leaves the handle without records.  Refused: B outside [1, max_batch], parameters missing. */
+int  loco_asyrp_forward(loco_asyrp* p, const float* h_dev, const float* e_dev, int32_t B, float s, float* dh_dev, int32_t keep_records,
+                        void* stream);
+/* For the cotangent g_dh_dev [B][C][H][W] of dh: ADDS the gradients of the ten parameters to the gradient store, from the
+ * records of the last forward, and writes the cotangent of h to g_h_dev [B][C][H][W] unless it is NULL.  Refused: no
+ * records, B other than the records'. */
+int  loco_asyrp_backward(loco_asyrp* p, const float* g_dh_dev, int32_t B, float* g_h_dev, void* stream);
+int  loco_asyrp_zero_grad(loco_asyrp* p, void* stream);
+/* One Adam step of every parameter from the gradient store, in one launch (torch.optim.Adam's arithmetic, no weight decay):
+ *     m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g^2;
+ *     p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
+ * step counts from 1 and is the caller's.  loco_asyrp_reset_moments zeroes m and v. */
+int  loco_asyrp_adam_step(loco_asyrp* p, float lr, float beta1, float beta2, float eps, int32_t step, void* stream);
+int  loco_asyrp_reset_moments(loco_asyrp* p, void* stream);
+/* Message of the last failed call on p; p == NULL: of the last failed loco_asyrp_create. */
+const char* loco_asyrp_last_error(loco_asyrp* p);
+void loco_asyrp_destroy(loco_asyrp* p);
 
 #ifdef __cplusplus
 }

@@ -1549,6 +1549,17 @@ int loco_sched_step(loco_ctx* c, const float* x, const float* et, float at, floa
     return 0;
 }
 
+int loco_sched_step_asym(loco_ctx* c, const float* x, const float* et_edit, const float* et_src, float at, float at_next, int64_t count,
+                         float* x_next, float* x0_out, void* stream) {
+    if (!c) return -2;
+    if (!x || !et_edit || !et_src || !x_next) { c->err = "loco_sched_step_asym: null argument"; return -2; }
+    float s1, s2, s3, ce, cn;
+    sched_coeffs(at, at_next, 0.f, &s1, &s2, &s3, &ce, &cn);
+    launch_asym_step(x, et_edit, et_src, x_next, x0_out, (long)count, s2, s1, s3, ce, (hipStream_t)stream);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
 int loco_ddim_step(loco_ctx* c, const float* x, float t, float at, float at_next, float eta, const float* noise,
                    int32_t B, float* x_next, void* stream) {
     if (!c) return -2;
@@ -1564,13 +1575,18 @@ int loco_pmp_primal(loco_ctx* c, const float* x, float t, float at, const uint8_
     return loco_pmp_primal_tap(c, x, t, at, mask, use_et, 0, stream);
 }
 
-int loco_pmp_primal_tap(loco_ctx* c, const float* x, float t, float at, const uint8_t* mask, int32_t use_et, int32_t tap,
-                        void* stream) {
-    if (!c) return -2;
+// the primal of every tap; `dh` (tap 2 only, may be null): the shift of the bottleneck the forward pass injects, so that every record
+// behind the tap -- the arena tensors, the GroupNorm statistics, the {S, xhat} caches -- is taken at h + dh
+static int pmp_primal_at(loco_ctx* c, const float* x, float t, float at, const uint8_t* mask, int32_t use_et, int32_t tap, const float* dh,
+                         void* stream) {
     if (tap < 0 || tap > 2) { c->err = "loco_pmp_primal_tap: tap must be 0 (x_t -> x0 / eps), 1 (encoder, x_t -> h) or 2 (decoder, h -> eps)"; return -2; }
     if (tap && tap_refuse(c, "loco_pmp_primal_tap")) return -2;
     if (tap == 1 && mask) { c->err = "loco_pmp_primal_tap: the encoder tap (x_t -> h) takes no mask: h has no pixel positions to select"; return -2; }
     if (finalize_params(c)) return -3;
+    if (dh) {
+        const Op& op = c->ops[c->prog->h_last_op];
+        if (op.kind != OP_RES || op.has_nin || op.updown) { c->err = "loco_pmp_primal_tap_dh: the tap op is not an identity-shortcut ResBlock"; return -2; }
+    }
     if (tap == 1) use_et = 1;     // (no x0 combination at the tap: `at` and use_et are not read)
     if (c->prog->n_out != c->prog->n_in && !use_et) {
         c->err = "loco_pmp_primal: a network whose output size differs from its input has no x0 combination; use_et = 1 "
@@ -1581,7 +1597,7 @@ int loco_pmp_primal_tap(loco_ctx* c, const float* x, float t, float at, const ui
     // the ops whose linearisation the products of this primal run: all, the encoder half, or the decoder half (whose primal needs
     // the whole forward pass)
     const int op_lo = tap == 2 ? c->prog->h_last_op + 1 : 0, op_hi = tap == 1 ? c->prog->h_last_op : (int)c->ops.size() - 1;
-    if (forward_pass(c, x, t, 1, c->arenaP, c->statsP, st, nullptr, tap == 1 ? op_hi : -1)) return -1;
+    if (forward_pass(c, x, t, 1, c->arenaP, c->statsP, st, nullptr, tap == 1 ? op_hi : -1, dh)) return -1;
     c->primal_B = 1;
     if (c->prec >= 1) {
         // {S, xhat} cache for the tangent / cotangent staging of the split-bf16 convs
@@ -1619,6 +1635,19 @@ int loco_pmp_primal_tap(loco_ctx* c, const float* x, float t, float at, const ui
     HIPCHK(c, hipGetLastError());
     c->primal_ok = true;
     return 0;
+}
+
+int loco_pmp_primal_tap(loco_ctx* c, const float* x, float t, float at, const uint8_t* mask, int32_t use_et, int32_t tap,
+                        void* stream) {
+    if (!c) return -2;
+    return pmp_primal_at(c, x, t, at, mask, use_et, tap, nullptr, stream);
+}
+
+int loco_pmp_primal_tap_dh(loco_ctx* c, const float* x, float t, float at, const uint8_t* mask, int32_t use_et, const float* dh,
+                           void* stream) {
+    if (!c) return -2;
+    if (tap_refuse(c, "loco_pmp_primal_tap_dh")) return -2;
+    return pmp_primal_at(c, x, t, at, mask, use_et, 2, dh, stream);
 }
 
 int loco_pmp_primal_eps(loco_ctx* c, float* eps, void* stream) {

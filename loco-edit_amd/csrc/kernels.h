@@ -412,6 +412,10 @@ void launch_zero_rows(float* out, long out_bs, int B, long per_sample, hipStream
 void launch_ddim_step(const float* x, const float* eps, const float* noise, float* out, float* x0_out, long count,
                       float c_x0_x, float c_x0_e, float c_next_x0, float c_next_e, float c_noise,
                       hipStream_t st);
+// eta = 0 step with two network outputs (Asyrp's asymmetric step): x0 = (x - c_x0_e eps_edit) / c_x0_x,
+// out = c_next_x0 x0 + c_next_e eps_src; with eps_edit == eps_src bit-identical to launch_ddim_step.  x0_out may be nullptr
+void launch_asym_step(const float* x, const float* eps_edit, const float* eps_src, float* out, float* x0_out, long count, float c_x0_x,
+                      float c_x0_e, float c_next_x0, float c_next_e, hipStream_t st);
 // U = mask * (cv*V + ce*dEps); rows >= split use mask2 when it is given (two solves sharing a probe batch)
 void launch_latent_sample(const float* mom, const float* noise, float scale, float* z, int B, long zhw, hipStream_t st);
 void launch_masked_axpby(const float* V, const float* dE, const uint8_t* mask, float cv, float ce,

@@ -981,6 +981,26 @@ void launch_ddim_step(const float* x, const float* eps, const float* noise, floa
                        c_next_x0, c_next_e, c_noise);
 }
 
+// Asyrp's asymmetric DDIM step (eta = 0): the x0 estimate from the EDITED output, the direction term from the ORIGINAL one,
+//     p = (x - sq1mat e_edit) / sqat,  out = sqatn p + ce e_src.
+// The roundings are spelled out as ddim_step_kernel compiles (one fused multiply-add ahead of the division, two rounded products and
+// a sum), so with e_edit == e_src the step is ddim_step_kernel's to the last bit whatever the compiler contracts.
+__global__ void asym_step_kernel(const float* x, const float* eps_edit, const float* eps_src, float* out, float* x0_out, long count,
+                                 float sq1mat, float sqat, float sqatn, float ce) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (long)gridDim.x * blockDim.x) {
+        const float p = __fdiv_rn(fmaf(-sq1mat, eps_edit[i], x[i]), sqat);
+        if (x0_out) x0_out[i] = p;
+        out[i] = __fadd_rn(__fmul_rn(ce, eps_src[i]), __fmul_rn(sqatn, p));
+    }
+}
+void launch_asym_step(const float* x, const float* eps_edit, const float* eps_src, float* out, float* x0_out, long count, float c_x0_x,
+                      float c_x0_e, float c_next_x0, float c_next_e, hipStream_t st) {
+    int blocks = (int)((count + 255) / 256);
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(asym_step_kernel, dim3(blocks), dim3(256), 0, st, x, eps_edit, eps_src, out, x0_out, count, c_x0_e, c_x0_x, c_next_x0,
+                       c_next_e);
+}
+
 __global__ void masked_axpby_kernel(const float* V, const float* dE, const uint8_t* mask, float cv, float ce,
                                     float* U, long n, long total, const uint8_t* mask2, long split) {
     // rows >= split use mask2 (two subspace solves with different masks sharing one probe batch)

@@ -188,6 +188,26 @@ def build_parser():
                         "decode; 'x' moves x_t along inv_jac_xt(u_k) as --run_edit_null_space_projection moves it along its basis")
     p.add_argument('--hspace_edit_scale', type=float, default=1.0,
                    help='--run_edit_hspace_pca --hspace_edit h: multiplies the walk, in standard deviations of h along the direction')
+    p.add_argument('--run_edit_asyrp', type=str2bool, default=False,
+                   help='the Asyrp baseline: train a small h-space block f_t from one text pair (--asyrp_src_prompt, '
+                        '--asyrp_tgt_prompt) with a directional CLIP loss on the device, then edit --sample_idx with the asymmetric '
+                        'DDIM step from T down to --edit_t. Unconditional models only; needs --clip_model_path')
+    p.add_argument('--asyrp_src_prompt', type=str, default='', help='--run_edit_asyrp: the text of the source attribute, e.g. "a face"')
+    p.add_argument('--asyrp_tgt_prompt', type=str, default='', help='--run_edit_asyrp: the text of the target attribute, e.g. "a smiling face"')
+    p.add_argument('--asyrp_ckpt', type=str, default='',
+                   help='--run_edit_asyrp: the trained block (a state dict of its ten tensors plus the Adam step count): loaded when '
+                        'the file exists, else trained and saved there. Empty: <result_folder>/asyrp_ckpt.pt')
+    p.add_argument('--asyrp_train_idx', type=str, default='0-99',
+                   help='--run_edit_asyrp: the dataset images the block is trained on, e.g. 0-99 or 3,7,11 (inclusive ranges)')
+    p.add_argument('--asyrp_epochs', type=int, default=1, help='--run_edit_asyrp: passes over the training images')
+    p.add_argument('--asyrp_lr', type=float, default=1e-3,
+                   help="--run_edit_asyrp: Adam's step size, constant (no scheduler is built). Asyrp publishes 0.5 with its own "
+                        'scheduler; here the first Adam step moves every weight of the C x C output conv by lr with coherent signs, '
+                        'which shifts h by about 0.35 C lr: 1e-3 keeps that below a fifth of the spread of h at C = 512')
+    p.add_argument('--asyrp_clip_weight', type=float, default=0.8, help='--run_edit_asyrp: weight of the directional CLIP loss (as published)')
+    p.add_argument('--asyrp_rec_weight', type=float, default=3.0,
+                   help='--run_edit_asyrp: weight of the reconstruction loss mean |x0_edit - x0_src| (as published)')
+    p.add_argument('--asyrp_scale', type=float, default=1.0, help='--run_edit_asyrp: multiplies the learned dh at inference')
     p.add_argument('--mask_prompts', type=str, default='',
                    help='text-prompted edit masks: a comma list such as "hair,eyes,mouth"; when mask/mask.pt is missing, CLIPSeg '
                         '(--mask_prompt_model_path) writes one mask per entry, in order, so --mask_index selects a prompt')
@@ -229,6 +249,26 @@ def check_blended_args(args, edit_prompt=None):
         raise ValueError(f"--blended_start_t {args.blended_start_t}: a noise level in (0, 1]")
     if int(args.blended_num_aug) < 1:
         raise ValueError("--blended_num_aug must be at least 1")
+
+
+def check_asyrp_args(args):
+    """--run_edit_asyrp needs a CLIP model and the text pair: checked before any device work."""
+    if any(s in args.model_name for s in ('stable-diffusion', 'DeepFloyd', 'LCM')):
+        raise ValueError("--run_edit_asyrp trains on an unconditional denoiser's bottleneck: the text-to-image classes are not wired to it")
+    if not getattr(args, "clip_model_path", ""):
+        raise ValueError("--run_edit_asyrp needs --clip_model_path (the CLIP model whose directional loss trains the block)")
+    if not args.asyrp_src_prompt or not args.asyrp_tgt_prompt:
+        raise ValueError("--run_edit_asyrp needs --asyrp_src_prompt and --asyrp_tgt_prompt (the text pair the edit direction is read from)")
+    if args.asyrp_src_prompt == args.asyrp_tgt_prompt:
+        raise ValueError("--asyrp_src_prompt and --asyrp_tgt_prompt are the same text: the pair has no direction")
+    if int(args.asyrp_epochs) < 1:
+        raise ValueError("--asyrp_epochs must be at least 1")
+    if not float(args.asyrp_lr) > 0 or not np.isfinite(args.asyrp_lr):
+        raise ValueError(f"--asyrp_lr {args.asyrp_lr} must be positive and finite")
+    if not np.isfinite(args.asyrp_scale):
+        raise ValueError(f"--asyrp_scale {args.asyrp_scale} must be finite")
+    from .asyrp import parse_index_range
+    parse_index_range(args.asyrp_train_idx)
 
 
 HSPACE_PCA_Q_LIMIT = 512          # hip.LocoPca.Q_LIMIT (not imported here: parsing needs no device library)
@@ -280,6 +320,8 @@ def parse_args(argv=None):
         if any(s in args.model_name for s in ('stable-diffusion', 'DeepFloyd', 'LCM')):
             raise ValueError("--run_edit_blended_diffusion edits with an unconditional DDPM: the text-to-image classes are not wired to it")
         check_blended_args(args)
+    if args.run_edit_asyrp:
+        check_asyrp_args(args)
     check_mask_prompt_args(args)
     if args.text_encoder_path and args.prompt_emb_path:
         raise ValueError("--text_encoder_path and --prompt_emb_path both give the prompt embeddings: pass one of them")

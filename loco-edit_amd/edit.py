@@ -638,6 +638,84 @@ class EditUncondDiffusion(object):
         self._score_quality(image, self.EXP_NAME, None, mask, original_index=0)
         return out
 
+    @torch.no_grad()
+    def run_edit_asyrp(self, idx):
+        """The Asyrp baseline (asyrp.py): a block f_t on the bottleneck, trained from the text pair --asyrp_src_prompt /
+        --asyrp_tgt_prompt on the images --asyrp_train_idx (or loaded from --asyrp_ckpt when that file exists), then applied to
+        image ``idx``: inversion, the asymmetric step from T to ``edit_t``, a plain decode below it.  Writes
+        <EXP_NAME>_asyrp.png (the plain decode of the same x_T | the edit), <EXP_NAME>_clip.json, with --quality_metrics
+        <EXP_NAME>_quality.json, and <EXP_NAME>_asyrp.json with the learning time and the transfer (edit) time.  Returns the
+        edited image [1, 3, H, W] in [-1, 1]."""
+        import json
+        from . import asyrp, hspace_pca
+        from .clip_score import load_clip
+        from .define_argparser import check_asyrp_args
+        from .hip import LocoAsyrpBlock
+        args = self.args
+        check_asyrp_args(args)
+        if self.dataset is None:
+            raise ValueError(f"--run_edit_asyrp trains on and edits dataset images: --dataset_name {self.dataset_name} has none")
+        cfg = self.engine.cfg
+        src, tgt = args.asyrp_src_prompt, args.asyrp_tgt_prompt
+        scorer = load_clip(args.clip_model_path, tokenizer_path=getattr(args, "tokenizer_path", "") or None, device=self.device,
+                           max_images=2, preprocess=getattr(args, "clip_preprocess", "device"), grad=True)
+        text = scorer.text_embeds([src, tgt])
+        Ch, Hh, Wh = self.engine.h_shape
+        block = LocoAsyrpBlock(Ch, Hh, Wh, cfg.temb_ch, max_batch=1, gn_eps=cfg.gn_eps, seed=int(self.seed) % (2 ** 31), device=self.device)
+        ckpt = args.asyrp_ckpt or os.path.join(self.result_folder, "asyrp_ckpt.pt")
+        self.asyrp_trained = not self._exists(ckpt)
+        learning_time, steps, mean_loss = 0.0, 0, None
+        if self.asyrp_trained:
+            train_idx = asyrp.parse_index_range(args.asyrp_train_idx)
+            trainer = asyrp.AsyrpTrainer(self.engine, self.scheduler, scorer, block, text[0], text[1], cfg, lr=args.asyrp_lr,
+                                         clip_weight=args.asyrp_clip_weight, rec_weight=args.asyrp_rec_weight)
+
+            def learn():
+                latents = {}
+                loss = 0.0
+                for epoch in range(int(args.asyrp_epochs)):
+                    for i in train_idx:
+                        if i not in latents:                 # the inversion is the same every epoch: kept on the host
+                            latents[i] = self.run_DDIMinversion(idx=i).cpu()
+                        self.scheduler.set_timesteps(self.for_steps, device=self.device)
+                        loss = trainer.train_image(latents[i].to(self.device), self.edit_t_idx)
+                        print(f"asyrp: epoch {epoch}, image {i}: mean loss {loss:.5f}")
+                return loss
+            mean_loss, learning_time = asyrp.timed(learn)
+            steps = trainer.adam_step
+            if self.sharder.is_main:
+                asyrp.save_checkpoint(ckpt, block, steps, {"src_prompt": src, "tgt_prompt": tgt, "lr": args.asyrp_lr,
+                                                           "epochs": int(args.asyrp_epochs), "train_idx": args.asyrp_train_idx})
+        else:
+            print(f"loading the Asyrp block {ckpt}")
+            steps = asyrp.load_checkpoint(ckpt, block)
+        xT = self.run_DDIMinversion(idx=idx)
+        self.scheduler.set_timesteps(self.for_steps, device=self.device)
+
+        def transfer():
+            x_mid = asyrp.edit(self.engine, self.scheduler, block, cfg, xT, self.edit_t_idx, scale=args.asyrp_scale)
+            return hspace_pca.decode_with_dh(self, x_mid, self.edit_t_idx, None)
+        out, transfer_time = asyrp.timed(transfer)
+        plain = hspace_pca.decode_with_dh(self, xT, 0, None)
+        self.EXP_NAME = f'{idx}-Asyrp-edit_{self.edit_t}T-scale_{args.asyrp_scale}'
+        image = (torch.cat([plain, out]) / 2 + 0.5).clamp(0, 1)
+        self._save_image(image, os.path.join(self.result_folder, f'{self.EXP_NAME}_asyrp.png'), nrow=2)
+        print(f"asyrp: learning time {learning_time:.2f} s ({steps} Adam steps), transfer edit time {transfer_time:.2f} s")
+        if self.sharder.is_main:
+            frames = (image * 255).round().to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+            recs = scorer.score(frames, 0, src, tgt)
+            with open(os.path.join(self.result_folder, f"{self.EXP_NAME}_clip.json"), "w") as f:
+                json.dump({"clip_model_path": args.clip_model_path, "clip_preprocess": scorer.preprocess_mode, "for_prompt": src,
+                           "edit_prompt": tgt, "exp_name": self.EXP_NAME, "original": "the plain decode of the inverted image",
+                           "original_frame": recs[0], "frames": [dict(alpha=None, **recs[1])]}, f, indent=1)
+            with open(os.path.join(self.result_folder, f"{self.EXP_NAME}_asyrp.json"), "w") as f:
+                json.dump({"exp_name": self.EXP_NAME, "checkpoint": ckpt, "trained": bool(self.asyrp_trained), "adam_steps": int(steps),
+                           "learning_time_s": learning_time, "transfer_edit_time_s": transfer_time, "final_mean_loss": mean_loss,
+                           "src_prompt": src, "tgt_prompt": tgt, "lr": args.asyrp_lr, "epochs": int(args.asyrp_epochs),
+                           "train_idx": args.asyrp_train_idx, "scale": args.asyrp_scale, "edit_t": self.edit_t}, f, indent=1)
+        self._score_quality(image, self.EXP_NAME, None, None, original_index=0)
+        return out
+
     def _score_quality(self, image, name, alphas, mask, original_index=None):
         """--quality_metrics: scores the decoded frames `image` [n,3,H,W] in [0, 1] (before they are quantised for the PNG) against
         the walk's alpha = 0 frame (or frame `original_index`) with quality.QualityScorer and writes

@@ -35,7 +35,7 @@ SYMBOLS = [
     "loco_text_create", "loco_text_load_param", "loco_text_params_missing", "loco_text_encode", "loco_text_last_error",
     "loco_text_destroy", "loco_t5_create", "loco_text_encode_masked",
     "loco_diffedit_mask", "loco_cfg_masked_step", "loco_set_time_cond", "loco_lcm_step",
-    "loco_h_dims", "loco_unet_get_h", "loco_unet_forward_dh", "loco_pmp_primal_tap", "loco_pmp_primal_eps",
+    "loco_h_dims", "loco_unet_get_h", "loco_unet_forward_dh", "loco_pmp_primal_tap", "loco_pmp_primal_eps", "loco_pmp_primal_tap_dh", "loco_sched_step_asym",
     "loco_sam_create", "loco_sam_load_param", "loco_sam_params_missing", "loco_sam_encode", "loco_sam_profile",
     "loco_sam_profile_read", "loco_sam_last_error", "loco_sam_destroy",
     "loco_samdec_create", "loco_samdec_load_param", "loco_samdec_params_missing", "loco_samdec_set_image", "loco_samdec_predict",
@@ -50,6 +50,9 @@ SYMBOLS = [
     "loco_quality_masked_mse", "loco_quality_last_error", "loco_quality_destroy",
     "loco_pca_create", "loco_pca_reset", "loco_pca_rows", "loco_pca_add_rows", "loco_pca_fit", "loco_pca_center", "loco_pca_gram",
     "loco_pca_project", "loco_pca_set_route", "loco_pca_routes", "loco_pca_last_error", "loco_pca_destroy",
+    "loco_asyrp_create", "loco_asyrp_load_param", "loco_asyrp_params_missing", "loco_asyrp_read_param", "loco_asyrp_read_grad",
+    "loco_asyrp_forward", "loco_asyrp_backward", "loco_asyrp_zero_grad", "loco_asyrp_adam_step", "loco_asyrp_reset_moments",
+    "loco_asyrp_last_error", "loco_asyrp_destroy",
 ]
 
 # operators of loco_pmp_primal_tap (include/loco_hip.h): None x_t -> x0 / eps, "enc" x_t -> h, "dec" h -> eps
@@ -213,12 +216,16 @@ def load_library():
     lib.loco_unet_forward.argtypes = [vp, vp, f32, i32, vp, vp]
     lib.loco_ddim_step.argtypes = [vp, vp, f32, f32, f32, f32, vp, i32, vp, vp]
     lib.loco_sched_step.argtypes = [vp, vp, vp, f32, f32, f32, vp, i64, vp, vp, vp]
+    if hasattr(lib, "loco_sched_step_asym"):
+        lib.loco_sched_step_asym.argtypes = [vp, vp, vp, vp, f32, f32, i64, vp, vp, vp]
     lib.loco_pmp_primal.argtypes = [vp, vp, f32, f32, vp, i32, vp]
     lib.loco_pmp_set_second_mask.argtypes = [vp, vp, i32, vp]
     lib.loco_h_dims.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     lib.loco_unet_get_h.argtypes = [vp, vp, f32, i32, vp, vp]
     lib.loco_unet_forward_dh.argtypes = [vp, vp, f32, i32, vp, vp, vp]
     lib.loco_pmp_primal_tap.argtypes = [vp, vp, f32, f32, vp, i32, i32, vp]
+    if hasattr(lib, "loco_pmp_primal_tap_dh"):
+        lib.loco_pmp_primal_tap_dh.argtypes = [vp, vp, f32, f32, vp, i32, vp, vp]
     if hasattr(lib, "loco_pmp_primal_eps"):
         lib.loco_pmp_primal_eps.argtypes = [vp, vp, vp]
     lib.loco_pmp_jvp.argtypes = [vp, vp, i32, vp, vp]
@@ -352,6 +359,21 @@ def load_library():
         lib.loco_pca_last_error.restype = C.c_char_p
         lib.loco_pca_destroy.argtypes = [vp]
         lib.loco_pca_destroy.restype = None
+    if hasattr(lib, "loco_asyrp_create"):
+        lib.loco_asyrp_create.argtypes = [i32, i32, i32, i32, i32, i32, f32, C.POINTER(vp)]
+        lib.loco_asyrp_load_param.argtypes = [vp, C.c_char_p, vp, C.POINTER(i64), i32]
+        lib.loco_asyrp_params_missing.argtypes = [vp]
+        lib.loco_asyrp_read_param.argtypes = [vp, C.c_char_p, vp, i64]
+        lib.loco_asyrp_read_grad.argtypes = [vp, C.c_char_p, vp, i64]
+        lib.loco_asyrp_forward.argtypes = [vp, vp, vp, i32, f32, vp, i32, vp]
+        lib.loco_asyrp_backward.argtypes = [vp, vp, i32, vp, vp]
+        lib.loco_asyrp_zero_grad.argtypes = [vp, vp]
+        lib.loco_asyrp_adam_step.argtypes = [vp, f32, f32, f32, f32, i32, vp]
+        lib.loco_asyrp_reset_moments.argtypes = [vp, vp]
+        lib.loco_asyrp_last_error.argtypes = [vp]
+        lib.loco_asyrp_last_error.restype = C.c_char_p
+        lib.loco_asyrp_destroy.argtypes = [vp]
+        lib.loco_asyrp_destroy.restype = None
     if hasattr(lib, "loco_bench_conv"):          # diag build only
         lib.loco_bench_conv.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(f32), vp]
         lib.loco_debug_tensor.argtypes = [vp, C.c_char_p, vp, i64, vp]
@@ -562,12 +584,33 @@ class LocoEngine:
                     "loco_sched_step")
         return out, x0
 
+    def sched_step_asym(self, x, et_edit, et_src, at, at_next, want_x0=False):
+        """The eta = 0 step with the x0 estimate from ``et_edit`` and the direction term from ``et_src`` (Asyrp's asymmetric step):
+        ``(x_next, x0 or None)``."""
+        for t_ in (x, et_edit, et_src):
+            _chk_dev(t_)
+        if et_edit.numel() != x.numel() or et_src.numel() != x.numel():
+            raise ValueError("sched_step_asym: x, et_edit and et_src must have the same number of elements")
+        out = torch.empty_like(x)
+        x0 = torch.empty_like(x) if want_x0 else None
+        self._check(self.lib.loco_sched_step_asym(self._ctx, _ptr(x), _ptr(et_edit), _ptr(et_src), float(at), float(at_next), x.numel(),
+                                                  _ptr(out), _ptr(x0), _stream()), "loco_sched_step_asym")
+        return out, x0
+
     # ---- PMP-Jacobian operator
-    def pmp_primal(self, x, t, at, mask: Optional[torch.Tensor] = None, use_et: bool = False, tap: Optional[str] = None):
+    def pmp_primal(self, x, t, at, mask: Optional[torch.Tensor] = None, use_et: bool = False, tap: Optional[str] = None,
+                   dh: Optional[torch.Tensor] = None):
         """``tap``: None (J = d x0_hat[mask] / d x_t), ``"enc"`` (J = d h / d x_t, no mask) or ``"dec"`` (J = mask . c . d eps / d h);
-        pmp_jvp / pmp_vjp take and return rows of that operator's widths until the next pmp_primal."""
+        pmp_jvp / pmp_vjp take and return rows of that operator's widths until the next pmp_primal.  ``dh`` (``tap="dec"`` only):
+        the decoder tap is linearised at the shifted bottleneck ``h(x_t) + dh`` and ``pmp_primal_eps`` is the network output there."""
         if tap not in TAPS:
             raise ValueError(f"tap must be None, 'enc' or 'dec', got {tap!r}")
+        if dh is not None:
+            if tap != "dec":
+                raise ValueError("dh shifts the bottleneck of the decoder tap: it needs tap='dec'")
+            _chk_dev(dh)
+            if dh.numel() != self.n_h:
+                raise ValueError(f"dh must have the {self.n_h} elements of h, got {tuple(dh.shape)}")
         _chk_dev(x)
         if x.numel() != self.n:
             raise ValueError(f"the linearisation point is one sample of {self.n} elements, got {tuple(x.shape)}")
@@ -577,6 +620,11 @@ class LocoEngine:
             if m8.numel() != self.n_out:
                 raise ValueError("mask must have C*H*W elements (of the network output)")
         self._mask_keepalive = m8
+        if dh is not None:
+            self._check(self.lib.loco_pmp_primal_tap_dh(self._ctx, _ptr(x), float(t), float(at), _ptr(m8), int(use_et), _ptr(dh), _stream()),
+                        "loco_pmp_primal_tap_dh")
+            self._tap = tap
+            return
         if tap is not None:
             self._check(self.lib.loco_pmp_primal_tap(self._ctx, _ptr(x), float(t), float(at), _ptr(m8), int(use_et), TAPS[tap],
                                                      _stream()), "loco_pmp_primal_tap")
@@ -1772,3 +1820,107 @@ class LocoPca(_EncoderEngine):
             self._check(self.lib.loco_pca_project(self._t, _ptr(W), W.shape[1], int(bool(transpose)), int(bool(center)), _ptr(out), _stream()),
                         "loco_pca_project")
         return out
+
+
+class LocoAsyrpBlock(_EncoderEngine):
+    """The trainable h-space block f_t of the Asyrp baseline (= loco_asyrp, include/loco_hip.h):
+    ``dh = s (W2 swish(GN(W1 swish(GN(h)) + c1 + Wt swish(e) + ct)) + c2)`` for ``h [B, C, H, W]`` and a time vector ``e [E]``.
+    The parameters, their gradient store and Adam's moments live in the handle.  ``forward`` keeps the records ``backward``
+    reads; ``backward`` ADDS the parameter gradients to the store.  ``ValueError`` for arguments refused here (dtype, device,
+    shapes), ``RuntimeError`` with the library's message for what it refuses (geometry, missing records)."""
+    _prefix, _label = "loco_asyrp", "Asyrp block"
+    PARAMS = ("g1", "b1", "W1", "c1", "Wt", "ct", "g2", "b2", "W2", "c2")
+    GROUPS = 32
+
+    @staticmethod
+    def param_shapes(C_: int, E: int) -> Dict[str, tuple]:
+        return {"g1": (C_,), "b1": (C_,), "W1": (C_, C_), "c1": (C_,), "Wt": (C_, E), "ct": (C_,), "g2": (C_,), "b2": (C_,),
+                "W2": (C_, C_), "c2": (C_,)}
+
+    @staticmethod
+    def init_params(C_: int, E: int, seed: int = 0) -> Dict[str, torch.Tensor]:
+        """The seeded initial state (fp32, CPU): unit gains, zero offsets and biases, W1 / Wt uniform in +-1 / sqrt(fan_in),
+        W2 = c2 = 0 -- an untrained block is the identity edit (dh = 0)."""
+        gen = torch.Generator().manual_seed(int(seed))
+        sd = {k: torch.zeros(s, dtype=torch.float32) for k, s in LocoAsyrpBlock.param_shapes(C_, E).items()}
+        sd["g1"].fill_(1.0)
+        sd["g2"].fill_(1.0)
+        sd["W1"] = (torch.rand(C_, C_, generator=gen, dtype=torch.float64) * 2 - 1).div(C_ ** 0.5).to(torch.float32)
+        sd["Wt"] = (torch.rand(C_, E, generator=gen, dtype=torch.float64) * 2 - 1).div(E ** 0.5).to(torch.float32)
+        return sd
+
+    def __init__(self, C_: int, H: int, W: int, E: int, max_batch: int = 1, gn_eps: float = 1e-6, seed: Optional[int] = 0,
+                 device: Optional[torch.device] = None):
+        self._open(device)
+        self.C, self.H, self.W, self.E, self.max_batch, self.gn_eps = int(C_), int(H), int(W), int(E), int(max_batch), float(gn_eps)
+        with torch.cuda.device(self.device):
+            rc = self.lib.loco_asyrp_create(self.device.index, self.C, self.H, self.W, self.E, self.max_batch, self.gn_eps, C.byref(self._t))
+        if rc != 0:
+            raise RuntimeError(f"loco_asyrp_create failed ({rc}): {self.lib.loco_asyrp_last_error(None).decode()}")
+        if seed is not None:
+            self.load_state_dict(self.init_params(self.C, self.E, seed))
+
+    def _chk(self, t: torch.Tensor, what: str, shape) -> torch.Tensor:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{what}: expected a tensor")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{what}: expected torch.float32, got {t.dtype}")
+        if t.device != self.device:
+            raise ValueError(f"{what}: expected a tensor on {self.device}, got one on {t.device}")
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{what}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+        return t.contiguous()
+
+    def _read(self, fn: str) -> Dict[str, torch.Tensor]:
+        out = {}
+        with torch.cuda.device(self.device):
+            for name, shape in self.param_shapes(self.C, self.E).items():
+                t = torch.empty(shape, dtype=torch.float32)
+                self._check(self._fn(fn)(self._t, name.encode(), C.c_void_p(t.data_ptr()), t.numel()), f"loco_asyrp_{fn}({name})")
+                out[name] = t
+        return out
+
+    def state_dict(self) -> Dict[str, torch.Tensor]:
+        """The ten parameters (fp32, CPU)."""
+        return self._read("read_param")
+
+    def grads(self) -> Dict[str, torch.Tensor]:
+        """The accumulated gradients of the ten parameters (fp32, CPU)."""
+        return self._read("read_grad")
+
+    def forward(self, h: torch.Tensor, e: torch.Tensor, s: float = 1.0, keep_records: bool = True) -> torch.Tensor:
+        """``dh [B, C, H, W]`` for ``h [B, C, H, W]`` and the time vector ``e [E]``."""
+        if not isinstance(h, torch.Tensor) or h.dim() != 4:
+            raise ValueError("forward: expected h [B, C, H, W]")
+        h = self._chk(h, "forward: h", (h.shape[0], self.C, self.H, self.W))
+        e = self._chk(e, "forward: e", (self.E,))
+        dh = torch.empty_like(h)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.loco_asyrp_forward(self._t, _ptr(h), _ptr(e), h.shape[0], float(s), _ptr(dh), int(bool(keep_records)), _stream()),
+                        "loco_asyrp_forward")
+        return dh
+
+    def backward(self, g_dh: torch.Tensor, need_g_h: bool = False) -> Optional[torch.Tensor]:
+        """Adds the parameter gradients for the cotangent ``g_dh [B, C, H, W]`` of the last forward's output to the store;
+        with ``need_g_h`` returns the cotangent of h."""
+        if not isinstance(g_dh, torch.Tensor) or g_dh.dim() != 4:
+            raise ValueError("backward: expected g_dh [B, C, H, W]")
+        g_dh = self._chk(g_dh, "backward: g_dh", (g_dh.shape[0], self.C, self.H, self.W))
+        g_h = torch.empty_like(g_dh) if need_g_h else None
+        with torch.cuda.device(self.device):
+            self._check(self.lib.loco_asyrp_backward(self._t, _ptr(g_dh), g_dh.shape[0], _ptr(g_h), _stream()), "loco_asyrp_backward")
+        return g_h
+
+    def zero_grad(self):
+        with torch.cuda.device(self.device):
+            self._check(self.lib.loco_asyrp_zero_grad(self._t, _stream()), "loco_asyrp_zero_grad")
+
+    def adam_step(self, step: int, lr: float, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8):
+        """One Adam step of all ten parameters from the gradient store; ``step`` counts from 1."""
+        with torch.cuda.device(self.device):
+            self._check(self.lib.loco_asyrp_adam_step(self._t, float(lr), float(beta1), float(beta2), float(eps), int(step), _stream()),
+                        "loco_asyrp_adam_step")
+
+    def reset_moments(self):
+        with torch.cuda.device(self.device):
+            self._check(self.lib.loco_asyrp_reset_moments(self._t, _stream()), "loco_asyrp_reset_moments")

@@ -80,6 +80,8 @@ def main(argv=None):
             idx=args.sample_idx, op='mid', block_idx=0, vis_num=args.vis_num, vis_num_pc=args.pca_rank,
             pca_rank=args.hspace_pca_rank, kind=args.hspace_pca, num_samples=args.hspace_pca_samples, edit=args.hspace_edit,
             scale=args.hspace_edit_scale, use_mask=args.use_mask)
+    if args.run_edit_asyrp:                      # the Asyrp baseline (asyrp.py; not in the reference)
+        out = edit.run_edit_asyrp(idx=args.sample_idx)
     if args.run_ddim_forward:                    # main.py:98-99
         edit.run_DDIMforward(num_samples=5)
     if args.run_ddim_inversion:                  # main.py:102-103
