@@ -41,8 +41,7 @@ struct Pass {
     int B;
     float* arena;      // activation arena of this pass
     float* stats;      // stats arena of this pass
-    float* T(int id) const { return arena + c->tens[id].off; }
-    long bs() const { return c->prog->per_sample; }
+    TView T(int id) const { return tview(c, arena, id); }
 };
 
 // attention products: exact fp32 MFMA in the f32 mode and for the short / small ones, split-bf16 on the bf16 matrix
@@ -107,11 +106,6 @@ inline void attn_softmax_jac(loco_ctx* c, float* dS, const float* P, long rows, 
     attn_note(c, "softmax_jac"); launch_softmax_jac(dS, P, rows, T, rows, scale, st, B, bs);
 }
 }  // namespace
-
-void conv_defaults(ConvArgs& a) {
-    std::memset(&a, 0, sizeof(a));
-    a.stride = 1; a.pad = 1; a.nsplit = 1; a.mode = CM_NONE; a.res_scale = 1.f;
-}
 
 NS nstats(const loco_ctx* c, float* base, const NormP& n) {
     NS s;
@@ -217,17 +211,6 @@ bool run_conv(loco_ctx* c, const ConvArgs& a0, int taps, hipStream_t st, const S
     return p.cot;
 }
 
-void setw(ConvArgs& a, const ConvP& p, bool dgrad) {
-    a.w = dgrad ? p.wd : p.wf;
-    a.wb = dgrad ? (const void*)p.wbd : (const void*)p.wbf;
-    a.wh = dgrad ? (const void*)p.whd : (const void*)p.whf;
-    const bool folded = p.wpb && p.poly_dgrad == dgrad;      // (plan_conv takes them on the up / zero-insert launches it routes polyphase)
-    a.wpb = folded ? p.wpb : nullptr;
-    a.wph = folded ? p.wph : nullptr;
-    a.wqb = dgrad ? p.wqb : nullptr;
-    a.wqh = dgrad ? p.wqh : nullptr;
-}
-
 namespace {
 // the norm (if any) that takes its statistics over exactly tensor `tid`
 NormP* consumer_norm(loco_ctx* c, int tid) {
@@ -288,12 +271,6 @@ bool cat_fused_tstats(loco_ctx* c, const NormP& n, int tid, int B, hipStream_t s
                                  Bt.keep + c->lane_s0 * (Bt.keep_floats / MB), Bt.keep_ntile, B, q.C, q.H * q.W,
                                  c->cfg.gn_groups, sp.mr, stt.tst, stt.tc, c->prog->stats_per_sample, st);
     return true;
-}
-
-void gn_forward_stats(const Pass& p, const NormP& n, const float* x, long xbs, int HW) {
-    NS s = nstats(p.c, p.stats, n);
-    launch_gn_stats(x, xbs, p.B, n.C, HW, p.c->cfg.gn_groups, eps_of(p.c, n), n.gamma, n.beta, s.mr, s.sc, s.sh,
-                    p.c->prog->stats_per_sample, p.c->red, p.st);
 }
 
 
@@ -523,232 +500,57 @@ void attn_cotangent(const Attn& s) {    // g_o in s.to -> g_q, g_k, g_v in s.tq,
 namespace {
 
 // y[Cout][T] (+ bias, + residual) = W x[Cin][T] as a 1x1 conv; dgrad: the transposed map
-void lin1x1(loco_ctx* c, const ConvP& w, bool dgrad, const float* in, long in_bs, int Cin, float* out, long out_bs, int Cout,
-            int H, int W, int B, const float* res, long res_bs, bool with_bias, hipStream_t st, const StatReq* rq = nullptr) {
-    ConvArgs a; conv_defaults(a);
-    a.in = in; a.in_bs = in_bs; a.Cin = Cin; a.Hin = H; a.Win = W;
-    setw(a, w, dgrad); a.pad = 0;
-    if (with_bias) a.bias = w.bias;
-    a.res = res; a.res_bs = res_bs;
-    a.out = out; a.out_bs = out_bs; a.Cout = Cout; a.Hout = H; a.Wout = W; a.B = B;
+void lin1x1(loco_ctx* c, const ConvP& w, bool dgrad, const TView& in, const TView& out, int B, hipStream_t st,
+            const float* bias = nullptr, const float* res = nullptr, const StatReq* rq = nullptr) {
+    ConvArgs a = conv_args(in, w, dgrad, out, B, 1);
+    a.bias = bias; a.res = res; a.res_bs = res ? out.bs : 0;
     run_conv(c, a, 1, st, rq);
 }
 
-// ------------------------------ forward ------------------------------------
-// `op_hi` >= 0: stop after that op (the encoder half of loco_unet_get_h and of the encoder tap's primal).  `dh` [B][n_h]: added to
-// the tap tensor h as the tap op writes it -- the op is an identity-shortcut ResBlock, out = conv2(..) + in, so conv2 takes
-// in + dh (staged in the block's cotangent scratch a1, idle in a forward pass) as its residual and the statistics its epilogue
-// delivers or keeps for the norm over cat([h, skip]) are those of the modified h, on the launch list of the plain forward.
-int forward_pass(loco_ctx* c, const float* x, float t, int B, float* arena, float* stats, hipStream_t st,
-                 const float* t_ptr = nullptr, int op_hi = -1, const float* dh = nullptr) {
-    const loco_unet_cfg& cfg = c->cfg;
-    Pass p{c, st, B, arena, stats};
-    const long SB = c->prog->stats_per_sample;
-    clear_ready(c);
-    auto next_fwd = [&](int tid) { return req_fwd_of(c, tid, stats); };   // forward statistics for the consumer of `tid` (+ kept partials of a concatenation part)
-    if (cfg.arch < 2) {
-        launch_temb(t, cfg.ch, cfg.ch * 4, c->wts->freq, c->wts->td0w, c->wts->td0b, c->wts->td1w, c->wts->td1b, c->tact, st, cfg.arch == 1,
-                    c->has_cond ? c->cond_add : nullptr, t_ptr, cfg.act, c->has_tcond ? c->cond_in : nullptr);
-        launch_temb_proj(c->tact, cfg.ch * 4, c->wts->tp_w, c->wts->tp_b, (int)c->wts->tproj_total, c->tproj, st);
+// Statistics unless a producer already delivered them: the conv that finished tensor `tid` may have carried the request of the
+// norm that consumes it (StatReq -> ready); else, `cat`, the kept partials of a concatenation's two parts may serve; else the
+// standalone pass over the tensor.  Either way the flag is spent.
+void need_fwd_stats(const Pass& p, NormP& n, int tid, bool cat = false) {
+    loco_ctx* c = p.c;
+    if (!n.ready && !(cat && cat_fused_stats(c, n, tid, p.stats, p.B, p.st))) {
+        const TView x = p.T(tid);
+        NS s = nstats(c, p.stats, n);
+        launch_gn_stats(x, x.bs, p.B, n.C, x.H * x.W, c->cfg.gn_groups, eps_of(c, n), n.gamma, n.beta, s.mr, s.sc, s.sh,
+                        c->prog->stats_per_sample, c->red, p.st);
     }
-    const int op_end = op_hi >= 0 ? op_hi : (int)c->ops.size() - 1;
-    for (int oi = 0; oi <= op_end; ++oi) {
-        Op& op = c->ops[oi];
-        const Tens& to = c->tens[op.out];
-        const int HW = to.H * to.W;
-        switch (op.kind) {
-            case OP_CONV_IN: {
-                ConvArgs a; conv_defaults(a);
-                a.in = x; a.in_bs = c->prog->n_in; a.Cin = cfg.in_channels; a.Hin = cfg.resolution; a.Win = cfg.resolution;
-                setw(a, op.conv, false); a.bias = op.conv.bias;
-                a.out = p.T(op.out); a.out_bs = p.bs(); a.Cout = to.C; a.Hout = to.H; a.Wout = to.W; a.B = B;
-                if (op.ksize == 1) a.pad = 0;
-                const StatReq rq = next_fwd(op.out);
-                run_conv(c, a, op.ksize == 1 ? 1 : 9, st, &rq);
-                break;
-            }
-            case OP_CONV: {
-                const Tens& ti = c->tens[op.in];
-                ConvArgs a; conv_defaults(a);
-                a.in = p.T(op.in); a.in_bs = p.bs(); a.Cin = ti.C; a.Hin = ti.H; a.Win = ti.W;
-                setw(a, op.conv, false); a.bias = op.conv.bias;
-                a.out = p.T(op.out); a.out_bs = p.bs(); a.Cout = to.C; a.Hout = to.H; a.Wout = to.W; a.B = B;
-                if (op.ksize == 1) a.pad = 0;
-                const StatReq rq = next_fwd(op.out);
-                run_conv(c, a, op.ksize == 1 ? 1 : 9, st, &rq);
-                break;
-            }
-            case OP_RES: {
-                const Tens& ti = c->tens[op.in];
-                const int HWi = ti.H * ti.W;
-                if (!op.n1.ready && !cat_fused_stats(c, op.n1, op.in, stats, B, st)) gn_forward_stats(p, op.n1, p.T(op.in), p.bs(), HWi);
-                op.n1.ready = false;
-                NS s1 = nstats(c, stats, op.n1);
-                ConvArgs a; conv_defaults(a);
-                a.Cin = ti.C;
-                setw(a, op.c1, false); a.bias = op.c1.bias;
-                if (!op.scale_shift && op.has_temb) { a.bias2 = c->tproj + op.tproj_off; a.bias2_bs = 0; }
-                if (op.updown == 1) {
-                    // h = conv(avg_pool(silu(gn(x)))), x' = avg_pool(x)      (unet.py:198-200, 239-244)
-                    launch_gn_apply(4, nullptr, 0, p.T(op.in), p.bs(), nullptr, 0, p.T(op.a1), p.bs(), 0, B, ti.C, HWi,
-                                    cfg.gn_groups, s1.sc, s1.sh, s1.mr, SB, SB, nullptr, 0, st, cfg.act);
-                    launch_pool2x2_sum(p.T(op.a1), p.bs(), p.T(op.ap), p.bs(), 0, B, ti.C, to.H, to.W, st, 0.25f);
-                    launch_pool2x2_sum(p.T(op.in), p.bs(), p.T(op.xu), p.bs(), 0, B, ti.C, to.H, to.W, st, 0.25f);
-                    a.in = p.T(op.ap); a.in_bs = p.bs(); a.Hin = to.H; a.Win = to.W;
-                } else {
-                    a.in = p.T(op.in); a.in_bs = p.bs(); a.Hin = ti.H; a.Win = ti.W;
-                    a.mode = CM_GN_SILU; a.sc = s1.sc; a.sh = s1.sh; a.scsh_bs = SB;
-                    if (op.updown == 2) {
-                        a.upsample = 1;
-                        launch_upsample2x(p.T(op.in), p.bs(), p.T(op.xu), p.bs(), 0, 1.0f, B, ti.C, ti.H, ti.W, st);
-                    }
-                }
-                a.out = p.T(op.h1); a.out_bs = p.bs(); a.Cout = to.C; a.Hout = to.H; a.Wout = to.W; a.B = B;
-                {   // conv1 also delivers norm2's statistics of its output (scale-shift folded in for the ADM blocks)
-                    const float* ssc = op.scale_shift ? c->tproj + op.tproj_off : nullptr;
-                    const StatReq rq2 = req_fwd(&op.n2, stats, ssc, ssc ? ssc + to.C : nullptr);
-                    run_conv(c, a, 9, st, &rq2);
-                    op.n2.ready = false;
-                }
-                NS s2 = nstats(c, stats, op.n2);
-                const float* xin = op.updown ? p.T(op.xu) : p.T(op.in);   // shortcut input after x_upd
-                if (dh && oi == c->prog->h_last_op) {                     // h + dh: (xin + dh / res_scale + conv2) * res_scale
-                    launch_add_rows(xin, p.bs(), dh, c->prog->n_h, 1.f / c->prog->res_scale, p.T(op.a1), p.bs(), B, c->prog->n_h, st);
-                    xin = p.T(op.a1);
-                }
-                ConvArgs n; conv_defaults(n);                             // the 1x1 shortcut (diffusion.py:887-912), if any
-                if (op.has_nin) {
-                    n.in = xin; n.in_bs = p.bs(); n.Cin = ti.C; n.Hin = to.H; n.Win = to.W;
-                    setw(n, op.nin, false); n.bias = op.nin.bias; n.pad = 0;
-                    n.out = p.T(op.out); n.out_bs = p.bs(); n.Cout = to.C; n.Hout = to.H; n.Wout = to.W; n.B = B;
-                }
-                ConvArgs b; conv_defaults(b);
-                b.in = p.T(op.h1); b.in_bs = p.bs(); b.Cin = to.C; b.Hin = to.H; b.Win = to.W;
-                setw(b, op.c2, false); b.bias = op.c2.bias; b.res = xin; b.res_bs = p.bs();
-                b.res_scale = op.has_nin ? 1.f : c->prog->res_scale;        // (shortcut + h) * res_scale: c2 / nin carry it in their weights
-                b.mode = CM_GN_SILU; b.sc = s2.sc; b.sh = s2.sh; b.scsh_bs = SB;
-                b.out = p.T(op.out); b.out_bs = p.bs(); b.Cout = to.C; b.Hout = to.H; b.Wout = to.W; b.B = B;
-                const StatReq rq = next_fwd(op.out);
-                run_conv(c, b, 9, st, &rq, op.has_nin ? &n : nullptr);     // shortcut K-concatenated, or run first as the residual
-                break;
-            }
-            case OP_ATTN: {
-                const int C = to.C;
-                if (!op.n1.ready) gn_forward_stats(p, op.n1, p.T(op.in), p.bs(), HW);
-                op.n1.ready = false;
-                NS s = nstats(c, stats, op.n1);
-                ConvArgs a; conv_defaults(a);
-                a.in = p.T(op.in); a.in_bs = p.bs(); a.Cin = C; a.Hin = to.H; a.Win = to.W;
-                setw(a, op.qkvc, false); a.bias = op.qkvc.bias; a.pad = 0;
-                a.mode = CM_GN; a.sc = s.sc; a.sh = s.sh; a.scsh_bs = SB;
-                a.out = p.T(op.qkv); a.out_bs = p.bs(); a.Cout = 3 * C; a.Hout = to.H; a.Wout = to.W; a.B = B;
-                run_conv(c, a, 1, st);
-                // per head h: q = qkv[h*3*CH ...], k = +CH, v = +2CH channels (QKVAttentionLegacy, unet.py:346;
-                // with one head this is the [q|k|v] stacking of the fused DDPM projection)
-                if (op.added_kv && !c->has_ctx) { c->err = "this architecture attends over the prompt's states: call loco_set_context first"; return -1; }
-                attn_forward(attn_of(c, op, B, st, arena, p.bs()));
-                ConvArgs pr; conv_defaults(pr);
-                pr.in = p.T(op.o); pr.in_bs = p.bs(); pr.Cin = C; pr.Hin = to.H; pr.Win = to.W;
-                setw(pr, op.proj, false); pr.bias = op.proj.bias; pr.pad = 0;
-                pr.res = p.T(op.in); pr.res_bs = p.bs();
-                pr.out = p.T(op.has_x ? op.xmid : op.out); pr.out_bs = p.bs(); pr.Cout = C; pr.Hout = to.H; pr.Wout = to.W; pr.B = B;
-                {
-                    const StatReq rq = next_fwd(op.has_x ? op.xmid : op.out);
-                    run_conv(c, pr, 1, st, &rq);
-                }
-                if (op.has_x) {
-                    if (!c->has_ctx) { c->err = "this architecture has cross-attention stages: call loco_set_context first"; return -1; }
-                    const XA x = xa_of(c, op, B, st);
-                    if (!op.nx.ready) gn_forward_stats(p, op.nx, p.T(op.xmid), p.bs(), HW);
-                    op.nx.ready = false;
-                    NS sx = nstats(c, stats, op.nx);
-                    ConvArgs qa; conv_defaults(qa);
-                    qa.in = p.T(op.xmid); qa.in_bs = p.bs(); qa.Cin = C; qa.Hin = to.H; qa.Win = to.W;
-                    setw(qa, op.xqc, false); qa.bias = op.xqc.bias; qa.pad = 0;
-                    qa.mode = CM_GN; qa.sc = sx.sc; qa.sh = sx.sh; qa.scsh_bs = SB;
-                    qa.out = p.T(op.xq); qa.out_bs = p.bs(); qa.Cout = C; qa.Hout = to.H; qa.Wout = to.W; qa.B = B;
-                    run_conv(c, qa, 1, st);
-                    xa_forward(x, p.T(op.xq), p.T(op.xS), p.T(op.xo));
-                    const StatReq rqx = next_fwd(op.out);
-                    lin1x1(c, op.xproj, false, p.T(op.xo), p.bs(), C, p.T(op.out), p.bs(), C, to.H, to.W, B,
-                           p.T(op.xmid), p.bs(), true, st, &rqx);
-                }
-                break;
-            }
-            case OP_XFMR: {      // latent-diffusion SpatialTransformer (oracle/loco_oracle.py _ldm_spatial_transformer)
-                if (!c->has_ctx) { c->err = "this architecture has cross-attention stages: call loco_set_context first"; return -1; }
-                const int C = to.C, T = HW, H = to.H, W = to.W;
-                const long PSb = p.bs();
-                auto X = [&](int i) { return p.T(op.xt[i]); };
-                if (!op.n1.ready) gn_forward_stats(p, op.n1, p.T(op.in), PSb, HW);
-                op.n1.ready = false;
-                NS s = nstats(c, stats, op.n1);
-                {   // h0 = proj_in(GN(x))
-                    ConvArgs a; conv_defaults(a);
-                    a.in = p.T(op.in); a.in_bs = PSb; a.Cin = C; a.Hin = H; a.Win = W;
-                    setw(a, op.pj_in, false); a.bias = op.pj_in.bias; a.pad = 0;
-                    a.mode = CM_GN; a.sc = s.sc; a.sh = s.sh; a.scsh_bs = SB;
-                    a.out = X(X_H0); a.out_bs = PSb; a.Cout = C; a.Hout = H; a.Wout = W; a.B = B;
-                    run_conv(c, a, 1, st);
-                }
-                const XA xa = xa_of(c, op, B, st);
-                // x = x + attn1(LN1(x))
-                launch_ln_fwd(X(X_H0), PSb, B, C, T, op.lng[0], op.lnb[0], 1e-5f, X(X_A1), PSb, X(X_LN1), PSb, st);
-                lin1x1(c, op.qkvc, false, X(X_A1), PSb, C, X(X_QKV), PSb, 3 * C, H, W, B, nullptr, 0, false, st);
-                attn_forward(attn_of(c, op, B, st, arena, PSb));
-                lin1x1(c, op.to_out1, false, X(X_O), PSb, C, X(X_H1), PSb, C, H, W, B, X(X_H0), PSb, true, st);
-                // x = x + attn2(LN2(x), context)
-                launch_ln_fwd(X(X_H1), PSb, B, C, T, op.lng[1], op.lnb[1], 1e-5f, X(X_A2), PSb, X(X_LN2), PSb, st);
-                lin1x1(c, op.xqc, false, X(X_A2), PSb, C, X(X_XQ), PSb, C, H, W, B, nullptr, 0, false, st);
-                xa_forward(xa, X(X_XQ), X(X_XS), X(X_XO));
-                lin1x1(c, op.to_out2, false, X(X_XO), PSb, C, X(X_H2), PSb, C, H, W, B, X(X_H1), PSb, true, st);
-                // x = x + Linear(GEGLU(LN3(x)))
-                launch_ln_fwd(X(X_H2), PSb, B, C, T, op.lng[2], op.lnb[2], 1e-5f, X(X_A3), PSb, X(X_LN3), PSb, st);
-                lin1x1(c, op.ff1, false, X(X_A3), PSb, C, X(X_F), PSb, 8 * C, H, W, B, nullptr, 0, true, st);
-                launch_geglu(0, X(X_F), PSb, nullptr, B, 4L * C * T, X(X_GG), PSb, st);
-                lin1x1(c, op.ff2, false, X(X_GG), PSb, 4 * C, X(X_H3), PSb, C, H, W, B, X(X_H2), PSb, true, st);
-                // out = input + proj_out(x)
-                const StatReq rq = next_fwd(op.out);
-                lin1x1(c, op.pj_out, false, X(X_H3), PSb, C, p.T(op.out), PSb, C, H, W, B, p.T(op.in), PSb, true, st, &rq);
-                break;
-            }
-            case OP_DOWN: case OP_UP: {
-                const Tens& ti = c->tens[op.in];
-                ConvArgs a; conv_defaults(a);
-                a.in = p.T(op.in); a.in_bs = p.bs(); a.Cin = ti.C; a.Hin = ti.H; a.Win = ti.W;
-                setw(a, op.conv, false); a.bias = op.conv.bias;
-                if (op.kind == OP_DOWN) { a.stride = 2; a.pad = op.sym_down ? 1 : 0; } else { a.upsample = 1; }
-                a.out = p.T(op.out); a.out_bs = p.bs(); a.Cout = to.C; a.Hout = to.H; a.Wout = to.W; a.B = B;
-                const StatReq rq = next_fwd(op.out);
-                run_conv(c, a, 9, st, &rq);
-                break;
-            }
-            case OP_OUT: {
-                const Tens& ti = c->tens[op.in];
-                if (!op.n1.ready) gn_forward_stats(p, op.n1, p.T(op.in), p.bs(), ti.H * ti.W);
-                op.n1.ready = false;
-                NS s = nstats(c, stats, op.n1);
-                ConvArgs a; conv_defaults(a);
-                a.in = p.T(op.in); a.in_bs = p.bs(); a.Cin = ti.C; a.Hin = ti.H; a.Win = ti.W;
-                setw(a, op.conv, false); a.bias = op.conv.bias;
-                a.mode = CM_GN_SILU; a.sc = s.sc; a.sh = s.sh; a.scsh_bs = SB;
-                a.out = p.T(op.out); a.out_bs = p.bs(); a.Cout = to.C; a.Hout = to.H; a.Wout = to.W; a.B = B;
-                run_conv(c, a, 9, st);
-                break;
-            }
-        }
-    }
-    return 0;
+    n.ready = false;
 }
 
-// ------------------------------ tangent ------------------------------------
-// primal: arenaP/statsP with B = 1 (broadcast); tangents: arenaT/statsT with B = k
-void tangent_stats(loco_ctx* c, const NormP& n, const float* d, long dbs, const float* x, int HW, int B,
-                   hipStream_t st) {
+// ------------------------------ linear passes ------------------------------
+// primal: arenaP/statsP with B = 1 (broadcast); tangents / cotangents: arenaT/statsT with B = k (the Pass of a linear pass)
+// group means of a norm's tangent (kind 0) / cotangent (1: behind the activation, 2: plain) d at the primal x
+void lin_stats(const Pass& p, const NormP& n, int kind, const TView& d, const float* x) {
+    loco_ctx* c = p.c;
     NS sp = nstats(c, c->statsP, n);
-    NS stt = nstats(c, c->statsT, n);
-    launch_gn_tstats(d, dbs, x, 0, B, n.C, HW, c->cfg.gn_groups, sp.sc, sp.sh, sp.mr, 0, 0, 0, stt.tst,
-                     stt.tc, c->prog->stats_per_sample, c->red, st);
+    NS stt = nstats(c, p.stats, n);
+    launch_gn_tstats(d, d.bs, x, 0, p.B, n.C, d.H * d.W, c->cfg.gn_groups, sp.sc, sp.sh, sp.mr, 0, 0, kind, stt.tst,
+                     stt.tc, c->prog->stats_per_sample, c->red, p.st, kind ? c->cfg.act : 0);
+}
+void need_tan_stats(const Pass& p, NormP& n, int tid, bool cat = false) {      // of the tangent of tensor `tid`
+    loco_ctx* c = p.c;
+    if (!n.ready && !(cat && cat_fused_tstats(c, n, tid, p.B, p.st))) lin_stats(p, n, 0, p.T(tid), tview(c, c->arenaP, tid));
+    n.ready = false;
+}
+void need_cot_stats(const Pass& p, NormP& n, const TView& d, const float* x) {
+    if (!n.ready) lin_stats(p, n, 1, d, x);
+    n.ready = false;
+}
+// The linearised GroupNorm (launch_gn_apply kinds 1 / 5: tangent without / with the activation, 2 / 3: cotangent with / without)
+// of the differential d at the primal x: out (+)= [base_scale * base +] norm'(x) d, from the primal statistics and the means
+// lin_stats (or a conv epilogue) left in the pass's stats arena
+void gn_lin_apply(const Pass& p, const NormP& n, int kind, const TView& d, const float* x, const float* base, float* out,
+                  int accumulate = 0, float base_scale = 1.0f) {
+    loco_ctx* c = p.c;
+    NS sp = nstats(c, c->statsP, n);
+    NS stt = nstats(c, p.stats, n);
+    launch_gn_apply(kind, d, d.bs, x, 0, base, base ? d.bs : 0, out, d.bs, accumulate, p.B, d.C, d.H * d.W, c->cfg.gn_groups,
+                    sp.sc, sp.sh, sp.mr, 0, 0, stt.tst, c->prog->stats_per_sample, p.st, kind == 2 || kind == 5 ? c->cfg.act : 0,
+                    base_scale);
 }
 void set_tan(loco_ctx* c, ConvArgs& a, const NormP& n, const float* prim) {
     NS sp = nstats(c, c->statsP, n);
@@ -762,13 +564,170 @@ void set_tan(loco_ctx* c, ConvArgs& a, const NormP& n, const float* prim) {
 
 constexpr size_t RED_BYTES = (size_t)4 << 20;   // reduction scratch (GN partial sums)
 
+// ------------------------------ forward ------------------------------------
+// `op_hi` >= 0: stop after that op (the encoder half of loco_unet_get_h and of the encoder tap's primal).  `dh` [B][n_h]: added to
+// the tap tensor h as the tap op writes it -- the op is an identity-shortcut ResBlock, out = conv2(..) + in, so conv2 takes
+// in + dh (staged in the block's cotangent scratch a1, idle in a forward pass) as its residual and the statistics its epilogue
+// delivers or keeps for the norm over cat([h, skip]) are those of the modified h, on the launch list of the plain forward.
+int forward_pass(loco_ctx* c, const float* x, float t, int B, float* arena, float* stats, hipStream_t st,
+                 const float* t_ptr = nullptr, int op_hi = -1, const float* dh = nullptr) {
+    const loco_unet_cfg& cfg = c->cfg;
+    const Pass p{c, st, B, arena, stats};
+    const long PS = c->prog->per_sample, SB = c->prog->stats_per_sample;
+    auto T = [&](int id) { return p.T(id); };
+    const TView xv = tview_in(x, c->prog->n_in, cfg.in_channels, cfg.resolution, cfg.resolution);      // the network input
+    clear_ready(c);
+    auto next_fwd = [&](int tid) { return req_fwd_of(c, tid, stats); };   // forward statistics for the consumer of `tid` (+ kept partials of a concatenation part)
+    auto gn_prologue = [&](ConvArgs& a, int mode, const NS& s) { a.mode = mode; a.sc = s.sc; a.sh = s.sh; a.scsh_bs = SB; };
+    if (cfg.arch < 2) {
+        launch_temb(t, cfg.ch, cfg.ch * 4, c->wts->freq, c->wts->td0w, c->wts->td0b, c->wts->td1w, c->wts->td1b, c->tact, st, cfg.arch == 1,
+                    c->has_cond ? c->cond_add : nullptr, t_ptr, cfg.act, c->has_tcond ? c->cond_in : nullptr);
+        launch_temb_proj(c->tact, cfg.ch * 4, c->wts->tp_w, c->wts->tp_b, (int)c->wts->tproj_total, c->tproj, st);
+    }
+    const int op_end = op_hi >= 0 ? op_hi : (int)c->ops.size() - 1;
+    for (int oi = 0; oi <= op_end; ++oi) {
+        Op& op = c->ops[oi];
+        const Tens& to = c->tens[op.out];
+        switch (op.kind) {
+            case OP_CONV_IN: case OP_CONV: {
+                ConvArgs a = conv_args(op.kind == OP_CONV_IN ? xv : T(op.in), op.conv, false, T(op.out), B, op.ksize);
+                a.bias = op.conv.bias;
+                const StatReq rq = next_fwd(op.out);
+                run_conv(c, a, op.ksize == 1 ? 1 : 9, st, &rq);
+                break;
+            }
+            case OP_RES: {
+                const Tens& ti = c->tens[op.in];
+                need_fwd_stats(p, op.n1, op.in, true);
+                NS s1 = nstats(c, stats, op.n1);
+                if (op.updown == 1) {
+                    // h = conv(avg_pool(silu(gn(x)))), x' = avg_pool(x)      (unet.py:198-200, 239-244)
+                    launch_gn_apply(4, nullptr, 0, T(op.in), PS, nullptr, 0, T(op.a1), PS, 0, B, ti.C, ti.H * ti.W,
+                                    cfg.gn_groups, s1.sc, s1.sh, s1.mr, SB, SB, nullptr, 0, st, cfg.act);
+                    launch_pool2x2_sum(T(op.a1), PS, T(op.ap), PS, 0, B, ti.C, to.H, to.W, st, 0.25f);
+                    launch_pool2x2_sum(T(op.in), PS, T(op.xu), PS, 0, B, ti.C, to.H, to.W, st, 0.25f);
+                } else if (op.updown == 2) {
+                    launch_upsample2x(T(op.in), PS, T(op.xu), PS, 0, 1.0f, B, ti.C, ti.H, ti.W, st);
+                }
+                // conv1 of a down block runs on the pooled activation op.ap, at the output resolution; else norm + activation (and
+                // the nearest x2 of an up block) are its prologue on the block's input
+                ConvArgs a = conv_args(op.updown == 1 ? T(op.ap) : T(op.in), op.c1, false, T(op.h1), B, 3);
+                a.bias = op.c1.bias;
+                if (!op.scale_shift && op.has_temb) { a.bias2 = c->tproj + op.tproj_off; a.bias2_bs = 0; }
+                if (op.updown != 1) { gn_prologue(a, CM_GN_SILU, s1); a.upsample = op.updown == 2; }
+                {   // conv1 also delivers norm2's statistics of its output (scale-shift folded in for the ADM blocks)
+                    const float* ssc = op.scale_shift ? c->tproj + op.tproj_off : nullptr;
+                    const StatReq rq2 = req_fwd(&op.n2, stats, ssc, ssc ? ssc + to.C : nullptr);
+                    run_conv(c, a, 9, st, &rq2);
+                    op.n2.ready = false;
+                }
+                TView xin = op.updown ? T(op.xu) : T(op.in);              // shortcut input after x_upd, at the output resolution
+                if (dh && oi == c->prog->h_last_op) {                     // h + dh: (xin + dh / res_scale + conv2) * res_scale
+                    launch_add_rows(xin, PS, dh, c->prog->n_h, 1.f / c->prog->res_scale, T(op.a1), PS, B, c->prog->n_h, st);
+                    xin = T(op.a1);
+                }
+                ConvArgs n{};                                             // the 1x1 shortcut (diffusion.py:887-912), if any
+                if (op.has_nin) { n = conv_args(xin, op.nin, false, T(op.out), B, 1); n.bias = op.nin.bias; }
+                ConvArgs b = conv_args(T(op.h1), op.c2, false, T(op.out), B, 3);
+                b.bias = op.c2.bias; b.res = xin; b.res_bs = PS;
+                b.res_scale = op.has_nin ? 1.f : c->prog->res_scale;        // (shortcut + h) * res_scale: c2 / nin carry it in their weights
+                gn_prologue(b, CM_GN_SILU, nstats(c, stats, op.n2));
+                const StatReq rq = next_fwd(op.out);
+                run_conv(c, b, 9, st, &rq, op.has_nin ? &n : nullptr);     // shortcut K-concatenated, or run first as the residual
+                break;
+            }
+            case OP_ATTN: {
+                const int so = op.has_x ? op.xmid : op.out;       // output tensor of the self-attention stage
+                need_fwd_stats(p, op.n1, op.in);
+                ConvArgs a = conv_args(T(op.in), op.qkvc, false, T(op.qkv), B, 1);
+                a.bias = op.qkvc.bias;
+                gn_prologue(a, CM_GN, nstats(c, stats, op.n1));
+                run_conv(c, a, 1, st);
+                // per head h: q = qkv[h*3*CH ...], k = +CH, v = +2CH channels (QKVAttentionLegacy, unet.py:346;
+                // with one head this is the [q|k|v] stacking of the fused DDPM projection)
+                if (op.added_kv && !c->has_ctx) { c->err = "this architecture attends over the prompt's states: call loco_set_context first"; return -1; }
+                attn_forward(attn_of(c, op, B, st, arena, PS));
+                {
+                    const StatReq rq = next_fwd(so);
+                    lin1x1(c, op.proj, false, T(op.o), T(so), B, st, op.proj.bias, T(op.in), &rq);
+                }
+                if (op.has_x) {
+                    if (!c->has_ctx) { c->err = "this architecture has cross-attention stages: call loco_set_context first"; return -1; }
+                    const XA x = xa_of(c, op, B, st);
+                    need_fwd_stats(p, op.nx, op.xmid);
+                    ConvArgs qa = conv_args(T(op.xmid), op.xqc, false, T(op.xq), B, 1);
+                    qa.bias = op.xqc.bias;
+                    gn_prologue(qa, CM_GN, nstats(c, stats, op.nx));
+                    run_conv(c, qa, 1, st);
+                    xa_forward(x, T(op.xq), T(op.xS), T(op.xo));
+                    const StatReq rqx = next_fwd(op.out);
+                    lin1x1(c, op.xproj, false, T(op.xo), T(op.out), B, st, op.xproj.bias, T(op.xmid), &rqx);
+                }
+                break;
+            }
+            case OP_XFMR: {      // latent-diffusion SpatialTransformer (oracle/loco_oracle.py _ldm_spatial_transformer)
+                if (!c->has_ctx) { c->err = "this architecture has cross-attention stages: call loco_set_context first"; return -1; }
+                const int C = to.C, HW = to.H * to.W;
+                auto X = [&](int i) { return T(op.xt[i]); };
+                need_fwd_stats(p, op.n1, op.in);
+                {   // h0 = proj_in(GN(x))
+                    ConvArgs a = conv_args(T(op.in), op.pj_in, false, X(X_H0), B, 1);
+                    a.bias = op.pj_in.bias;
+                    gn_prologue(a, CM_GN, nstats(c, stats, op.n1));
+                    run_conv(c, a, 1, st);
+                }
+                const XA xa = xa_of(c, op, B, st);
+                // x = x + attn1(LN1(x))
+                launch_ln_fwd(X(X_H0), PS, B, C, HW, op.lng[0], op.lnb[0], 1e-5f, X(X_A1), PS, X(X_LN1), PS, st);
+                lin1x1(c, op.qkvc, false, X(X_A1), X(X_QKV), B, st);
+                attn_forward(attn_of(c, op, B, st, arena, PS));
+                lin1x1(c, op.to_out1, false, X(X_O), X(X_H1), B, st, op.to_out1.bias, X(X_H0));
+                // x = x + attn2(LN2(x), context)
+                launch_ln_fwd(X(X_H1), PS, B, C, HW, op.lng[1], op.lnb[1], 1e-5f, X(X_A2), PS, X(X_LN2), PS, st);
+                lin1x1(c, op.xqc, false, X(X_A2), X(X_XQ), B, st);
+                xa_forward(xa, X(X_XQ), X(X_XS), X(X_XO));
+                lin1x1(c, op.to_out2, false, X(X_XO), X(X_H2), B, st, op.to_out2.bias, X(X_H1));
+                // x = x + Linear(GEGLU(LN3(x)))
+                launch_ln_fwd(X(X_H2), PS, B, C, HW, op.lng[2], op.lnb[2], 1e-5f, X(X_A3), PS, X(X_LN3), PS, st);
+                lin1x1(c, op.ff1, false, X(X_A3), X(X_F), B, st, op.ff1.bias);
+                launch_geglu(0, X(X_F), PS, nullptr, B, 4L * C * HW, X(X_GG), PS, st);
+                lin1x1(c, op.ff2, false, X(X_GG), X(X_H3), B, st, op.ff2.bias, X(X_H2));
+                // out = input + proj_out(x)
+                const StatReq rq = next_fwd(op.out);
+                lin1x1(c, op.pj_out, false, X(X_H3), T(op.out), B, st, op.pj_out.bias, T(op.in), &rq);
+                break;
+            }
+            case OP_DOWN: case OP_UP: {
+                ConvArgs a = conv_args(T(op.in), op.conv, false, T(op.out), B, 3);
+                a.bias = op.conv.bias;
+                if (op.kind == OP_DOWN) { a.stride = 2; a.pad = op.sym_down ? 1 : 0; } else { a.upsample = 1; }
+                const StatReq rq = next_fwd(op.out);
+                run_conv(c, a, 9, st, &rq);
+                break;
+            }
+            case OP_OUT: {
+                need_fwd_stats(p, op.n1, op.in);
+                ConvArgs a = conv_args(T(op.in), op.conv, false, T(op.out), B, 3);
+                a.bias = op.conv.bias;
+                gn_prologue(a, CM_GN_SILU, nstats(c, stats, op.n1));
+                run_conv(c, a, 9, st);
+                break;
+            }
+        }
+    }
+    return 0;
+}
+
+// ------------------------------ tangent ------------------------------------
 // ops op_lo..op_hi (op_hi < 0: the last).  A pass that starts behind the encoder half (op_lo > 0: the decoder tap) finds the
 // tangent of h and of the skip tensors in arena T (loco_pmp_jvp puts them there); V is not read.
 int tangent_pass(loco_ctx* c, const float* V, int B, hipStream_t st, int op_lo = 0, int op_hi = -1) {
     const loco_unet_cfg& cfg = c->cfg;
     const long PS = c->prog->per_sample;
-    auto TP = [&](int id) { return c->arenaP + c->tens[id].off; };   // primal
-    auto TT = [&](int id) { return c->arenaT + c->tens[id].off; };   // tangent
+    const Pass p{c, st, B, c->arenaT, c->statsT};
+    auto TP = [&](int id) { return tview(c, c->arenaP, id); };   // primal
+    auto TT = [&](int id) { return p.T(id); };                   // tangent
+    const TView Vv = tview_in(V, c->prog->n_in, cfg.in_channels, cfg.resolution, cfg.resolution);      // of the network input
     clear_ready(c);
     // tangent group means for the norm that consumes tensor `tid`, delivered with the conv that finishes it
     // (+ the kept raw partials of a concatenation part: the up-path norm over torch.cat([h, skip]) is finalised from both parts')
@@ -785,161 +744,98 @@ int tangent_pass(loco_ctx* c, const float* V, int B, hipStream_t st, int op_lo =
     for (int oi = op_lo; oi <= op_end; ++oi) {
         Op& op = c->ops[oi];
         const Tens& to = c->tens[op.out];
-        const int HW = to.H * to.W;
         switch (op.kind) {
-            case OP_CONV_IN: {
-                ConvArgs a; conv_defaults(a);
-                a.in = V; a.in_bs = c->prog->n_in; a.Cin = cfg.in_channels; a.Hin = cfg.resolution; a.Win = cfg.resolution;
-                setw(a, op.conv, false);
-                a.out = TT(op.out); a.out_bs = PS; a.Cout = to.C; a.Hout = to.H; a.Wout = to.W; a.B = B;
-                if (op.ksize == 1) a.pad = 0;
-                const StatReq rq = next_tan(op.out);
-                run_conv(c, a, op.ksize == 1 ? 1 : 9, st, &rq);
-                break;
-            }
-            case OP_CONV: {
-                const Tens& ti = c->tens[op.in];
-                ConvArgs a; conv_defaults(a);
-                a.in = TT(op.in); a.in_bs = PS; a.Cin = ti.C; a.Hin = ti.H; a.Win = ti.W;
-                setw(a, op.conv, false);
-                a.out = TT(op.out); a.out_bs = PS; a.Cout = to.C; a.Hout = to.H; a.Wout = to.W; a.B = B;
-                if (op.ksize == 1) a.pad = 0;
+            case OP_CONV_IN: case OP_CONV: {
+                const ConvArgs a = conv_args(op.kind == OP_CONV_IN ? Vv : TT(op.in), op.conv, false, TT(op.out), B, op.ksize);
                 const StatReq rq = next_tan(op.out);
                 run_conv(c, a, op.ksize == 1 ? 1 : 9, st, &rq);
                 break;
             }
             case OP_RES: {
                 const Tens& ti = c->tens[op.in];
-                const int HWi = ti.H * ti.W;
-                if (!op.n1.ready && !cat_fused_tstats(c, op.n1, op.in, B, st)) tangent_stats(c, op.n1, TT(op.in), PS, TP(op.in), HWi, B, st);
-                op.n1.ready = false;
-                ConvArgs a; conv_defaults(a);
-                a.Cin = ti.C;
-                setw(a, op.c1, false);
+                need_tan_stats(p, op.n1, op.in, true);
                 if (op.updown == 1) {
-                    NS sp = nstats(c, c->statsP, op.n1);
-                    NS stt = nstats(c, c->statsT, op.n1);
-                    launch_gn_apply(5, TT(op.in), PS, TP(op.in), 0, nullptr, 0, TT(op.a1), PS, 0, B, ti.C, HWi,
-                                    cfg.gn_groups, sp.sc, sp.sh, sp.mr, 0, 0, stt.tst, c->prog->stats_per_sample, st, cfg.act);
+                    gn_lin_apply(p, op.n1, 5, TT(op.in), TP(op.in), nullptr, TT(op.a1));
                     launch_pool2x2_sum(TT(op.a1), PS, TT(op.ap), PS, 0, B, ti.C, to.H, to.W, st, 0.25f);
                     launch_pool2x2_sum(TT(op.in), PS, TT(op.xu), PS, 0, B, ti.C, to.H, to.W, st, 0.25f);
-                    a.in = TT(op.ap); a.in_bs = PS; a.Hin = to.H; a.Win = to.W;
-                } else {
-                    a.in = TT(op.in); a.in_bs = PS; a.Hin = ti.H; a.Win = ti.W;
-                    set_tan(c, a, op.n1, TP(op.in));
-                    if (op.updown == 2) {
-                        a.upsample = 1;
-                        launch_upsample2x(TT(op.in), PS, TT(op.xu), PS, 0, 1.0f, B, ti.C, ti.H, ti.W, st);
-                    }
+                } else if (op.updown == 2) {
+                    launch_upsample2x(TT(op.in), PS, TT(op.xu), PS, 0, 1.0f, B, ti.C, ti.H, ti.W, st);
                 }
-                a.out = TT(op.h1); a.out_bs = PS; a.Cout = to.C; a.Hout = to.H; a.Wout = to.W; a.B = B;
+                // conv1 as in the forward: on the pooled op.ap at the output resolution (down block), else norm1's tangent in the staging
+                ConvArgs a = conv_args(op.updown == 1 ? TT(op.ap) : TT(op.in), op.c1, false, TT(op.h1), B, 3);
+                if (op.updown != 1) { set_tan(c, a, op.n1, TP(op.in)); a.upsample = op.updown == 2; }
                 {
                     const StatReq rq2 = req_lin(c, ST_TAN, &op.n2, TP(op.h1));       // norm2's group means with conv1
                     run_conv(c, a, 9, st, &rq2);
                     op.n2.ready = false;
                 }
-                const float* xin = op.updown ? TT(op.xu) : TT(op.in);
-                ConvArgs n; conv_defaults(n);
-                if (op.has_nin) {
-                    n.in = xin; n.in_bs = PS; n.Cin = ti.C; n.Hin = to.H; n.Win = to.W;
-                    setw(n, op.nin, false); n.pad = 0;
-                    n.out = TT(op.out); n.out_bs = PS; n.Cout = to.C; n.Hout = to.H; n.Wout = to.W; n.B = B;
-                }
-                ConvArgs b; conv_defaults(b);
-                b.in = TT(op.h1); b.in_bs = PS; b.Cin = to.C; b.Hin = to.H; b.Win = to.W;
-                setw(b, op.c2, false); b.res = xin; b.res_bs = PS;
+                const TView xin = op.updown ? TT(op.xu) : TT(op.in);
+                ConvArgs n{};
+                if (op.has_nin) n = conv_args(xin, op.nin, false, TT(op.out), B, 1);
+                ConvArgs b = conv_args(TT(op.h1), op.c2, false, TT(op.out), B, 3);
+                b.res = xin; b.res_bs = PS;
                 b.res_scale = op.has_nin ? 1.f : c->prog->res_scale;
                 set_tan(c, b, op.n2, TP(op.h1));
-                b.out = TT(op.out); b.out_bs = PS; b.Cout = to.C; b.Hout = to.H; b.Wout = to.W; b.B = B;
                 const StatReq rq = next_tan(op.out);
                 run_conv(c, b, 9, st, &rq, op.has_nin ? &n : nullptr);
                 break;
             }
             case OP_ATTN: {
-                const int C = to.C;
-                if (!op.n1.ready) tangent_stats(c, op.n1, TT(op.in), PS, TP(op.in), HW, B, st);
-                op.n1.ready = false;
-                NS sp = nstats(c, c->statsP, op.n1);
-                NS stt = nstats(c, c->statsT, op.n1);
-                launch_gn_apply(1, TT(op.in), PS, TP(op.in), 0, nullptr, 0, TT(op.hn), PS, 0, B, C, HW,
-                                cfg.gn_groups, sp.sc, sp.sh, sp.mr, 0, 0, stt.tst, c->prog->stats_per_sample, st);
-                ConvArgs a; conv_defaults(a);
-                a.in = TT(op.hn); a.in_bs = PS; a.Cin = C; a.Hin = to.H; a.Win = to.W;
-                setw(a, op.qkvc, false); a.pad = 0;
-                a.out = TT(op.qkv); a.out_bs = PS; a.Cout = 3 * C; a.Hout = to.H; a.Wout = to.W; a.B = B;
-                run_conv(c, a, 1, st);
+                const int so = op.has_x ? op.xmid : op.out;
+                need_tan_stats(p, op.n1, op.in);
+                gn_lin_apply(p, op.n1, 1, TT(op.in), TP(op.in), nullptr, TT(op.hn));
+                lin1x1(c, op.qkvc, false, TT(op.hn), TT(op.qkv), B, st);
                 attn_tangent(attn_of(c, op, B, st));
-                ConvArgs pr; conv_defaults(pr);
-                pr.in = TT(op.o); pr.in_bs = PS; pr.Cin = C; pr.Hin = to.H; pr.Win = to.W;
-                setw(pr, op.proj, false); pr.pad = 0; pr.res = TT(op.in); pr.res_bs = PS;
-                pr.out = TT(op.has_x ? op.xmid : op.out); pr.out_bs = PS; pr.Cout = C; pr.Hout = to.H; pr.Wout = to.W; pr.B = B;
                 {
-                    const StatReq rq = next_tan(op.has_x ? op.xmid : op.out);
-                    run_conv(c, pr, 1, st, &rq);
+                    const StatReq rq = next_tan(so);
+                    lin1x1(c, op.proj, false, TT(op.o), TT(so), B, st, nullptr, TT(op.in), &rq);
                 }
                 if (op.has_x) {
                     const XA x = xa_of(c, op, B, st);
-                    if (!op.nx.ready) tangent_stats(c, op.nx, TT(op.xmid), PS, TP(op.xmid), HW, B, st);
-                    op.nx.ready = false;
-                    NS spx = nstats(c, c->statsP, op.nx);
-                    NS stx = nstats(c, c->statsT, op.nx);
-                    launch_gn_apply(1, TT(op.xmid), PS, TP(op.xmid), 0, nullptr, 0, TT(op.xhn), PS, 0, B, C, HW,
-                                    cfg.gn_groups, spx.sc, spx.sh, spx.mr, 0, 0, stx.tst, c->prog->stats_per_sample, st);
-                    lin1x1(c, op.xqc, false, TT(op.xhn), PS, C, TT(op.xq), PS, C, to.H, to.W, B, nullptr, 0, false, st);
+                    need_tan_stats(p, op.nx, op.xmid);
+                    gn_lin_apply(p, op.nx, 1, TT(op.xmid), TP(op.xmid), nullptr, TT(op.xhn));
+                    lin1x1(c, op.xqc, false, TT(op.xhn), TT(op.xq), B, st);
                     xa_linear(x, TT(op.xq), op.xK, op.xV, TP(op.xS), TT(op.xS), TT(op.xo));           // dq -> do
                     const StatReq rqx = next_tan(op.out);
-                    lin1x1(c, op.xproj, false, TT(op.xo), PS, C, TT(op.out), PS, C, to.H, to.W, B, TT(op.xmid), PS, false, st, &rqx);
+                    lin1x1(c, op.xproj, false, TT(op.xo), TT(op.out), B, st, nullptr, TT(op.xmid), &rqx);
                 }
                 break;
             }
             case OP_XFMR: {
-                const int C = to.C, T = HW, H = to.H, W = to.W;
+                const int C = to.C, HW = to.H * to.W;
                 auto XP = [&](int i) { return TP(op.xt[i]); };
                 auto XT_ = [&](int i) { return TT(op.xt[i]); };
-                if (!op.n1.ready) tangent_stats(c, op.n1, TT(op.in), PS, TP(op.in), HW, B, st);
-                op.n1.ready = false;
-                NS sp = nstats(c, c->statsP, op.n1);
-                NS stt = nstats(c, c->statsT, op.n1);
-                launch_gn_apply(1, TT(op.in), PS, TP(op.in), 0, nullptr, 0, XT_(X_G0), PS, 0, B, C, HW,
-                                cfg.gn_groups, sp.sc, sp.sh, sp.mr, 0, 0, stt.tst, c->prog->stats_per_sample, st);
-                lin1x1(c, op.pj_in, false, XT_(X_G0), PS, C, XT_(X_H0), PS, C, H, W, B, nullptr, 0, false, st);
+                need_tan_stats(p, op.n1, op.in);
+                gn_lin_apply(p, op.n1, 1, TT(op.in), TP(op.in), nullptr, XT_(X_G0));
+                lin1x1(c, op.pj_in, false, XT_(X_G0), XT_(X_H0), B, st);
                 const XA xa = xa_of(c, op, B, st);
-                launch_ln_tan(XT_(X_H0), PS, XP(X_H0), XP(X_LN1), B, C, T, op.lng[0], XT_(X_A1), PS, st);
-                lin1x1(c, op.qkvc, false, XT_(X_A1), PS, C, XT_(X_QKV), PS, 3 * C, H, W, B, nullptr, 0, false, st);
+                launch_ln_tan(XT_(X_H0), PS, XP(X_H0), XP(X_LN1), B, C, HW, op.lng[0], XT_(X_A1), PS, st);
+                lin1x1(c, op.qkvc, false, XT_(X_A1), XT_(X_QKV), B, st);
                 attn_tangent(attn_of(c, op, B, st));
-                lin1x1(c, op.to_out1, false, XT_(X_O), PS, C, XT_(X_H1), PS, C, H, W, B, XT_(X_H0), PS, false, st);
-                launch_ln_tan(XT_(X_H1), PS, XP(X_H1), XP(X_LN2), B, C, T, op.lng[1], XT_(X_A2), PS, st);
-                lin1x1(c, op.xqc, false, XT_(X_A2), PS, C, XT_(X_XQ), PS, C, H, W, B, nullptr, 0, false, st);
+                lin1x1(c, op.to_out1, false, XT_(X_O), XT_(X_H1), B, st, nullptr, XT_(X_H0));
+                launch_ln_tan(XT_(X_H1), PS, XP(X_H1), XP(X_LN2), B, C, HW, op.lng[1], XT_(X_A2), PS, st);
+                lin1x1(c, op.xqc, false, XT_(X_A2), XT_(X_XQ), B, st);
                 xa_linear(xa, XT_(X_XQ), op.xK, op.xV, XP(X_XS), XT_(X_XS), XT_(X_XO));             // dq -> do
-                lin1x1(c, op.to_out2, false, XT_(X_XO), PS, C, XT_(X_H2), PS, C, H, W, B, XT_(X_H1), PS, false, st);
-                launch_ln_tan(XT_(X_H2), PS, XP(X_H2), XP(X_LN3), B, C, T, op.lng[2], XT_(X_A3), PS, st);
-                lin1x1(c, op.ff1, false, XT_(X_A3), PS, C, XT_(X_F), PS, 8 * C, H, W, B, nullptr, 0, false, st);
-                launch_geglu(1, XT_(X_F), PS, XP(X_F), B, 4L * C * T, XT_(X_GG), PS, st);
-                lin1x1(c, op.ff2, false, XT_(X_GG), PS, 4 * C, XT_(X_H3), PS, C, H, W, B, XT_(X_H2), PS, false, st);
+                lin1x1(c, op.to_out2, false, XT_(X_XO), XT_(X_H2), B, st, nullptr, XT_(X_H1));
+                launch_ln_tan(XT_(X_H2), PS, XP(X_H2), XP(X_LN3), B, C, HW, op.lng[2], XT_(X_A3), PS, st);
+                lin1x1(c, op.ff1, false, XT_(X_A3), XT_(X_F), B, st);
+                launch_geglu(1, XT_(X_F), PS, XP(X_F), B, 4L * C * HW, XT_(X_GG), PS, st);
+                lin1x1(c, op.ff2, false, XT_(X_GG), XT_(X_H3), B, st, nullptr, XT_(X_H2));
                 const StatReq rq = next_tan(op.out);
-                lin1x1(c, op.pj_out, false, XT_(X_H3), PS, C, TT(op.out), PS, C, H, W, B, TT(op.in), PS, false, st, &rq);
+                lin1x1(c, op.pj_out, false, XT_(X_H3), TT(op.out), B, st, nullptr, TT(op.in), &rq);
                 break;
             }
             case OP_DOWN: case OP_UP: {
-                const Tens& ti = c->tens[op.in];
-                ConvArgs a; conv_defaults(a);
-                a.in = TT(op.in); a.in_bs = PS; a.Cin = ti.C; a.Hin = ti.H; a.Win = ti.W;
-                setw(a, op.conv, false);
+                ConvArgs a = conv_args(TT(op.in), op.conv, false, TT(op.out), B, 3);
                 if (op.kind == OP_DOWN) { a.stride = 2; a.pad = op.sym_down ? 1 : 0; } else { a.upsample = 1; }
-                a.out = TT(op.out); a.out_bs = PS; a.Cout = to.C; a.Hout = to.H; a.Wout = to.W; a.B = B;
                 const StatReq rq = next_tan(op.out);
                 run_conv(c, a, 9, st, &rq);
                 break;
             }
             case OP_OUT: {
-                const Tens& ti = c->tens[op.in];
-                if (!op.n1.ready) tangent_stats(c, op.n1, TT(op.in), PS, TP(op.in), ti.H * ti.W, B, st);
-                op.n1.ready = false;
-                ConvArgs a; conv_defaults(a);
-                a.in = TT(op.in); a.in_bs = PS; a.Cin = ti.C; a.Hin = ti.H; a.Win = ti.W;
-                setw(a, op.conv, false);
+                need_tan_stats(p, op.n1, op.in);
+                ConvArgs a = conv_args(TT(op.in), op.conv, false, TT(op.out), B, 3);
                 set_tan(c, a, op.n1, TP(op.in));
-                a.out = TT(op.out); a.out_bs = PS; a.Cout = to.C; a.Hout = to.H; a.Wout = to.W; a.B = B;
                 run_conv(c, a, 9, st);
                 break;
             }
@@ -949,225 +845,151 @@ int tangent_pass(loco_ctx* c, const float* V, int B, hipStream_t st, int op_lo =
 }
 
 // ------------------------------ cotangent ----------------------------------
-void cot_stats(loco_ctx* c, const NormP& n, const float* d, long dbs, const float* x, int HW, int B, int kind,
-               hipStream_t st) {
-    NS sp = nstats(c, c->statsP, n);
-    NS stt = nstats(c, c->statsT, n);
-    launch_gn_tstats(d, dbs, x, 0, B, n.C, HW, c->cfg.gn_groups, sp.sc, sp.sh, sp.mr, 0, 0, kind, stt.tst,
-                     stt.tc, c->prog->stats_per_sample, c->red, st, c->cfg.act);
-}
-
 // ge: cotangent of eps [B][n]; result A[B][n] = conv_in^T(...) + gx0
 // ops op_hi (< 0: the last) down to op_lo.  A pass that starts at the tap (op_hi = h_last_op) finds the cotangent of h and zeros in
 // the skip slots in arena T; one that stops behind it (op_lo = h_last_op + 1) leaves the cotangent of h there (loco_pmp_vjp).
+// Every conv here is the transposed map: its `in` view is the op's output tensor, its `out` view the op's input tensor.
 int cotangent_pass(loco_ctx* c, const float* ge, const float* gx0, float* Aout, int B, hipStream_t st, int op_lo = 0,
                    int op_hi = -1) {
     const loco_unet_cfg& cfg = c->cfg;
     const long PS = c->prog->per_sample;
-    const int G = cfg.gn_groups;
-    auto TP = [&](int id) { return c->arenaP + c->tens[id].off; };
-    auto TG = [&](int id) { return c->arenaT + c->tens[id].off; };   // cotangent of tensor id
+    const Pass p{c, st, B, c->arenaT, c->statsT};
+    auto TP = [&](int id) { return tview(c, c->arenaP, id); };
+    auto TG = [&](int id) { return p.T(id); };                   // cotangent of tensor id
     // the op that produces the network output takes the caller's cotangent (conv_out; the encoder's quant_conv)
-    auto GO = [&](const Op& o) -> const float* { return o.out == c->prog->eps_t ? ge : TG(o.out); };
-    auto GOS = [&](const Op& o) -> long { return o.out == c->prog->eps_t ? (long)c->prog->n_out : PS; };
+    auto GO = [&](const Op& o) {
+        const Tens& t = c->tens[o.out];
+        return o.out == c->prog->eps_t ? tview_in(ge, c->prog->n_out, t.C, t.H, t.W) : TG(o.out);
+    };
+    const TView Av{Aout, c->prog->n_in, cfg.in_channels, cfg.resolution, cfg.resolution};      // the caller's result
     clear_ready(c);
     for (int oi = op_hi >= 0 ? op_hi : (int)c->ops.size() - 1; oi >= op_lo; --oi) {
         Op& op = c->ops[oi];
         const Tens& to = c->tens[op.out];
-        const int HW = to.H * to.W;
+        const int acc = op.in_is_skip ? 1 : 0;      // the skip's other consumer wrote the input's cotangent first
         switch (op.kind) {
             case OP_OUT: {
-                const Tens& ti = c->tens[op.in];
-                ConvArgs a; conv_defaults(a);
-                a.in = GO(op); a.in_bs = GOS(op); a.Cin = to.C; a.Hin = to.H; a.Win = to.W;
-                setw(a, op.conv, true);
-                a.out = TG(op.a1); a.out_bs = PS; a.Cout = ti.C; a.Hout = ti.H; a.Wout = ti.W; a.B = B;
+                const ConvArgs a = conv_args(GO(op), op.conv, true, TG(op.a1), B, 3);
                 {
                     const StatReq rq = req_lin(c, ST_COT, &op.n1, TP(op.in));        // the norm's cotangent means with the conv
                     run_conv(c, a, 9, st, &rq);
                     op.n1.ready = false;
                 }
-                NS sp = nstats(c, c->statsP, op.n1);
-                NS stt = nstats(c, c->statsT, op.n1);
-                launch_gn_apply(2, TG(op.a1), PS, TP(op.in), 0, nullptr, 0, TG(op.in), PS, 0, B, ti.C, ti.H * ti.W, G,
-                                sp.sc, sp.sh, sp.mr, 0, 0, stt.tst, c->prog->stats_per_sample, st, cfg.act);
+                gn_lin_apply(p, op.n1, 2, TG(op.a1), TP(op.in), nullptr, TG(op.in));
                 break;
             }
             case OP_UP: {
-                const Tens& ti = c->tens[op.in];
-                ConvArgs a; conv_defaults(a);
-                a.in = TG(op.out); a.in_bs = PS; a.Cin = to.C; a.Hin = to.H; a.Win = to.W;
-                setw(a, op.conv, true);
+                ConvArgs a = conv_args(TG(op.out), op.conv, true, TG(op.in), B, 3);
                 // nearest^T (conv^T g): one polyphase launch where plan_conv takes it, else the conv into op.up and the pooling pass
                 a.pool2 = 1; a.pool_tmp = TG(op.up); a.pool_tmp_bs = PS;
-                a.out = TG(op.in); a.out_bs = PS; a.Cout = ti.C; a.Hout = ti.H; a.Wout = ti.W; a.B = B;
                 run_conv(c, a, 9, st);
                 break;
             }
             case OP_DOWN: {
-                const Tens& ti = c->tens[op.in];
-                ConvArgs a; conv_defaults(a);
-                a.in = TG(op.out); a.in_bs = PS; a.Cin = to.C; a.Hin = to.H; a.Win = to.W;
-                setw(a, op.conv, true); a.zins = 1; a.pad = op.sym_down ? 1 : 2; a.accumulate = op.in_is_skip ? 1 : 0;
-                a.out = TG(op.in); a.out_bs = PS; a.Cout = ti.C; a.Hout = ti.H; a.Wout = ti.W; a.B = B;
+                ConvArgs a = conv_args(TG(op.out), op.conv, true, TG(op.in), B, 3);
+                a.zins = 1; a.pad = op.sym_down ? 1 : 2; a.accumulate = acc;
                 run_conv(c, a, 9, st);
                 break;
             }
             case OP_RES: {
                 const Tens& ti = c->tens[op.in];
-                const int HWi = ti.H * ti.W;
-                // g_a2 = dgrad conv2 (g_out)  -> slot h1
-                ConvArgs a; conv_defaults(a);
-                a.in = TG(op.out); a.in_bs = PS; a.Cin = to.C; a.Hin = to.H; a.Win = to.W;
-                setw(a, op.c2, true);
-                a.out = TG(op.h1); a.out_bs = PS; a.Cout = to.C; a.Hout = to.H; a.Wout = to.W; a.B = B;
-                {
+                {   // g_a2 = dgrad conv2 (g_out)  -> slot h1
+                    const ConvArgs a = conv_args(TG(op.out), op.c2, true, TG(op.h1), B, 3);
                     const StatReq rq2 = req_lin(c, ST_COT, &op.n2, TP(op.h1));
                     run_conv(c, a, 9, st, &rq2);
                     op.n2.ready = false;
                 }
-                // dgrad conv1 of the norm2/silu cotangent of g_a2 (fused in the staging), at conv1's resolution
-                ConvArgs b; conv_defaults(b);
-                b.in = TG(op.h1); b.in_bs = PS; b.Cin = to.C; b.Hin = to.H; b.Win = to.W;
-                setw(b, op.c1, true);
+                // dgrad conv1 of the norm2/silu cotangent of g_a2 (fused in the staging), at conv1's resolution: the input's channels
+                // at the OUTPUT resolution -- g_a1 itself, or the cotangent of the pooled (op.ap) / nearest-upsampled (op.xu) activation
+                ConvArgs b = conv_args(TG(op.h1), op.c1, true, TG(op.updown == 0 ? op.a1 : op.updown == 1 ? op.ap : op.xu), B, 3);
                 set_tan(c, b, op.n2, TP(op.h1));
                 b.mode = CM_COT_SILU;
-                b.out_bs = PS; b.Cout = ti.C; b.Hout = to.H; b.Wout = to.W; b.B = B;
                 if (op.updown == 0) {
-                    b.out = TG(op.a1);
                     const StatReq rq1 = req_lin(c, ST_COT, &op.n1, TP(op.in));
                     run_conv(c, b, 9, st, &rq1);
                 } else if (op.updown == 1) {
-                    b.out = TG(op.ap);                                     // cotangent of the pooled activation
                     run_conv(c, b, 9, st);
                     launch_upsample2x(TG(op.ap), PS, TG(op.a1), PS, 0, 0.25f, B, ti.C, to.H, to.W, st);   // avg-pool^T
                 } else {
-                    b.out = TG(op.xu);                                     // cotangent of the nearest-upsampled activation
                     run_conv(c, b, 9, st);
                     launch_pool2x2_sum(TG(op.xu), PS, TG(op.a1), PS, 0, B, ti.C, ti.H, ti.W, st);           // nearest^T
                 }
-                if (!op.n1.ready) cot_stats(c, op.n1, TG(op.a1), PS, TP(op.in), HWi, B, 1, st);
-                op.n1.ready = false;
-                NS sp = nstats(c, c->statsP, op.n1);
-                NS stt = nstats(c, c->statsT, op.n1);
-                int acc = op.in_is_skip ? 1 : 0;
+                need_cot_stats(p, op.n1, TG(op.a1), TP(op.in));
                 // shortcut cotangent at the block's output resolution: identity or nin^T
-                const float* gsk = TG(op.out);
                 bool cot_in_epilogue = false;
-                if (op.has_nin) {
-                    ConvArgs n; conv_defaults(n);
-                    n.in = TG(op.out); n.in_bs = PS; n.Cin = to.C; n.Hin = to.H; n.Win = to.W;
-                    setw(n, op.nin, true); n.pad = 0;
-                    n.Cout = ti.C; n.Hout = to.H; n.Wout = to.W; n.B = B; n.out_bs = PS;
-                    n.out = TG(op.in); n.accumulate = acc;      // (resampling blocks never change channels: no nin there)
+                if (op.has_nin) {      // (resampling blocks never change channels: no nin there)
+                    ConvArgs n = conv_args(TG(op.out), op.nin, true, TG(op.in), B, 1);
+                    n.accumulate = acc;
                     // g_in = nin^T g_out + norm1^T g_a1: the norm-cotangent term in the shortcut conv's epilogue instead of a
                     // read-modify-write pass of gn_apply_kernel<2> over g_in where plan_conv takes it (from norm1's {S, xhat}
                     // records and the per-channel {rstd m1, rstd m2} its cotangent statistics left)
                     if (op.updown == 0 && c->prec >= 1 && c->fuse_cot && op.n1.sx_off >= 0 && c->sxcache) {
                         n.cot_d = TG(op.a1); n.cot_d_bs = PS; n.cot_sx = c->sxcache + op.n1.sx_off;
-                        n.cot_tc = stt.tc; n.cot_tc_bs = c->prog->stats_per_sample;
+                        n.cot_tc = nstats(c, c->statsT, op.n1).tc; n.cot_tc_bs = c->prog->stats_per_sample;
                     }
                     cot_in_epilogue = run_conv(c, n, 1, st);
-                    gsk = nullptr;
                 }
                 if (op.updown == 0) {
                     if (cot_in_epilogue) { /* done by the shortcut conv */ }
-                    else if (op.has_nin)
-                        launch_gn_apply(2, TG(op.a1), PS, TP(op.in), 0, nullptr, 0, TG(op.in), PS, 1, B, ti.C, HWi, G,
-                                        sp.sc, sp.sh, sp.mr, 0, 0, stt.tst, c->prog->stats_per_sample, st, cfg.act);
+                    else if (op.has_nin) gn_lin_apply(p, op.n1, 2, TG(op.a1), TP(op.in), nullptr, TG(op.in), 1);
                     else        // identity shortcut: g_in = res_scale * g_out + norm1^T g_a1
-                        launch_gn_apply(2, TG(op.a1), PS, TP(op.in), 0, gsk, PS, TG(op.in), PS, acc, B, ti.C, HWi, G,
-                                        sp.sc, sp.sh, sp.mr, 0, 0, stt.tst, c->prog->stats_per_sample, st, cfg.act, c->prog->res_scale);
+                        gn_lin_apply(p, op.n1, 2, TG(op.a1), TP(op.in), TG(op.out), TG(op.in), acc, c->prog->res_scale);
                 } else {
-                    launch_gn_apply(2, TG(op.a1), PS, TP(op.in), 0, nullptr, 0, TG(op.in), PS, acc, B, ti.C, HWi, G,
-                                    sp.sc, sp.sh, sp.mr, 0, 0, stt.tst, c->prog->stats_per_sample, st, cfg.act);
-                    if (op.updown == 1) launch_upsample2x(gsk, PS, TG(op.in), PS, 1, 0.25f * c->prog->res_scale, B, ti.C, to.H, to.W, st);
-                    else launch_pool2x2_sum(gsk, PS, TG(op.in), PS, 1, B, ti.C, ti.H, ti.W, st, c->prog->res_scale);
+                    gn_lin_apply(p, op.n1, 2, TG(op.a1), TP(op.in), nullptr, TG(op.in), acc);
+                    if (op.updown == 1) launch_upsample2x(TG(op.out), PS, TG(op.in), PS, 1, 0.25f * c->prog->res_scale, B, ti.C, to.H, to.W, st);
+                    else launch_pool2x2_sum(TG(op.out), PS, TG(op.in), PS, 1, B, ti.C, ti.H, ti.W, st, c->prog->res_scale);
                 }
                 break;
             }
             case OP_ATTN: {
-                const int C = to.C;
                 const int so = op.has_x ? op.xmid : op.out;       // output tensor of the self-attention stage
                 if (op.has_x) {
                     // cotangent of the cross-attention stage: g_out -> g_xmid (residual + the q path through GN)
                     const XA x = xa_of(c, op, B, st);
-                    lin1x1(c, op.xproj, true, TG(op.out), PS, C, TG(op.xo), PS, C, to.H, to.W, B, nullptr, 0, false, st);
+                    lin1x1(c, op.xproj, true, TG(op.out), TG(op.xo), B, st);
                     xa_linear(x, TG(op.xo), op.xV, op.xK, TP(op.xS), TG(op.xS), TG(op.xq));           // g_o -> g_q
-                    lin1x1(c, op.xqc, true, TG(op.xq), PS, C, TG(op.xhn), PS, C, to.H, to.W, B, nullptr, 0, false, st);
-                    cot_stats(c, op.nx, TG(op.xhn), PS, TP(op.xmid), HW, B, 2, st);
-                    NS spx = nstats(c, c->statsP, op.nx);
-                    NS stx = nstats(c, c->statsT, op.nx);
-                    launch_gn_apply(3, TG(op.xhn), PS, TP(op.xmid), 0, TG(op.out), PS, TG(op.xmid), PS, 0, B, C, HW, G,
-                                    spx.sc, spx.sh, spx.mr, 0, 0, stx.tst, c->prog->stats_per_sample, st);
+                    lin1x1(c, op.xqc, true, TG(op.xq), TG(op.xhn), B, st);
+                    lin_stats(p, op.nx, 2, TG(op.xhn), TP(op.xmid));
+                    gn_lin_apply(p, op.nx, 3, TG(op.xhn), TP(op.xmid), TG(op.out), TG(op.xmid));
                 }
-                // g_o = proj^T g_out
-                ConvArgs pr; conv_defaults(pr);
-                pr.in = TG(so); pr.in_bs = PS; pr.Cin = C; pr.Hin = to.H; pr.Win = to.W;
-                setw(pr, op.proj, true); pr.pad = 0;
-                pr.out = TG(op.o); pr.out_bs = PS; pr.Cout = C; pr.Hout = to.H; pr.Wout = to.W; pr.B = B;
-                run_conv(c, pr, 1, st);
+                lin1x1(c, op.proj, true, TG(so), TG(op.o), B, st);                  // g_o = proj^T g_out
                 attn_cotangent(attn_of(c, op, B, st));      // g_q, g_k, g_v = the transposes of q^T k -> P -> v P^T
-                // g_hn = Wqkv^T g_qkv
-                ConvArgs a; conv_defaults(a);
-                a.in = TG(op.qkv); a.in_bs = PS; a.Cin = 3 * C; a.Hin = to.H; a.Win = to.W;
-                setw(a, op.qkvc, true); a.pad = 0;
-                a.out = TG(op.hn); a.out_bs = PS; a.Cout = C; a.Hout = to.H; a.Wout = to.W; a.B = B;
-                run_conv(c, a, 1, st);
-                cot_stats(c, op.n1, TG(op.hn), PS, TP(op.in), HW, B, 2, st);
-                NS sp = nstats(c, c->statsP, op.n1);
-                NS stt = nstats(c, c->statsT, op.n1);
-                launch_gn_apply(3, TG(op.hn), PS, TP(op.in), 0, TG(so), PS, TG(op.in), PS,
-                                op.in_is_skip ? 1 : 0, B, C, HW, G, sp.sc, sp.sh, sp.mr, 0, 0, stt.tst, c->prog->stats_per_sample, st);
+                lin1x1(c, op.qkvc, true, TG(op.qkv), TG(op.hn), B, st);             // g_hn = Wqkv^T g_qkv
+                lin_stats(p, op.n1, 2, TG(op.hn), TP(op.in));
+                gn_lin_apply(p, op.n1, 3, TG(op.hn), TP(op.in), TG(so), TG(op.in), acc);
                 break;
             }
             case OP_XFMR: {      // transposes of the forward chain, last map first
-                const int C = to.C, T = HW, H = to.H, W = to.W;
+                const int C = to.C, HW = to.H * to.W;
                 auto XP = [&](int i) { return TP(op.xt[i]); };
                 auto XG = [&](int i) { return TG(op.xt[i]); };
                 const XA xa = xa_of(c, op, B, st);
-                lin1x1(c, op.pj_out, true, TG(op.out), PS, C, XG(X_H3), PS, C, H, W, B, nullptr, 0, false, st);          // g_h3
+                lin1x1(c, op.pj_out, true, TG(op.out), XG(X_H3), B, st);            // g_h3
                 // feed-forward: h3 = h2 + ff2(geglu(ff1(LN3(h2))))
-                lin1x1(c, op.ff2, true, XG(X_H3), PS, C, XG(X_GG), PS, 4 * C, H, W, B, nullptr, 0, false, st);
-                launch_geglu(2, XG(X_GG), PS, XP(X_F), B, 4L * C * T, XG(X_F), PS, st);
-                lin1x1(c, op.ff1, true, XG(X_F), PS, 8 * C, XG(X_A3), PS, C, H, W, B, nullptr, 0, false, st);
-                launch_ln_cot(XG(X_A3), PS, XP(X_H2), XP(X_LN3), B, C, T, op.lng[2], XG(X_H3), PS, XG(X_H2), PS, st);  // g_h2
+                lin1x1(c, op.ff2, true, XG(X_H3), XG(X_GG), B, st);
+                launch_geglu(2, XG(X_GG), PS, XP(X_F), B, 4L * C * HW, XG(X_F), PS, st);
+                lin1x1(c, op.ff1, true, XG(X_F), XG(X_A3), B, st);
+                launch_ln_cot(XG(X_A3), PS, XP(X_H2), XP(X_LN3), B, C, HW, op.lng[2], XG(X_H3), PS, XG(X_H2), PS, st);  // g_h2
                 // cross-attention: h2 = h1 + to_out2(V P^T), q = to_q(LN2(h1))
-                lin1x1(c, op.to_out2, true, XG(X_H2), PS, C, XG(X_XO), PS, C, H, W, B, nullptr, 0, false, st);
+                lin1x1(c, op.to_out2, true, XG(X_H2), XG(X_XO), B, st);
                 xa_linear(xa, XG(X_XO), op.xV, op.xK, XP(X_XS), XG(X_XS), XG(X_XQ));                // g_o -> g_q
-                lin1x1(c, op.xqc, true, XG(X_XQ), PS, C, XG(X_A2), PS, C, H, W, B, nullptr, 0, false, st);
-                launch_ln_cot(XG(X_A2), PS, XP(X_H1), XP(X_LN2), B, C, T, op.lng[1], XG(X_H2), PS, XG(X_H1), PS, st);  // g_h1
+                lin1x1(c, op.xqc, true, XG(X_XQ), XG(X_A2), B, st);
+                launch_ln_cot(XG(X_A2), PS, XP(X_H1), XP(X_LN2), B, C, HW, op.lng[1], XG(X_H2), PS, XG(X_H1), PS, st);  // g_h1
                 // self-attention: h1 = h0 + to_out1(attn(qkv(LN1(h0))))
-                lin1x1(c, op.to_out1, true, XG(X_H1), PS, C, XG(X_O), PS, C, H, W, B, nullptr, 0, false, st);
+                lin1x1(c, op.to_out1, true, XG(X_H1), XG(X_O), B, st);
                 attn_cotangent(attn_of(c, op, B, st));
-                lin1x1(c, op.qkvc, true, XG(X_QKV), PS, 3 * C, XG(X_A1), PS, C, H, W, B, nullptr, 0, false, st);
-                launch_ln_cot(XG(X_A1), PS, XP(X_H0), XP(X_LN1), B, C, T, op.lng[0], XG(X_H1), PS, XG(X_H0), PS, st);  // g_h0
+                lin1x1(c, op.qkvc, true, XG(X_QKV), XG(X_A1), B, st);
+                launch_ln_cot(XG(X_A1), PS, XP(X_H0), XP(X_LN1), B, C, HW, op.lng[0], XG(X_H1), PS, XG(X_H0), PS, st);  // g_h0
                 // proj_in of GN(x), and the residual  out = x + ...
-                lin1x1(c, op.pj_in, true, XG(X_H0), PS, C, XG(X_G0), PS, C, H, W, B, nullptr, 0, false, st);
-                cot_stats(c, op.n1, XG(X_G0), PS, TP(op.in), HW, B, 2, st);
-                NS sp = nstats(c, c->statsP, op.n1);
-                NS stt = nstats(c, c->statsT, op.n1);
-                launch_gn_apply(3, XG(X_G0), PS, TP(op.in), 0, TG(op.out), PS, TG(op.in), PS,
-                                op.in_is_skip ? 1 : 0, B, C, HW, G, sp.sc, sp.sh, sp.mr, 0, 0, stt.tst, c->prog->stats_per_sample, st);
+                lin1x1(c, op.pj_in, true, XG(X_H0), XG(X_G0), B, st);
+                lin_stats(p, op.n1, 2, XG(X_G0), TP(op.in));
+                gn_lin_apply(p, op.n1, 3, XG(X_G0), TP(op.in), TG(op.out), TG(op.in), acc);
                 break;
             }
-            case OP_CONV_IN: {
-                ConvArgs a; conv_defaults(a);
-                a.in = TG(op.out); a.in_bs = PS; a.Cin = to.C; a.Hin = to.H; a.Win = to.W;
-                setw(a, op.conv, true); a.res = gx0; a.res_bs = c->prog->n_in;
-                a.out = Aout; a.out_bs = c->prog->n_in; a.Cout = cfg.in_channels; a.Hout = cfg.resolution;
-                a.Wout = cfg.resolution; a.B = B;
-                if (op.ksize == 1) a.pad = 0;
-                run_conv(c, a, op.ksize == 1 ? 1 : 9, st);
-                break;
-            }
-            case OP_CONV: {
-                const Tens& ti = c->tens[op.in];
-                ConvArgs a; conv_defaults(a);
-                a.in = GO(op); a.in_bs = GOS(op); a.Cin = to.C; a.Hin = to.H; a.Win = to.W;
-                setw(a, op.conv, true);
-                a.out = TG(op.in); a.out_bs = PS; a.Cout = ti.C; a.Hout = ti.H; a.Wout = ti.W; a.B = B;
-                if (op.ksize == 1) a.pad = 0;
+            case OP_CONV_IN: case OP_CONV: {
+                const bool first = op.kind == OP_CONV_IN;      // conv_in^T writes the caller's A and adds the direct term gx0
+                ConvArgs a = conv_args(GO(op), op.conv, true, first ? Av : TG(op.in), B, op.ksize);
+                if (first) { a.res = gx0; a.res_bs = c->prog->n_in; }
                 run_conv(c, a, op.ksize == 1 ? 1 : 9, st);
                 break;
             }

@@ -266,12 +266,11 @@ int loco_debug_conv(loco_ctx* c, const loco_conv_desc* d, char* plan, int64_t ca
         return hipMemcpyAsync(dst, src, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st);
     };
     hipError_t he = hipSuccess;
-    ConvArgs a; conv_defaults(a);
-    if (d->in_arena) { he = copy(c->arenaT, d->in, in_e * B); a.in = c->arenaT; } else a.in = d->in;
-    a.in_bs = in_e; a.Cin = d->Cin; a.Hin = d->Hin; a.Win = d->Win;
-    setw(a, cp, d->transposed != 0);
+    if (d->in_arena) he = copy(c->arenaT, d->in, in_e * B);
+    const TView out{d->out, out_e, d->Cout, Hout, Wout};
+    ConvArgs a = conv_args(tview_in(d->in_arena ? c->arenaT : d->in, in_e, d->Cin, d->Hin, d->Win), cp, d->transposed != 0, out, B,
+                           taps == 1 ? 1 : 3);
     a.bias = bias_d;
-    a.out = d->out; a.out_bs = out_e; a.Cout = d->Cout; a.Hout = Hout; a.Wout = Wout; a.B = B;
     a.bias2 = d->bias2; a.bias2_bs = d->Cout;
     a.res = d->res; a.res_bs = out_e; a.res_scale = d->res_scale;
     a.mode = d->mode; a.stride = d->stride; a.upsample = d->upsample; a.zins = d->zins; a.accumulate = d->accumulate;
@@ -296,9 +295,8 @@ int loco_debug_conv(loco_ctx* c, const loco_conv_desc* d, char* plan, int64_t ca
     if (d->Cin2 > 0) {
         float* in2 = c->arenaT + offT_in2;
         if (he == hipSuccess) he = copy(in2, d->in2, in2_e * B);
-        n2.in = in2; n2.in_bs = in2_e; n2.Cin = d->Cin2; n2.Hin = Hout; n2.Win = Wout;
-        setw(n2, cp2, false); n2.bias = bias2nd_d; n2.pad = 0;
-        n2.out = d->out; n2.out_bs = out_e; n2.Cout = d->Cout; n2.Hout = Hout; n2.Wout = Wout; n2.B = B;
+        n2 = conv_args(TView{in2, in2_e, d->Cin2, Hout, Wout}, cp2, false, out, B, 1);
+        n2.bias = bias2nd_d;
         a.res = d->out; a.res_bs = out_e;      // (as the ResBlock: the block output is the shortcut's output + conv2)
     }
     if (d->cot_d) {

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstring>
 #include <map>
 #include <memory>
 #include <string>
@@ -246,8 +247,43 @@ struct StatReq {
     float* keep = nullptr; size_t keep_floats = 0; int* keep_ntile = nullptr;
 };
 
-void conv_defaults(ConvArgs& a);
-void setw(ConvArgs& a, const ConvP& p, bool dgrad);
+inline void conv_defaults(ConvArgs& a) {
+    std::memset(&a, 0, sizeof(a));
+    a.stride = 1; a.pad = 1; a.nsplit = 1; a.mode = CM_NONE; a.res_scale = 1.f;
+}
+inline void setw(ConvArgs& a, const ConvP& p, bool dgrad) {
+    a.w = dgrad ? p.wd : p.wf;
+    a.wb = dgrad ? (const void*)p.wbd : (const void*)p.wbf;
+    a.wh = dgrad ? (const void*)p.whd : (const void*)p.whf;
+    const bool folded = p.wpb && p.poly_dgrad == dgrad;      // (plan_conv takes them on the up / zero-insert launches it routes polyphase)
+    a.wpb = folded ? p.wpb : nullptr;
+    a.wph = folded ? p.wph : nullptr;
+    a.wqb = dgrad ? p.wqb : nullptr;
+    a.wqh = dgrad ? p.wqh : nullptr;
+}
+
+// A tensor as one launch sees it: base, sample stride, extents.  Stands in for its base pointer where a launcher takes one.
+struct TView {
+    float* p; long bs; int C, H, W;
+    operator float*() const { return p; }
+};
+// tensor `id` of the program in an activation arena
+inline TView tview(const loco_ctx* c, float* arena, int id) {
+    const Tens& t = c->tens[id];
+    return {arena + t.off, c->prog->per_sample, t.C, t.H, t.W};
+}
+// a caller's read-only buffer (x, V, ge): only ever the `in` of a launch
+inline TView tview_in(const float* p, long bs, int C, int H, int W) { return {const_cast<float*>(p), bs, C, H, W}; }
+// The geometry every conv launch has: defaults, in / out, the operator's weights (dgrad: of the transposed map), B, and no
+// padding for a 1x1.  Everything else stays at conv_defaults' value for the call site to set: bias, residual, mode, resampling.
+inline ConvArgs conv_args(const TView& in, const ConvP& w, bool dgrad, const TView& out, int B, int ksize) {
+    ConvArgs a; conv_defaults(a);
+    a.in = in.p; a.in_bs = in.bs; a.Cin = in.C; a.Hin = in.H; a.Win = in.W;
+    setw(a, w, dgrad);
+    a.out = out.p; a.out_bs = out.bs; a.Cout = out.C; a.Hout = out.H; a.Wout = out.W; a.B = B;
+    if (ksize == 1) a.pad = 0;
+    return a;
+}
 bool run_conv(loco_ctx* c, const ConvArgs& a0, int taps, hipStream_t st, const StatReq* rq = nullptr,
               const ConvArgs* second = nullptr);
 
