@@ -173,6 +173,16 @@ int  loco_pmp_jvp(loco_ctx* ctx, const float* V, int32_t k, float* U, void* stre
 /* A = U^T J (replaces torch.autograd.functional.jacobian at edit.py:2460-2480).
  * U: dense [k, n] (entries outside the mask are ignored); A: [k, n]. */
 int  loco_pmp_vjp(loco_ctx* ctx, const float* U, int32_t k, float* A, void* stream);
+/* loco_pmp_vjp plus the gradient with respect to the states given to loco_set_context:
+ * G[p] = U[p]^T d f / d tokens, f = the function the last loco_pmp_primal selected (x0_hat[mask] or eps[mask]).
+ * A [k, n] may be NULL; G is [k, context_len, context_dim].  A is what loco_pmp_vjp writes, to the bit; a row of G does not
+ * depend on k or on the row's position: the rows of G are taken from one single-probe cotangent pass each (the batched pass
+ * plans its convolutions by k), so k > 1 costs k such passes on top of loco_pmp_vjp's, k = 1 is one pass for A and G, and
+ * without A a pass stops behind the first op that reads the states.  The x_t term of x0_hat does not depend on the states,
+ * so G = c_e . U^T d eps / d tokens.
+ * Refused (-2, text in loco_last_error): context_dim == 0; no valid primal (loco_set_context invalidates it); a primal of an
+ * h-space tap (loco_pmp_primal_tap, tap 1 / 2); cfg.added_kv; G == NULL. */
+int  loco_pmp_vjp_context(loco_ctx* ctx, const float* U, int32_t k, float* A, float* G, void* stream);
 
 /* --- h-space tap: the U-Net bottleneck h of a denoiser (arch 0 / 1) ---
  * h is the output of the middle block's last op, PullBackDDPM.get_h(x, t, op='mid', block_idx=0)

@@ -288,14 +288,15 @@ XA xa_of(loco_ctx* c, const Op& op, int B, hipStream_t st) {
     return x;
 }
 // S[b][h][i][l] = alpha * sum_c X[b][h*CH+c][i] K[h*CH+c][l]      (X: q / dq / g_o, K: K_ctx or V_ctx)
-void xa_scores(const XA& x, const float* X, long x_bs, const float* K, float* S, long s_bs, float alpha, bool mask) {
+void xa_scores(const XA& x, const float* X, long x_bs, const float* K, float* S, long s_bs, float alpha, bool mask, bool fixed = false) {
     GemmArgs g; std::memset(&g, 0, sizeof(g));
     g.A = X; g.sam = 1; g.sak = x.T; g.sab = x_bs; g.sah = (long)x.CH * x.T;
     g.Bm = K; g.sbk = x.Lp; g.sbn = 1; g.sbb = 0; g.sbh = (long)x.CH * x.Lp;
     g.C = S; g.scm = x.Lp; g.scn = 1; g.scb = s_bs; g.sch = (long)x.T * x.Lp;
     g.M = x.T; g.N = x.Lp; g.K = x.CH; g.batch = x.B; g.batch2 = x.NH; g.alpha = alpha; g.beta = 0.f;
     g.colbias = mask ? x.colbias : nullptr;
-    attn_gemm_f32(x.c, g, x.st);
+    if (fixed) { attn_note(x.c, "gemm_f32_fixed", &g); launch_gemm_fixed(g, GEMM_ACT_NONE, x.st); }      // the same bits whatever B is
+    else attn_gemm_f32(x.c, g, x.st);
 }
 // O[b][h*CH+c][i] = sum_l K[h*CH+c][l] S[b][h][i][l]              (K: V_ctx or K_ctx, S: P / dP / g_S)
 void xa_values(const XA& x, const float* K, const float* S, long s_bs, float* O, long o_bs) {
@@ -335,6 +336,65 @@ void xa_linear(const XA& x, const float* X, const float* K1, const float* K2, fl
     xa_scores(x, X, x.xs, K1, S, x.ss, 1.f, false);
     attn_softmax_jac(x.c, S, P, (long)x.NH * x.T, x.Lp, x.scale, x.st, x.B, x.ss);
     xa_values(x, K2, S, x.ss, O, x.xs);
+}
+
+// ------------------------------ cotangent to the prompt states ------------------------------
+// The states enter a stage through K_ctx = Wk tokens^T + bk and V_ctx = Wv tokens^T + bv only, so with this pass's g_o, the primal
+// P and q, and R = scale P o (g_o^T V_ctx - <P, g_o^T V_ctx>) (the row operation xa_linear just applied),
+//     g_V[c][l] = sum_t g_o[c][t] P[t][l],   g_K[c][l] = sum_t q[c][t] R[t][l],   G[l][d] += sum_c Wk[c][d] g_K[c][l] + Wv[c][d] g_V[c][l]
+// (the biases drop out).  The two token contractions: xattn_ctx.hip where the shape allows, else strided GEMMs over the pass's
+// S buffer, which the unfused xa_linear left holding R (it is recomputed into S where xa_linear ran fused).  Every product is on a
+// tiling that does not depend on the batch (launch_gemm_fixed), so a probe's row of G has the same bits wherever it stands.
+// Called from the single-probe passes of loco_pmp_vjp_context only (x.B = 1, the caller's stream, no probe lanes).
+// Workspace: the split-K scratch (c->partial), [2][C][W] reduced rows + the token-block partials [NH][blocks / walk][2][CH][W]:
+// 2 C W (1 + blocks / walk) floats.  The launch arguments keep a probe index (strides x.xs / red_bs) for a batched G, which
+// nothing runs and no test covers.
+int xa_context_grad(const XA& x, const Op& op, const float* go, const float* q, const float* P, float* S) {
+    loco_ctx* c = x.c;
+    const int D = c->cfg.context_dim;
+    const bool fused = c->fuse_xattn && xattn_fused_supported(x.T, x.CH, x.L, x.Lp);      // what xa_linear took
+    const bool kern = fused && xattn_ctx_supported(x.T, x.CH, x.L, x.Lp);
+    const int W = kern ? xattn_ctx_width(x.L) : x.Lp;
+    const size_t avail = c->partial_floats;
+    float* red = c->partial;                                      // [B][2][C][W]
+    const long red_bs = 2L * x.C * W;
+    if ((size_t)x.B * red_bs > avail) { c->err = "loco_pmp_vjp_context: the split-K workspace is too small for the prompt-state rows"; return -1; }
+    if (kern) {
+        XCtxArgs a; std::memset(&a, 0, sizeof(a));
+        a.T = x.T; a.NH = x.NH; a.B = x.B; a.CH = x.CH; a.L = x.L; a.Lp = x.Lp; a.alpha = x.scale;
+        a.walk = xattn_ctx_walk(x.T, x.NH, x.CH, x.L, x.B, avail);
+        if (a.walk <= 0) { c->err = "loco_pmp_vjp_context: the split-K workspace is too small for the token-block partials"; return -1; }
+        a.nchunk = (x.T / 64 + a.walk - 1) / a.walk;
+        a.go = go; a.go_bs = x.xs; a.q = q; a.V = x.xV; a.P = P;
+        a.out = red; a.out_bs = red_bs; a.part = red + (size_t)x.B * red_bs;
+        attn_note(c, "xattn_ctx");
+        launch_xattn_ctx(a, x.st);
+    } else {
+        if (fused) {      // R into S, as the unfused xa_linear leaves it
+            xa_scores(x, go, x.xs, x.xV, S, x.ss, 1.f, false, true);
+            attn_softmax_jac(c, S, P, (long)x.NH * x.T, x.Lp, x.scale, x.st, x.B, x.ss);
+        }
+        for (int w = 0; w < 2; ++w) {       // g_K = q R, g_V = g_o P: [CH][Lp] per head, contracted over the tokens
+            GemmArgs g; std::memset(&g, 0, sizeof(g));
+            g.A = w ? go : q; g.sam = x.T; g.sak = 1; g.sab = w ? x.xs : 0; g.sah = (long)x.CH * x.T;
+            g.Bm = w ? P : S; g.sbk = x.Lp; g.sbn = 1; g.sbb = w ? 0 : x.ss; g.sbh = (long)x.T * x.Lp;
+            g.C = red + (long)w * x.C * W; g.scm = W; g.scn = 1; g.scb = red_bs; g.sch = (long)x.CH * W;
+            g.M = x.CH; g.N = x.Lp; g.K = x.T; g.batch = x.B; g.batch2 = x.NH; g.alpha = 1.f; g.beta = 0.f;
+            attn_note(c, "gemm_f32_fixed", &g);
+            launch_gemm_fixed(g, GEMM_ACT_NONE, x.st);
+        }
+    }
+    // G[b][l][d] (+)= sum_c g_K[b][c][l] Wk[c][d] + g_V[b][c][l] Wv[c][d]
+    GemmArgs g; std::memset(&g, 0, sizeof(g));
+    g.A = red; g.sam = 1; g.sak = W; g.sab = red_bs;
+    g.Bm = op.xkw; g.sbk = D; g.sbn = 1; g.sbb = 0;
+    g.A2 = red + (long)x.C * W; g.sab2 = red_bs; g.Bm2 = op.xvw; g.sbb2 = 0;
+    g.C = c->ctx_G; g.scm = D; g.scn = 1; g.scb = (long)x.L * D;
+    g.M = x.L; g.N = D; g.K = x.C; g.batch = x.B; g.alpha = 1.f; g.beta = c->ctx_G_first ? 0.f : 1.f;
+    attn_note(c, "gemm_f32_fixed", &g);
+    launch_gemm_fixed(g, GEMM_ACT_NONE, x.st);
+    c->ctx_G_first = false;
+    return 0;
 }
 
 // ------------------------------ multi-head self-attention core ------------------------------
@@ -948,6 +1008,7 @@ int cotangent_pass(loco_ctx* c, const float* ge, const float* gx0, float* Aout, 
                     const XA x = xa_of(c, op, B, st);
                     lin1x1(c, op.xproj, true, TG(op.out), TG(op.xo), B, st);
                     xa_linear(x, TG(op.xo), op.xV, op.xK, TP(op.xS), TG(op.xS), TG(op.xq));           // g_o -> g_q
+                    if (c->ctx_G && xa_context_grad(x, op, TG(op.xo), TP(op.xq), TP(op.xS), TG(op.xS))) return -1;
                     lin1x1(c, op.xqc, true, TG(op.xq), TG(op.xhn), B, st);
                     lin_stats(p, op.nx, 2, TG(op.xhn), TP(op.xmid));
                     gn_lin_apply(p, op.nx, 3, TG(op.xhn), TP(op.xmid), TG(op.out), TG(op.xmid));
@@ -973,6 +1034,7 @@ int cotangent_pass(loco_ctx* c, const float* ge, const float* gx0, float* Aout, 
                 // cross-attention: h2 = h1 + to_out2(V P^T), q = to_q(LN2(h1))
                 lin1x1(c, op.to_out2, true, XG(X_H2), XG(X_XO), B, st);
                 xa_linear(xa, XG(X_XO), op.xV, op.xK, XP(X_XS), XG(X_XS), XG(X_XQ));                // g_o -> g_q
+                if (c->ctx_G && xa_context_grad(xa, op, XG(X_XO), XP(X_XQ), XP(X_XS), XG(X_XS))) return -1;
                 lin1x1(c, op.xqc, true, XG(X_XQ), XG(X_A2), B, st);
                 launch_ln_cot(XG(X_A2), PS, XP(X_H1), XP(X_LN2), B, C, HW, op.lng[1], XG(X_H2), PS, XG(X_H1), PS, st);  // g_h1
                 // self-attention: h1 = h0 + to_out1(attn(qkv(LN1(h0))))
@@ -1532,9 +1594,7 @@ int loco_pmp_jvp(loco_ctx* c, const float* V, int32_t k, float* U, void* stream)
     return 0;
 }
 
-int loco_pmp_vjp(loco_ctx* c, const float* U, int32_t k, float* A, void* stream) {
-    if (!c) return -2;
-    if (!c->primal_ok) { c->err = "loco_pmp_primal has not been called"; return -2; }
+static int pmp_vjp_run(loco_ctx* c, const float* U, int32_t k, float* A, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     const int MB = c->cfg.max_batch;
     for (int b0 = 0; b0 < k; b0 += MB) {
@@ -1559,6 +1619,48 @@ int loco_pmp_vjp(loco_ctx* c, const float* U, int32_t k, float* A, void* stream)
                             (long)c->mask2_from - (b0 + s0));
             return cotangent_pass(c, c->ge, same ? c->gx0 : nullptr, A + (long)(b0 + s0) * c->prog->n_in, nb, ls);
         });
+        if (rc) return rc;
+    }
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+int loco_pmp_vjp(loco_ctx* c, const float* U, int32_t k, float* A, void* stream) {
+    if (!c) return -2;
+    if (!c->primal_ok) { c->err = "loco_pmp_primal has not been called"; return -2; }
+    return pmp_vjp_run(c, U, k, A, stream);
+}
+
+int loco_pmp_vjp_context(loco_ctx* c, const float* U, int32_t k, float* A, float* G, void* stream) {
+    if (!c) return -2;
+    if (c->cfg.context_dim <= 0) { c->err = "loco_pmp_vjp_context: this architecture has no cross-attention stages (context_dim = 0)"; return -2; }
+    if (c->cfg.added_kv) {
+        c->err = "loco_pmp_vjp_context: the added_kv attention blocks (DeepFloyd IF) pass the states through a per-block GroupNorm and "
+                 "the pooled time embedding: their gradient is not built";
+        return -2;
+    }
+    if (!G) { c->err = "loco_pmp_vjp_context: G is NULL"; return -2; }
+    if (!c->primal_ok) { c->err = "loco_pmp_vjp_context: no valid primal (loco_pmp_primal has not been called since the last loco_set_context)"; return -2; }
+    if (c->tap != 0) { c->err = "loco_pmp_vjp_context: the cached primal is an h-space tap's (tap = 1 / 2); the prompt-state gradient is of the whole network (tap = 0)"; return -2; }
+    // The convolutions of a cotangent pass are planned by its batch (tile, split-K factor: conv_plan.hip), so the bits of g_o at
+    // a stage -- and of A -- depend on k and on a probe's place in the batch.  A keeps loco_pmp_vjp's batched passes; the rows
+    // of G come from one single-probe pass each, which is what makes a row the same bits wherever it stands.  k = 1 (null-text
+    // inversion) is one pass for both; without A a pass stops behind the first op that reads the states.
+    hipStream_t st = (hipStream_t)stream;
+    const Program& P = *c->prog;
+    const bool withA = A && k == 1;
+    if (A && k > 1)
+        if (int rc = pmp_vjp_run(c, U, k, A, stream)) return rc;
+    float* gx0 = withA && P.n_out == P.n_in ? c->gx0 : nullptr;
+    int ctx_lo = 0;
+    if (!withA)
+        while (ctx_lo < (int)c->ops.size() && !c->ops[ctx_lo].has_ctx_kv()) ++ctx_lo;
+    for (int p = 0; p < k; ++p) {
+        c->ctx_G = G + (long)p * c->cfg.context_len * c->cfg.context_dim; c->ctx_G_first = true;
+        launch_cot_seed(U + (long)p * P.n_out, c->has_mask ? c->mask : nullptr, c->p_cv, c->p_ce, c->ge, gx0, 1, P.n_out, st,
+                        c->has_mask2 ? c->mask2 : nullptr, (long)c->mask2_from - p);
+        const int rc = cotangent_pass(c, c->ge, gx0, withA ? A : nullptr, 1, st, ctx_lo);
+        c->ctx_G = nullptr;
         if (rc) return rc;
     }
     HIPCHK(c, hipGetLastError());

@@ -132,6 +132,10 @@ struct loco_ctx {
     float* alphas = nullptr;
     float* ctx_colbias = nullptr;  // [Lp]: 0 for real tokens, -1e30 for the padding
     bool has_ctx = false;
+    // loco_pmp_vjp_context: where the cotangent pass being enqueued adds its probes' rows of G [B][context_len][context_dim]
+    // (nullptr: no gradient asked for), and whether its next cross-attention stage is the first to write them
+    float* ctx_G = nullptr;
+    bool ctx_G_first = false;
     float* cond_add = nullptr;     // [temb_ch] conditioning embedding of the time embedding (loco_set_cond)
     float* ctx_norm = nullptr;     // [context_len][context_dim] scratch: the states behind one block's norm_encoder (added_kv)
     bool has_cond = false;
@@ -297,6 +301,8 @@ struct XA {                     // shape and constants of one stage; the tensors
 };
 void xa_forward(const XA& x, const float* Xq, float* P, float* O);
 void xa_linear(const XA& x, const float* X, const float* K1, const float* K2, float* P, float* S, float* O);
+// behind the cotangent's xa_linear: the stage's term of c->ctx_G (engine.hip)
+int xa_context_grad(const XA& x, const Op& op, const float* go, const float* q, const float* P, float* S);
 
 // the multi-head self-attention core (engine.hip)
 struct Attn {

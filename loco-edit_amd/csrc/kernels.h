@@ -320,6 +320,25 @@ struct XAttnArgs {
 };
 bool xattn_fused_supported(int T, int CH, int L, int Lp);
 void launch_xattn_fused(const XAttnArgs& a, hipStream_t st);
+int  xattn_lg(int L);                 // score columns per lane of the fused kernels: the smallest instantiated LG with 4 LG >= L (0: none)
+// cotangent of a cross-attention stage to the projected prompt states (xattn_ctx.hip): g_K = q R, g_V = g_o P over the tokens,
+// R recomputed from g_o, V_ctx and the primal P as launch_xattn_fused's cotangent form does
+struct XCtxArgs {
+    int T, NH, B, CH, L, Lp;
+    int walk, nchunk;                 // token blocks one workgroup walks, workgroups per (probe, head) = ceil(T / 64 / walk)
+    float alpha;                      // softmax scale
+    const float* go; long go_bs;      // this pass's g_o [B][C][T]
+    const float* q;                   // primal q [C][T]
+    const float* V;                   // V_ctx [C][Lp]
+    const float* P;                   // primal P [NH][T][Lp]
+    float* part;                      // workspace [B][NH][nchunk][2][CH][W], W = xattn_ctx_width(L); 16-byte aligned
+    float* out; long out_bs;          // [B][2][C][W]: g_K, g_V (columns >= L zero)
+};
+bool xattn_ctx_supported(int T, int CH, int L, int Lp);
+int  xattn_ctx_width(int L);
+// the smallest walk for which the reduced rows + partials of `probes` probes fit `avail_floats` (0: none does)
+int  xattn_ctx_walk(int T, int NH, int CH, int L, int probes, size_t avail_floats);
+void launch_xattn_ctx(const XCtxArgs& a, hipStream_t st);        // the contraction kernel + the block-order reduce
 void launch_geglu(int kind, const float* in, long in_bs, const float* fprim, int B, long n4, float* out, long out_bs,
                   hipStream_t st);
 

@@ -132,14 +132,14 @@ void xattn_launch(const XAttnArgs& a, hipStream_t st) {
     else hipLaunchKernelGGL(kl, grid, dim3(256), lds, st, a);
 }
 
+}  // namespace
+
 int xattn_lg(int L) {           // columns per lane: the smallest instantiated LG with 4 LG >= L
     const int need = (L + 3) / 4;
     for (int lg : {4, 8, 12, 20, 32})
         if (lg >= need) return lg;
     return 0;
 }
-
-}  // namespace
 
 bool xattn_fused_supported(int T, int CH, int L, int Lp) {
     const int lg = xattn_lg(L);

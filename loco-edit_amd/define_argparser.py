@@ -208,6 +208,15 @@ def build_parser():
     p.add_argument('--asyrp_rec_weight', type=float, default=3.0,
                    help='--run_edit_asyrp: weight of the reconstruction loss mean |x0_edit - x0_src| (as published)')
     p.add_argument('--asyrp_scale', type=float, default=1.0, help='--run_edit_asyrp: multiplies the learned dh at inference')
+    p.add_argument('--null_text_inversion', type=str2bool, default=False,
+                   help='Stable Diffusion edit runs on an image of the dataset (--dataset_name other than Random, --sample_idx): DDIM '
+                        'inversion under the for prompt, then null-text inversion (Mokady et al. 2023) -- the unconditional prompt '
+                        'states are optimised per timestep so that the guided decode returns to the image; cached as '
+                        'null_text-<idx>.pt in the result folder. Needs --inv_steps == --for_steps')
+    p.add_argument('--null_text_inner_steps', type=int, default=10, help='--null_text_inversion: Adam steps per timestep at most (as published)')
+    p.add_argument('--null_text_lr', type=float, default=1e-2, help='--null_text_inversion: lr of step i is this times (1 - i / 100) (as published)')
+    p.add_argument('--null_text_early_stop', type=float, default=1e-5,
+                   help='--null_text_inversion: the inner loop of step i stops at loss < this + 2e-5 i (as published)')
     p.add_argument('--mask_prompts', type=str, default='',
                    help='text-prompted edit masks: a comma list such as "hair,eyes,mouth"; when mask/mask.pt is missing, CLIPSeg '
                         '(--mask_prompt_model_path) writes one mask per entry, in order, so --mask_index selects a prompt')
@@ -449,6 +458,9 @@ def _preset_t2i(args, family):
             r = args.vae_encoder_config.resolution
             args.dataset = (SyntheticDataset(r, 3) if args.dataset_name == 'Synthetic'
                             else FolderDataset(args.dataset_root, res=r, numeric=args.dataset_name != 'AFHQ'))
+        if getattr(args, 'null_text_inversion', False):
+            from .null_text import check_steps
+            check_steps(args.inv_steps, args.for_steps)
         args.c_in = args.unet_config.in_channels           # 4
     else:
         if getattr(args, 'unet_config', None) is None:

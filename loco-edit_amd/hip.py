@@ -27,7 +27,7 @@ DIAG_SYMBOLS = ["loco_bench_conv", "loco_debug_conv", "loco_debug_attn", "loco_d
 SYMBOLS = [
     "loco_version", "loco_device_count", "loco_create", "loco_fork", "loco_destroy", "loco_last_error",
     "loco_load_param", "loco_params_missing", "loco_unet_forward", "loco_ddim_step", "loco_sched_step",
-    "loco_pmp_primal", "loco_pmp_set_second_mask", "loco_pmp_jvp", "loco_pmp_vjp", "loco_orthonormalize", "loco_qr_rows",
+    "loco_pmp_primal", "loco_pmp_set_second_mask", "loco_pmp_jvp", "loco_pmp_vjp", "loco_pmp_vjp_context", "loco_orthonormalize", "loco_qr_rows",
     "loco_convergence", "loco_convergence_rows", "loco_krylov_extend", "loco_krylov_ritz", "loco_krylov_left", "loco_null_project", "loco_edit_axpy", "loco_mask_gather", "loco_mask_count",
     "loco_unet_flops", "loco_workspace_bytes", "loco_clock_stamp", "loco_set_side_stream", "loco_timer_start", "loco_timer_stop",
     "loco_profile_enable", "loco_profile_report", "loco_set_precision", "loco_get_precision", "loco_set_streams", "loco_set_chip_share",
@@ -230,6 +230,8 @@ def load_library():
         lib.loco_pmp_primal_eps.argtypes = [vp, vp, vp]
     lib.loco_pmp_jvp.argtypes = [vp, vp, i32, vp, vp]
     lib.loco_pmp_vjp.argtypes = [vp, vp, i32, vp, vp]
+    if hasattr(lib, "loco_pmp_vjp_context"):      # (absent from a library of an earlier round loaded by LOCO_HIP_LIB for an A/B)
+        lib.loco_pmp_vjp_context.argtypes = [vp, vp, i32, vp, vp, vp]
     lib.loco_orthonormalize.argtypes = [vp, vp, i32, i64, vp, vp]
     lib.loco_qr_rows.argtypes = [vp, vp, i32, i64, vp]
     lib.loco_convergence.argtypes = [vp, vp, vp, i64, f32, vp, vp]
@@ -666,7 +668,10 @@ class LocoEngine:
         self._check(self.lib.loco_pmp_jvp(self._ctx, _ptr(V), k, _ptr(U), _stream()), "loco_pmp_jvp")
         return U
 
-    def pmp_vjp(self, U: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def pmp_vjp(self, U: torch.Tensor, out: Optional[torch.Tensor] = None, context_grad: bool = False):
+        """``context_grad``: also return G [k, context_len, context_dim], the gradient of the same rows with respect to the
+        states of the last ``set_context`` -- ``(A, G)``; A is what the call without the flag returns, to the bit.  A row of G
+        does not depend on k or its position: the rows come from single-probe passes (k = 1: one pass for A and G)."""
         _chk_dev(U)
         k = U.shape[0]
         n_in = self._rows("in")
@@ -677,6 +682,10 @@ class LocoEngine:
             _chk_dev(out)
             if tuple(out.shape) != (k, n_in):
                 raise ValueError(f"out must be {(k, n_in)}, got {tuple(out.shape)}")
+        if context_grad:
+            G = torch.empty(k, self.cfg.context_len, self.cfg.context_dim, device=U.device, dtype=torch.float32)
+            self._check(self.lib.loco_pmp_vjp_context(self._ctx, _ptr(U), k, _ptr(A), _ptr(G), _stream()), "loco_pmp_vjp_context")
+            return A, G
         self._check(self.lib.loco_pmp_vjp(self._ctx, _ptr(U), k, _ptr(A), _stream()), "loco_pmp_vjp")
         return A
 

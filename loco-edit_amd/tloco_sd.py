@@ -35,8 +35,10 @@ same stand-ins (oracle/make_golden_tloco_sd.py).  SAM masks are an input (``mask
 """
 from __future__ import annotations
 
+import contextlib
 import os
-from typing import Dict, Optional
+import time
+from typing import Dict, List, Optional
 
 import numpy as np
 import torch
@@ -153,6 +155,11 @@ class EditStableDiffusion(EditDeepFloydIF):
         self.inv_prompt_emb = pe["inv"] if (pe is not None and "inv" in pe) else self.for_prompt_emb
         self.enc_engine: Optional[LocoEngine] = None
         self.dataset = getattr(args, "dataset", None)
+        # ---- null-text inversion (null_text.py): edit an image of the dataset instead of a sample of the model
+        self.null_text = bool(getattr(args, "null_text_inversion", False))
+        self._nt_embs: Optional[List[Optional[torch.Tensor]]] = None     # per decode timestep index the optimised null states [1, L, D]
+        self._nt_idx, self._nt_zT, self._nt_report = None, None, None
+        self._t0 = 0                    # index of the decode timestep the run's z_T sits at (an inverted latent: 1)
 
     # ------------------------------------------------------------------ prompts (edit.py:523-538, 1187-1194)
     def _build_text_encoder(self, args, cfg):
@@ -216,9 +223,10 @@ class EditStableDiffusion(EditDeepFloydIF):
         return torch.cat(out)
 
     @torch.no_grad()
-    def run_DDIMinversion(self, idx, guidance=None, vis_traj=False, noise=None):
+    def run_DDIMinversion(self, idx, guidance=None, vis_traj=False, noise=None, return_trajectory=False):
         """edit.py:568-633.  Prompt: (CFG) pos inv_prompt / neg null_prompt, (no CFG) inv_prompt alone; CFG only when
-        ``guidance`` is given and guidance_scale > 1.  Ascending custom-scheduler timesteps, the last one is not stepped."""
+        ``guidance`` is given and guidance_scale > 1.  Ascending custom-scheduler timesteps, the last one is not stepped.
+        ``return_trajectory``: -> (z_T, [z_0, ..., z_T]), the latent at every timestep of the loop."""
         print('start DDIMinversion')
         self.EXP_NAME = f'DDIMinversion-{self.dataset_name}-{idx}-for_{self.for_prompt}-inv_{self.inv_prompt}'
         do_cfg = (self.guidance_scale > 1.0) and (guidance is not None)
@@ -233,13 +241,16 @@ class EditStableDiffusion(EditDeepFloydIF):
             _save_image((x0 / 2 + 0.5).clamp(0, 1), os.path.join(self.result_folder, 'original_x0.png'))
         latents = self.encode(x0, noise=noise)
         F, E, N = self.inv_prompt_emb, self.edit_prompt_emb, self.null_prompt_emb      # the "for" branch carries inv_prompt
+        traj = [latents]
         for i, t in enumerate(timesteps):
             if i == len(timesteps) - 1:
                 break
             noise_pred = self._classifer_free_guidance(latents, t, F, E, N, mode="null+(for-null)",
                                                        do_classifier_free_guidance=do_cfg)
             latents = self.scheduler.step(noise_pred, t, latents, eta=0).prev_sample
-        return latents
+            if return_trajectory:
+                traj.append(latents)
+        return (latents, traj) if return_trajectory else latents
 
     # ------------------------------------------------------------------ decode (edit.py:748-750, 769-771)
     def decode(self, z_scaled: torch.Tensor) -> torch.Tensor:
@@ -320,7 +331,8 @@ class EditStableDiffusion(EditDeepFloydIF):
     # ------------------------------------------------------------------ sampler (edit.py:677-754)
     @torch.no_grad()
     def DDIMforwardsteps(self, zt, t_start_idx, t_end_idx, for_prompt_emb, edit_prompt_emb, null_prompt_emb,
-                         mode="null+(for-null)", **kwargs):
+                         mode="null+(for-null)", null_prompt_embs=None, **kwargs):
+        """``null_prompt_embs``: one [1, L, D] per timestep index (null-text inversion) in place of ``null_prompt_emb``."""
         assert mode in ["null+(for-null)+(edit-null)", "null+(for-null)", "null+(edit-null)"]
         print('start DDIMforward')
         do_cfg = self.guidance_scale > 1.0
@@ -333,7 +345,8 @@ class EditStableDiffusion(EditDeepFloydIF):
                 pass
             elif t_idx == t_end_idx:
                 return latents, t, t_idx
-            noise_pred = self._classifer_free_guidance(latents, t, for_prompt_emb, edit_prompt_emb, null_prompt_emb,
+            null_e = null_prompt_emb if null_prompt_embs is None else null_prompt_embs[t_idx]
+            noise_pred = self._classifer_free_guidance(latents, t, for_prompt_emb, edit_prompt_emb, null_e,
                                                        mode=mode, do_classifier_free_guidance=do_cfg)
             latents = self.scheduler.step(noise_pred, t, latents, eta=0).prev_sample
         latents = self.engine.lincomb([(float(np.float32(1.0) / np.float32(LATENT_SCALE)), latents)])   # :748
@@ -356,9 +369,88 @@ class EditStableDiffusion(EditDeepFloydIF):
     # ------------------------------------------------------------------ drivers
     def _zT(self):
         if self.dataset_name != 'Random':
+            if self.null_text:
+                return self._null_text_zT(int(getattr(self.args, "sample_idx", 0)))
             raise ValueError("the edit runs start from z_T ~ N(0, I) (dataset_name 'Random', edit.py:937-938); "
                              "run_DDIMinversion is the image entry point")
         return torch.randn(1, self.c_in, self.image_size, self.image_size, dtype=self.dtype, device=self.device)
+
+    # ------------------------------------------------------------------ null-text inversion (null_text.py)
+    def _null_text_zT(self, idx):
+        """The inverted latent of dataset image ``idx`` and, per decode step, the unconditional states with which the guided
+        decode follows the inversion back to the image: conditional-branch inversion under the `for` prompt, then the
+        optimisation -- once per sample, cached as null_text-<idx>.pt in the result folder."""
+        from . import null_text as nt
+        if "null" not in self.branches:
+            raise ValueError("--null_text_inversion optimises the prompt of the `null` guidance branch: this class runs the "
+                             f"branches {' / '.join(self.branches)} (not built for the latent-consistency class)")
+        nt.check_steps(self.inv_steps, self.for_steps)
+        if self.edit_t_idx < 1:
+            raise ValueError("--null_text_inversion: the inverted latent sits at decode step 1 (the inversion's last timestep is "
+                             f"not stepped), so the edit step must come after it; edit_t {self.edit_t} selects step {self.edit_t_idx}")
+        if self._nt_idx == idx and self._nt_embs is not None:
+            return self._nt_zT
+        L, D = self.cfg.context_len, self.cfg.context_dim
+        S = self.for_steps - 2                 # the inversion's last timestep is not stepped: z_T sits at decode index 1
+        if S < 1:
+            raise ValueError("--null_text_inversion needs for_steps >= 3")
+        path = nt.cache_path(self.result_folder, idx)
+        args = self.args
+        inner = int(getattr(args, "null_text_inner_steps", 10))
+        lr, stop = float(getattr(args, "null_text_lr", 1e-2)), float(getattr(args, "null_text_early_stop", 1e-5))
+        if self.dataset is None:
+            raise ValueError("--null_text_inversion needs an image dataset (dataset_name 'Random' has none)")
+        # the cache serves this image under these settings only
+        settings = {"inner_steps": inner, "lr": lr, "early_stop": stop, "guidance_scale": float(self.guidance_scale),
+                    "image_sha256": nt.image_digest(self.dataset[idx])}
+        cached = nt.load_cache(path, S, (L, D), settings)
+        if self.sharder.agree(cached is not None):
+            embs, zT = cached["embs"].to(self.device), cached["zT"].to(self.device, torch.float32)
+            report = dict(cached["report"], cached=True)
+        else:
+            inv_e, exp = self.inv_prompt_emb, self.EXP_NAME
+            self.inv_prompt_emb = self.for_prompt_emb      # the edit decodes under the `for` prompt: so does the inversion
+            try:
+                zT, traj = self.run_DDIMinversion(idx, guidance=None, return_trajectory=True)
+            finally:
+                self.inv_prompt_emb, self.EXP_NAME = inv_e, exp
+            self.scheduler.set_timesteps(self.for_steps, device=self.device)
+            ts, traj = self.scheduler.timesteps[1:], traj[::-1]
+            F, N = self.for_prompt_emb, self.null_prompt_emb
+            t_0 = time.perf_counter()
+            opt = nt.NullTextInversion(self)
+            embs, z_bar, losses = opt.run(traj, ts, N, F, inner, lr, stop)
+            seconds = time.perf_counter() - t_0
+            _, z_plain, _ = nt.NullTextInversion(self).run(traj, ts, N, F, 0)         # the guided decode with the one null prompt
+            inv_scale = float(np.float32(1.0) / np.float32(LATENT_SCALE))
+            x_rt, x_nt, x_pl = (self.decode(self.engine.lincomb([(inv_scale, z.contiguous())])) for z in (traj[-1], z_bar, z_plain))
+            psnr = lambda x: float(10.0 * torch.log10(4.0 / ((x - x_rt) ** 2).mean().clamp_min(1e-30)))     # images in [-1, 1]
+            report = {"sample_idx": idx, "steps": S, "inner_steps": inner, "lr": lr, "early_stop": stop, "seconds": seconds,
+                      "guidance_scale": float(self.guidance_scale), "image_sha256": settings["image_sha256"], "cached": False,
+                      "per_step": [{"t": float(t), "first_loss": l[0] if l else None, "last_loss": l[-1] if l else None,
+                                    "inner_steps_used": len(l), "seconds": sec} for t, l, sec in zip(ts, losses, opt.seconds)],
+                      "psnr_vs_autoencoder_round_trip": {"null_text": psnr(x_nt), "plain_guided": psnr(x_pl)}}
+            if self.sharder.is_main:
+                nt.save_cache(path, embs, zT, report)
+        self._nt_embs = [None] + [embs[i][None].contiguous() for i in range(S)]
+        self._nt_idx, self._nt_zT, self._nt_report, self._t0 = idx, zT, report, 1
+        return zT
+
+    @contextlib.contextmanager
+    def _null_bound(self, t_idx):
+        """The unconditional states of decode step ``t_idx`` as the run's null prompt while a solve at that step runs."""
+        keep = self.null_prompt_emb
+        if self._nt_embs is not None:
+            self.null_prompt_emb = self._nt_embs[t_idx]
+        try:
+            yield self.null_prompt_emb
+        finally:
+            self.null_prompt_emb = keep
+
+    def _write_null_text_report(self):
+        if self._nt_report is not None and self.sharder.is_main:
+            from .null_text import write_report
+            write_report(os.path.join(self.result_folder, f"{self.EXP_NAME}_null_text.json"), self._nt_report)
 
     def _solve_or_load(self, save_dir, zt, t, t_idx, mask, op, block_idx, pca_rank, pca_rank_null, null_space_projection,
                        modify_fn):
@@ -398,15 +490,16 @@ class EditStableDiffusion(EditDeepFloydIF):
         x0 = None
         segment = wants_segmentation(self.args) and not self._exists(os.path.join(self.result_folder, "mask/mask.pt"))
         if self.sharder.agree(not os.path.exists(os.path.join(self.result_folder, "original.png"))) or segment:
-            _, x0 = self.DDIMforwardsteps(zT, t_start_idx=0, t_end_idx=-1, for_prompt_emb=F, edit_prompt_emb=E, null_prompt_emb=N,
-                                          mode="null+(for-null)")         # the image SAM segments (edit.py:942-948)
+            _, x0 = self.DDIMforwardsteps(zT, t_start_idx=self._t0, t_end_idx=-1, for_prompt_emb=F, edit_prompt_emb=E, null_prompt_emb=N,
+                                          mode="null+(for-null)", null_prompt_embs=self._nt_embs)   # the image SAM segments (edit.py:942-948)
         # masks at the size of the decoded sample (512 for Stable Diffusion)
         masks = self._masks((lambda: x0[0].detach().cpu().numpy()) if segment else None, x0.shape[1] if segment else None)
         if self.sampling_mode:
             return None
         mask = masks[mask_index].squeeze(dim=0).repeat(3, 1, 1)
-        zt, t, t_idx = self.DDIMforwardsteps(zT, t_start_idx=0, t_end_idx=self.edit_t_idx, for_prompt_emb=F,
-                                             edit_prompt_emb=E, null_prompt_emb=N, mode="null+(for-null)")
+        zt, t, t_idx = self.DDIMforwardsteps(zT, t_start_idx=self._t0, t_end_idx=self.edit_t_idx, for_prompt_emb=F,
+                                             edit_prompt_emb=E, null_prompt_emb=N, mode="null+(for-null)",
+                                             null_prompt_embs=self._nt_embs)
         assert t_idx == self.edit_t_idx
         return zt, t, t_idx, mask
 
@@ -422,12 +515,13 @@ class EditStableDiffusion(EditDeepFloydIF):
         F, E, N = self.for_prompt_emb, self.edit_prompt_emb, self.null_prompt_emb
         save_dir = os.path.join(self.result_folder, "basis", f'local_basis-{self.edit_t}T-pca-rank-{pca_rank}-select-mask{mask_index}')
 
-        def modify():
+        def modify():      # (self.null_prompt_emb: under null-text inversion the states of the edit step, bound by _null_bound)
             u, s, vT = self.local_encoder_decoder_pullback_zt(
-                zt, t, t_idx, F, E, N, op=op, block_idx=block_idx, pca_rank=pca_rank, chunk_size=5, min_iter=10, max_iter=50,
+                zt, t, t_idx, F, E, self.null_prompt_emb, op=op, block_idx=block_idx, pca_rank=pca_rank, chunk_size=5, min_iter=10, max_iter=50,
                 convergence_threshold=1e-3, mask=mask, mode="null+(for-null)")
             return u, vT
-        vT = self._solve_or_load(save_dir, zt, t, t_idx, mask, op, block_idx, pca_rank, pca_rank_null, null_space_projection, modify)
+        with self._null_bound(t_idx):      # (null-text inversion: the solve sees the states of the edit step)
+            vT = self._solve_or_load(save_dir, zt, t, t_idx, mask, op, block_idx, pca_rank, pca_rank_null, null_space_projection, modify)
         original_zt = zt.clone()
         out = None
         for pc_idx in range(vis_num_pc):
@@ -435,7 +529,9 @@ class EditStableDiffusion(EditDeepFloydIF):
                              f'{null_space_projection}_null_space_rank_{pca_rank_null}')
             zb = self._walk(original_zt, vT[pc_idx, :], vis_num)
         out = self.DDIMforwardsteps(zb, t_start_idx=self.edit_t_idx, t_end_idx=-1, for_prompt_emb=F, edit_prompt_emb=E,
-                                    null_prompt_emb=N, mode="null+(for-null)")      # after the loop, as in :1036-1041
+                                    null_prompt_emb=N, mode="null+(for-null)",      # after the loop, as in :1036-1041
+                                    null_prompt_embs=self._nt_embs)
+        self._write_null_text_report()
         return out
 
     @torch.no_grad()
@@ -453,20 +549,22 @@ class EditStableDiffusion(EditDeepFloydIF):
         if self.use_sega:
             self.EXP_NAME = f'sega-edit_prompt-{self.edit_prompt}'
             out = self.DDIMforwardsteps(zt, t_start_idx=self.edit_t_idx, t_end_idx=-1, for_prompt_emb=F, edit_prompt_emb=E,
-                                        null_prompt_emb=N, mode="null+(for-null)+(edit-null)")
+                                        null_prompt_emb=N, mode="null+(for-null)+(edit-null)", null_prompt_embs=self._nt_embs)
+            self._write_null_text_report()
             if self.clip_scoring:
                 # no unedited frame comes back: zt decoded once more under the `for` prompt (on every rank: the sampler is shared)
                 _, x_orig = self._decoded_as("_clip_original", lambda: self.DDIMforwardsteps(
                     zt, t_start_idx=self.edit_t_idx, t_end_idx=-1, for_prompt_emb=F, edit_prompt_emb=E, null_prompt_emb=N,
-                    mode="null+(for-null)"))
+                    mode="null+(for-null)", null_prompt_embs=self._nt_embs))
                 self._score_clip(out[1], original_frame=x_orig)
             return out
         save_dir = os.path.join(self.result_folder, "basis",
                                 f'local_basis-{self.edit_t}T-"{self.edit_prompt}"-pca-rank-{pca_rank}-select-mask{mask_index}')
 
         def modify():
-            return None, self.get_delta_zt_via_grad(zt, t, t_idx, F, E, N, mask=mask, mode=self.tilda_v_score_type)
-        vT = self._solve_or_load(save_dir, zt, t, t_idx, mask, op, block_idx, pca_rank, pca_rank_null, null_space_projection, modify)
+            return None, self.get_delta_zt_via_grad(zt, t, t_idx, F, E, self.null_prompt_emb, mask=mask, mode=self.tilda_v_score_type)
+        with self._null_bound(t_idx):
+            vT = self._solve_or_load(save_dir, zt, t, t_idx, mask, op, block_idx, pca_rank, pca_rank_null, null_space_projection, modify)
         original_zt = zt.clone()
         for pc_idx in range(vis_num_pc):
             self.EXP_NAME = (f'Edit_zt-edit_{self.edit_t}T-{op}-block_{block_idx}-pc_{pc_idx:0=3d}_pos-edit_prompt-{self.edit_prompt}'
@@ -474,7 +572,8 @@ class EditStableDiffusion(EditDeepFloydIF):
                              f'{pca_rank_null}_{self.tilda_v_score_type}')
             zb = self._walk(original_zt, vT[pc_idx, :], vis_num)
         out = self.DDIMforwardsteps(zb, t_start_idx=self.edit_t_idx, t_end_idx=-1, for_prompt_emb=F, edit_prompt_emb=E,
-                                    null_prompt_emb=N, mode="null+(for-null)")
+                                    null_prompt_emb=N, mode="null+(for-null)", null_prompt_embs=self._nt_embs)
+        self._write_null_text_report()
         self._score_clip(out[1], alphas=self._walk_alphas(vis_num))
         self._score_quality(out[1], self._walk_alphas(vis_num), mask)
         return out
