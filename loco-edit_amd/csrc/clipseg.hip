@@ -429,12 +429,7 @@ int loco_clipseg_preprocess(loco_clipseg* t, const void* frames_dev, int32_t is_
     DeviceGuard dg(t->device);
     hipStream_t st = (hipStream_t)stream;
     const size_t need = (size_t)n * 3 * H * S;
-    if (need > t->rows_floats) {
-        if (t->rows) (void)hipFree(t->rows);         // (waits for the launches that read it)
-        t->rows = nullptr; t->rows_floats = 0;
-        if (hipMalloc(&t->rows, need * sizeof(float)) != hipSuccess) return t->fail("loco_clipseg_preprocess: hipMalloc failed");
-        t->rows_floats = need;
-    }
+    if (!EncoderBase::grow(&t->rows, &t->rows_floats, need)) return t->fail("loco_clipseg_preprocess: hipMalloc failed");
     const dim3 gx(blocks256((long)need)), gy(blocks256((long)n * 3 * S * S));
     if (is_u8) {
         hipLaunchKernelGGL(seg_resize_x_kernel<true>, gx, dim3(256), 0, st, frames_dev, n, H, W, S, resample, t->rows);

@@ -7,10 +7,11 @@
 // [D][Tp] tensor, token column i * T + t (t = 0: the class token, t = 1 + row * G + col: a patch), Tp = n * T rounded up to
 // 16; the padding columns are zero-fed and stay independent of the real ones.  The patch projection, the packed q | k | v
 // operator, out_proj, fc1 (with its activation), fc2 and visual_projection are launch_gemm_fixed, the LayerNorms xfmr.hip's
-// launch_ln_fwd.  New here: the batched patch gather, the class / position add, the attention (the scheme of samenc.hip's
-// sam_attn_kernel without its bias tables, written again in this unit: samenc.hip is untouched), the class column gather,
-// the transposes of the results, and the two resize passes of the preprocessing.  Every kernel computes a token column
-// from the columns of its own image alone, in a fixed order: an image's rows are bit-identical whatever n and its position.
+// launch_ln_fwd; the layer's parameters and its seven launches are encoder_common.h's add_clip_layer / pre_ln_block, as in
+// the text tower.  The batched patch gather, the attention (the streamed kernel samenc.hip runs with its bias tables, here
+// without them) and the transposes of the results are encoder_kernels.hip's.  New here: the class / position add, the class
+// column gather and the two resize passes of the preprocessing.  Every kernel computes a token column from the columns of
+// its own image alone, in a fixed order: an image's rows are bit-identical whatever n and its position.
 //
 // The cotangent pass (loco_clipvis_enable_grad / _encode_vjp: the pixel gradient of a CLIP score) walks the same
 // launches backwards on records the forward keeps per layer: every W^T is launch_gemm_fixed on the forward's weight with A's
@@ -20,8 +21,6 @@
 #include "encoder_common.h"
 
 #include <cmath>
-
-struct ClipVisLayer { float *ln1_g, *ln1_b, *wqkv, *bqkv, *wo, *bo, *ln2_g, *ln2_b, *w1, *b1, *w2, *b2; };
 
 // What the cotangent pass keeps of a layer: its input h and the residual stream after the attention (h_mid), both [D][Tp];
 // qkv [3 D][Tp]; the attention output [D][Tp]; the statistics of the two LayerNorms [2][Tp]; the softmax row max and row sum
@@ -34,7 +33,7 @@ struct loco_clipvis : loco::EncoderBase {
     long frows = 0;                                // rows of f: max(mlp_dim, 3 patch^2)
     float *cls = nullptr, *patch_w = nullptr, *pos = nullptr, *pre_g = nullptr, *pre_b = nullptr, *post_g = nullptr,
           *post_b = nullptr, *proj = nullptr;
-    std::vector<ClipVisLayer> layer;
+    std::vector<loco::PreLnLayer> layer;
     float *h = nullptr, *x = nullptr, *qkv = nullptr, *attn = nullptr, *f = nullptr, *stats = nullptr, *pool = nullptr,
           *pooln = nullptr, *emb = nullptr;
     float* rows = nullptr;                         // the preprocessing's horizontally resized rows, grown on demand
@@ -58,22 +57,6 @@ struct loco_clipvis : loco::EncoderBase {
 namespace loco {
 namespace {
 
-constexpr int CV_THREADS = 256, CV_WAVES = CV_THREADS / 64, CV_QW = 4, CV_QB = CV_WAVES * CV_QW, CV_KC = 64;
-
-// P[(ci ps + ky) ps + kx][i T + 1 + ty G + tx] = pix[i][ci][ty ps + ky][tx ps + kx]; 0 in the class and the padding columns
-__global__ __launch_bounds__(256) void clipvis_patch_kernel(const float* pix, int S, int ps, int G, int T, int nT, int Tp, float* P) {
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= (long)3 * ps * ps * Tp) return;
-    const int r = (int)(e / Tp), col = (int)(e % Tp);
-    float v = 0.f;
-    const int i = col / T, t = col % T;
-    if (col < nT && t > 0) {
-        const int ci = r / (ps * ps), ky = (r / ps) % ps, kx = r % ps, ty = (t - 1) / G, tx = (t - 1) % G;
-        v = pix[(((long)i * 3 + ci) * S + ty * ps + ky) * S + tx * ps + kx];
-    }
-    P[e] = v;
-}
-
 // h[c][i T + t] += pos[t][c] (+ cls[c] at t = 0) for the real columns
 __global__ __launch_bounds__(256) void clipvis_embed_kernel(float* h, const float* cls, const float* pos, int D, int T, int nT, int Tp) {
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
@@ -84,105 +67,8 @@ __global__ __launch_bounds__(256) void clipvis_embed_kernel(float* h, const floa
     h[(long)c * Tp + col] = v;
 }
 
-// parts of clipvis_attn_kernel's LDS start at multiples of 4 floats (float4 reads of Qs and Ps)
-__host__ __device__ constexpr size_t cv_r4(size_t n) { return (n + 3) / 4 * 4; }
-
-// One workgroup per (query block of 16, head, image): the T keys of the image are streamed in order in chunks of 64 -- K
-// [hd][64] and V [64][hd + 1] of the chunk in LDS.  A wave owns 4 queries; lane j scores key k0 + j against them,
-// (q scale) . k, then the running max / sum update (fp32, max and sum over the chunk by shuffles), then lane c (and c + 64)
-// adds P V of the chunk to its output channel in key order.  qkv: [3 D][ld] = q | k | v channel rows, out [D][ld]; hd <= 128.
-// KEEP: the row max and the row sum of every query go to ml [2][heads][ld] for the cotangent pass; the arithmetic is the same.
-template <bool KEEP>
-__global__ __launch_bounds__(CV_THREADS) void clipvis_attn_kernel(const float* qkv, long ld, int D, int hd, int T, float scale, float* out,
-                                                                  float* ml) {
-    extern __shared__ __align__(16) float cv_sm[];
-    const int hdp = hd + 1;
-    float* Ks = cv_sm;                                     // [hd][64]
-    float* Vs = Ks + cv_r4(hd * CV_KC);                    // [64][hd + 1]
-    float* Qs = Vs + cv_r4(CV_KC * hdp);                   // [hd][16]
-    float* Ps = Qs + cv_r4(hd * CV_QB);                    // [waves][64][4]
-    const int qb = blockIdx.x, h = blockIdx.y, img = blockIdx.z;
-    const long col0 = (long)img * T;
-    const int q0 = qb * CV_QB;
-    const float* q = qkv + (long)(h * hd) * ld + col0;
-    const float* k = qkv + (long)(D + h * hd) * ld + col0;
-    const float* v = qkv + (long)(2 * D + h * hd) * ld + col0;
-    for (int e = threadIdx.x; e < hd * CV_QB; e += CV_THREADS) {
-        const int c = e / CV_QB, ql = min(q0 + e % CV_QB, T - 1);
-        Qs[e] = q[(long)c * ld + ql] * scale;
-    }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int c0 = lane < hd ? lane : 0, c1 = lane + 64 < hd ? lane + 64 : 0;
-    float* pw = Ps + wv * (CV_KC * CV_QW);
-    float m[CV_QW], l[CV_QW], o0[CV_QW], o1[CV_QW];
-#pragma unroll
-    for (int u = 0; u < CV_QW; ++u) { m[u] = -INFINITY; l[u] = 0.f; o0[u] = 0.f; o1[u] = 0.f; }
-    for (int k0 = 0; k0 < T; k0 += CV_KC) {
-        __syncthreads();
-        for (int e = threadIdx.x; e < hd * CV_KC; e += CV_THREADS) {
-            const int c = e / CV_KC, j = e % CV_KC, kj = k0 + j;
-            const bool ok = kj < T;
-            Ks[e] = ok ? k[(long)c * ld + kj] : 0.f;
-            Vs[j * hdp + c] = ok ? v[(long)c * ld + kj] : 0.f;
-        }
-        __syncthreads();
-        const bool valid = k0 + lane < T;
-        float s[CV_QW];
-#pragma unroll
-        for (int u = 0; u < CV_QW; ++u) s[u] = 0.f;
-        for (int c = 0; c < hd; ++c) {
-            const float kv = Ks[c * CV_KC + lane];
-            const float4 qv = *reinterpret_cast<const float4*>(Qs + c * CV_QB + wv * CV_QW);
-            s[0] = fmaf(qv.x, kv, s[0]);
-            s[1] = fmaf(qv.y, kv, s[1]);
-            s[2] = fmaf(qv.z, kv, s[2]);
-            s[3] = fmaf(qv.w, kv, s[3]);
-        }
-#pragma unroll
-        for (int u = 0; u < CV_QW; ++u) {
-            const float sc = valid ? s[u] : -INFINITY;     // key k0 is always live: the chunk's max is finite
-            const float mn = fmaxf(m[u], wave_max(sc));
-            const float corr = expf(m[u] - mn);
-            const float p = valid ? expf(sc - mn) : 0.f;
-            l[u] = l[u] * corr + wave_sum(p);
-            o0[u] *= corr;
-            o1[u] *= corr;
-            m[u] = mn;
-            pw[lane * CV_QW + u] = p;
-        }
-        __syncthreads();
-        for (int j = 0; j < CV_KC; ++j) {
-            const float4 pv = *reinterpret_cast<const float4*>(pw + j * CV_QW);
-            const float v0 = Vs[j * hdp + c0];
-            o0[0] = fmaf(pv.x, v0, o0[0]);
-            o0[1] = fmaf(pv.y, v0, o0[1]);
-            o0[2] = fmaf(pv.z, v0, o0[2]);
-            o0[3] = fmaf(pv.w, v0, o0[3]);
-            if (hd > 64) {                                 // uniform
-                const float v1 = Vs[j * hdp + c1];
-                o1[0] = fmaf(pv.x, v1, o1[0]);
-                o1[1] = fmaf(pv.y, v1, o1[1]);
-                o1[2] = fmaf(pv.z, v1, o1[2]);
-                o1[3] = fmaf(pv.w, v1, o1[3]);
-            }
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < CV_QW; ++u) {
-        const int ql = q0 + wv * CV_QW + u;
-        if (ql >= T) continue;
-        const float inv = 1.0f / l[u];
-        if (lane < hd) out[(long)(h * hd + lane) * ld + col0 + ql] = o0[u] * inv;
-        if (lane + 64 < hd) out[(long)(h * hd + lane + 64) * ld + col0 + ql] = o1[u] * inv;
-        if (KEEP && lane == 0) {
-            ml[(long)h * ld + col0 + ql] = m[u];
-            ml[(long)(gridDim.y + h) * ld + col0 + ql] = l[u];
-        }
-    }
-}
-
 // ---- cotangent of the attention.  Given g_o, the kept q, k, v, o and the row max m / row sum l of the forward kernel:
-// P_ij = exp((q_i scale) . k_j - m_i) / l_i (the forward's own chain of FMAs, so the same scores), delta_i = <g_o_i, o_i>,
+// P_ij = exp((q_i scale) . k_j - m_i) / l_i (enc_attn_kernel's own chain of FMAs, so the same scores), delta_i = <g_o_i, o_i>,
 // dS = P o (g_o v^T - delta), dQ = scale dS k, dK = scale dS^T q, dV = P^T g_o.  Two kernels, both in the scheme of the forward
 // one (4 rows per wave, chunks of the other side streamed through LDS in order, fp32 FMAs), no atomics: every output element
 // has one owner that sums in a fixed order, over the columns of its own image alone.
@@ -192,43 +78,43 @@ __global__ __launch_bounds__(CV_THREADS) void clipvis_attn_kernel(const float* q
 //   * the chunk is 64 tokens where the carve-up fits the 64 KiB the forward kernel allows itself, else 32 (head widths above
 //     95 / 88; lanes 32 .. 63 then idle in the score phase).  Two streamed tensors and two owned ones are resident, against the
 //     forward's two and one.
-constexpr int CV_COT_ROWS = CV_QB;     // queries (dQ kernel) / keys (dK, dV kernel) a workgroup owns
+constexpr int CV_COT_ROWS = ENC_ATTN_QB;     // queries (dQ kernel) / keys (dK, dV kernel) a workgroup owns
 
 // dQ and delta: one workgroup per (query block of 16, head, image), keys and values streamed in order
 template <int KC>
-__global__ __launch_bounds__(CV_THREADS) void clipvis_attn_cot_q_kernel(const float* qkv, const float* o, const float* go, const float* ml,
+__global__ __launch_bounds__(ENC_ATTN_THREADS) void clipvis_attn_cot_q_kernel(const float* qkv, const float* o, const float* go, const float* ml,
                                                                         long ld, int D, int hd, int T, float scale, float* gqkv,
                                                                         float* delta) {
     extern __shared__ __align__(16) float cv_sm[];
     const int hdp = hd + 1;
     float* Kt = cv_sm;                                     // [KC][hd + 1]
-    float* Vt = Kt + cv_r4(KC * hdp);                      // [KC][hd + 1]
-    float* Qs = Vt + cv_r4(KC * hdp);                      // [hd][16], scaled
-    float* Gs = Qs + cv_r4(hd * CV_QB);                    // [hd][16]
-    float* Ps = Gs + cv_r4(hd * CV_QB);                    // [waves][64][4]: dS
+    float* Vt = Kt + enc_r4(KC * hdp);                      // [KC][hd + 1]
+    float* Qs = Vt + enc_r4(KC * hdp);                      // [hd][16], scaled
+    float* Gs = Qs + enc_r4(hd * ENC_ATTN_QB);                    // [hd][16]
+    float* Ps = Gs + enc_r4(hd * ENC_ATTN_QB);                    // [waves][64][4]: dS
     const int qb = blockIdx.x, h = blockIdx.y, img = blockIdx.z, heads = gridDim.y;
     const long col0 = (long)img * T;
-    const int q0 = qb * CV_QB;
+    const int q0 = qb * ENC_ATTN_QB;
     const float* q = qkv + (long)(h * hd) * ld + col0;
     const float* k = qkv + (long)(D + h * hd) * ld + col0;
     const float* v = qkv + (long)(2 * D + h * hd) * ld + col0;
     const float* op = o + (long)(h * hd) * ld + col0;
     const float* gp = go + (long)(h * hd) * ld + col0;
-    for (int e = threadIdx.x; e < hd * CV_QB; e += CV_THREADS) {
-        const int c = e / CV_QB, ql = min(q0 + e % CV_QB, T - 1);
+    for (int e = threadIdx.x; e < hd * ENC_ATTN_QB; e += ENC_ATTN_THREADS) {
+        const int c = e / ENC_ATTN_QB, ql = min(q0 + e % ENC_ATTN_QB, T - 1);
         Qs[e] = q[(long)c * ld + ql] * scale;
         Gs[e] = gp[(long)c * ld + ql];
     }
     __syncthreads();
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int c0 = lane < hd ? lane : 0, c1 = lane + 64 < hd ? lane + 64 : 0;
-    float* pw = Ps + wv * (64 * CV_QW);
-    float mq[CV_QW], il[CV_QW], dl[CV_QW], a0[CV_QW], a1[CV_QW];
+    float* pw = Ps + wv * (64 * ENC_ATTN_QW);
+    float mq[ENC_ATTN_QW], il[ENC_ATTN_QW], dl[ENC_ATTN_QW], a0[ENC_ATTN_QW], a1[ENC_ATTN_QW];
 #pragma unroll
-    for (int u = 0; u < CV_QW; ++u) {
-        const int qr = q0 + wv * CV_QW + u, ql = min(qr, T - 1);
+    for (int u = 0; u < ENC_ATTN_QW; ++u) {
+        const int qr = q0 + wv * ENC_ATTN_QW + u, ql = min(qr, T - 1);
         float a = 0.f;
-        for (int c = lane; c < hd; c += 64) a = fmaf(Gs[c * CV_QB + wv * CV_QW + u], op[(long)c * ld + ql], a);
+        for (int c = lane; c < hd; c += 64) a = fmaf(Gs[c * ENC_ATTN_QB + wv * ENC_ATTN_QW + u], op[(long)c * ld + ql], a);
         dl[u] = wave_sum(a);
         mq[u] = ml[(long)h * ld + col0 + ql];
         il[u] = 1.0f / ml[(long)(heads + h) * ld + col0 + ql];
@@ -237,7 +123,7 @@ __global__ __launch_bounds__(CV_THREADS) void clipvis_attn_cot_q_kernel(const fl
     }
     for (int k0 = 0; k0 < T; k0 += KC) {
         __syncthreads();
-        for (int e = threadIdx.x; e < hd * KC; e += CV_THREADS) {
+        for (int e = threadIdx.x; e < hd * KC; e += ENC_ATTN_THREADS) {
             const int c = e / KC, j = e % KC, kj = k0 + j;
             const bool ok = kj < T;
             Kt[j * hdp + c] = ok ? k[(long)c * ld + kj] : 0.f;
@@ -246,13 +132,13 @@ __global__ __launch_bounds__(CV_THREADS) void clipvis_attn_cot_q_kernel(const fl
         __syncthreads();
         const bool valid = lane < KC && k0 + lane < T;
         const int jl = lane < KC ? lane : 0;
-        float s[CV_QW], dp[CV_QW];
+        float s[ENC_ATTN_QW], dp[ENC_ATTN_QW];
 #pragma unroll
-        for (int u = 0; u < CV_QW; ++u) { s[u] = 0.f; dp[u] = 0.f; }
+        for (int u = 0; u < ENC_ATTN_QW; ++u) { s[u] = 0.f; dp[u] = 0.f; }
         for (int c = 0; c < hd; ++c) {
             const float kv = Kt[jl * hdp + c], vv = Vt[jl * hdp + c];
-            const float4 qv = *reinterpret_cast<const float4*>(Qs + c * CV_QB + wv * CV_QW);
-            const float4 gv = *reinterpret_cast<const float4*>(Gs + c * CV_QB + wv * CV_QW);
+            const float4 qv = *reinterpret_cast<const float4*>(Qs + c * ENC_ATTN_QB + wv * ENC_ATTN_QW);
+            const float4 gv = *reinterpret_cast<const float4*>(Gs + c * ENC_ATTN_QB + wv * ENC_ATTN_QW);
             s[0] = fmaf(qv.x, kv, s[0]);
             s[1] = fmaf(qv.y, kv, s[1]);
             s[2] = fmaf(qv.z, kv, s[2]);
@@ -263,13 +149,13 @@ __global__ __launch_bounds__(CV_THREADS) void clipvis_attn_cot_q_kernel(const fl
             dp[3] = fmaf(gv.w, vv, dp[3]);
         }
 #pragma unroll
-        for (int u = 0; u < CV_QW; ++u) {
+        for (int u = 0; u < ENC_ATTN_QW; ++u) {
             const float p = valid ? expf(s[u] - mq[u]) * il[u] : 0.f;
-            pw[lane * CV_QW + u] = p * (dp[u] - dl[u]);
+            pw[lane * ENC_ATTN_QW + u] = p * (dp[u] - dl[u]);
         }
         __syncthreads();
         for (int j = 0; j < KC; ++j) {
-            const float4 dv = *reinterpret_cast<const float4*>(pw + j * CV_QW);
+            const float4 dv = *reinterpret_cast<const float4*>(pw + j * ENC_ATTN_QW);
             const float k0v = Kt[j * hdp + c0];
             a0[0] = fmaf(dv.x, k0v, a0[0]);
             a0[1] = fmaf(dv.y, k0v, a0[1]);
@@ -285,8 +171,8 @@ __global__ __launch_bounds__(CV_THREADS) void clipvis_attn_cot_q_kernel(const fl
         }
     }
 #pragma unroll
-    for (int u = 0; u < CV_QW; ++u) {
-        const int ql = q0 + wv * CV_QW + u;
+    for (int u = 0; u < ENC_ATTN_QW; ++u) {
+        const int ql = q0 + wv * ENC_ATTN_QW + u;
         if (ql >= T) continue;
         if (lane < hd) gqkv[(long)(h * hd + lane) * ld + col0 + ql] = a0[u] * scale;
         if (lane + 64 < hd) gqkv[(long)(h * hd + lane + 64) * ld + col0 + ql] = a1[u] * scale;
@@ -295,17 +181,17 @@ __global__ __launch_bounds__(CV_THREADS) void clipvis_attn_cot_q_kernel(const fl
 
 // dK and dV: one workgroup per (key block of 16, head, image), the queries (q scaled, g_o, m, l, delta) streamed in order
 template <int QC>
-__global__ __launch_bounds__(CV_THREADS) void clipvis_attn_cot_kv_kernel(const float* qkv, const float* go, const float* ml,
+__global__ __launch_bounds__(ENC_ATTN_THREADS) void clipvis_attn_cot_kv_kernel(const float* qkv, const float* go, const float* ml,
                                                                          const float* delta, long ld, int D, int hd, int T, float scale,
                                                                          float* gqkv) {
     extern __shared__ __align__(16) float cv_sm[];
     const int hdp = hd + 1;
     float* Qt = cv_sm;                                     // [QC][hd + 1], scaled
-    float* Gt = Qt + cv_r4(QC * hdp);                      // [QC][hd + 1]
-    float* Ks = Gt + cv_r4(QC * hdp);                      // [hd][16]
-    float* Vs = Ks + cv_r4(hd * CV_COT_ROWS);              // [hd][16]
-    float* Ps = Vs + cv_r4(hd * CV_COT_ROWS);              // [waves][64][4]: P
-    float* Ds = Ps + CV_WAVES * 64 * CV_QW;                // [waves][64][4]: dS
+    float* Gt = Qt + enc_r4(QC * hdp);                      // [QC][hd + 1]
+    float* Ks = Gt + enc_r4(QC * hdp);                      // [hd][16]
+    float* Vs = Ks + enc_r4(hd * CV_COT_ROWS);              // [hd][16]
+    float* Ps = Vs + enc_r4(hd * CV_COT_ROWS);              // [waves][64][4]: P
+    float* Ds = Ps + ENC_ATTN_WAVES * 64 * ENC_ATTN_QW;                // [waves][64][4]: dS
     const int kb = blockIdx.x, h = blockIdx.y, img = blockIdx.z, heads = gridDim.y;
     const long col0 = (long)img * T;
     const int kb0 = kb * CV_COT_ROWS;
@@ -313,21 +199,21 @@ __global__ __launch_bounds__(CV_THREADS) void clipvis_attn_cot_kv_kernel(const f
     const float* k = qkv + (long)(D + h * hd) * ld + col0;
     const float* v = qkv + (long)(2 * D + h * hd) * ld + col0;
     const float* gp = go + (long)(h * hd) * ld + col0;
-    for (int e = threadIdx.x; e < hd * CV_COT_ROWS; e += CV_THREADS) {
+    for (int e = threadIdx.x; e < hd * CV_COT_ROWS; e += ENC_ATTN_THREADS) {
         const int c = e / CV_COT_ROWS, kl = min(kb0 + e % CV_COT_ROWS, T - 1);
         Ks[e] = k[(long)c * ld + kl];
         Vs[e] = v[(long)c * ld + kl];
     }
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int c0 = lane < hd ? lane : 0, c1 = lane + 64 < hd ? lane + 64 : 0;
-    float* pw = Ps + wv * (64 * CV_QW);
-    float* dw = Ds + wv * (64 * CV_QW);
-    float dk0[CV_QW], dk1[CV_QW], dv0[CV_QW], dv1[CV_QW];
+    float* pw = Ps + wv * (64 * ENC_ATTN_QW);
+    float* dw = Ds + wv * (64 * ENC_ATTN_QW);
+    float dk0[ENC_ATTN_QW], dk1[ENC_ATTN_QW], dv0[ENC_ATTN_QW], dv1[ENC_ATTN_QW];
 #pragma unroll
-    for (int u = 0; u < CV_QW; ++u) { dk0[u] = 0.f; dk1[u] = 0.f; dv0[u] = 0.f; dv1[u] = 0.f; }
+    for (int u = 0; u < ENC_ATTN_QW; ++u) { dk0[u] = 0.f; dk1[u] = 0.f; dv0[u] = 0.f; dv1[u] = 0.f; }
     for (int i0 = 0; i0 < T; i0 += QC) {
         __syncthreads();
-        for (int e = threadIdx.x; e < hd * QC; e += CV_THREADS) {
+        for (int e = threadIdx.x; e < hd * QC; e += ENC_ATTN_THREADS) {
             const int c = e / QC, i = e % QC, qi = i0 + i;
             const bool ok = qi < T;
             Qt[i * hdp + c] = ok ? q[(long)c * ld + qi] * scale : 0.f;
@@ -338,13 +224,13 @@ __global__ __launch_bounds__(CV_THREADS) void clipvis_attn_cot_kv_kernel(const f
         const int il = lane < QC ? lane : 0, qi = valid ? i0 + lane : 0;
         const float mi = ml[(long)h * ld + col0 + qi], inv = 1.0f / ml[(long)(heads + h) * ld + col0 + qi];
         const float di = delta[(long)h * ld + col0 + qi];
-        float s[CV_QW], dp[CV_QW];
+        float s[ENC_ATTN_QW], dp[ENC_ATTN_QW];
 #pragma unroll
-        for (int u = 0; u < CV_QW; ++u) { s[u] = 0.f; dp[u] = 0.f; }
+        for (int u = 0; u < ENC_ATTN_QW; ++u) { s[u] = 0.f; dp[u] = 0.f; }
         for (int c = 0; c < hd; ++c) {
             const float qv = Qt[il * hdp + c], gv = Gt[il * hdp + c];
-            const float4 kv = *reinterpret_cast<const float4*>(Ks + c * CV_COT_ROWS + wv * CV_QW);
-            const float4 vv = *reinterpret_cast<const float4*>(Vs + c * CV_COT_ROWS + wv * CV_QW);
+            const float4 kv = *reinterpret_cast<const float4*>(Ks + c * CV_COT_ROWS + wv * ENC_ATTN_QW);
+            const float4 vv = *reinterpret_cast<const float4*>(Vs + c * CV_COT_ROWS + wv * ENC_ATTN_QW);
             s[0] = fmaf(qv, kv.x, s[0]);
             s[1] = fmaf(qv, kv.y, s[1]);
             s[2] = fmaf(qv, kv.z, s[2]);
@@ -355,15 +241,15 @@ __global__ __launch_bounds__(CV_THREADS) void clipvis_attn_cot_kv_kernel(const f
             dp[3] = fmaf(gv, vv.w, dp[3]);
         }
 #pragma unroll
-        for (int u = 0; u < CV_QW; ++u) {
+        for (int u = 0; u < ENC_ATTN_QW; ++u) {
             const float p = valid ? expf(s[u] - mi) * inv : 0.f;
-            pw[lane * CV_QW + u] = p;
-            dw[lane * CV_QW + u] = p * (dp[u] - di);
+            pw[lane * ENC_ATTN_QW + u] = p;
+            dw[lane * ENC_ATTN_QW + u] = p * (dp[u] - di);
         }
         __syncthreads();
         for (int i = 0; i < QC; ++i) {
-            const float4 pv = *reinterpret_cast<const float4*>(pw + i * CV_QW);
-            const float4 dv = *reinterpret_cast<const float4*>(dw + i * CV_QW);
+            const float4 pv = *reinterpret_cast<const float4*>(pw + i * ENC_ATTN_QW);
+            const float4 dv = *reinterpret_cast<const float4*>(dw + i * ENC_ATTN_QW);
             const float g0 = Gt[i * hdp + c0], q0v = Qt[i * hdp + c0];
             dv0[0] = fmaf(pv.x, g0, dv0[0]);
             dv0[1] = fmaf(pv.y, g0, dv0[1]);
@@ -388,8 +274,8 @@ __global__ __launch_bounds__(CV_THREADS) void clipvis_attn_cot_kv_kernel(const f
     }
     // q came in scaled: dk already carries the softmax scale
 #pragma unroll
-    for (int u = 0; u < CV_QW; ++u) {
-        const int kl = kb0 + wv * CV_QW + u;
+    for (int u = 0; u < ENC_ATTN_QW; ++u) {
+        const int kl = kb0 + wv * ENC_ATTN_QW + u;
         if (kl >= T) continue;
         if (lane < hd) {
             gqkv[(long)(D + h * hd + lane) * ld + col0 + kl] = dk0[u];
@@ -417,7 +303,7 @@ __global__ __launch_bounds__(256) void clipvis_dact_kernel(const float* f, long 
     gf[e] *= d;
 }
 
-// out[c][i] = in[i][c] for i < n, 0 in the padding columns (the transpose of clipvis_transpose_kernel)
+// out[c][i] = in[i][c] for i < n, 0 in the padding columns (the transpose of launch_enc_transpose)
 __global__ __launch_bounds__(256) void clipvis_columns_kernel(const float* in, int n, int C, int Np, float* out) {
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
     if (e >= (long)C * Np) return;
@@ -433,7 +319,7 @@ __global__ __launch_bounds__(256) void clipvis_pool_cot_kernel(const float* gpoo
     gh[e] = col < nT && col % T == 0 ? gpool[(long)c * Np + col / T] : 0.f;
 }
 
-// the adjoint of clipvis_patch_kernel: patches do not overlap, every pixel reads the one element it was copied to
+// the adjoint of launch_enc_patch (cls = 1): patches do not overlap, every pixel reads the one element it was copied to
 __global__ __launch_bounds__(256) void clipvis_patch_cot_kernel(const float* gP, int n, int S, int ps, int G, int T, int Tp, float* gpix) {
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
     if (e >= (long)n * 3 * S * S) return;
@@ -448,14 +334,6 @@ __global__ __launch_bounds__(256) void clipvis_pool_kernel(const float* h, int D
     if (e >= (long)D * Np) return;
     const int c = (int)(e / Np), i = (int)(e % Np);
     pool[e] = i < n ? h[(long)c * Tp + (long)i * T] : 0.f;
-}
-
-// out[col][c] = x[c][col] for the first `cols` columns of x [C][ld]
-__global__ __launch_bounds__(256) void clipvis_transpose_kernel(const float* x, int ld, int cols, int C, float* out) {
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= (long)cols * C) return;
-    const int col = (int)(e / C), c = (int)(e % C);
-    out[e] = x[(long)c * ld + col];
 }
 
 // ---- preprocessing: the antialiased bicubic resize of PIL / torch (a = -0.5) as two passes, then crop, / 255, normalise
@@ -626,13 +504,9 @@ using namespace loco;
 namespace {
 thread_local std::string g_clipvis_create_err;
 
-// the carve-up of clipvis_attn_kernel's LDS
-size_t clipvis_attn_lds_floats(int hd) {
-    return cv_r4((size_t)hd * CV_KC) + cv_r4((size_t)CV_KC * (hd + 1)) + cv_r4((size_t)hd * CV_QB) + (size_t)CV_WAVES * CV_KC * CV_QW;
-}
 // the carve-ups of the two cotangent kernels at a chunk of `kc` tokens; `tables`: 1 (dS) or 2 (P and dS) per-wave tables
 size_t clipvis_attn_cot_lds_floats(int hd, int kc, int tables) {
-    return 2 * cv_r4((size_t)kc * (hd + 1)) + 2 * cv_r4((size_t)hd * CV_QB) + (size_t)tables * CV_WAVES * 64 * CV_QW;
+    return 2 * enc_r4((size_t)kc * (hd + 1)) + 2 * enc_r4((size_t)hd * ENC_ATTN_QB) + (size_t)tables * ENC_ATTN_WAVES * 64 * ENC_ATTN_QW;
 }
 int clipvis_attn_cot_chunk(int hd, int tables) { return clipvis_attn_cot_lds_floats(hd, 64, tables) * sizeof(float) <= 65536 ? 64 : 32; }
 
@@ -667,38 +541,27 @@ int clipvis_check_windows(loco_clipvis* t, const char* fn, const int32_t* boxes_
 // patch projection, class / position add, pre_layrnorm: pixel_values -> xe (the embeddings) -> h0
 void clipvis_embed_fwd(loco_clipvis* t, const float* pixel_values, int n, int Tp, float* xe, float* h0, float* st_pre, hipStream_t st) {
     const loco_clipvis_cfg& c = t->cfg;
-    const int D = c.width, ps = c.patch_size, PK = 3 * ps * ps, G = t->G, T = t->T, nT = n * T;
-    hipLaunchKernelGGL(clipvis_patch_kernel, dim3(blocks256((long)PK * Tp)), dim3(256), 0, st, pixel_values, c.image_size, ps, G, T, nT, Tp,
-                       t->f);
+    const int D = c.width, ps = c.patch_size, PK = 3 * ps * ps, T = t->T, nT = n * T;
+    launch_enc_patch(pixel_values, n, c.image_size, ps, t->G, 1, Tp, t->f, st);
     launch_gemm_fixed(enc_linear(t->patch_w, nullptr, t->f, xe, nullptr, D, PK, Tp), GEMM_ACT_NONE, st);
     hipLaunchKernelGGL(clipvis_embed_kernel, dim3(blocks256((long)D * nT)), dim3(256), 0, st, xe, t->cls, t->pos, D, T, nT, Tp);
     launch_ln_fwd(xe, 0, 1, D, Tp, t->pre_g, t->pre_b, c.ln_eps, h0, 0, st_pre, 0, st);
 }
 
-// one block on the shared buffers (no records): t->h -> t->h
-void clipvis_layer_plain(loco_clipvis* t, const ClipVisLayer& ly, int n, int Tp, hipStream_t st) {
+// one block of the tower on n images: b's tensors, the row max / sum of the attention to ml unless null
+void clipvis_block(loco_clipvis* t, const PreLnLayer& ly, const PreLnBufs& b, float* ml, int n, int Tp, hipStream_t st) {
     const loco_clipvis_cfg& c = t->cfg;
-    const int D = c.width, F = c.mlp_dim, T = t->T, hd = t->hd;
+    const int D = c.width, T = t->T, hd = t->hd;
     const float scale = 1.0f / std::sqrt((float)hd);
-    const int gact = c.act == 0 ? GEMM_ACT_QUICK_GELU : GEMM_ACT_GELU;
-    const dim3 attn_grid((T + CV_QB - 1) / CV_QB, c.heads, n);
-    launch_ln_fwd(t->h, 0, 1, D, Tp, ly.ln1_g, ly.ln1_b, c.ln_eps, t->x, 0, t->stats, 0, st);
-    launch_gemm_fixed(enc_linear(ly.wqkv, ly.bqkv, t->x, t->qkv, nullptr, 3 * D, D, Tp), GEMM_ACT_NONE, st);
-    hipLaunchKernelGGL(clipvis_attn_kernel<false>, attn_grid, dim3(CV_THREADS), clipvis_attn_lds_floats(hd) * sizeof(float), st, t->qkv,
-                       (long)Tp, D, hd, T, scale, t->attn, (float*)nullptr);
-    launch_gemm_fixed(enc_linear(ly.wo, ly.bo, t->attn, t->h, t->h, D, D, Tp), GEMM_ACT_NONE, st);
-    launch_ln_fwd(t->h, 0, 1, D, Tp, ly.ln2_g, ly.ln2_b, c.ln_eps, t->x, 0, t->stats, 0, st);
-    launch_gemm_fixed(enc_linear(ly.w1, ly.b1, t->x, t->f, nullptr, F, D, Tp), gact, st);
-    launch_gemm_fixed(enc_linear(ly.w2, ly.b2, t->f, t->h, t->h, D, F, Tp), GEMM_ACT_NONE, st);
+    pre_ln_block(ly, b, D, c.mlp_dim, Tp, c.ln_eps, c.act == 0 ? GEMM_ACT_QUICK_GELU : GEMM_ACT_GELU, st, [&](const float* qkv, float* attn) {
+        launch_enc_attn({qkv, (long)Tp, D, hd, T, n, c.heads, scale, attn, nullptr, nullptr, 0, 0, ml}, st);
+    });
 }
+// the block in place on the shared buffers (no records): t->h -> t->h
+PreLnBufs clipvis_plain_bufs(loco_clipvis* t) { return {t->h, t->x, t->qkv, t->attn, t->h, t->f, t->h, t->stats, t->stats}; }
 
 int clipvis_grow_rows(loco_clipvis* t, const char* fn, size_t need) {
-    if (need <= t->rows_floats) return 0;
-    if (t->rows) (void)hipFree(t->rows);             // (waits for the launches that read it)
-    t->rows = nullptr; t->rows_floats = 0;
-    if (hipMalloc(&t->rows, need * sizeof(float)) != hipSuccess) return t->fail(std::string(fn) + ": hipMalloc failed");
-    t->rows_floats = need;
-    return 0;
+    return EncoderBase::grow(&t->rows, &t->rows_floats, need) ? 0 : t->fail(std::string(fn) + ": hipMalloc failed");
 }
 }  // namespace
 
@@ -715,7 +578,7 @@ int loco_clipvis_create(const loco_clipvis_cfg* cfg, int32_t device, int32_t max
         if (!(c.ln_eps > 0.f)) return "ln_eps must be positive";
         const long G = c.image_size / c.patch_size, hd = c.width / c.heads;
         if (hd > 128) return "head width > 128 (the attention kernel holds 2 channels per lane)";
-        if (clipvis_attn_lds_floats((int)hd) * sizeof(float) > 65536)
+        if (enc_attn_lds_floats((int)hd, 0) * sizeof(float) > 65536)
             return "head width too large for the attention kernel's LDS (64 KiB)";
         if ((1 + G * G) * (long)max_images > (1L << 24)) return "max_images x tokens > 2^24";
         return "";
@@ -728,8 +591,7 @@ int loco_clipvis_create(const loco_clipvis_cfg* cfg, int32_t device, int32_t max
         t.Nmax = (max_images + 15) / 16 * 16;
         const long D = c.width, F = c.mlp_dim, P = c.projection_dim, ps = c.patch_size, Tm = t.Tmax, Nm = t.Nmax;
         t.frows = std::max(F, 3 * ps * ps);
-        // names of transformers' CLIPVisionModelWithProjection without the `vision_model.` prefix; q / k / v land in one packed
-        // [3 D][D] operator
+        // names of transformers' CLIPVisionModelWithProjection without the `vision_model.` prefix
         ParamTable& pt = t.table;
         pt.add("embeddings.class_embedding", {D}, &t.cls);
         pt.add("embeddings.patch_embedding.weight", {D, 3, ps, ps}, &t.patch_w);
@@ -737,26 +599,7 @@ int loco_clipvis_create(const loco_clipvis_cfg* cfg, int32_t device, int32_t max
         pt.add("pre_layrnorm.weight", {D}, &t.pre_g);
         pt.add("pre_layrnorm.bias", {D}, &t.pre_b);
         t.layer.resize(c.layers);
-        for (int l = 0; l < c.layers; ++l) {
-            const std::string p = "encoder.layers." + std::to_string(l) + ".";
-            ClipVisLayer& ly = t.layer[l];
-            pt.add(p + "layer_norm1.weight", {D}, &ly.ln1_g);
-            pt.add(p + "layer_norm1.bias", {D}, &ly.ln1_b);
-            const size_t wq = pt.reserve((size_t)3 * D * D, &ly.wqkv), bq = pt.reserve(round64(3 * D), &ly.bqkv);
-            const char* qkvn[3] = {"q_proj", "k_proj", "v_proj"};
-            for (int j = 0; j < 3; ++j) {
-                pt.view(p + "self_attn." + qkvn[j] + ".weight", {D, D}, wq + (size_t)j * D * D);
-                pt.view(p + "self_attn." + qkvn[j] + ".bias", {D}, bq + (size_t)j * D);
-            }
-            pt.add(p + "self_attn.out_proj.weight", {D, D}, &ly.wo);
-            pt.add(p + "self_attn.out_proj.bias", {D}, &ly.bo);
-            pt.add(p + "layer_norm2.weight", {D}, &ly.ln2_g);
-            pt.add(p + "layer_norm2.bias", {D}, &ly.ln2_b);
-            pt.add(p + "mlp.fc1.weight", {F, D}, &ly.w1);
-            pt.add(p + "mlp.fc1.bias", {F}, &ly.b1);
-            pt.add(p + "mlp.fc2.weight", {D, F}, &ly.w2);
-            pt.add(p + "mlp.fc2.bias", {D}, &ly.b2);
-        }
+        for (int l = 0; l < c.layers; ++l) add_clip_layer(pt, "encoder.layers." + std::to_string(l) + ".", D, F, t.layer[l]);
         pt.add("post_layernorm.weight", {D}, &t.post_g);
         pt.add("post_layernorm.bias", {D}, &t.post_b);
         pt.add("visual_projection.weight", {P, D}, &t.proj);
@@ -788,12 +631,7 @@ int loco_clipvis_preprocess(loco_clipvis* t, const uint8_t* frames_dev, int32_t 
     DeviceGuard dg(t->device);
     hipStream_t st = (hipStream_t)stream;
     const size_t need = (size_t)n * 3 * H * S;
-    if (need > t->rows_floats) {
-        if (t->rows) (void)hipFree(t->rows);         // (waits for the launches that read it)
-        t->rows = nullptr; t->rows_floats = 0;
-        if (hipMalloc(&t->rows, need * sizeof(float)) != hipSuccess) return t->fail("loco_clipvis_preprocess: hipMalloc failed");
-        t->rows_floats = need;
-    }
+    if (clipvis_grow_rows(t, "loco_clipvis_preprocess", need)) return -1;
     hipLaunchKernelGGL(clipvis_resize_x_kernel, dim3(blocks256((long)need)), dim3(256), 0, st, frames_dev, n, H, W, Wn, left, S, t->rows);
     hipLaunchKernelGGL(clipvis_resize_y_kernel, dim3(blocks256((long)n * 3 * S * S)), dim3(256), 0, st, t->rows, n, H, Hn, top, S,
                        t->cfg.image_mean[0], t->cfg.image_mean[1], t->cfg.image_mean[2], t->cfg.image_std[0], t->cfg.image_std[1],
@@ -812,41 +650,29 @@ int loco_clipvis_encode(loco_clipvis* t, const float* pixel_values, int32_t n, f
     DeviceGuard dg(t->device);
     hipStream_t st = (hipStream_t)stream;
     const loco_clipvis_cfg& c = t->cfg;
-    const int D = c.width, F = c.mlp_dim, P = c.projection_dim;
-    const int T = t->T, hd = t->hd, nT = n * T, Tp = (nT + 15) / 16 * 16, Np = (n + 15) / 16 * 16;
-    const float scale = 1.0f / std::sqrt((float)hd);
-    const int gact = c.act == 0 ? GEMM_ACT_QUICK_GELU : GEMM_ACT_GELU;
+    const int D = c.width, P = c.projection_dim;
+    const int T = t->T, nT = n * T, Tp = (nT + 15) / 16 * 16, Np = (n + 15) / 16 * 16;
     // with grad enabled the same launches write the layer's tensors into its record instead of the shared buffers
     const bool keep = t->grad;
     if (keep) t->kept_n = 0;
-    const size_t attn_lds = clipvis_attn_lds_floats(hd) * sizeof(float);
-    const dim3 attn_grid((T + CV_QB - 1) / CV_QB, c.heads, n);
     float* xe = keep ? t->xemb : t->x;
     clipvis_embed_fwd(t, pixel_values, n, Tp, xe, keep ? t->rec[0].h_in : t->h, keep ? t->st_pre : t->stats, st);
     for (size_t l = 0; l < t->layer.size(); ++l) {
-        const ClipVisLayer& ly = t->layer[l];
         if (!keep) {
-            clipvis_layer_plain(t, ly, n, Tp, st);
+            clipvis_block(t, t->layer[l], clipvis_plain_bufs(t), nullptr, n, Tp, st);
             continue;
         }
         const ClipVisRec& r = t->rec[l];
         float* hout = l + 1 < t->layer.size() ? t->rec[l + 1].h_in : t->h;
-        launch_ln_fwd(r.h_in, 0, 1, D, Tp, ly.ln1_g, ly.ln1_b, c.ln_eps, t->x, 0, r.st1, 0, st);
-        launch_gemm_fixed(enc_linear(ly.wqkv, ly.bqkv, t->x, r.qkv, nullptr, 3 * D, D, Tp), GEMM_ACT_NONE, st);
-        hipLaunchKernelGGL(clipvis_attn_kernel<true>, attn_grid, dim3(CV_THREADS), attn_lds, st, r.qkv, (long)Tp, D, hd, T, scale, r.attn,
-                           r.ml);
-        launch_gemm_fixed(enc_linear(ly.wo, ly.bo, r.attn, r.h_mid, r.h_in, D, D, Tp), GEMM_ACT_NONE, st);
-        launch_ln_fwd(r.h_mid, 0, 1, D, Tp, ly.ln2_g, ly.ln2_b, c.ln_eps, t->x, 0, r.st2, 0, st);
-        launch_gemm_fixed(enc_linear(ly.w1, ly.b1, t->x, t->f, nullptr, F, D, Tp), gact, st);
-        launch_gemm_fixed(enc_linear(ly.w2, ly.b2, t->f, hout, r.h_mid, D, F, Tp), GEMM_ACT_NONE, st);
+        clipvis_block(t, t->layer[l], {r.h_in, t->x, r.qkv, r.attn, r.h_mid, t->f, hout, r.st1, r.st2}, r.ml, n, Tp, st);
     }
-    if (hidden_dev) hipLaunchKernelGGL(clipvis_transpose_kernel, dim3(blocks256((long)nT * D)), dim3(256), 0, st, t->h, Tp, nT, D, hidden_dev);
+    if (hidden_dev) launch_enc_transpose(t->h, Tp, nT, D, hidden_dev, st);
     // pooling and heads: class columns -> post_layernorm -> visual_projection
     hipLaunchKernelGGL(clipvis_pool_kernel, dim3(blocks256((long)D * Np)), dim3(256), 0, st, t->h, D, T, Tp, n, Np, t->pool);
     launch_ln_fwd(t->pool, 0, 1, D, Np, t->post_g, t->post_b, c.ln_eps, t->pooln, 0, keep ? t->st_post : t->stats, 0, st);
-    if (pooled_dev) hipLaunchKernelGGL(clipvis_transpose_kernel, dim3(blocks256((long)n * D)), dim3(256), 0, st, t->pooln, Np, n, D, pooled_dev);
+    if (pooled_dev) launch_enc_transpose(t->pooln, Np, n, D, pooled_dev, st);
     launch_gemm_fixed(enc_linear(t->proj, nullptr, t->pooln, t->emb, nullptr, P, D, Np), GEMM_ACT_NONE, st);
-    hipLaunchKernelGGL(clipvis_transpose_kernel, dim3(blocks256((long)n * P)), dim3(256), 0, st, t->emb, Np, n, P, embeds_dev);
+    launch_enc_transpose(t->emb, Np, n, P, embeds_dev, st);
     if (hipGetLastError() != hipSuccess) return t->fail("loco_clipvis_encode: kernel launch failed");
     if (keep) t->kept_n = n;
     return 0;
@@ -872,10 +698,9 @@ int loco_clipvis_encode_taps(loco_clipvis* t, const float* pixel_values, int32_t
     clipvis_embed_fwd(t, pixel_values, n, Tp, t->x, t->h, t->stats, st);
     int j = 0;
     for (int l = 0; l <= layers[n_taps - 1]; ++l) {
-        clipvis_layer_plain(t, t->layer[l], n, Tp, st);
+        clipvis_block(t, t->layer[l], clipvis_plain_bufs(t), nullptr, n, Tp, st);
         if (l == layers[j]) {
-            hipLaunchKernelGGL(clipvis_transpose_kernel, dim3(blocks256((long)nT * D)), dim3(256), 0, st, t->h, Tp, nT, D,
-                               taps_dev + (size_t)j * nT * D);
+            launch_enc_transpose(t->h, Tp, nT, D, taps_dev + (size_t)j * nT * D, st);
             ++j;
         }
     }
@@ -952,7 +777,7 @@ int loco_clipvis_encode_vjp(loco_clipvis* t, const float* g_embeds_dev, int32_t 
     launch_ln_cot(t->gpn, 0, t->pool, t->st_post, 1, D, Np, t->post_g, nullptr, 0, t->gpool, 0, st);
     hipLaunchKernelGGL(clipvis_pool_cot_kernel, dim3(blocks256((long)D * Tp)), dim3(256), 0, st, t->gpool, D, T, Tp, nT, Np, t->gA);
     for (int l = (int)t->layer.size() - 1; l >= 0; --l) {
-        const ClipVisLayer& ly = t->layer[l];
+        const PreLnLayer& ly = t->layer[l];
         const ClipVisRec& r = t->rec[l];
         // the MLP: its input and the fc1 pre-activation are computed again from h_mid
         launch_ln_fwd(r.h_mid, 0, 1, D, Tp, ly.ln2_g, ly.ln2_b, c.ln_eps, t->x, 0, t->stats, 0, st);
@@ -964,17 +789,17 @@ int loco_clipvis_encode_vjp(loco_clipvis* t, const float* g_embeds_dev, int32_t 
         // the attention
         launch_gemm_fixed(enc_linear_t(ly.wo, t->gC, t->gB, D, D, Tp), GEMM_ACT_NONE, st);
         if (kcq == 64)
-            hipLaunchKernelGGL(clipvis_attn_cot_q_kernel<64>, agrid, dim3(CV_THREADS), ldsq, st, r.qkv, r.attn, t->gB, r.ml, (long)Tp, D, hd, T,
+            hipLaunchKernelGGL(clipvis_attn_cot_q_kernel<64>, agrid, dim3(ENC_ATTN_THREADS), ldsq, st, r.qkv, r.attn, t->gB, r.ml, (long)Tp, D, hd, T,
                                scale, t->gqkv, t->delta);
         else
-            hipLaunchKernelGGL(clipvis_attn_cot_q_kernel<32>, agrid, dim3(CV_THREADS), ldsq, st, r.qkv, r.attn, t->gB, r.ml, (long)Tp, D, hd, T,
+            hipLaunchKernelGGL(clipvis_attn_cot_q_kernel<32>, agrid, dim3(ENC_ATTN_THREADS), ldsq, st, r.qkv, r.attn, t->gB, r.ml, (long)Tp, D, hd, T,
                                scale, t->gqkv, t->delta);
         if (kckv == 64)
-            hipLaunchKernelGGL(clipvis_attn_cot_kv_kernel<64>, agrid, dim3(CV_THREADS), ldskv, st, r.qkv, t->gB, r.ml, t->delta, (long)Tp, D, hd,
-                               T, scale, t->gqkv);
+            hipLaunchKernelGGL(clipvis_attn_cot_kv_kernel<64>, agrid, dim3(ENC_ATTN_THREADS), ldskv, st, r.qkv, t->gB, r.ml, t->delta, (long)Tp, D,
+                               hd, T, scale, t->gqkv);
         else
-            hipLaunchKernelGGL(clipvis_attn_cot_kv_kernel<32>, agrid, dim3(CV_THREADS), ldskv, st, r.qkv, t->gB, r.ml, t->delta, (long)Tp, D, hd,
-                               T, scale, t->gqkv);
+            hipLaunchKernelGGL(clipvis_attn_cot_kv_kernel<32>, agrid, dim3(ENC_ATTN_THREADS), ldskv, st, r.qkv, t->gB, r.ml, t->delta, (long)Tp, D,
+                               hd, T, scale, t->gqkv);
         launch_gemm_fixed(enc_linear_t(ly.wqkv, t->gqkv, t->gB, 3 * D, D, Tp), GEMM_ACT_NONE, st);
         launch_ln_cot(t->gB, 0, r.h_in, r.st1, 1, D, Tp, ly.ln1_g, t->gC, 0, t->gA, 0, st);
     }

@@ -1,7 +1,9 @@
-// What the encoder units (textenc.hip, t5enc.hip, samenc.hip) share: the parameter table with its loader, the base of
-// their handles (device, last error, parameters, owned device buffers), the prologue of their create functions, and the
-// small host / device helpers of the channel-major [D][Tp] layout.
+// What the encoder units (textenc.hip, t5enc.hip, samenc.hip, clipvis.hip, clipseg.hip) share: the parameter table with its
+// loader, the base of their handles (device, last error, parameters, owned device buffers), the prologue of their create
+// functions, the small host / device helpers of the channel-major [D][Tp] layout, the pre-LN transformer block of the CLIP
+// towers, and the launchers of encoder_kernels.hip.
 #pragma once
+#include "enc_attn_lds.h"
 #include "kernels.h"
 #include "../../include/loco_hip.h"
 
@@ -137,6 +139,15 @@ struct EncoderBase {
         table.bind(params);
         return true;
     }
+    // a buffer outside alloc() that grows on demand (the owner's destructor frees it); false when hipMalloc failed
+    static bool grow(float** p, size_t* have, size_t need) {
+        if (need <= *have) return true;
+        if (*p) (void)hipFree(*p);                 // (waits for the launches that read it)
+        *p = nullptr; *have = 0;
+        if (hipMalloc(p, need * sizeof(float)) != hipSuccess) return false;
+        *have = need;
+        return true;
+    }
     virtual ~EncoderBase() {
         DeviceGuard dg(device);
         for (void* p : owned) (void)hipFree(p);
@@ -166,5 +177,61 @@ int encoder_create(const char* fn, std::string& create_err, const Cfg* cfg, int3
     *out = t;
     return 0;
 }
+
+// ---- the pre-LN transformer block of the CLIP towers (textenc.hip, clipvis.hip)
+struct PreLnLayer { float *ln1_g, *ln1_b, *wqkv, *bqkv, *wo, *bo, *ln2_g, *ln2_b, *w1, *b1, *w2, *b2; };
+
+// the parameters of layer `prefix` under transformers' CLIP names; q / k / v land in one packed [3 D][D] operator
+inline void add_clip_layer(ParamTable& pt, const std::string& p, long D, long F, PreLnLayer& ly) {
+    pt.add(p + "layer_norm1.weight", {D}, &ly.ln1_g);
+    pt.add(p + "layer_norm1.bias", {D}, &ly.ln1_b);
+    const size_t wq = pt.reserve((size_t)3 * D * D, &ly.wqkv), bq = pt.reserve(round64(3 * D), &ly.bqkv);
+    const char* qkvn[3] = {"q_proj", "k_proj", "v_proj"};
+    for (int j = 0; j < 3; ++j) {
+        pt.view(p + "self_attn." + qkvn[j] + ".weight", {D, D}, wq + (size_t)j * D * D);
+        pt.view(p + "self_attn." + qkvn[j] + ".bias", {D}, bq + (size_t)j * D);
+    }
+    pt.add(p + "self_attn.out_proj.weight", {D, D}, &ly.wo);
+    pt.add(p + "self_attn.out_proj.bias", {D}, &ly.bo);
+    pt.add(p + "layer_norm2.weight", {D}, &ly.ln2_g);
+    pt.add(p + "layer_norm2.bias", {D}, &ly.ln2_b);
+    pt.add(p + "mlp.fc1.weight", {F, D}, &ly.w1);
+    pt.add(p + "mlp.fc1.bias", {F}, &ly.b1);
+    pt.add(p + "mlp.fc2.weight", {D, F}, &ly.w2);
+    pt.add(p + "mlp.fc2.bias", {D}, &ly.b2);
+}
+
+// The tensors of one block, [.][Tp] each: h_in -> h_mid (after the attention) -> h_out; x and f are scratch, st1 / st2 the
+// statistics of the two LayerNorms.  h_mid and h_out may be h_in (the block in place), st2 may be st1.
+struct PreLnBufs { float *h_in, *x, *qkv, *attn, *h_mid, *f, *h_out, *st1, *st2; };
+
+// LN -> packed qkv -> attn(qkv, attn) -> out_proj + h_in -> LN -> fc1 with `act` (a GEMM_ACT_*) -> fc2 + h_mid
+template <class Attn>
+void pre_ln_block(const PreLnLayer& ly, const PreLnBufs& b, int D, int F, int Tp, float eps, int act, hipStream_t st, Attn attn) {
+    launch_ln_fwd(b.h_in, 0, 1, D, Tp, ly.ln1_g, ly.ln1_b, eps, b.x, 0, b.st1, 0, st);
+    launch_gemm_fixed(enc_linear(ly.wqkv, ly.bqkv, b.x, b.qkv, nullptr, 3 * D, D, Tp), GEMM_ACT_NONE, st);
+    attn(b.qkv, b.attn);
+    launch_gemm_fixed(enc_linear(ly.wo, ly.bo, b.attn, b.h_mid, b.h_in, D, D, Tp), GEMM_ACT_NONE, st);
+    launch_ln_fwd(b.h_mid, 0, 1, D, Tp, ly.ln2_g, ly.ln2_b, eps, b.x, 0, b.st2, 0, st);
+    launch_gemm_fixed(enc_linear(ly.w1, ly.b1, b.x, b.f, nullptr, F, D, Tp), act, st);
+    launch_gemm_fixed(enc_linear(ly.w2, ly.b2, b.f, b.h_out, b.h_mid, D, F, Tp), GEMM_ACT_NONE, st);
+}
+
+// ---- encoder_kernels.hip
+// The streamed attention of the ViT encoders over qkv [3 D][ld] = q | k | v channel rows, out [D][ld]: `groups` groups of nk
+// tokens each at columns g * nk + [0, nk), every query against the keys of its own group, score (q scale) . k.  relh / relw
+// [heads][Tall][size] (or null): added to the score of key (row, col) of a size x size group (nk = size^2) as relh[q][row] +
+// relw[q][col].  ml [2][heads][ld] (or null): receives the row max and the row sum of every query.  Not both (not built).
+struct EncAttnArgs {
+    const float* qkv; long ld; int D, hd, nk, groups, heads; float scale; float* out;
+    const float *relh, *relw; long Tall; int size;
+    float* ml;
+};
+void launch_enc_attn(const EncAttnArgs& a, hipStream_t st);
+// P[(ci ps + ky) ps + kx][i T + cls + ty G + tx] = pix[i][ci][ty ps + ky][tx ps + kx] for the n images [3][S][S] of pix, T = cls
+// + G^2 tokens each, the first cls (0 or 1) of them class columns; 0 in the class and the padding columns of P [3 ps^2][Tp]
+void launch_enc_patch(const float* pix, int n, int S, int ps, int G, int cls, int Tp, float* P, hipStream_t st);
+// out[col][c] = x[c][col] for the first `cols` columns of x [C][ld]
+void launch_enc_transpose(const float* x, int ld, int cols, int C, float* out, hipStream_t st);
 
 }  // namespace loco

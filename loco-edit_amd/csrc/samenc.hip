@@ -8,10 +8,11 @@
 // the padded tokens' k and v are the qkv biases, as in transformers); its attention output goes through proj in that
 // order and is scattered back (cropped) with the residual.  The linear layers, the 1x1 neck conv and the 3x3 neck conv
 // (im2col) are launch_gemm_fixed, the LayerNorms -- the per-pixel channel LayerNorm of the neck included -- xfmr.hip's
-// launch_ln_fwd.  New here: the patch gather, the partition / un-partition, the relative position tables
-// rel_h / rel_w [heads][T][size] from the unscaled queries, the im2col, and one attention kernel for both regimes: a
-// workgroup owns 16 queries of one (window, head) and streams the keys in order in chunks of 64 through LDS with a running
-// max and sum, so the T x T scores never reach memory.  Every sum runs in a fixed order set by compile-time constants.
+// launch_ln_fwd.  New here: the partition / un-partition, the relative position tables rel_h / rel_w [heads][T][size] from
+// the unscaled queries, and the im2col.  The patch gather and the attention of both regimes are encoder_kernels.hip's, shared
+// with the CLIP image tower: a workgroup owns 16 queries of one (window, head) and streams the keys in order in chunks of 64
+// through LDS with a running max and sum -- here with the two tables added to the score -- so the T x T scores never reach
+// memory.  Every sum runs in a fixed order set by compile-time constants.
 #include "encoder_common.h"
 
 #include <cmath>
@@ -43,21 +44,6 @@ struct loco_sam : loco::EncoderBase {
 
 namespace loco {
 namespace {
-
-constexpr int SA_THREADS = 256, SA_WAVES = SA_THREADS / 64, SA_QW = 4, SA_QB = SA_WAVES * SA_QW, SA_KC = 64;
-
-// P[(ci ps + ky) ps + kx][col] = pix[ci][ty ps + ky][tx ps + kx] for token col = ty G + tx < T, 0 for the padding columns
-__global__ __launch_bounds__(256) void sam_patch_kernel(const float* pix, int S, int ps, int G, int T, int Tp, float* P) {
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= (long)3 * ps * ps * Tp) return;
-    const int r = (int)(e / Tp), col = (int)(e % Tp);
-    float v = 0.f;
-    if (col < T) {
-        const int ci = r / (ps * ps), ky = (r / ps) % ps, kx = r % ps, ty = col / G, tx = col % G;
-        v = pix[((long)ci * S + ty * ps + ky) * S + tx * ps + kx];
-    }
-    P[e] = v;
-}
 
 // h[c][t] += pos[t][c] (pos_embed is stored token-major [G][G][D])
 __global__ __launch_bounds__(256) void sam_add_pos_kernel(float* h, const float* pos, int D, int T, int Tp) {
@@ -117,109 +103,6 @@ __global__ __launch_bounds__(256) void sam_relpos_kernel(const float* q, long ld
     relw[e] = aw;
 }
 
-// parts of sam_attn_kernel's LDS start at multiples of 4 floats (float4 reads of Qs and Ps)
-__host__ __device__ constexpr size_t sam_r4(size_t n) { return (n + 3) / 4 * 4; }
-
-// One workgroup per (query block of 16, head, window): the nk = size^2 keys of the window (size = ws) or of the map
-// (size = G, one "window") are streamed in order in chunks of 64 -- K [hd][64] and V [64][hd + 1] of the chunk in LDS.  A wave
-// owns 4 queries; lane j scores key k0 + j against them: (q scale) . k + rel_h[q][row(k)] + rel_w[q][col(k)], then the
-// running max / sum update (fp32, max and sum over the chunk by shuffles), then lane c (and c + 64) adds P V of the chunk to
-// its output channel in key order.  qkv: [3 D][ld] = q | k | v channel rows, out [D][ld]; hd <= 128.
-__global__ __launch_bounds__(SA_THREADS) void sam_attn_kernel(const float* qkv, long ld, int D, int hd, int nk, int size, float scale,
-                                                              const float* relh, const float* relw, long Tall, float* out) {
-    extern __shared__ __align__(16) float sam_sm[];
-    const int hdp = hd + 1;
-    float* Ks = sam_sm;                                    // [hd][64]
-    float* Vs = Ks + sam_r4(hd * SA_KC);                   // [64][hd + 1]
-    float* Qs = Vs + sam_r4(SA_KC * hdp);                  // [hd][16]
-    float* Bh = Qs + sam_r4(hd * SA_QB);                   // [16][size]
-    float* Bw = Bh + SA_QB * size;                         // [16][size]
-    float* Ps = Bh + sam_r4(2 * SA_QB * size);             // [waves][64][4]
-    const int qb = blockIdx.x, h = blockIdx.y, w = blockIdx.z;
-    const long col0 = (long)w * nk;
-    const int q0 = qb * SA_QB;
-    const float* q = qkv + (long)(h * hd) * ld + col0;
-    const float* k = qkv + (long)(D + h * hd) * ld + col0;
-    const float* v = qkv + (long)(2 * D + h * hd) * ld + col0;
-    for (int e = threadIdx.x; e < hd * SA_QB; e += SA_THREADS) {
-        const int c = e / SA_QB, ql = min(q0 + e % SA_QB, nk - 1);
-        Qs[e] = q[(long)c * ld + ql] * scale;
-    }
-    for (int e = threadIdx.x; e < SA_QB * size; e += SA_THREADS) {
-        const int ql = min(q0 + e / size, nk - 1), j = e % size;
-        const long o = ((long)h * Tall + col0 + ql) * size + j;
-        Bh[e] = relh[o];
-        Bw[e] = relw[o];
-    }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int c0 = lane < hd ? lane : 0, c1 = lane + 64 < hd ? lane + 64 : 0;
-    float* pw = Ps + wv * (SA_KC * SA_QW);
-    float m[SA_QW], l[SA_QW], o0[SA_QW], o1[SA_QW];
-#pragma unroll
-    for (int u = 0; u < SA_QW; ++u) { m[u] = -INFINITY; l[u] = 0.f; o0[u] = 0.f; o1[u] = 0.f; }
-    for (int k0 = 0; k0 < nk; k0 += SA_KC) {
-        __syncthreads();
-        for (int e = threadIdx.x; e < hd * SA_KC; e += SA_THREADS) {
-            const int c = e / SA_KC, j = e % SA_KC, kj = k0 + j;
-            const bool ok = kj < nk;
-            Ks[e] = ok ? k[(long)c * ld + kj] : 0.f;
-            Vs[j * hdp + c] = ok ? v[(long)c * ld + kj] : 0.f;
-        }
-        __syncthreads();
-        const int kj = k0 + lane;
-        const bool valid = kj < nk;
-        const int kr = valid ? kj / size : 0, kc = valid ? kj - kr * size : 0;
-        float s[SA_QW];
-#pragma unroll
-        for (int u = 0; u < SA_QW; ++u) s[u] = 0.f;
-        for (int c = 0; c < hd; ++c) {
-            const float kv = Ks[c * SA_KC + lane];
-            const float4 qv = *reinterpret_cast<const float4*>(Qs + c * SA_QB + wv * SA_QW);
-            s[0] = fmaf(qv.x, kv, s[0]);
-            s[1] = fmaf(qv.y, kv, s[1]);
-            s[2] = fmaf(qv.z, kv, s[2]);
-            s[3] = fmaf(qv.w, kv, s[3]);
-        }
-#pragma unroll
-        for (int u = 0; u < SA_QW; ++u) {
-            const int qi = wv * SA_QW + u;
-            const float sc = valid ? s[u] + Bh[qi * size + kr] + Bw[qi * size + kc] : -INFINITY;
-            const float mn = fmaxf(m[u], wave_max(sc));
-            const float corr = expf(m[u] - mn);
-            const float p = valid ? expf(sc - mn) : 0.f;
-            l[u] = l[u] * corr + wave_sum(p);
-            o0[u] *= corr;
-            o1[u] *= corr;
-            m[u] = mn;
-            pw[lane * SA_QW + u] = p;
-        }
-        __syncthreads();
-        for (int j = 0; j < SA_KC; ++j) {
-            const float4 pv = *reinterpret_cast<const float4*>(pw + j * SA_QW);
-            const float v0 = Vs[j * hdp + c0];
-            o0[0] = fmaf(pv.x, v0, o0[0]);
-            o0[1] = fmaf(pv.y, v0, o0[1]);
-            o0[2] = fmaf(pv.z, v0, o0[2]);
-            o0[3] = fmaf(pv.w, v0, o0[3]);
-            if (hd > 64) {                                 // uniform
-                const float v1 = Vs[j * hdp + c1];
-                o1[0] = fmaf(pv.x, v1, o1[0]);
-                o1[1] = fmaf(pv.y, v1, o1[1]);
-                o1[2] = fmaf(pv.z, v1, o1[2]);
-                o1[3] = fmaf(pv.w, v1, o1[3]);
-            }
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < SA_QW; ++u) {
-        const int ql = q0 + wv * SA_QW + u;
-        if (ql >= nk) continue;
-        const float inv = 1.0f / l[u];
-        if (lane < hd) out[(long)(h * hd + lane) * ld + col0 + ql] = o0[u] * inv;
-        if (lane + 64 < hd) out[(long)(h * hd + lane + 64) * ld + col0 + ql] = o1[u] * inv;
-    }
-}
-
 // col[(ci 9 + ky 3 + kx)][t] = x[ci][(row + ky - 1) G + col + kx - 1] inside the map, 0 outside and in the padding columns
 __global__ __launch_bounds__(256) void sam_im2col3_kernel(const float* x, int C, int G, int T, int Tp, float* colbuf) {
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
@@ -247,12 +130,6 @@ using namespace loco;
 
 namespace {
 thread_local std::string g_sam_create_err;
-
-// the carve-up of sam_attn_kernel's LDS
-size_t sam_attn_lds_floats(int hd, int size) {
-    return sam_r4((size_t)hd * SA_KC) + sam_r4((size_t)SA_KC * (hd + 1)) + sam_r4((size_t)hd * SA_QB) + sam_r4((size_t)2 * SA_QB * size) +
-           (size_t)SA_WAVES * SA_KC * SA_QW;
-}
 
 struct SamTimer {             // brackets a run of launches with two events while the profile is on
     loco_sam* t; hipStream_t st; int at = -1;
@@ -285,7 +162,7 @@ int loco_sam_create(const loco_sam_cfg* cfg, int32_t device, loco_sam** out) {
         if (!(c.ln_eps > 0.f)) return "ln_eps must be positive";
         const int G = c.image_size / c.patch_size, hd = c.width / c.heads;
         if (hd > 128) return "head width > 128 (the attention kernel holds 2 channels per lane)";
-        if (sam_attn_lds_floats(hd, std::max(G, c.window_size)) * sizeof(float) > 65536)
+        if (enc_attn_lds_floats(hd, std::max(G, c.window_size)) * sizeof(float) > 65536)
             return "head width x grid too large for the attention kernel's LDS (64 KiB)";
         return "";
     };
@@ -363,7 +240,7 @@ int loco_sam_encode(loco_sam* t, const float* pixel_values, float* out_dev, void
     }
     {
         SamTimer tm(t, st, SAM_CAT_OTHER);
-        hipLaunchKernelGGL(sam_patch_kernel, dim3(blocks256((long)PK * Tp)), dim3(256), 0, st, pixel_values, c.image_size, ps, G, T, Tp, t->f);
+        launch_enc_patch(pixel_values, 1, c.image_size, ps, G, 0, Tp, t->f, st);
     }
     {
         SamTimer tm(t, st, SAM_CAT_GEMM);
@@ -392,9 +269,7 @@ int loco_sam_encode(loco_sam* t, const float* pixel_values, float* out_dev, void
             SamTimer tm(t, st, acat);
             hipLaunchKernelGGL(sam_relpos_kernel, dim3(blocks256((long)heads * Tall * size)), dim3(256), 0, st, t->qkv, (long)ldl, hd, heads,
                                Tall, size, ly.rel_h, ly.rel_w, t->relh, t->relw);
-            hipLaunchKernelGGL(sam_attn_kernel, dim3((nk + SA_QB - 1) / SA_QB, heads, nwin), dim3(SA_THREADS),
-                               sam_attn_lds_floats(hd, size) * sizeof(float), st, t->qkv, (long)ldl, D, hd, nk, size, scale, t->relh, t->relw,
-                               Tall, t->attn);
+            launch_enc_attn({t->qkv, (long)ldl, D, hd, nk, nwin, heads, scale, t->attn, t->relh, t->relw, Tall, size, nullptr}, st);
         }
         if (gl) {
             SamTimer tm(t, st, SAM_CAT_GEMM);

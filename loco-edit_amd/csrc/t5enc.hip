@@ -7,7 +7,7 @@
 // launch_gemm_fixed over all prompts (no bias anywhere in T5): q | k | v as one packed [3 inner][D] operator, o and wo with
 // the residual in the epilogue, wi_0 | wi_1 as one packed [2 F][D] operator.  The embedding gather (without positions), the
 // self-attention of one (prompt, head) per workgroup (its bidirectional form: relative position bias and key padding mask),
-// the transpose and the id staging are textenc.hip's, through textenc.h.  New here: the RMS norm over channel-major columns
+// and the id staging are textenc.hip's, through textenc.h; the transpose is encoder_kernels.hip's.  New here: the RMS norm over channel-major columns
 // and the gate gelu_new(a) * b.  Every kernel computes a token column from that column (the attention: from the columns and
 // the length of its own prompt) alone, in a fixed order: a prompt's rows are bit-identical whatever n, its position in the
 // batch and the lengths of the other prompts.
@@ -127,7 +127,7 @@ int T5Text::encode(const int32_t* ids_dev, const int32_t* lens_in, int32_t n, fl
         launch_gemm_fixed(enc_linear(ly.wff, nullptr, f, h, h, D, F, Tp), GEMM_ACT_NONE, st);
     }
     hipLaunchKernelGGL(t5_rmsnorm_kernel, rn_grid, rn_block, 0, st, h, lnf_g, eps, D, Tp, x);
-    launch_text_transpose(x, Tp, T, D, out_dev, st);
+    launch_enc_transpose(x, Tp, T, D, out_dev, st);
     if (hipGetLastError() != hipSuccess) return fail("loco_text_encode: kernel launch failed");
     return 0;
 }

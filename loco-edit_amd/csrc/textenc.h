@@ -1,6 +1,7 @@
 // The handle behind include/loco_hip.h's loco_text: the base of the two text encoders, CLIP (textenc.hip,
-// loco_text_create) and the T5 encoder of DeepFloyd IF (t5enc.hip, loco_t5_create), and the kernels both launch.  The six
-// loco_text_* functions (textenc.hip) work on this base alone: what differs between the encoders is behind its virtuals.
+// loco_text_create) and the T5 encoder of DeepFloyd IF (t5enc.hip, loco_t5_create), and the kernels both launch (but for the
+// transpose of the final states, encoder_common.h's launch_enc_transpose).  The six loco_text_* functions (textenc.hip) work
+// on this base alone: what differs between the encoders is behind its virtuals.
 #pragma once
 #include "encoder_common.h"
 
@@ -35,7 +36,5 @@ void launch_text_embed(const int* ids, int T, int Tp, int L, int D, const float*
 size_t prompt_attn_lds_bytes(int hd, int L);
 void launch_prompt_attn(bool causal_scaled, const float* qkv, long ld, int n, int heads, int L, int inner, int hd, float scale,
                         const float* bias_tab, const int* lens, float* out, hipStream_t st);
-// out[col][c] = x[c][col] for the T real columns of x [D][Tp]
-void launch_text_transpose(const float* x, int Tp, int T, int D, float* out, hipStream_t st);
 
 }  // namespace loco

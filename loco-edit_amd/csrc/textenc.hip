@@ -6,9 +6,11 @@
 // ones).  In that layout the linear layers are one launch_gemm_fixed each over all prompts (W [out][in] row-major as
 // stored, so each layer's weights are read once per call), and LayerNorm is xfmr.hip's launch_ln_fwd unchanged.  New
 // here, and shared with the T5 encoder (t5enc.hip) through textenc.h: the embedding gather, the self-attention of one
-// (prompt, head) per workgroup in its two forms, the transpose of the final states to [n][L][D], and the staging of the
-// token ids.  Every kernel computes a token column from that column (and, in the attention, from the columns of its own
-// prompt) alone, in a fixed order: a prompt's rows are bit-identical whatever n and its position in the batch.
+// (prompt, head) per workgroup in its two forms, and the staging of the token ids.  The layer's parameters and its seven
+// launches are encoder_common.h's add_clip_layer / pre_ln_block, which the image tower (clipvis.hip) uses too; the transpose
+// of the final states to [n][L][D] is encoder_kernels.hip's.  Every kernel computes a token column from that column (and,
+// in the attention, from the columns of its own prompt) alone, in a fixed order: a prompt's rows are bit-identical whatever
+// n and its position in the batch.
 //
 // Also here: the six loco_text_* functions of the handle base (textenc.h), which serve both encoders.
 #include "textenc.h"
@@ -107,13 +109,6 @@ void prompt_attn_kernel(const float* qkv, long ld, int L, int inner, int hd, flo
     }
 }
 
-__global__ __launch_bounds__(256) void text_transpose_kernel(const float* x, int Tp, int T, int D, float* out) {
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= (long)T * D) return;
-    const int col = (int)(e / D), c = (int)(e % D);
-    out[e] = x[(long)c * Tp + col];
-}
-
 }  // namespace
 
 thread_local std::string g_text_create_err;
@@ -129,10 +124,6 @@ void launch_prompt_attn(bool causal_scaled, const float* qkv, long ld, int n, in
     auto kernel = causal_scaled ? prompt_attn_kernel<true> : prompt_attn_kernel<false>;
     hipLaunchKernelGGL(kernel, dim3(n, heads), dim3(PA_THREADS), prompt_attn_lds_bytes(hd, L), st, qkv, ld, L, inner, hd, scale, bias_tab,
                        lens, out);
-}
-
-void launch_text_transpose(const float* x, int Tp, int T, int D, float* out, hipStream_t st) {
-    hipLaunchKernelGGL(text_transpose_kernel, dim3(blocks256((long)T * D)), dim3(256), 0, st, x, Tp, T, D, out);
 }
 
 int text_check_call(loco_text* t, const int32_t* ids_dev, int32_t n, const float* out_dev) {
@@ -164,12 +155,10 @@ using namespace loco;
 
 namespace {
 
-struct ClipLayer { float *ln1_g, *ln1_b, *wqkv, *bqkv, *wo, *bo, *ln2_g, *ln2_b, *w1, *b1, *w2, *b2; };
-
 struct ClipText final : loco_text {
     loco_text_cfg cfg;
     float *pos = nullptr, *lnf_b = nullptr, *stats = nullptr;
-    std::vector<ClipLayer> layer;
+    std::vector<PreLnLayer> layer;
 
     int encode(const int32_t* ids_dev, const int32_t* lens, int32_t n, float* out_dev, hipStream_t st) override;
     int encode_masked(const int32_t*, const int32_t*, int32_t, float*, hipStream_t) override {
@@ -185,17 +174,13 @@ int ClipText::encode(const int32_t* ids_dev, const int32_t*, int32_t n, float* o
     launch_text_embed(ids, T, Tp, L, D, tok, pos, h, st);
     const float scale = 1.0f / std::sqrt((float)hd);
     const int gact = cfg.act == 0 ? GEMM_ACT_QUICK_GELU : GEMM_ACT_GELU;
-    for (const ClipLayer& ly : layer) {
-        launch_ln_fwd(h, 0, 1, D, Tp, ly.ln1_g, ly.ln1_b, cfg.ln_eps, x, 0, stats, 0, st);
-        launch_gemm_fixed(enc_linear(ly.wqkv, ly.bqkv, x, qkv, nullptr, 3 * D, D, Tp), GEMM_ACT_NONE, st);
-        launch_prompt_attn(true, qkv, (long)Tp, n, cfg.heads, L, D, hd, scale, nullptr, nullptr, attn, st);
-        launch_gemm_fixed(enc_linear(ly.wo, ly.bo, attn, h, h, D, D, Tp), GEMM_ACT_NONE, st);
-        launch_ln_fwd(h, 0, 1, D, Tp, ly.ln2_g, ly.ln2_b, cfg.ln_eps, x, 0, stats, 0, st);
-        launch_gemm_fixed(enc_linear(ly.w1, ly.b1, x, f, nullptr, F, D, Tp), gact, st);
-        launch_gemm_fixed(enc_linear(ly.w2, ly.b2, f, h, h, D, F, Tp), GEMM_ACT_NONE, st);
-    }
+    const PreLnBufs bufs{h, x, qkv, attn, h, f, h, stats, stats};      // every block in place on h
+    for (const PreLnLayer& ly : layer)
+        pre_ln_block(ly, bufs, D, F, Tp, cfg.ln_eps, gact, st, [&](const float* qkv_, float* attn_) {
+            launch_prompt_attn(true, qkv_, (long)Tp, n, cfg.heads, L, D, hd, scale, nullptr, nullptr, attn_, st);
+        });
     launch_ln_fwd(h, 0, 1, D, Tp, lnf_g, lnf_b, cfg.ln_eps, x, 0, stats, 0, st);
-    launch_text_transpose(x, Tp, T, D, out_dev, st);
+    launch_enc_transpose(x, Tp, T, D, out_dev, st);
     if (hipGetLastError() != hipSuccess) return fail("loco_text_encode: kernel launch failed");
     return 0;
 }
@@ -221,31 +206,12 @@ int loco_text_create(const loco_text_cfg* cfg, int32_t device, int32_t max_promp
         t.L = c.positions; t.D = c.width; t.hd = c.width / c.heads;
         t.Tmax = (max_prompts * c.positions + 15) / 16 * 16;
         const long D = c.width, F = c.ffn, Tm = t.Tmax;
-        // parameter table (names of transformers' CLIPTextTransformer); q / k / v land in one packed [3 D][D] operator
+        // parameter table (names of transformers' CLIPTextTransformer)
         ParamTable& pt = t.table;
         pt.add("embeddings.token_embedding.weight", {c.vocab, D}, &t.tok);
         pt.add("embeddings.position_embedding.weight", {c.positions, D}, &t.pos);
         t.layer.resize(c.layers);
-        for (int l = 0; l < c.layers; ++l) {
-            const std::string p = "encoder.layers." + std::to_string(l) + ".";
-            ClipLayer& ly = t.layer[l];
-            pt.add(p + "layer_norm1.weight", {D}, &ly.ln1_g);
-            pt.add(p + "layer_norm1.bias", {D}, &ly.ln1_b);
-            const size_t wq = pt.reserve((size_t)3 * D * D, &ly.wqkv), bq = pt.reserve(round64(3 * D), &ly.bqkv);
-            const char* qkvn[3] = {"q_proj", "k_proj", "v_proj"};
-            for (int j = 0; j < 3; ++j) {
-                pt.view(p + "self_attn." + qkvn[j] + ".weight", {D, D}, wq + (size_t)j * D * D);
-                pt.view(p + "self_attn." + qkvn[j] + ".bias", {D}, bq + (size_t)j * D);
-            }
-            pt.add(p + "self_attn.out_proj.weight", {D, D}, &ly.wo);
-            pt.add(p + "self_attn.out_proj.bias", {D}, &ly.bo);
-            pt.add(p + "layer_norm2.weight", {D}, &ly.ln2_g);
-            pt.add(p + "layer_norm2.bias", {D}, &ly.ln2_b);
-            pt.add(p + "mlp.fc1.weight", {F, D}, &ly.w1);
-            pt.add(p + "mlp.fc1.bias", {F}, &ly.b1);
-            pt.add(p + "mlp.fc2.weight", {D, F}, &ly.w2);
-            pt.add(p + "mlp.fc2.bias", {D}, &ly.b2);
-        }
+        for (int l = 0; l < c.layers; ++l) add_clip_layer(pt, "encoder.layers." + std::to_string(l) + ".", D, F, t.layer[l]);
         pt.add("final_layer_norm.weight", {D}, &t.lnf_g);
         pt.add("final_layer_norm.bias", {D}, &t.lnf_b);
         t.ids_host.resize((size_t)max_prompts * c.positions);

@@ -1,4 +1,4 @@
-"""GPU test of the second output channel of sam_attn_kernel (csrc/samenc.hip): heads wider than 64, where a lane
+"""GPU test of the second output channel of enc_attn_kernel (csrc/encoder_kernels.hip) with SAM's bias tables: heads wider than 64, where a lane
 accumulates channel c and channel c + 64 (ViT-H has heads of 80; the kernel's LDS ends the range near 100).
 
 Three tiny geometries with seeded weights, heads of 80, 96 and 65: grid 10, window 4 (the windows pad 10 -> 12, 16 keys: one
