@@ -1,8 +1,8 @@
 /* Diagnostics of libloco_hip -- NOT part of the drop-in boundary (include/loco_hip.h).
  *
- * These entry points live in their own unit, loco-edit_amd/csrc/engine_diag.hip, which is linked only into the diagnostics
- * library (`make -C loco-edit_amd/csrc diag` -> loco-edit_amd/libloco_hip_diag.so: the product's objects + that unit, every unit
- * that includes this header built with -DLOCO_DIAG); the by-hand tuning scripts under tests/ load that build through
+ * These entry points live in units of their own, loco-edit_amd/csrc/engine_diag.hip and enc_attn_diag.hip, which are linked only
+ * into the diagnostics library (`make -C loco-edit_amd/csrc diag` -> loco-edit_amd/libloco_hip_diag.so: the product's objects +
+ * those units, every unit that includes this header built with -DLOCO_DIAG); the by-hand tuning scripts under tests/ load that build through
  * LOCO_HIP_LIB.  The shipped libloco_hip.so does not export them. */
 #ifndef LOCO_HIP_DIAG_H
 #define LOCO_HIP_DIAG_H
@@ -267,6 +267,55 @@ typedef struct loco_pointwise_desc {
     float *out, *out2, *t_dev;
 } loco_pointwise_desc;
 int  loco_debug_pointwise(loco_ctx* ctx, const loco_pointwise_desc* desc, void* stream);
+
+/* Test hook: ONE launch of ONE attention kernel of the encoders on caller-supplied DEVICE tensors, through the launcher the
+ * product's call site uses (tests/test_gpu_enc_attn_oracle.py compares it with the float64 reference of
+ * tests/enc_attn_oracle.py).  No engine: every tensor is the caller's, contiguous fp32 (lens: int32); err (err_cap bytes, may be
+ * null) receives the message of a refusal or a HIP error.  The call returns after the launch has finished.
+ *
+ * Activations are channel-major [rows][ld], head h owns the rows h hd ... h hd + hd - 1, group g the columns g nk + [0, nk).
+ *   op 0  launch_enc_attn, no tables, no statistics:  qkv [3 D][ld] = q | k | v -> out [D][ld];  score (q scale) . k over the nk
+ *         keys of the query's own group
+ *   op 1  the same keeping the statistics:            -> out, ml [2][heads][ld] = row max | row sum of exp(score - max)
+ *   op 2  the same with the tables relh, relw [heads][Tall][size] (nk = size^2): the score of key (row, col) gains
+ *         relh[h][g nk + i][row] + relw[h][g nk + i][col]
+ *   op 3  launch_prompt_attn, causal and scaled:      qkv [3 D][ld], nk = L, groups = n prompts -> out [D][ld];  keys j <= i
+ *   op 4  launch_prompt_attn, length mask + bias:     qkv, bias_tab [heads][2 L - 1], lens [n] -> out;  keys j < lens[p], score
+ *         q . k + bias_tab[h][j - i + L - 1], no scale; padded query rows are outputs
+ *   op 5  launch_clipvis_attn_cot_q:   qkv, o, go [D][ld], ml (read) -> the q block of gqkv [3 D][ld], delta [heads][ld] (written)
+ *   op 6  launch_clipvis_attn_cot_kv:  qkv, go, ml, delta (all read) -> the k and v blocks of gqkv
+ *         P = exp((q scale) . k - m) / l,  delta_i = <go_i, o_i>,  dS = P o (go v^T - delta),  dQ = scale dS k,  dK = scale dS^T q,
+ *         dV = P^T go;  nk = T, groups = n images
+ *   op 7  launch_seg_attn:             qkv [3 D][ld] (D = reduce_dim), nk = T, groups = M masks -> out [D][ld]
+ *   op 8  launch_sd_t2i:   q = qx [P][8][D] (rows NQ ... 7 unread), k, v [D][ld] per prompt at a stride of kbs floats (0: shared),
+ *         nk = T, groups = P -> out [P][8][D], rows NQ ... 7 untouched
+ *   op 9  launch_sd_i2t:   q [D][ld] per prompt at a stride of qbs floats (0: shared), k = kx, v = vx [P][8][D], nk = T, Tp >= T the
+ *         padded columns -> out [P][D][ld], columns T ... Tp - 1 zero; out may be q when groups = 1
+ *
+ * Refused (-2) before any launch: an op outside 0 ... 9; a null required operand; a non-positive dimension; D != heads hd; relh
+ * or relw together with ml, or one table without the other (ops 0 - 2); hd > 128 (ops 0 - 2, 5, 6); nk != size^2 or Tall < groups
+ * nk (op 2); more than 65536 bytes of LDS by the launcher's own carve-up (ops 0 - 6, 8); L > 128 (ops 3, 4); a lens entry outside
+ * [1, L] (op 4: lens is read back); a head width outside {4, 8, 16, 32, 64} or T > 2048 (op 7); hd not a power of two <= 64 or NQ
+ * outside [1, 8] (ops 8, 9); ld smaller than the columns addressed (groups nk; T for op 8; Tp for op 9, and Tp < T); out == q with
+ * groups > 1 (op 9).
+ *
+ * route (cap bytes, may be null) receives one line per launch, written from the predicates the launcher itself branches on:
+ *   "kernel=enc_attn bias=0|1 keep=0|1\n"   "kernel=prompt_attn causal=0|1\n"   "kernel=clipvis_attn_cot_q chunk=64|32\n"
+ *   "kernel=clipvis_attn_cot_kv chunk=64|32\n"   "kernel=seg_attn hd=<instantiation>\n"   "kernel=sd_t2i\n"   "kernel=sd_i2t\n"
+ * Returns 0; -2 refused; -1 a HIP error; -4 route buffer too small. */
+typedef struct loco_enc_attn_desc {
+    int32_t struct_size;
+    int32_t op;
+    int32_t D, hd, heads, nk, groups;                           /* D: D / inner / reduce_dim / Ci; nk: nk / L / T; groups: groups / n / M / P */
+    int32_t size, NQ, Tp;
+    int64_t ld, Tall, kbs, qbs;
+    float   scale;
+    int32_t pad2_;
+    const float *qkv, *relh, *relw, *bias_tab, *o, *go, *q, *k, *v;
+    const int32_t* lens;
+    float *out, *ml, *gqkv, *delta;
+} loco_enc_attn_desc;
+int  loco_debug_enc_attn(const loco_enc_attn_desc* desc, char* route, int64_t cap, char* err, int64_t err_cap, void* stream);
 
 /* Debug / test hook: copy an internal primal activation ("down.0.block.0" ...)
  * of the last forward/primal call into dst (device), returns element count or <0. */

@@ -11,7 +11,7 @@
 // (one wave per query), the heads (every transposed convolution has stride = kernel: an output pixel has ONE source token,
 // a gather without atomics), the two resize passes and the mask kernel.  Every kernel computes a mask's columns from the
 // columns of that mask alone, in a fixed order: a mask's logits are bit-identical whatever M and its position.
-#include "encoder_common.h"
+#include "enc_attn_launch.h"
 
 #include <cmath>
 
@@ -250,6 +250,19 @@ void seg_attn_launch(dim3 grid, size_t lds, hipStream_t st, const float* qkv, lo
 }
 
 }  // namespace
+
+void launch_seg_attn(const float* qkv, long ld, int R, int hd, int heads, int T, int M, float scale, float* out, hipStream_t st) {
+    const dim3 grid((T + SEG_QW - 1) / SEG_QW, heads, M);
+    const size_t lds = (size_t)SEG_QW * T * sizeof(float);
+    switch (seg_attn_instance(hd)) {
+        case 4: seg_attn_launch<4>(grid, lds, st, qkv, ld, R, T, scale, out); break;
+        case 8: seg_attn_launch<8>(grid, lds, st, qkv, ld, R, T, scale, out); break;
+        case 16: seg_attn_launch<16>(grid, lds, st, qkv, ld, R, T, scale, out); break;
+        case 32: seg_attn_launch<32>(grid, lds, st, qkv, ld, R, T, scale, out); break;
+        default: seg_attn_launch<64>(grid, lds, st, qkv, ld, R, T, scale, out); break;
+    }
+}
+
 }  // namespace loco
 
 using namespace loco;
@@ -377,8 +390,6 @@ int loco_clipseg_decode(loco_clipseg* t, const float* taps_dev, int32_t n_images
         g.sbk = 1; g.sbn = P;
         launch_gemm_fixed(g, GEMM_ACT_NONE, st);
     }
-    const dim3 attn_grid((T + SEG_QW - 1) / SEG_QW, c.heads, M);
-    const size_t attn_lds = (size_t)SEG_QW * T * sizeof(float);
     for (int i = 0; i < c.n_taps; ++i) {
         const ClipSegLayer& ly = t->layer[i];
         // red [rd][n T] = reduces[i] on the token-major tap of every image, deepest tap first
@@ -388,13 +399,7 @@ int loco_clipseg_decode(loco_clipseg* t, const float* taps_dev, int32_t n_images
         hipLaunchKernelGGL(seg_combine_kernel, dim3(blocks256((long)R * Tp)), dim3(256), 0, st, t->red, (long)nT, map, R, T, MT, Tp, M,
                            i == 0 ? 1 : 0, i == c.conditional_layer ? t->film : (const float*)nullptr, t->x);
         launch_gemm_fixed(enc_linear(ly.wqkv, ly.bqkv, t->x, t->qkv, nullptr, 3 * R, R, Tp), GEMM_ACT_NONE, st);
-        switch (hd) {
-            case 4: seg_attn_launch<4>(attn_grid, attn_lds, st, t->qkv, (long)Tp, R, T, scale, t->attn); break;
-            case 8: seg_attn_launch<8>(attn_grid, attn_lds, st, t->qkv, (long)Tp, R, T, scale, t->attn); break;
-            case 16: seg_attn_launch<16>(attn_grid, attn_lds, st, t->qkv, (long)Tp, R, T, scale, t->attn); break;
-            case 32: seg_attn_launch<32>(attn_grid, attn_lds, st, t->qkv, (long)Tp, R, T, scale, t->attn); break;
-            default: seg_attn_launch<64>(attn_grid, attn_lds, st, t->qkv, (long)Tp, R, T, scale, t->attn); break;
-        }
+        launch_seg_attn(t->qkv, (long)Tp, R, hd, c.heads, T, M, scale, t->attn, st);
         launch_gemm_fixed(enc_linear(ly.wo, ly.bo, t->attn, t->y, t->x, R, R, Tp), GEMM_ACT_NONE, st);
         launch_ln_fwd(t->y, 0, 1, R, Tp, ly.ln1_g, ly.ln1_b, c.ln_eps, t->x, 0, t->stats, 0, st);
         launch_gemm_fixed(enc_linear(ly.w1, ly.b1, t->x, t->f, nullptr, F, R, Tp), GEMM_ACT_RELU, st);

@@ -18,7 +18,7 @@
 // strides swapped, the LayerNorms xfmr.hip's launch_ln_cot; new are the two attention cotangent kernels, the activation
 // derivative, the class column scatter and the patch adjoint.  No atomics, the forward's invariant carries over.  The float
 // preprocessing (loco_clipvis_preprocess_f32 and its transpose) resizes windows of [-1, 1] frames by the same tap rule.
-#include "encoder_common.h"
+#include "enc_attn_launch.h"
 
 #include <cmath>
 
@@ -497,18 +497,35 @@ __global__ __launch_bounds__(256) void clipvis_win_x_cot_kernel(const float* gro
 }
 
 }  // namespace
+
+void launch_clipvis_attn_cot_q(const float* qkv, const float* o, const float* go, const float* ml, long ld, int D, int hd, int T, int heads,
+                               int n, float scale, float* gqkv, float* delta, hipStream_t st) {
+    const int kc = clipvis_attn_cot_chunk(hd, 1);
+    const size_t lds = clipvis_attn_cot_lds_floats(hd, kc, 1) * sizeof(float);
+    const dim3 grid((T + CV_COT_ROWS - 1) / CV_COT_ROWS, heads, n);
+    if (kc == 64)
+        hipLaunchKernelGGL(clipvis_attn_cot_q_kernel<64>, grid, dim3(ENC_ATTN_THREADS), lds, st, qkv, o, go, ml, ld, D, hd, T, scale, gqkv, delta);
+    else
+        hipLaunchKernelGGL(clipvis_attn_cot_q_kernel<32>, grid, dim3(ENC_ATTN_THREADS), lds, st, qkv, o, go, ml, ld, D, hd, T, scale, gqkv, delta);
+}
+
+void launch_clipvis_attn_cot_kv(const float* qkv, const float* go, const float* ml, const float* delta, long ld, int D, int hd, int T,
+                                int heads, int n, float scale, float* gqkv, hipStream_t st) {
+    const int kc = clipvis_attn_cot_chunk(hd, 2);
+    const size_t lds = clipvis_attn_cot_lds_floats(hd, kc, 2) * sizeof(float);
+    const dim3 grid((T + CV_COT_ROWS - 1) / CV_COT_ROWS, heads, n);
+    if (kc == 64)
+        hipLaunchKernelGGL(clipvis_attn_cot_kv_kernel<64>, grid, dim3(ENC_ATTN_THREADS), lds, st, qkv, go, ml, delta, ld, D, hd, T, scale, gqkv);
+    else
+        hipLaunchKernelGGL(clipvis_attn_cot_kv_kernel<32>, grid, dim3(ENC_ATTN_THREADS), lds, st, qkv, go, ml, delta, ld, D, hd, T, scale, gqkv);
+}
+
 }  // namespace loco
 
 using namespace loco;
 
 namespace {
 thread_local std::string g_clipvis_create_err;
-
-// the carve-ups of the two cotangent kernels at a chunk of `kc` tokens; `tables`: 1 (dS) or 2 (P and dS) per-wave tables
-size_t clipvis_attn_cot_lds_floats(int hd, int kc, int tables) {
-    return 2 * enc_r4((size_t)kc * (hd + 1)) + 2 * enc_r4((size_t)hd * ENC_ATTN_QB) + (size_t)tables * ENC_ATTN_WAVES * 64 * ENC_ATTN_QW;
-}
-int clipvis_attn_cot_chunk(int hd, int tables) { return clipvis_attn_cot_lds_floats(hd, 64, tables) * sizeof(float) <= 65536 ? 64 : 32; }
 
 // W^T: the operator of enc_linear read through swapped strides (gemm_f32_kernel stages either order)
 GemmArgs enc_linear_t(const float* W, const float* X, float* Y, int rows, int cols, int Tp) {
@@ -768,9 +785,6 @@ int loco_clipvis_encode_vjp(loco_clipvis* t, const float* g_embeds_dev, int32_t 
     const int D = c.width, F = c.mlp_dim, P = c.projection_dim, ps = c.patch_size, PK = 3 * ps * ps, S = c.image_size;
     const int G = t->G, T = t->T, hd = t->hd, nT = n * T, Tp = (nT + 15) / 16 * 16, Np = (n + 15) / 16 * 16;
     const float scale = 1.0f / std::sqrt((float)hd);
-    const int kcq = clipvis_attn_cot_chunk(hd, 1), kckv = clipvis_attn_cot_chunk(hd, 2);
-    const size_t ldsq = clipvis_attn_cot_lds_floats(hd, kcq, 1) * sizeof(float), ldskv = clipvis_attn_cot_lds_floats(hd, kckv, 2) * sizeof(float);
-    const dim3 agrid((T + CV_COT_ROWS - 1) / CV_COT_ROWS, c.heads, n);
     // visual_projection^T, post_layernorm on the class columns, back to column i T
     hipLaunchKernelGGL(clipvis_columns_kernel, dim3(blocks256((long)P * Np)), dim3(256), 0, st, g_embeds_dev, n, P, Np, t->gE);
     launch_gemm_fixed(enc_linear_t(t->proj, t->gE, t->gpn, P, D, Np), GEMM_ACT_NONE, st);
@@ -788,18 +802,8 @@ int loco_clipvis_encode_vjp(loco_clipvis* t, const float* g_embeds_dev, int32_t 
         launch_ln_cot(t->gB, 0, r.h_mid, r.st2, 1, D, Tp, ly.ln2_g, t->gA, 0, t->gC, 0, st);
         // the attention
         launch_gemm_fixed(enc_linear_t(ly.wo, t->gC, t->gB, D, D, Tp), GEMM_ACT_NONE, st);
-        if (kcq == 64)
-            hipLaunchKernelGGL(clipvis_attn_cot_q_kernel<64>, agrid, dim3(ENC_ATTN_THREADS), ldsq, st, r.qkv, r.attn, t->gB, r.ml, (long)Tp, D, hd, T,
-                               scale, t->gqkv, t->delta);
-        else
-            hipLaunchKernelGGL(clipvis_attn_cot_q_kernel<32>, agrid, dim3(ENC_ATTN_THREADS), ldsq, st, r.qkv, r.attn, t->gB, r.ml, (long)Tp, D, hd, T,
-                               scale, t->gqkv, t->delta);
-        if (kckv == 64)
-            hipLaunchKernelGGL(clipvis_attn_cot_kv_kernel<64>, agrid, dim3(ENC_ATTN_THREADS), ldskv, st, r.qkv, t->gB, r.ml, t->delta, (long)Tp, D,
-                               hd, T, scale, t->gqkv);
-        else
-            hipLaunchKernelGGL(clipvis_attn_cot_kv_kernel<32>, agrid, dim3(ENC_ATTN_THREADS), ldskv, st, r.qkv, t->gB, r.ml, t->delta, (long)Tp, D,
-                               hd, T, scale, t->gqkv);
+        launch_clipvis_attn_cot_q(r.qkv, r.attn, t->gB, r.ml, (long)Tp, D, hd, T, c.heads, n, scale, t->gqkv, t->delta, st);
+        launch_clipvis_attn_cot_kv(r.qkv, t->gB, r.ml, t->delta, (long)Tp, D, hd, T, c.heads, n, scale, t->gqkv, st);
         launch_gemm_fixed(enc_linear_t(ly.wqkv, t->gqkv, t->gB, 3 * D, D, Tp), GEMM_ACT_NONE, st);
         launch_ln_cot(t->gB, 0, r.h_in, r.st1, 1, D, Tp, ly.ln1_g, t->gC, 0, t->gA, 0, st);
     }

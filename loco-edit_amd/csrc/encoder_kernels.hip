@@ -2,7 +2,7 @@
 // position tables) and clipvis.hip (without, optionally keeping the softmax statistics), the patch gather of both, and the
 // transpose of channel-major results that the text encoders use too.  Exact fp32; every sum runs in a fixed order set by
 // compile-time constants.
-#include "encoder_common.h"
+#include "enc_attn_launch.h"
 
 #include <cmath>
 
@@ -157,8 +157,9 @@ __global__ __launch_bounds__(256) void enc_transpose_kernel(const float* x, int 
 }  // namespace
 
 void launch_enc_attn(const EncAttnArgs& a, hipStream_t st) {
-    auto kernel = a.relh ? enc_attn_kernel<true, false> : a.ml ? enc_attn_kernel<false, true> : enc_attn_kernel<false, false>;
-    const int size = a.relh ? a.size : 0;
+    const bool bias = enc_attn_bias(a);
+    auto kernel = bias ? enc_attn_kernel<true, false> : enc_attn_keep(a) ? enc_attn_kernel<false, true> : enc_attn_kernel<false, false>;
+    const int size = bias ? a.size : 0;
     hipLaunchKernelGGL(kernel, dim3((a.nk + ENC_ATTN_QB - 1) / ENC_ATTN_QB, a.heads, a.groups), dim3(ENC_ATTN_THREADS),
                        enc_attn_lds_floats(a.hd, size) * sizeof(float), st, a.qkv, a.ld, a.D, a.hd, a.nk, size, a.scale, a.relh, a.relw, a.Tall,
                        a.out, a.ml);

@@ -20,7 +20,7 @@
 //               product with the hyper-vectors: the maps at 4G x 4G x C / 8 stay in registers.
 //   score / binarize   the two bilinear stages of MaskGenerator.upsample evaluated per output pixel from the low-resolution
 //               logits; counts and boxes reduce in integers.
-#include "encoder_common.h"
+#include "enc_attn_launch.h"
 
 #include <cmath>
 
@@ -590,6 +590,20 @@ __global__ __launch_bounds__(SD_TH) void sd_binarize_kernel(const float* low, in
 }
 
 }  // namespace
+
+size_t sd_t2i_lds_bytes(int hd) { return sd_t2i_lds_floats(hd) * sizeof(float); }
+
+void launch_sd_t2i(const float* qx, const float* K, const float* V, long kbs, long ld, int T, int Ci, int hd, int heads, int P, int NQ,
+                   float scale, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(sd_t2i_kernel, dim3(heads, P), dim3(SD_TH), sd_t2i_lds_bytes(hd), st, qx, K, V, kbs, ld, T, Ci, hd, NQ, scale, out);
+}
+
+void launch_sd_i2t(const float* q, long qbs, const float* kx, const float* vx, long ld, int T, int Tp, int Ci, int hd, int heads, int P,
+                   int NQ, float scale, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(sd_i2t_kernel, dim3((Tp + SD_TH - 1) / SD_TH, heads, P), dim3(SD_TH), (size_t)2 * SD_Q * hd * sizeof(float), st, q, qbs,
+                       kx, vx, ld, T, Tp, Ci, hd, NQ, scale, out);
+}
+
 }  // namespace loco
 
 using namespace loco;
@@ -780,8 +794,7 @@ int loco_samdec_predict(loco_samdec* t, const float* coords_dev, int32_t P, floa
     a.tok = t->tok; a.qry = t->qry; a.qx = t->qx; a.ox = t->ox; a.kx = t->kx; a.vx = t->vx; a.hbuf = t->hbuf; a.hyp = t->hyp; a.iou_out = iou_out;
     for (int i = 0; i < t->NM; ++i) a.hyper[i] = mlp_p(t->hyper[i]);
     a.iou = mlp_p(t->iou);
-    const size_t tok_lds = (size_t)6 * SD_Q * C * sizeof(float), t2i_lds = sd_t2i_lds_floats(hd) * sizeof(float),
-                 i2t_lds = (size_t)2 * SD_Q * hd * sizeof(float);
+    const size_t tok_lds = (size_t)6 * SD_Q * C * sizeof(float);
     auto tok = [&](int stage) {
         if (stage == SD_ST_PRE) hipLaunchKernelGGL(sd_tok_kernel<SD_ST_PRE>, dim3(P), dim3(SD_TH), tok_lds, st, a);
         else if (stage == SD_ST_MID) hipLaunchKernelGGL(sd_tok_kernel<SD_ST_MID>, dim3(P), dim3(SD_TH), tok_lds, st, a);
@@ -789,7 +802,7 @@ int loco_samdec_predict(loco_samdec* t, const float* coords_dev, int32_t P, floa
         else hipLaunchKernelGGL(sd_tok_kernel<SD_ST_FINAL_POST>, dim3(P), dim3(SD_TH), tok_lds, st, a);
     };
     auto t2i = [&](const float* K, const float* V, long kbs) {
-        hipLaunchKernelGGL(sd_t2i_kernel, dim3(H, P), dim3(SD_TH), t2i_lds, st, t->qx, K, V, kbs, (long)Tp, T, Ci, hd, NQ, scale, t->ox);
+        launch_sd_t2i(t->qx, K, V, kbs, (long)Tp, T, Ci, hd, H, P, NQ, scale, t->ox, st);
     };
     for (int l = 0; l < L; ++l) {
         const SdLayer& ly = t->layer[l];
@@ -813,8 +826,7 @@ int loco_samdec_predict(loco_samdec* t, const float* coords_dev, int32_t P, floa
             q = pa;
             qbs = pst;
         }
-        hipLaunchKernelGGL(sd_i2t_kernel, dim3((Tp + SD_TH - 1) / SD_TH, H, P), dim3(SD_TH), i2t_lds, st, q, qbs, t->kx, t->vx, (long)Tp, T, Tp,
-                           Ci, hd, NQ, scale, pa);
+        launch_sd_i2t(q, qbs, t->kx, t->vx, (long)Tp, T, Tp, Ci, hd, H, P, NQ, scale, pa, st);
         // keys = LayerNorm 4 (keys + out_proj(attention)); layer 0's keys are src for every prompt
         launch_gemm_fixed(sd_proj(ly.i2t.wo, ly.i2t.bo, pa, pst, t->keys, l == 0 ? t->src : t->keys, l == 0 ? 0 : kst, C, Ci, Tp, P),
                           GEMM_ACT_NONE, st);

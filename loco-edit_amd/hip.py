@@ -21,7 +21,7 @@ _lib = None
 
 # diagnostics of include/loco_hip_diag.h: only in a -DLOCO_DIAG build (make -C loco-edit_amd/csrc diag)
 DIAG_SYMBOLS = ["loco_bench_conv", "loco_debug_conv", "loco_debug_attn", "loco_debug_norm", "loco_debug_gemm", "loco_debug_pointwise",
-                "loco_debug_tensor"]
+                "loco_debug_enc_attn", "loco_debug_tensor"]
 
 # every symbol include/loco_hip.h declares
 SYMBOLS = [
@@ -125,6 +125,17 @@ class LocoAttnDesc(C.Structure):
     _PTRS = ("q", "k", "v", "kt", "vt", "P", "o", "dq", "dk", "dv", "out", "go", "gq", "gk", "gv")
     _fields_ = ([("struct_size", C.c_int32)] +
                 [(k, C.c_int32) for k in ("kind", "pass_", "T", "NH", "CH", "B", "Lt", "L", "pair", "no_workspace")] +
+                [(k, C.c_void_p) for k in _PTRS])
+
+
+class LocoEncAttnDesc(C.Structure):
+    """loco_enc_attn_desc of include/loco_hip_diag.h (loco_debug_enc_attn): one launch of one attention kernel of the encoders."""
+    OPS = {"enc_attn": 0, "enc_attn_keep": 1, "enc_attn_bias": 2, "prompt_attn_causal": 3, "prompt_attn_bias": 4,
+           "clipvis_attn_cot_q": 5, "clipvis_attn_cot_kv": 6, "seg_attn": 7, "sd_t2i": 8, "sd_i2t": 9}
+    _PTRS = ("qkv", "relh", "relw", "bias_tab", "o", "go", "q", "k", "v", "lens", "out", "ml", "gqkv", "delta")
+    _fields_ = ([("struct_size", C.c_int32)] +
+                [(k, C.c_int32) for k in ("op", "D", "hd", "heads", "nk", "groups", "size", "NQ", "Tp")] +
+                [(k, C.c_int64) for k in ("ld", "Tall", "kbs", "qbs")] + [("scale", C.c_float), ("pad2_", C.c_int32)] +
                 [(k, C.c_void_p) for k in _PTRS])
 
 
@@ -390,6 +401,8 @@ def load_library():
         lib.loco_debug_pointwise.argtypes = [vp, C.POINTER(LocoPointwiseDesc), vp]
     if hasattr(lib, "loco_debug_gemm"):
         lib.loco_debug_gemm.argtypes = [vp, C.POINTER(LocoGemmDesc), C.c_char_p, i64, vp]
+    if hasattr(lib, "loco_debug_enc_attn"):
+        lib.loco_debug_enc_attn.argtypes = [C.POINTER(LocoEncAttnDesc), C.c_char_p, i64, C.c_char_p, i64, vp]
     _lib = lib
     return lib
 
@@ -409,6 +422,40 @@ def _chk_dev(t: torch.Tensor, dtype=torch.float32):
         raise ValueError(f"expected {dtype}, got {t.dtype}")
     if not t.is_contiguous():
         raise ValueError("tensor must be contiguous")
+
+
+def debug_enc_attn(**desc):
+    """One launch of one attention kernel of the encoders on caller-supplied tensors through the product's launcher
+    (loco_debug_enc_attn, include/loco_hip_diag.h; no engine).  `desc`: the fields of loco_enc_attn_desc, `op` a number or a name of
+    LocoEncAttnDesc.OPS; every tensor a contiguous device tensor, float32 but for `lens` (int32).  Returns the route: one dict
+    per launch.  A refusal or a HIP error raises RuntimeError with the entry point's message."""
+    lib = load_library()
+    if not hasattr(lib, "loco_debug_enc_attn"):
+        raise RuntimeError("loco_debug_enc_attn is a diagnostic of include/loco_hip_diag.h: build `make -C loco-edit_amd/csrc diag` "
+                           "and set LOCO_HIP_LIB=<repo>/loco-edit_amd/libloco_hip_diag.so")
+    d = LocoEncAttnDesc()
+    d.struct_size = C.sizeof(LocoEncAttnDesc)
+    keep = []
+    for k, v in desc.items():
+        if k == "op":
+            d.op = LocoEncAttnDesc.OPS[v] if isinstance(v, str) else int(v)
+        elif k not in LocoEncAttnDesc._PTRS:
+            if not hasattr(d, k) or k == "struct_size":
+                raise TypeError(f"debug_enc_attn: no descriptor field {k!r}")
+            setattr(d, k, v)
+        elif v is not None:
+            _chk_dev(v, torch.int32 if k == "lens" else torch.float32)
+            keep.append(v)
+            setattr(d, k, v.data_ptr())
+    buf, err = C.create_string_buffer(256), C.create_string_buffer(512)
+    rc = lib.loco_debug_enc_attn(C.byref(d), buf, len(buf), err, len(err), _stream())
+    if rc != 0:
+        raise RuntimeError(f"loco_debug_enc_attn failed ({rc}): {err.value.decode()}")
+    route = []
+    for line in buf.value.decode().splitlines():
+        rec = dict(f.split("=", 1) for f in line.split(" "))
+        route.append({k: (v if k == "kernel" else int(v)) for k, v in rec.items()})
+    return route
 
 
 def c_cfg(cfg: UNetConfig, max_batch: int) -> LocoCfg:

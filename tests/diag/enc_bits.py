@@ -13,6 +13,8 @@ inputs where a fixture has none):
   cotangent kernels);
 * SAM (sam/tiny_a, tiny_b and the three wide-head geometries of test_gpu_sam_wide_heads.py, heads of 80, 96 and 65): a padded
   window, a window equal to the grid, global layers at exactly one chunk and at several, the bias tables with hd > 64;
+* the SAM mask decoder (sam/tiny_a, tiny_b through mask_segmentation.SamHeadHip: both cross-attention kernels in every layer):
+  masks and IoU scores for one prompt and for all of the fixture's;
 * CLIPSeg (clipseg/seg_*): its preprocessing, the taps of the tower and the decoder's logits.
 
 A child prints one line per output with its sha256.  The parent stops at the first child that does not exit 0 and exits
@@ -105,6 +107,15 @@ def child():
         eng = LocoSamEngine(cfg, device=dev)
         eng.load_state_dict(vis)
         put("sam", name, "encode", eng.encode(pv))
+
+    for name in ("tiny_a", "tiny_b"):
+        g = host.load_tiny(name)
+        head = ms.SamHeadHip(g["cfg"], g["sd"], device=dev)
+        emb = g["image_embeddings"].float()
+        for k, pts in (("p1", g["points"][:1]), ("pall", g["points"])):
+            masks, iou = head.predict(emb, pts)
+            put("samdec", name, k, "masks", masks)
+            put("samdec", name, k, "iou", iou)
 
     tok = os.path.join(GOLD, "clip_text", "tokenizer_sd1")
     for name in ("seg_a", "seg_b"):
